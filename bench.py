@@ -81,6 +81,29 @@ def ffn_traffic(calls):
     return main + (tail if tail is not None else 0.0)
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, res, id_count):
+    """--dump-outputs: what a caller of the timed path receives from one step -- per frame an Instances after short-track removal
+    and rescaling -- as one array per field over the frames' rows (DIR/<field>.npy; pred_boxes = its tensor), with
+    detections_per_frame.npy to split them and id_count.npy.  Floating fields keep their dtype (float32); integer ones (track ids,
+    characters, classes) become float64, which holds them exactly."""
+    insts = [r["instances"] for r in res]
+    fields = set.intersection(*(set(x.get_fields()) for x in insts))
+    arrays = {"detections_per_frame": np.array([len(x) for x in insts], np.float64), "id_count": np.array([int(id_count)], np.float64)}
+    for name in sorted(fields):
+        parts = [x.get(name) for x in insts]
+        parts = [(p.tensor if hasattr(p, "tensor") else p).detach().cpu() for p in parts]
+        a = torch.cat(parts).numpy()
+        arrays[name] = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "outputs of one step are %d bytes, above the %d of --dump-outputs" % (total, DUMP_LIMIT)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def build_model(cfg, device):
     from gomatching_amd.modeling import GoMatching
     from gomatching_amd.weights import synth_state_dict
@@ -321,7 +344,12 @@ def main():
     ap.add_argument("--frames-per-gpu", type=int, default=FRAMES_PER_GPU,
                     help="diagnostic: frames of the clip each rank owns per step (BASELINE.json: 8; the self-launch test compares "
                          "N=2 x 8 with N=1 x 16, the same 16-frame clip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the last timed step returned (per-field arrays over the clip's detections) as "
+                         "DIR/<name>.npy, to compare two builds output for output on the same seeded inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     globals()["FRAMES_PER_GPU"] = args.frames_per_gpu
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -489,6 +517,8 @@ def main():
     primary = host_inputs if args.inputs == "host" else hbm_inputs
     setup(pipe, tc_box, primary)
     elapsed, res, id_count = timed(pipe, tc_box, primary, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, id_count)
     tc = tc_box[0]
     # the other placement of the frames, same K steps, as a secondary figure
     elapsed_other, _, _ = timed(pipe, tc_box, hbm_inputs if args.inputs == "host" else host_inputs, args.steps, 1)

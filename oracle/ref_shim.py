@@ -6,9 +6,10 @@ TEST INFRASTRUCTURE -- never imported by the product path (`gomatching_amd/`).
 `adet._C` CUDA op, none of which exist in this image.  This module installs
 `sys.modules` stand-ins for exactly the third-party *symbols* the inference
 path touches, so the reference's own arithmetic files
-import and execute unmodified on CPU.  It is used ONLY by
-`oracle/gen_golden.py` to produce the committed fixtures in `tests/golden/`;
-nothing here (and nothing under /root/reference) travels to the GPU box.
+import and execute unmodified on CPU.  `install()` is used ONLY by
+`oracle/gen_golden*.py` to produce the committed fixtures in `tests/golden/`;
+`install_stand_ins()` (the third-party stand-ins without the reference tree) also
+serves tests/test_compat_cpu.py.
 
 The Detectron2 containers (`Instances`, `Boxes`, `pairwise_iou`, `nms`,
 `ImageList`) are restated from their published v0.6 semantics: they are NOT
@@ -241,6 +242,7 @@ def to_cfgnode(d):
 
 
 _installed = False
+_stand_ins_installed = False
 
 
 def _mod(name, **attrs):
@@ -258,14 +260,16 @@ def _pkg(name, path):
     return m
 
 
-def install():
-    """Install the stand-ins and the namespace packages that skip the reference __init__ files."""
-    global _installed
-    if _installed:
+def _unused(*a, **k):
+    raise RuntimeError("training-only Detectron2 symbol called on the inference path")
+
+
+def install_stand_ins():
+    """Install the third-party stand-ins only (torchvision, fvcore, Detectron2 registries and containers); needs no
+    reference tree, so the tests of gomatching_amd/compat can register into these registries anywhere."""
+    global _stand_ins_installed
+    if _stand_ins_installed:
         return
-    if not reference_available():
-        raise RuntimeError("reference tree not present at %s" % REF_ROOT)
-    R = REF_ROOT + "/"
 
     # --- third-party symbols --------------------------------------------
     def box_area(b):
@@ -295,9 +299,6 @@ def install():
     class ROIHeads(nn.Module):
         pass
 
-    def _unused(*a, **k):
-        raise RuntimeError("training-only Detectron2 symbol called on the inference path")
-
     class _Meta:
         @staticmethod
         def get(name):
@@ -322,6 +323,18 @@ def install():
     _mod("detectron2.utils.events", get_event_storage=_unused)
     _mod("detectron2.utils.comm", get_world_size=lambda: 1)
     _mod("detectron2.data", MetadataCatalog=_Meta)
+    _stand_ins_installed = True
+
+
+def install():
+    """Install the stand-ins and the namespace packages that skip the reference __init__ files."""
+    global _installed
+    if _installed:
+        return
+    if not reference_available():
+        raise RuntimeError("reference tree not present at %s" % REF_ROOT)
+    R = REF_ROOT + "/"
+    install_stand_ins()
 
     # --- namespace packages over the reference tree -----------------------
     _pkg("adet", R + "third_party/adet")

@@ -36,7 +36,7 @@ def test_adet_C_preconditions_and_dispatcher_registration():
 def test_meta_arch_wrapper_in_the_shim_registry():
     from oracle import ref_shim
     from gomatching_amd.compat import d2_register
-    ref_shim.install()
+    ref_shim.install_stand_ins()
     from detectron2.modeling.meta_arch.build import META_ARCH_REGISTRY
     d2_register.register(META_ARCH_REGISTRY)
     cls = META_ARCH_REGISTRY.get(d2_register.ARCH_NAME)
@@ -72,7 +72,7 @@ def test_registration_under_the_reference_names():
     from oracle import ref_shim
     from gomatching_amd.compat import d2_register
     from gomatching_amd.weights import canonical_keys
-    ref_shim.install()
+    ref_shim.install_stand_ins()
     meta, heads = type(ref_shim._Registry())(), type(ref_shim._Registry())()
     cls = d2_register.register(meta, name="GoMatching", roi_heads_registry=heads)
     assert meta.get("GoMatching") is cls and cls.__name__ == "GoMatching" and issubclass(cls, d2_register.GoMatchingMI355X)

@@ -66,9 +66,8 @@ def test_pmc_reduction_splits_the_dominant_kernels_populations(tmp_path):
 
 
 def test_builtin_configs_cover_the_reference_yamls():
-    """The eight builtin configs = the inference-path keys of the reference's eight configs/*.yaml (values transcribed from them; when
-    /root/reference is present -- the build container -- the yamls themselves are parsed and compared)."""
-    import os
+    """The eight builtin configs = the inference-path keys of the reference's eight configs/*.yaml (values transcribed from them, and
+    every key against the yamls as parsed by setup_cfg: tests/golden/reference_configs.json, oracle/gen_golden_configs.py)."""
     from gomatching_amd.config import BUILTIN, REFERENCE_YAML, setup_cfg
     want = {  # head, rescoring, queries, vocabulary, score threshold, min / max size, NMS threshold
         "icdar15": ("LSTMatcher", True, 100, 37, 0.3, 1000, 3000, 0.5), "pp_icdar15": ("SHA_FFN_CRSATTN", True, 100, 37, 0.3, 1000, 3000, 0.5),
@@ -82,17 +81,19 @@ def test_builtin_configs_cover_the_reference_yamls():
         return (c.MODEL.ROI_HEADS.NAME, bool(c.MODEL.ROI_HEADS.WITH_RESR), T.NUM_QUERIES, T.VOC_SIZE, T.INFERENCE_TH_TEST,
                 c.INPUT.MIN_SIZE_TEST, c.INPUT.MAX_SIZE_TEST, c.VIDEO_TEST.NMS_THRESH)
 
-    def more(c):
-        A = c.MODEL.ASSO_HEAD
-        return (A.ASSO_THRESH_TEST, A.NUM_WEIGHT_LAYERS, A.NUM_FC, A.NO_POS_EMB, c.INPUT.VIDEO.TEST_LEN, c.INPUT.FORMAT,
-                tuple(sorted(dict(c.VIDEO_TEST).items())))
+    def lookup(c, key):
+        for part in key.split("."):
+            c = getattr(c, part)
+        return json.loads(json.dumps(dict(c) if isinstance(c, dict) else c))
+    with open(os.path.join(ROOT, "tests", "golden", "reference_configs.json")) as f:
+        ref = json.load(f)
+    assert sorted(ref) == sorted(want)
     for name, w in want.items():
         c = setup_cfg(builtin=name)
         assert keys(c) == w, name
-        ref = os.path.join("/root/reference/configs", REFERENCE_YAML[name])
-        if os.path.exists(ref):
-            r = setup_cfg(ref)
-            assert keys(r) == w and more(r) == more(c), name
+        assert len(ref[name]) == 14, name
+        for k, v in ref[name].items():
+            assert lookup(c, k) == v, (name, k)
 
 
 def test_tail_form_rule_takes_occupancy_for_short_launches_and_throughput_for_long_ones():
