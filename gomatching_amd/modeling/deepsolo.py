@@ -419,11 +419,11 @@ class DeepSolo:
             if tail is not None and tail.proj is not None:
                 # out_proj + norm_cross, FFN + norm3, the coordinate MLP + reference refinement (:484-488) and the next layer's query
                 # position: one launch from the sampled rows
-                tgt, refs, nqpos = ops.dec_tail(samp, tail, refs, want_qpos=more, residual=tgt)
+                tgt, refs, nqpos = ops.dec_tail(samp, tail, refs, want_qpos=more, residual=tgt, frames=B)
                 return refs, tgt, None, nqpos
             tgt = self._out_norm(samp, L, "cross", tgt)
             if tail is not None:
-                tgt, refs, nqpos = ops.dec_tail(tgt, tail, refs, want_qpos=more)
+                tgt, refs, nqpos = ops.dec_tail(tgt, tail, refs, want_qpos=more, frames=B)
                 return refs, tgt, None, nqpos
             if L["ffn"] is not None:
                 tgt = ops.ffn_fused_ln(tgt, L["ffn"])

@@ -234,7 +234,14 @@ class GoMatching:
 
     def _detect_core(self, raw, kind, time_cost, detector=None, flag=None):
         """Every detector kernel of a step, queued on the current stream: no host sync, no host<->device copy, shapes
-        fixed by (B, input kind) -- which is what lets `_detect_graphed` capture it."""
+        fixed by (B, input kind) -- which is what lets `_detect_graphed` capture it.  The kernel choices that depend on a
+        launch's row count are made for a step of `frames_per_step` frames whatever B is (ops.step_plan): a frame's bits do
+        not depend on how many frames share its step (a clip's short last step, the per-size steps of a mixed-resolution
+        clip)."""
+        with ops.step_plan(self.frames_per_step):
+            return self._detect_planned(raw, kind, time_cost, detector, flag)
+
+    def _detect_planned(self, raw, kind, time_cost, detector, flag):
         sync = torch.cuda.synchronize if time_cost.get("_sync") else (lambda: None)
         hw = kind[1]
         t0 = time.time()

@@ -159,6 +159,31 @@ def gemm_mode(mode):
         GEMM_MODE = old
 
 
+# Frames of the detector step the model plans (GoMatching.frames_per_step), or None.  Kernel choices that depend on a launch's row
+# count (`conv_plan`, `tail_form2_wins`) decide by the planned step's rows instead of the call's, so a frame's bits do not depend on
+# how many frames share its step: a clip's short last step and every per-size step of a mixed-resolution clip make the choices of a
+# full step.  None (direct op calls): each call decides by its own rows.
+STEP_FRAMES = None
+
+
+@contextlib.contextmanager
+def step_plan(frames):
+    """Run a block (one detector step, GoMatching._detect_core) under a step plan of `frames` frames."""
+    global STEP_FRAMES
+    assert frames is None or int(frames) > 0
+    old, STEP_FRAMES = STEP_FRAMES, (None if frames is None else int(frames))
+    try:
+        yield
+    finally:
+        STEP_FRAMES = old
+
+
+def plan_rows(frames, rows_per_frame):
+    """The row count a row-count-dependent dispatch decides by: the planned step's when a plan is set (also for a step with more
+    frames than planned), else the call's own `frames` x `rows_per_frame`."""
+    return (STEP_FRAMES or frames) * rows_per_frame
+
+
 def flag_nonfinite(x, flag):
     """flag |= 1 on the device when x holds an Inf / NaN (result check of the back-ends whose GEMMs carry no range flag)."""
     _chk_f32(x)
@@ -301,6 +326,23 @@ PW_K256_MIN_ROWS = 16384
 CONV3_PATCH = _switch("CONV3_PATCH")   # f16x3 back-end: 3x3 / stride 1 convolutions on the patch-resident kernel
 
 
+def conv_plan(rows, Cout, Cin, KH, KW, stride, pad, kind, residual=False):
+    """(kernel, splits) of a convolution with `rows` output pixels (B x OH x OW, or `plan_rows`) on back-end `kind` ("f16x3", "bf16x6"
+    or "fp32" = an unsplit weight).  kernel: "patch" (csrc/conv3x3_patch.hip), "pw_k256" (csrc/gemm_k256.hip), "tile" (the split-weight
+    implicit GEMM of csrc/gemm_f16x3.hip / gemm_bf16x6.hip, K sliced `splits` ways when splits > 1) or "fp32" (csrc/gemm_conv.hip).
+    The split count sets the K partition and so the fp32 summation order: it must come from the same rows for every step size."""
+    if kind == "fp32":
+        return "fp32", 0
+    splits = _L().gom_conv_bf16x6_splits(rows, Cout, KH * KW * Cin)    # few tiles x long K (input_proj[3]): slice K
+    if (kind == "f16x3" and CONV3_PATCH and KH == 3 and KW == 3 and stride == 1 and pad == 1 and not residual and splits <= 1
+            and _L().gom_conv3x3_patch_supported(Cin, Cout)):
+        return "patch", 0
+    if (kind == "f16x3" and PW_K256 and KH == 1 and KW == 1 and stride == 1 and pad == 0 and Cin == 256 and Cout % 32 == 0
+            and Cout >= 512 and rows >= PW_K256_MIN_ROWS and splits <= 1):
+        return "pw_k256", 0
+    return "tile", splits
+
+
 def conv2d_nhwc(x, w_ohwi, scale=None, shift=None, R=None, relu=False, stride=1, pad=0):
     """x [B,H,W,Cin] -> [B,OH,OW,Cout]; w [Cout,KH,KW,Cin] fp32, or a SplitWeight made by prep_conv_weight."""
     split = isinstance(w_ohwi, SplitWeight)
@@ -316,13 +358,12 @@ def conv2d_nhwc(x, w_ohwi, scale=None, shift=None, R=None, relu=False, stride=1,
     if split:
         pl = w_ohwi.planes
         M = B * OH * OW
-        splits = _L().gom_conv_bf16x6_splits(M, Cout, KH * KW * Cin)     # few tiles x long K (input_proj[3]): slice K
+        kernel, splits = conv_plan(plan_rows(B, OH * OW), Cout, Cin, KH, KW, stride, pad, w_ohwi.kind, residual=R is not None)
         ws, nbytes = None, 0
         if splits > 1:
             nbytes = 4 * splits * M * Cout
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-        if (w_ohwi.kind == "f16x3" and CONV3_PATCH and KH == 3 and KW == 3 and stride == 1 and pad == 1 and R is None and splits <= 1
-                and _L().gom_conv3x3_patch_supported(Cin, Cout)):
+        if kernel == "patch":
             # the bottlenecks' 3x3 / 1 convolutions: input patch resident in LDS (csrc/conv3x3_patch.hip)
             img = getattr(w_ohwi, "patch_image", None)
             if img is None:                                  # fragment-linear image of the planes, built once per weight
@@ -343,8 +384,7 @@ def conv2d_nhwc(x, w_ohwi, scale=None, shift=None, R=None, relu=False, stride=1,
                 prof.append((e0, e1, 2.0 * M * Cout * 9 * Cin, 4.0 * M * (Cin + Cout) + 4.0 * 9 * Cin * Cout,
                              "conv3:%dx%dx%d" % (M, Cout, 9 * Cin), _profile_scope))
             return y
-        if (w_ohwi.kind == "f16x3" and PW_K256 and KH == 1 and KW == 1 and stride == 1 and pad == 0 and Cin == 256 and Cout % 32 == 0
-                and Cout >= 512 and M >= PW_K256_MIN_ROWS and splits <= 1 and x.is_contiguous()):
+        if kernel == "pw_k256":
             # conv3 of the res4 bottlenecks (256 -> 1024, + BN + shortcut + ReLU): K = 256 is the row-resident kernel's shape
             # (csrc/gemm_k256.hip: rows as fragments once, weights by LDS-DMA, no A staging) -- FrozenBN's scale folds into the
             # image's inverse row scale, its shift is the bias
@@ -1020,8 +1060,8 @@ def tail_form2_wins(M, cus=256):
 
 def dec_tail_block(ffn_w, coord_w, qpos_w, dim_t, proj_w=None):
     """DecTail when the back-end and shapes allow, else None (callers keep the four-launch path).  Under `DEC_TAIL2` the block is the
-    CU-cooperative form with the round-5 form beside it (`.alt`): `dec_tail` takes the faster one for the call's row count
-    (`tail_form2_wins`)."""
+    CU-cooperative form with the round-5 form beside it (`.alt`): `dec_tail` takes the faster one for the planned step's row count
+    (`tail_form2_wins`, `plan_rows`): the two forms do not return the same bits."""
     ok = DEC_TAIL and FUSED_FFN and FUSED_MLP2 and REF_UPDATE and GEMM_MODE == "f16x3" and ffn_w[0].shape[1] == 256 and \
         ffn_w[0].shape[0] % 32 == 0 and all(tuple(w.shape) == (256, 256) for w in (coord_w[0][0], coord_w[1][0], qpos_w[0][0], qpos_w[1][0]))
     if proj_w is not None and not (DEC_TAIL_PROJ and tuple(proj_w[0].shape) == (256, 256)):
@@ -1033,16 +1073,20 @@ def dec_tail_block(ffn_w, coord_w, qpos_w, dim_t, proj_w=None):
     return blk
 
 
-def dec_tail(x, blk, ref, want_qpos=True, residual=None):
+def dec_tail(x, blk, ref, want_qpos=True, residual=None, frames=None):
     """(tgt [M,256], new_ref [M,2], qpos [M,256] | None) of one launch: LayerNorm(x + FFN(x)), the refined reference points and the
     NEXT layer's query position (deformable_transformer.py:352-369, :484-488, :470-473).  A block built with `proj_w` takes
-    x = the rows sampled by the cross attention and residual = tgt in front of that block: out_proj + norm_cross run first."""
+    x = the rows sampled by the cross attention and residual = tgt in front of that block: out_proj + norm_cross run first.
+    `frames`: how many frames the M rows hold; with it, a block that carries both forms picks by the step plan's rows
+    (`plan_rows`) rather than M."""
     assert x.dim() == 2 and x.stride(1) == 1 and x.shape[1] == 256 and x.dtype == _f32
     assert (residual is not None) == (blk.proj is not None)
     _chk_f32(ref)
     M = x.shape[0]
     assert ref.numel() == 2 * M
-    if blk.form == 2 and getattr(blk, "alt", None) is not None and not tail_form2_wins(M):
+    assert frames is None or (frames > 0 and M % frames == 0)
+    rows = M if frames is None else plan_rows(frames, M // frames)
+    if blk.form == 2 and getattr(blk, "alt", None) is not None and not tail_form2_wins(rows):
         blk = blk.alt                                            # many rounds of workgroups: the 128-row form's throughput wins
     out = torch.empty((M, 256), dtype=_f32, device=x.device)
     new_ref = torch.empty_like(ref)
