@@ -1,14 +1,17 @@
 #!/usr/bin/env python
 """Benchmark of the GoMatching inference hot path on MI355X (contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
 
 A "step" is one pass of the hot path -- the reference's timed window, GoMBatchPredictor.__call__ from
 `batch_inference` through short-track removal and rescaling (text_track_visualizer.py:325-334) -- over
 one synthetic clip.  `value` (round 6 on: the contract's definition) = the K steps with the resized fp32 frames already
-resident in HBM when the timed region starts; `value_pcie_inclusive` = the same K steps with the frames in (pinned) host
-memory and their H2D copy inside the window, on an upload stream under the previous step's detector -- the reference's
-window as it stands, which rounds 1-5 reported as `value`.  Workload (BASELINE.json configs[1]):
+resident in HBM when the timed region starts.  A plain run sets up, warms up, times the K steps, writes --dump-outputs
+and prints the line; --full adds every secondary figure after that: `value_pcie_inclusive` = the same K steps with the
+frames in (pinned) host memory and their H2D copy inside the window, on an upload stream under the previous step's detector
+-- the reference's window as it stands, which rounds 1-5 reported as `value` --, the rooflines of the
+instrumented kernels, the configs[3] / configs[4] legs, the other two contraction back-ends and the CPU baseline with its
+full-size parity check.  Workload (BASELINE.json configs[1]):
 1280x720 source frames -> harness resize to 1000x1778 (MIN_SIZE_TEST=1000), 8 frames per GPU,
 GoMatching_ICDAR15 config (R-50, 100 queries, LSTMatcher, rescoring), random-init synthetic weights.
 With N > 1 the clip has 8*N frames, block-sharded 8 per rank, one RCCL all-gather of per-frame
@@ -307,13 +310,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the other placement of the "
+                         "frames, the rooflines (eager profiled steps), the tracker alone (--emulate-world), the secondary "
+                         "configs[3] / configs[4] legs, the other two contraction back-ends and the CPU baseline (N=1 only, "
+                         "each of the last three can be left out below).  Off: the line carries the headline figures only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its full-size parity check")
     ap.add_argument("--no-alt-backends", action="store_true",
-                    help="skip the short secondary measurements of the other two contraction back-ends (N=1 only)")
+                    help="--full: skip the short secondary measurements of the other two contraction back-ends (N=1 only)")
     ap.add_argument("--inputs", default="hbm", choices=["host", "hbm"],
                     help="where the frames are when the timed region of `value` starts: hbm (default: the contract's definition) or "
                          "pinned host memory with the H2D inside the window (the reference's window; what rounds 1-5 printed as "
-                         "`value`); the other placement is always timed too (value_hbm_resident / value_pcie_inclusive)")
+                         "`value`); --full times the other placement too (value_hbm_resident / value_pcie_inclusive)")
     ap.add_argument("--backbone", default="r50", choices=["r50", "swin", "vitae"],
                     help="r50 = BASELINE.json's workload; swin = side measurement of the Swin-T backbone (§8-f3) on the "
                          "same frames (not the BASELINE workload)")
@@ -337,10 +345,11 @@ def main():
                     help="contraction back-end: two-plane fp16 split on the fp16 matrix cores (default), three-plane bf16 "
                          "split, or exact-fp32 MFMA")
     ap.add_argument("--config", default="all", choices=["ic15", "dstext", "bovtext", "all"],
-                    help="the headline, BASELINE.json configs[1], is always measured.  ic15 = the headline ONLY; dstext / bovtext ADD the "
-                         "secondary leg of configs[3] (GoMatching_PP_DSText: 1920x1080 -> 1280x2276, 300 queries) / configs[4] "
-                         "(GoMatching_BOVText: voc 5462, mixed-resolution clip) as `value_dstext` / `value_bovtext`; all (default) = both")
-    ap.add_argument("--no-config-legs", action="store_true", help="skip the secondary configs[3] / configs[4] legs of the default run")
+                    help="the headline, BASELINE.json configs[1], is always measured.  With --full: ic15 = the headline ONLY; dstext / "
+                         "bovtext ADD the secondary leg of configs[3] (GoMatching_PP_DSText: 1920x1080 -> 1280x2276, 300 queries) / "
+                         "configs[4] (GoMatching_BOVText: voc 5462, mixed-resolution clip) as `value_dstext` / `value_bovtext`; all "
+                         "(default) = both")
+    ap.add_argument("--no-config-legs", action="store_true", help="skip the secondary configs[3] / configs[4] legs of a --full run")
     ap.add_argument("--frames-per-gpu", type=int, default=FRAMES_PER_GPU,
                     help="diagnostic: frames of the clip each rank owns per step (BASELINE.json: 8; the self-launch test compares "
                          "N=2 x 8 with N=1 x 16, the same 16-frame clip)")
@@ -520,9 +529,69 @@ def main():
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, res, id_count)
     tc = tc_box[0]
-    # the other placement of the frames, same K steps, as a secondary figure
+    graphed = bool(model.use_graphs and model._graphs)
+    total_frames = FRAMES_PER_GPU * world * args.steps
+    line = {
+        "metric": "frames/sec (whole node), 1280x720 clip, 100 queries/frame",
+        "value": total_frames / elapsed, "unit": "frames/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": DTYPES[args.gemm], "data": "synthetic",
+        "config": {"workload": ("configs[1]: 1280x720 ICDAR15-video clip -> %dx%d net input, %d frames/GPU, "
+                                "100 queries, GoMatching_ICDAR15 (R-50 + DeepSolo + LSTMatcher, rescoring), "
+                                "random-init synthetic weights" % (net_hw[0], net_hw[1], FRAMES_PER_GPU))
+                   if args.backbone == "r50" else
+                   ("NOT the BASELINE workload: %s backbone side measurement, %dx%d net input, %d frames/GPU, 100 "
+                    "queries, DeepSolo + LSTMatcher, random-init synthetic weights"
+                    % ({"swin": "Swin-T", "vitae": "ViTAEv2-S"}[args.backbone], net_hw[0], net_hw[1], FRAMES_PER_GPU)),
+                   "inputs": ("resized fp32 CHW frames in pinned HOST memory when the timed window starts; the H2D copy "
+                              "(%.0f MB per step) is inside the window, on an upload stream under the previous step's detector "
+                              "(text_track_visualizer.py:325-334 + gom_lstmatcher.py:164-170); --full: value_hbm_resident = same "
+                              "steps, frames already in HBM" % (FRAMES_PER_GPU * 3 * net_hw[0] * net_hw[1] * 4 / 1e6))
+                   if args.inputs == "host" else
+                   ("resized fp32 CHW frames resident in HBM when the timed window starts (the contract's `value`); --full: "
+                    "value_pcie_inclusive = the same steps with the frames in pinned HOST memory and the H2D copy (%.0f MB per step) "
+                    "inside the window, on an upload stream under the previous step's detector -- what rounds 1-5 printed as `value`"
+                    % (FRAMES_PER_GPU * 3 * net_hw[0] * net_hw[1] * 4 / 1e6)),
+                   "frames_per_step": FRAMES_PER_GPU * world, "emulated_world": args.emulate_world,
+                   "tracker_alone_ms_per_step": None,
+                   "short_term_scores": ("replicated on every rank" if args.replicate_short_term else
+                                         "sharded: a rank scores the frame pairs it detected, second all-gather of the [F, 2 + nq^2] blocks")
+                   if world * args.emulate_world > 1 else "single rank",
+                   "long_term_match": "chain of 13 launches",
+                   "tracker_cus": args.tracker_cus if args.tracker_cus >= 0 else 0,
+                   "pipelining": "upload(step i+1) and detector(step i+1) overlap tracker(step i)",
+                   "detector_hipgraph": graphed,
+                   "parallelism": "frame-sharded dp%d + 1 all-gather/step"
+                   % world if world > 1 else "single GPU",
+                   "detect_frac": args.detect_frac,
+                   "detections_per_frame": [len(r["instances"]) for r in res[:FRAMES_PER_GPU]],
+                   "tracks": int(id_count),
+                   # ranks whose records arrived through the step's one all-gather (rows of the gathered buffer / frames per
+                   # rank), and the track ids of the whole clip after short-track removal (every rank holds the same)
+                   "rccl_ranks_seen": (getattr(model, "_last_gathered_frames", None) or FRAMES_PER_GPU) // FRAMES_PER_GPU
+                   if world > 1 else 1,
+                   "collective_backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None,
+                   "track_ids_per_frame": [r["instances"].track_ids.cpu().tolist() if len(r["instances"]) else []
+                                           for r in res]},
+        "stage_ms_per_step": {k: v / args.steps * 1e3 for k, v in tc.items() if isinstance(v, float) and v > 0},
+    }
+
+    def report():
+        line["fallback_steps"] = int(model.fallback_steps)      # steps of this run re-done on the bf16x6 twin (range flag tripped)
+        assert model.fallback_steps == 0 or args.gemm != "f16x3", "an f16x3 step fell back to bf16x6 inside the measurement"
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        return report()
+
+    # --full: every secondary figure, each measured after the headline's timed steps.
+    # The other placement of the frames, same K steps
     elapsed_other, _, _ = timed(pipe, tc_box, hbm_inputs if args.inputs == "host" else host_inputs, args.steps, 1)
     elapsed_hbm, elapsed_host = (elapsed_other, elapsed) if args.inputs == "host" else (elapsed, elapsed_other)
+    line["value_hbm_resident"], line["value_pcie_inclusive"] = total_frames / elapsed_hbm, total_frames / elapsed_host
 
     tracker_alone_ms = None
     if args.emulate_world > 1 and world == 1 and model._bench_last_rec[0] is not None:
@@ -542,12 +611,12 @@ def main():
             torch.cuda.synchronize()
             times.append((time.time() - t0) * 1e3)
         tracker_alone_ms = sorted(times)[len(times) // 2]
+    line["config"]["tracker_alone_ms_per_step"] = tracker_alone_ms
 
     # Roofline leg.  The timed steps replay the detector as a hipGraph, which hides individual launches from HIP
     # events; the dominant kernel is therefore bracketed with events in PROFILE_STEPS eager steps of the same
     # workload right after the timed region (same process, same buffers, same stream).  profiles/ holds the rocprofv3
     # per-kernel average over the timed (graph) steps of this command, which agrees.
-    graphed = bool(model.use_graphs and model._graphs)
     model.use_graphs = False
     prof = []
     ops.set_gemm_profile(prof)                                 # HIP events around the dominant kernel's launches
@@ -560,8 +629,6 @@ def main():
     ops.set_gemm_profile(None)
     model.use_graphs = graphed
 
-    total_frames = FRAMES_PER_GPU * world * args.steps
-    fps = total_frames / elapsed
     # north_star's decoder figure: every launch inside the six composite decoder layers that performs Q-side nn.Linear products
     # (M = frames x queries x points rows: ref_point_head, the self-attention blocks, cross-attention offsets | logits and
     # out_proj, FFN, the ctrl-point MLP) against those products' algorithmic FLOPs (7.375 GFLOP per layer and frame)
@@ -617,54 +684,11 @@ def main():
             for k_, v_ in sorted(by_shape.items(), key=lambda kv: -kv[1][1]):
                 f.write("%-44s x%-3d %9.1f us each %9.1f us per step %7.1f TFLOP/s\n" % (
                     k_, v_[0] // PROFILE_STEPS, v_[1] * 1e3 / v_[0], v_[1] * 1e3 / PROFILE_STEPS, v_[2] / (v_[1] * 1e-3) / 1e12))
-    line = {
-        "metric": "frames/sec (whole node), 1280x720 clip, 100 queries/frame",
-        "value": fps, "unit": "frames/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": DTYPES[args.gemm], "data": "synthetic",
-        "value_hbm_resident": total_frames / elapsed_hbm, "value_pcie_inclusive": total_frames / elapsed_host,
-        "config": {"workload": ("configs[1]: 1280x720 ICDAR15-video clip -> %dx%d net input, %d frames/GPU, "
-                                "100 queries, GoMatching_ICDAR15 (R-50 + DeepSolo + LSTMatcher, rescoring), "
-                                "random-init synthetic weights" % (net_hw[0], net_hw[1], FRAMES_PER_GPU))
-                   if args.backbone == "r50" else
-                   ("NOT the BASELINE workload: %s backbone side measurement, %dx%d net input, %d frames/GPU, 100 "
-                    "queries, DeepSolo + LSTMatcher, random-init synthetic weights"
-                    % ({"swin": "Swin-T", "vitae": "ViTAEv2-S"}[args.backbone], net_hw[0], net_hw[1], FRAMES_PER_GPU)),
-                   "inputs": ("resized fp32 CHW frames in pinned HOST memory when the timed window starts; the H2D copy "
-                              "(%.0f MB per step) is inside the window, on an upload stream under the previous step's detector "
-                              "(text_track_visualizer.py:325-334 + gom_lstmatcher.py:164-170); value_hbm_resident = same steps, "
-                              "frames already in HBM" % (FRAMES_PER_GPU * 3 * net_hw[0] * net_hw[1] * 4 / 1e6))
-                   if args.inputs == "host" else
-                   ("resized fp32 CHW frames resident in HBM when the timed window starts (the contract's `value`); "
-                    "value_pcie_inclusive = the same steps with the frames in pinned HOST memory and the H2D copy (%.0f MB per step) "
-                    "inside the window, on an upload stream under the previous step's detector -- what rounds 1-5 printed as `value`"
-                    % (FRAMES_PER_GPU * 3 * net_hw[0] * net_hw[1] * 4 / 1e6)),
-                   "frames_per_step": FRAMES_PER_GPU * world, "emulated_world": args.emulate_world,
-                   "tracker_alone_ms_per_step": tracker_alone_ms,
-                   "short_term_scores": ("replicated on every rank" if args.replicate_short_term else
-                                         "sharded: a rank scores the frame pairs it detected, second all-gather of the [F, 2 + nq^2] blocks")
-                   if world * args.emulate_world > 1 else "single rank",
-                   "long_term_match": "chain of 13 launches",
-                   "tracker_cus": args.tracker_cus if args.tracker_cus >= 0 else 0,
-                   "pipelining": "upload(step i+1) and detector(step i+1) overlap tracker(step i)",
-                   "detector_hipgraph": graphed,
-                   "parallelism": "frame-sharded dp%d + 1 all-gather/step"
-                   % world if world > 1 else "single GPU",
-                   "detect_frac": args.detect_frac,
-                   "detections_per_frame": [len(r["instances"]) for r in res[:FRAMES_PER_GPU]],
-                   "tracks": int(id_count),
-                   # ranks whose records arrived through the step's one all-gather (rows of the gathered buffer / frames per
-                   # rank), and the track ids of the whole clip after short-track removal (every rank holds the same)
-                   "rccl_ranks_seen": (getattr(model, "_last_gathered_frames", None) or FRAMES_PER_GPU) // FRAMES_PER_GPU
-                   if world > 1 else 1,
-                   "collective_backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None,
-                   "track_ids_per_frame": [r["instances"].track_ids.cpu().tolist() if len(r["instances"]) else []
-                                           for r in res]},
-        # The dominant kernel = the 128x128 tile kernel, EVERY launch of it in the step.  Its launches' mean intensity (algorithmic
-        # FLOP per algorithmic byte, fp32 in / fp32 out) is below the chip's balance point, so the roof that bounds it is HBM:
-        # `bound` / `achieved` / `peak` / `frac` are that view, `mfma_view` the other (the round-1 figure, 0.27, was this one on
-        # the GEMM-API launches only: `api_launches.mfma`).  The two populations are also given apart, each with its own PMC traffic.
-        "roofline": dict(
+    # The dominant kernel = the 128x128 tile kernel, EVERY launch of it in the step.  Its launches' mean intensity (algorithmic
+    # FLOP per algorithmic byte, fp32 in / fp32 out) is below the chip's balance point, so the roof that bounds it is HBM:
+    # `bound` / `achieved` / `peak` / `frac` are that view, `mfma_view` the other (the round-1 figure, 0.27, was this one on
+    # the GEMM-API launches only: `api_launches.mfma`).  The two populations are also given apart, each with its own PMC traffic.
+    line["roofline"] = dict(
             ({"bound": "hbm", "achieved": alg_bytes / (dur_ms * 1e-3) / 1e12 if dur_ms > 0 else 0.0, "peak": 8.0, "unit": "TB/s",
               "frac": alg_bytes / (dur_ms * 1e-3) / 1e12 / 8.0 if dur_ms > 0 else 0.0}
              if flops < alg_bytes * PEAKS[args.gemm][1] / 8.0 else
@@ -700,9 +724,7 @@ def main():
                                             "frac": v[2] / (v[1] * 1e-3) / 1e12 / PEAKS[args.gemm][1]}
                                         for k, v in sorted(by_shape.items(), key=lambda kv: -kv[1][1])[:12]},
                      "measured_in": "%d eager steps after the timed region (timed steps are hipGraph replays)" % PROFILE_STEPS
-                     if graphed else "%d eager steps after the timed region" % PROFILE_STEPS}),
-        "stage_ms_per_step": {k: v / args.steps * 1e3 for k, v in tc.items() if isinstance(v, float) and v > 0},
-    }
+                     if graphed else "%d eager steps after the timed region" % PROFILE_STEPS})
     if ffn_prof:
         fd = sum(p_[0].elapsed_time(p_[1]) for p_ in ffn_prof)
         ff = sum(p_[2] for p_ in ffn_prof)
@@ -943,8 +965,6 @@ def main():
                                 "(profiles/r05_clock_stamps.log, profiles/r06_lds_rate.log: 1.76-1.88 GHz in bare MFMA + LDS loops)"}
     line["roofline_top"] = contract_view(top)
     solo = rank == 0 and world == 1 and args.backbone == "r50" and args.emulate_world == 1
-    line["fallback_steps"] = int(model.fallback_steps)          # steps of this run re-done on the bf16x6 twin (range flag tripped)
-    assert model.fallback_steps == 0 or args.gemm != "f16x3", "an f16x3 step fell back to bf16x6 inside the measurement"
     legs = [] if (args.no_config_legs or not solo or args.config == "ic15") else (["dstext", "bovtext"] if args.config == "all" else [args.config])
     if legs:
         del pipe
@@ -969,10 +989,7 @@ def main():
         cpu_cfg.MODEL.DEVICE = "cpu"
         line["cpu_baseline"] = cpu_baseline(cpu_cfg, sd, shifts["s"], shifts["r"], [x["image"] for x in host_inputs],
                                             hw, res, id_count)
-    if rank == 0:
-        print(json.dumps(line))
-    if world > 1:
-        dist.destroy_process_group()
+    report()
 
 
 if __name__ == "__main__":

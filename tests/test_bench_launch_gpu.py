@@ -43,6 +43,29 @@ def test_self_launched_two_ranks_equal_single_rank():
     assert two["config"]["tracks"] == one["config"]["tracks"]
 
 
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_full_adds_the_secondary_figures():
+    """A plain run prints the headline figures only; --full (here without its N=1 extras: legs, other back-ends, CPU baseline)
+    adds the other placement of the frames and the rooflines to a line whose headline is measured the same way."""
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1"]
+    r, lines = _bench(common)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(lines) == 1, r.stdout[-2000:]
+    plain = json.loads(lines[0])
+    assert plain["unit"] == "frames/sec" and plain["higher_is_better"] is True and plain["dtype"] and plain["metric"]
+    assert plain["value"] > 0 and abs(plain["value"] - 8 * 2 / (plain["ms_per_step"] * 2e-3)) < 1e-6 * plain["value"]
+    extra = [k for k in plain if k.startswith(("roofline", "value_")) or k in ("alt_backends", "cpu_baseline")]
+    assert not extra, extra
+    r, lines = _bench(common + ["--full", "--no-cpu-baseline", "--no-alt-backends", "--no-config-legs"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(lines) == 1, r.stdout[-2000:]
+    full = json.loads(lines[0])
+    assert full["value_hbm_resident"] == full["value"] and full["value_pcie_inclusive"] > 0
+    assert full["roofline"]["frac"] > 0 and "roofline_tile_gemm" in full and "roofline_decoder_qside" in full
+    assert full["config"]["track_ids_per_frame"] == plain["config"]["track_ids_per_frame"]
+    assert sum(len(x) for x in plain["config"]["track_ids_per_frame"]) > 0
+
+
 def test_launcher_refuses_without_devices_and_propagates_failures():
     """No GPU here: with RCCL as the backend the launcher must refuse (rc 2) before starting anything; with the gloo dry-run
     backend the ranks start, fail at their first device call, and the launcher must return non-zero instead of hanging."""

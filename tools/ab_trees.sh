@@ -4,7 +4,7 @@
 old=$1
 for rnd in $(seq 1 ${2:-3}); do
   for which in "$old" "."; do
-    (cd $which && timeout 300 python3 bench.py --no-alt-backends --no-cpu-baseline --no-config-legs --steps 15 $BENCH_ARGS 2> /dev/null | python3 -c "
+    (cd $which && timeout 300 python3 bench.py --full --no-alt-backends --no-cpu-baseline --no-config-legs --steps 15 $BENCH_ARGS 2> /dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 q = d.get('roofline_decoder_qside', {})

@@ -31,7 +31,7 @@ for name, key in (("_assign", "assign"), ("precompute_short_term", "short"), ("t
 import bench
 from gomatching_amd import ops as _ops0
 _ops0.NATIVE_TRACKER = False          # these tools dissect the PYTHON loop of track_frames (the native runtime is one opaque call)
-sys.argv = ["bench.py", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--emulate-world", sys.argv[1] if len(sys.argv) > 1 else "8"]
+sys.argv = ["bench.py", "--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--emulate-world", sys.argv[1] if len(sys.argv) > 1 else "8"]
 bench.main()
 m = max(prof["matches"], 1)
 print("matches %d (avg %.0f selected rows); per match: host prep %.0f us, h2d + chain issue %.0f us, wait for device %.0f us; "
