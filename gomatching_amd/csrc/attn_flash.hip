@@ -15,10 +15,7 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int QT = 128, KT = 64;                  // queries per workgroup, keys per staged tile
 

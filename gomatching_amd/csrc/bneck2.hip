@@ -26,13 +26,6 @@
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma16(const half8 a, const half8 b, const f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 constexpr int CH = 32;                                   // X channels per chunk = one 128-byte line per pixel
 constexpr int FRAG = 1024;
 constexpr int WAVES = 8, BM = 16 * WAVES;
@@ -63,10 +56,6 @@ struct B2Args {
     int lda, ldr, ldx, ldy, M, chunks;
 };
 
-__device__ __forceinline__ void dma_fragment(__amdgpu_buffer_rsrc_t rs, unsigned byte_offset, unsigned char* lds_frag) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_frag, 16, (int)byte_offset, 0, 0, 0);
-}
-
 template <int K1, int MP>
 __global__ __launch_bounds__(512, 1) void bneck2_kernel(const B2Args p) {
     using C = Cfg2<K1, MP>;
@@ -76,7 +65,7 @@ __global__ __launch_bounds__(512, 1) void bneck2_kernel(const B2Args p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fn = lane & 15, fg = lane >> 4;
     const long row0 = (long)blockIdx.x * BM + wave * 16;
-    const __amdgpu_buffer_rsrc_t rs_img = __builtin_amdgcn_make_buffer_rsrc((void*)p.img, 0, p.chunks * STAGE_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, p.chunks * STAGE_BYTES);
     float* xt = reinterpret_cast<float*>(smem + C::XT_OFF + wave * XT_BYTES);
 
     // R in and X out move as whole 128-byte lines: lane l handles 16-byte piece (l & 7) of pixels (l >> 3) + 8 i of the wave's 16
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(512, 1) void bneck2_kernel(const B2Args p) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) rv[i] = *reinterpret_cast<const f32x4*>(p.R + (size_t)crow[i] * p.ldr + cpc);
                 __builtin_amdgcn_sched_barrier(0);
-                for (int f = wave; f < STAGE_FRAGS; f += WAVES) dma_fragment(rs_img, f * FRAG + lane * 16, smem + f * FRAG);   // stage 0
+                for (int f = wave; f < STAGE_FRAGS; f += WAVES) gom_dma_fragment(rs_img, f * FRAG + lane * 16, smem + f * FRAG);   // stage 0
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
@@ -140,27 +129,18 @@ __global__ __launch_bounds__(512, 1) void bneck2_kernel(const B2Args p) {
     __syncthreads();
 
     constexpr unsigned OOB = 0x7FFF0000u;
-#define B2_LOAD(dst, g)                                                                                       \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                          \
-        dst[i_] = *reinterpret_cast<const half8*>(base + ((g) * 8 + i_) * FRAG);
 #define B2_DMA(i)
-#define B2_PIN()                                          \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
     for (int c = 0; c < p.chunks; ++c) {
         const int st = c & 1;
         const bool more = c + 1 < p.chunks;
         // the next stage's 65 fragments: 64 + wave .. by wave 0 here, the others -- eight per wave -- inside the first product
         if (more && wave == 0)
-            dma_fragment(rs_img, (unsigned)(c + 1) * STAGE_BYTES + (WA_FRAGS + WB_FRAGS) * FRAG + lane * 16,
-                         smem + (st ^ 1) * STAGE_BYTES + (WA_FRAGS + WB_FRAGS) * FRAG);
+            gom_dma_fragment(rs_img, (unsigned)(c + 1) * STAGE_BYTES + (WA_FRAGS + WB_FRAGS) * FRAG + lane * 16,
+                             smem + (st ^ 1) * STAGE_BYTES + (WA_FRAGS + WB_FRAGS) * FRAG);
         const unsigned nsrc = more ? (unsigned)(c + 1) * STAGE_BYTES + wave * FRAG + lane * 16 : OOB;
         unsigned char* ndst = smem + (st ^ 1) * STAGE_BYTES + wave * FRAG;
 #undef B2_DMA
-#define B2_DMA(i) dma_fragment(rs_img, nsrc + (i) * WAVES * FRAG, ndst + (i) * WAVES * FRAG);
+#define B2_DMA(i) gom_dma_fragment(rs_img, nsrc + (i) * WAVES * FRAG, ndst + (i) * WAVES * FRAG);
         // ================= first product: H^T chunk = W3c . A^T =================
         f32x4 acc1[2];
         f32x4 rn[2];
@@ -178,22 +158,22 @@ __global__ __launch_bounds__(512, 1) void bneck2_kernel(const B2Args p) {
 #define B2_GEMM1(src, g)                                                                                      \
     _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                        \
         const int s_ = (g) * 2 + i_;                                                                          \
-        _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc1[h_] = mfma16(src[4 * i_ + 2 * h_ + 1], xf[0][s_], acc1[h_]);  \
-        _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc1[h_] = mfma16(src[4 * i_ + 2 * h_], xf[1][s_], acc1[h_]);      \
-        _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc1[h_] = mfma16(src[4 * i_ + 2 * h_], xf[0][s_], acc1[h_]);      \
+        _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc1[h_] = gom_mfma16(src[4 * i_ + 2 * h_ + 1], xf[0][s_], acc1[h_]); \
+        _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc1[h_] = gom_mfma16(src[4 * i_ + 2 * h_], xf[1][s_], acc1[h_]); \
+        _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc1[h_] = gom_mfma16(src[4 * i_ + 2 * h_], xf[0][s_], acc1[h_]); \
     }
             // (DMA pieces of this wave: fragments wave, wave + 8, ... below STAGE_FRAGS - 1; the last fragment went out above)
 #define B2_DMAX(i) if ((i) * WAVES < WA_FRAGS + WB_FRAGS) B2_DMA(i)
-            B2_LOAD(fa, 0)
-            __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+            GOM_READ_FRAGS(fa, base, 0)
+            gom_pin<8, 0, 0, 0>();
             if constexpr (K1 == 256) {
-                B2_LOAD(fb, 1) B2_GEMM1(fa, 0) B2_DMAX(0) B2_DMAX(1) B2_PIN()
-                B2_LOAD(fa, 2) B2_GEMM1(fb, 1) B2_DMAX(2) B2_DMAX(3) B2_PIN()
-                B2_LOAD(fb, 3) B2_GEMM1(fa, 2) B2_DMAX(4) B2_DMAX(5) B2_PIN()
+                GOM_READ_FRAGS(fb, base, 1) B2_GEMM1(fa, 0) B2_DMAX(0) B2_DMAX(1) gom_pin<8, 2, 6, 0>();
+                GOM_READ_FRAGS(fa, base, 2) B2_GEMM1(fb, 1) B2_DMAX(2) B2_DMAX(3) gom_pin<8, 2, 6, 0>();
+                GOM_READ_FRAGS(fb, base, 3) B2_GEMM1(fa, 2) B2_DMAX(4) B2_DMAX(5) gom_pin<8, 2, 6, 0>();
                 B2_GEMM1(fb, 3) B2_DMAX(6) B2_DMAX(7)
             } else {
                 static_assert(K1 == 128 || K1 == 256, "K1");
-                B2_LOAD(fb, 1) B2_GEMM1(fa, 0) B2_DMAX(0) B2_DMAX(1) B2_DMAX(2) B2_PIN()
+                GOM_READ_FRAGS(fb, base, 1) B2_GEMM1(fa, 0) B2_DMAX(0) B2_DMAX(1) B2_DMAX(2) gom_pin<8, 2, 6, 0>();
                 B2_GEMM1(fb, 1) B2_DMAX(3) B2_DMAX(4) B2_DMAX(5)
             }
 #undef B2_DMAX
@@ -245,22 +225,18 @@ __global__ __launch_bounds__(512, 1) void bneck2_kernel(const B2Args p) {
 #define B2_GEMM2(src, g)                                                                                      \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
         const int t_ = (g) * 4 + i_;                                                                          \
-        acc2[t_] = mfma16(src[2 * i_ + 1], hf[0], acc2[t_]);                                                  \
-        acc2[t_] = mfma16(src[2 * i_], hf[1], acc2[t_]);                                                      \
-        acc2[t_] = mfma16(src[2 * i_], hf[0], acc2[t_]);                                                      \
+        acc2[t_] = gom_mfma16(src[2 * i_ + 1], hf[0], acc2[t_]);                                              \
+        acc2[t_] = gom_mfma16(src[2 * i_], hf[1], acc2[t_]);                                                  \
+        acc2[t_] = gom_mfma16(src[2 * i_], hf[0], acc2[t_]);                                                  \
     }
-#define B2_PIN0()                                         \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
             static_assert(MP == 256, "MP");
-            B2_LOAD(fa, 0)
-            __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-            B2_LOAD(fb, 1) B2_GEMM2(fa, 0) B2_PIN0()
-            B2_LOAD(fa, 2) B2_GEMM2(fb, 1) B2_PIN0()
-            B2_LOAD(fb, 3) B2_GEMM2(fa, 2) B2_PIN0()
+            GOM_READ_FRAGS(fa, base, 0)
+            gom_pin<8, 0, 0, 0>();
+            GOM_READ_FRAGS(fb, base, 1) B2_GEMM2(fa, 0) gom_pin<8, 0, 0, 12>();
+            GOM_READ_FRAGS(fa, base, 2) B2_GEMM2(fb, 1) gom_pin<8, 0, 0, 12>();
+            GOM_READ_FRAGS(fb, base, 3) B2_GEMM2(fa, 2) gom_pin<8, 0, 0, 12>();
             B2_GEMM2(fb, 3)
 #undef B2_GEMM2
-#undef B2_PIN0
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) rv[i] = rn[i];
@@ -268,9 +244,7 @@ __global__ __launch_bounds__(512, 1) void bneck2_kernel(const B2Args p) {
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
     }
-#undef B2_LOAD
 #undef B2_DMA
-#undef B2_PIN
 
     // ---- Y1 = relu(acc2 * scale + shift): lane = pixel, registers = channels 16 t + 4 fg .. + 3 ----
     float* yrow = p.Y1 + (size_t)myrow * p.ldy + 4 * fg;

@@ -23,11 +23,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int CH = 32;                                   // X channels per chunk = one 128-byte line per pixel
 constexpr int FRAG = 1024;
 constexpr int BM = 128;
@@ -46,22 +41,6 @@ struct BnArgs {
     int* flag;
     int lda, ldr, ldx, ldy, M, chunks;
 };
-
-__device__ __forceinline__ void split2(float x, float y, unsigned int& q0, unsigned int& q1) { gom_split2_f16(x, y, q0, q1); }
-
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, half8& p0, half8& p1) {
-    unsigned int l0, l1, l2, l3, h0, h1, h2, h3;
-    split2(a[0], a[1], l0, h0);
-    split2(a[2], a[3], l1, h1);
-    split2(b[0], b[1], l2, h2);
-    split2(b[2], b[3], l3, h3);
-    p0 = __builtin_bit_cast(half8, (u32x4{l0, l1, l2, l3}));
-    p1 = __builtin_bit_cast(half8, (u32x4{h0, h1, h2, h3}));
-}
-
-__device__ __forceinline__ void dma_fragment(__amdgpu_buffer_rsrc_t rs, unsigned lane_off, unsigned frag_off, unsigned char* lds_frag) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_frag, 16, (int)lane_off, (int)frag_off, 0, 0);
-}
 
 template <int K1, int MP>
 struct Cfg {
@@ -85,11 +64,10 @@ __global__ __launch_bounds__(256, OCC) void bneck_kernel(const BnArgs p) {
     const long row = m < p.M ? m : p.M - 1;                  // tail pixels recompute (and re-store) the last one: same bits
     const unsigned lane16 = lane * 16;
 
-    const __amdgpu_buffer_rsrc_t rs_img =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.img, 0, p.chunks * C::STAGE_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, p.chunks * C::STAGE_BYTES);
     auto dma_stage = [&](int c, int slot) {
         for (int f = wave; f < C::STAGE_FRAGS; f += 4)
-            dma_fragment(rs_img, lane16, (unsigned)c * C::STAGE_BYTES + f * FRAG, smem + slot * C::STAGE_BYTES + f * FRAG);
+            gom_dma_fragment(rs_img, lane16, (unsigned)c * C::STAGE_BYTES + f * FRAG, smem + slot * C::STAGE_BYTES + f * FRAG);
     };
 
     // ---- this wave's 32 pixels of A as B-operand fragments (whole K1), the first chunk's residual piece ----
@@ -127,7 +105,7 @@ __global__ __launch_bounds__(256, OCC) void bneck_kernel(const BnArgs p) {
         for (int s = 0; s < K1 / 16; ++s) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fmaxf(fabsf(ra[2 * s][e]), fabsf(ra[2 * s + 1][e])));
-            split8(ra[2 * s], ra[2 * s + 1], xf[0][s], xf[1][s]);
+            gom_split8_f16(ra[2 * s], ra[2 * s + 1], xf[0][s], xf[1][s]);
         }
         asm volatile("" : "+v"(amax));
     }
@@ -204,7 +182,7 @@ __global__ __launch_bounds__(256, OCC) void bneck_kernel(const BnArgs p) {
                 }
                 vx[q] = v[qq];
             }
-            split8(v[0], v[1], hf[0][u], hf[1][u]);
+            gom_split8_f16(v[0], v[1], hf[0][u], hf[1][u]);
         }
         // the X chunk leaves as whole lines, XTR pixels at a time through the tile (tail pixels re-store the last pixel's bits: the
         // four stores are ALWAYS issued, the counted wait below relies on it)

@@ -20,10 +20,6 @@
 
 namespace {
 
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int TH = 8, TW = 16;                           // output pixels of a workgroup: 8 rows x 16 columns = 128 GEMM rows
 constexpr int PH = TH + 2, PW = TW + 2, NPIX = PH * PW;  // input patch: 10 x 18 = 180 pixels
 constexpr int KC = 64;                                   // channels resident at a time
@@ -43,14 +39,6 @@ struct PArgs {
     int* flag;
     int B, H, W, C, N, relu, tiles_x, tiles_y;
 };
-
-__device__ __forceinline__ void split4(const f32x4 v, u32x2& p0, u32x2& p1) {
-    unsigned int a0, a1, b0, b1;
-    gom_split2_f16(v[0], v[1], a0, a1);
-    gom_split2_f16(v[2], v[3], b0, b1);
-    p0 = u32x2{a0, b0};
-    p1 = u32x2{a1, b1};
-}
 
 template <int BN>
 __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(const PArgs p) {
@@ -83,10 +71,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(const PArgs p) {
     const int y0 = ty * TH, x0 = tx * TW, n0 = tn * BN;
 
     constexpr unsigned RANGE = 0x80000000u, INVALID = 0xC0000000u;
-    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)p.X, 0, (int)RANGE, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsX = gom_buffer_rsrc(p.X, (int)RANGE);
     const int chunks = p.C / KC, total = chunks * KT_PER_CHUNK;
-    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)(p.img + (size_t)tn * total * KT_BYTES), 0,
-                                                                         total * KT_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsW = gom_buffer_rsrc(p.img + (size_t)tn * total * KT_BYTES, total * KT_BYTES);
 
     // patch unit u = tid + 256 i: pixel u >> 4 of the patch, channels 4 (u & 15) .. + 3 of the chunk
     unsigned p_off[P_UNITS];
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(const PArgs p) {
             u32x2 h0, h1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fabsf(p_reg[i][e]));
-            split4(p_reg[i], h0, h1);
+            gom_split4_f16(p_reg[i], h0, h1);
             *reinterpret_cast<u32x2*>(Ps + p_dst[i]) = h0;
             *reinterpret_cast<u32x2*>(Ps + P_PLANE + p_dst[i]) = h1;
         }

@@ -30,11 +30,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int D = 256, NH = 8;                           // model width, heads (head dim 32 = one 32-column chunk)
 constexpr int FRAG = 1024;                               // bytes of one MFMA operand fragment
 constexpr int W_FRAGS = 32;                              // weight fragments of a stage
@@ -66,79 +61,28 @@ struct DecArgs {
     int ldp2, ldraw;
 };
 
-__device__ __forceinline__ void split2(float x, float y, unsigned int& q0, unsigned int& q1) { gom_split2_f16(x, y, q0, q1); }
-
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, half8& p0, half8& p1) {
-    unsigned int l0, l1, l2, l3, h0, h1, h2, h3;
-    split2(a[0], a[1], l0, h0);
-    split2(a[2], a[3], l1, h1);
-    split2(b[0], b[1], l2, h2);
-    split2(b[2], b[3], l3, h3);
-    p0 = __builtin_bit_cast(half8, (u32x4{l0, l1, l2, l3}));
-    p1 = __builtin_bit_cast(half8, (u32x4{h0, h1, h2, h3}));
-}
-
-// `lane_off` (vector) = this lane's 16 bytes inside a fragment, `frag_off` (scalar) = the fragment's offset in the image
-__device__ __forceinline__ void dma_fragment(__amdgpu_buffer_rsrc_t rs, unsigned lane_off, unsigned frag_off, unsigned char* lds_frag) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_frag, 16, (int)lane_off, (int)frag_off, 0, 0);
-}
-
-// registers 8 s .. 8 s + 7 of a 32x32 accumulator -> the two planes of k-step s of an operand fragment
-__device__ __forceinline__ void acc_to_frags(const f32x16& a, half8 (&f)[2][2]) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-        split8(f32x4{a[8 * s], a[8 * s + 1], a[8 * s + 2], a[8 * s + 3]},
-               f32x4{a[8 * s + 4], a[8 * s + 5], a[8 * s + 6], a[8 * s + 7]}, f[s][0], f[s][1]);
-}
-
-// C (+)= A . B on the f16x3 planes: a / b = [k-step][plane hi, lo]
-__device__ __forceinline__ f32x16 mfma_x3(const half8 a_hi, const half8 a_lo, const half8 b_hi, const half8 b_lo, f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_lo, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, c, 0, 0, 0);
-    return c;
-}
-
 // one weight stage: 32 fragments in four groups of eight, group g + 1 read while the MFMAs of group g issue (two-deep register
-// pipeline pinned with sched_group_barrier); the next stage's fragments of this wave are requested one per four MFMAs
-#define DA_LOAD(dst, g)                                                                                       \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                          \
-        dst[i_] = *reinterpret_cast<const half8*>(base + ((g) * 8 + i_) * FRAG);
-#define DA_DMA(i) dma_fragment(rs_img, lane16, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
-#define DA_PIN3()                                         \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-#define DA_PIN2()                                         \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+// pipeline pinned with gom_pin); the next stage's fragments of this wave are requested one per four MFMAs
+#define DA_DMA(i) gom_dma_fragment(rs_img, lane16, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
 #define DA_STAGE(MFMA)                                                                                        \
     {                                                                                                         \
         half8 fa[8], fb[8];                                                                                   \
-        DA_LOAD(fa, 0)                                                                                        \
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);                                                    \
-        DA_LOAD(fb, 1) MFMA(fa, 0) DA_DMA(0) DA_DMA(1) DA_DMA(2) DA_PIN3()                                    \
-        DA_LOAD(fa, 2) MFMA(fb, 1) DA_DMA(3) DA_DMA(4) DA_DMA(5) DA_PIN3()                                    \
-        DA_LOAD(fb, 3) MFMA(fa, 2) DA_DMA(6) DA_DMA(7) DA_DMA(8) DA_PIN3()                                    \
+        GOM_READ_FRAGS(fa, base, 0)                                                                           \
+        gom_pin<8, 0, 0, 0>();                                                                                \
+        GOM_READ_FRAGS(fb, base, 1) MFMA(fa, 0) DA_DMA(0) DA_DMA(1) DA_DMA(2) gom_pin<8, 3, 4, 0>();          \
+        GOM_READ_FRAGS(fa, base, 2) MFMA(fb, 1) DA_DMA(3) DA_DMA(4) DA_DMA(5) gom_pin<8, 3, 4, 0>();          \
+        GOM_READ_FRAGS(fb, base, 3) MFMA(fa, 2) DA_DMA(6) DA_DMA(7) DA_DMA(8) gom_pin<8, 3, 4, 0>();          \
         MFMA(fb, 3)                                                                                           \
     }
 
 #define DA_STAGE_LAST(MFMA)                                                                                   \
     {                                                                                                         \
         half8 fa[8], fb[8];                                                                                   \
-        DA_LOAD(fa, 0)                                                                                        \
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);                                                    \
-        DA_LOAD(fb, 1) MFMA(fa, 0) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0); __builtin_amdgcn_sched_group_barrier(0x008, 12, 0); \
-        DA_LOAD(fa, 2) MFMA(fb, 1) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0); __builtin_amdgcn_sched_group_barrier(0x008, 12, 0); \
-        DA_LOAD(fb, 3) MFMA(fa, 2) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0); __builtin_amdgcn_sched_group_barrier(0x008, 12, 0); \
+        GOM_READ_FRAGS(fa, base, 0)                                                                           \
+        gom_pin<8, 0, 0, 0>();                                                                                \
+        GOM_READ_FRAGS(fb, base, 1) MFMA(fa, 0) gom_pin<8, 0, 0, 12>();                                       \
+        GOM_READ_FRAGS(fa, base, 2) MFMA(fb, 1) gom_pin<8, 0, 0, 12>();                                       \
+        GOM_READ_FRAGS(fb, base, 3) MFMA(fa, 2) gom_pin<8, 0, 0, 12>();                                       \
         MFMA(fb, 3)                                                                                           \
     }
 
@@ -146,19 +90,19 @@ __device__ __forceinline__ f32x16 mfma_x3(const half8 a_hi, const half8 a_lo, co
 #define DA_MFMA_T(src, g)                                                                                     \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
         const int s_ = (g) * 4 + i_;                                                                          \
-        acc = mfma_x3(src[2 * i_], src[2 * i_ + 1], xf[0][s_], xf[1][s_], acc);                               \
+        acc = gom_mfma_x3(src[2 * i_], src[2 * i_ + 1], xf[0][s_], xf[1][s_], acc);                           \
     }
 // projection chunk, straight: acc[token][feature] += X . W chunk^T  (A = the rows in registers, B = weight fragment)
 #define DA_MFMA_S(src, g)                                                                                     \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
         const int s_ = (g) * 4 + i_;                                                                          \
-        acc = mfma_x3(xf[0][s_], xf[1][s_], src[2 * i_], src[2 * i_ + 1], acc);                               \
+        acc = gom_mfma_x3(xf[0][s_], xf[1][s_], src[2 * i_], src[2 * i_ + 1], acc);                           \
     }
 // out_proj stage of head `hh_`: fragments [tile][k-step][plane]; group g = output tiles 2 g, 2 g + 1
 #define DA_MFMA_O(src, g)                                                                                     \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
         const int t_ = 2 * (g) + (i_ >> 1), s_ = i_ & 1;                                                      \
-        yacc[t_] = mfma_x3(src[2 * i_], src[2 * i_ + 1], of[hh_][s_][0], of[hh_][s_][1], yacc[t_]);           \
+        yacc[t_] = gom_mfma_x3(src[2 * i_], src[2 * i_ + 1], of[hh_][s_][0], of[hh_][s_][1], yacc[t_]);       \
     }
 
 template <bool INTER, bool RAW = false>
@@ -197,7 +141,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
 
     unsigned pf[2];
     gom_prefetch_image(p.img, (unsigned)(NST * CHUNK_BYTES), tid, 256, pf);                 // (common.h: a one-round launch, the image cold)
-    const __amdgpu_buffer_rsrc_t rs_img = __builtin_amdgcn_make_buffer_rsrc((void*)p.img, 0, NST * CHUNK_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, NST * CHUNK_BYTES);
     constexpr unsigned OOB = 0x7FFF0000u;                    // beyond num_records: the DMA writes zeros (into an unused stage)
     const unsigned lane16 = lane * 16;
 
@@ -228,7 +172,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
         // kernel start: the ring's first two stages are requested behind the first loads, slot 2 is the scratch
         float* scratch = reinterpret_cast<float*>(smem + 2 * CHUNK_BYTES) + wave * (32 * 64);
         gom_rows_to_fragments<64, false>(xrow, xrow, scratch, lane, xf, amax, [&]() {
-            for (int f = wave; f < 2 * CHUNK_FRAGS; f += 4) dma_fragment(rs_img, lane16, f * FRAG, smem + f * FRAG);
+            for (int f = wave; f < 2 * CHUNK_FRAGS; f += 4) gom_dma_fragment(rs_img, lane16, f * FRAG, smem + f * FRAG);
         });
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -314,7 +258,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
             for (int g = 0; g < 16; ++g) acc[g] = 0.f;
             DA_STAGE(DA_MFMA_S)
             finish_s(acc, aux);
-            acc_to_frags(acc, of[h]);
+            gom_acc_to_frags(acc, of[h]);
             DA_STAGE_END()
         }
         // ---- sweep 2: q | k of (tgt + query_pos) per head (stages 8 + 2 h, 9 + 2 h), attention in registers ----
@@ -336,7 +280,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
                 for (int g = 0; g < 16; ++g) acc[g] = 0.f;
                 DA_STAGE(DA_MFMA_T)
                 finish_t(acc, aux);
-                acc_to_frags(acc, qf);
+                gom_acc_to_frags(acc, qf);
                 DA_STAGE_END()
             }
             {
@@ -346,25 +290,25 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
                 for (int g = 0; g < 16; ++g) acc[g] = 0.f;
                 DA_STAGE(DA_MFMA_T)
                 finish_t(acc, aux);
-                acc_to_frags(acc, kf);
+                gom_acc_to_frags(acc, kf);
                 DA_STAGE_END()
             }
             f32x16 s[1];
 #pragma unroll
             for (int g = 0; g < 16; ++g) s[0][g] = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) s[0] = mfma_x3(kf[ks][0], kf[ks][1], qf[ks][0], qf[ks][1], s[0]);
+            for (int ks = 0; ks < 2; ++ks) s[0] = gom_mfma_x3(kf[ks][0], kf[ks][1], qf[ks][0], qf[ks][1], s[0]);
             const float inv = softmax_keys(s);
             half8 pf[2][2];
-            acc_to_frags(s[0], pf);
+            gom_acc_to_frags(s[0], pf);
             f32x16 o;
 #pragma unroll
             for (int g = 0; g < 16; ++g) o[g] = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) o = mfma_x3(of[h][ks][0], of[h][ks][1], pf[ks][0], pf[ks][1], o);
+            for (int ks = 0; ks < 2; ++ks) o = gom_mfma_x3(of[h][ks][0], of[h][ks][1], pf[ks][0], pf[ks][1], o);
 #pragma unroll
             for (int g = 0; g < 16; ++g) o[g] *= inv;
-            acc_to_frags(o, of[h]);                          // V of this head is dead: its registers take O^T
+            gom_acc_to_frags(o, of[h]);                          // V of this head is dead: its registers take O^T
         }
     } else {
         // ---- per head: q, k, v of tgt (stages 3 h, 3 h + 1, 3 h + 2); K and V^T fragments shared through LDS ----
@@ -378,7 +322,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
                 for (int g = 0; g < 16; ++g) acc[g] = 0.f;
                 DA_STAGE(DA_MFMA_T)
                 finish_t(acc, aux);
-                acc_to_frags(acc, qf);
+                gom_acc_to_frags(acc, qf);
                 DA_STAGE_END()
             }
             {
@@ -389,7 +333,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
                 DA_STAGE(DA_MFMA_T)
                 finish_t(acc, aux);
                 half8 kf[2][2];
-                acc_to_frags(acc, kf);
+                gom_acc_to_frags(acc, kf);
 #pragma unroll
                 for (int f = 0; f < 4; ++f)
                     *reinterpret_cast<half8*>(xch + (wave * 8 + f) * FRAG + lane * 16) = kf[f >> 1][f & 1];
@@ -403,7 +347,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
                 DA_STAGE(DA_MFMA_S)
                 finish_s(acc, aux);
                 half8 vf[2][2];
-                acc_to_frags(acc, vf);
+                gom_acc_to_frags(acc, vf);
 #pragma unroll
                 for (int f = 0; f < 4; ++f)
                     *reinterpret_cast<half8*>(xch + (wave * 8 + 4 + f) * FRAG + lane * 16) = vf[f >> 1][f & 1];
@@ -418,7 +362,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
                 for (int ks = 0; ks < 2; ++ks) {
                     const half8 k_hi = *reinterpret_cast<const half8*>(xch + (b * 8 + 2 * ks) * FRAG + lane * 16);
                     const half8 k_lo = *reinterpret_cast<const half8*>(xch + (b * 8 + 2 * ks + 1) * FRAG + lane * 16);
-                    s[b] = mfma_x3(k_hi, k_lo, qf[ks][0], qf[ks][1], s[b]);
+                    s[b] = gom_mfma_x3(k_hi, k_lo, qf[ks][0], qf[ks][1], s[b]);
                 }
             }
             const float inv = softmax_keys(s);
@@ -428,17 +372,17 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 half8 pf[2][2];
-                acc_to_frags(s[b], pf);
+                gom_acc_to_frags(s[b], pf);
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     const half8 v_hi = *reinterpret_cast<const half8*>(xch + (b * 8 + 4 + 2 * ks) * FRAG + lane * 16);
                     const half8 v_lo = *reinterpret_cast<const half8*>(xch + (b * 8 + 4 + 2 * ks + 1) * FRAG + lane * 16);
-                    o = mfma_x3(v_hi, v_lo, pf[ks][0], pf[ks][1], o);
+                    o = gom_mfma_x3(v_hi, v_lo, pf[ks][0], pf[ks][1], o);
                 }
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) o[g] *= inv;
-            acc_to_frags(o, of[h]);
+            gom_acc_to_frags(o, of[h]);
         }
     }
 
@@ -539,7 +483,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
                 // the rows of the NEXT product as B-operand fragments: registers 8 s .. 8 s + 7 of tile t = k-step 2 t + s in accumulator
                 // order (the order out_proj's image uses for O^T; baked into the raw stages' image)
                 half8 f2[2][2];
-                acc_to_frags(x2, f2);
+                gom_acc_to_frags(x2, f2);
 #pragma unroll
                 for (int s_ = 0; s_ < 2; ++s_) {
                     xf[0][2 * t + s_] = f2[s_][0];
@@ -598,10 +542,7 @@ __global__ __launch_bounds__(256, 1) void dec_attn_kernel(const DecArgs p) {
     if ((!(amax <= 65504.f) || !(chk == 0.f)) && p.flag) atomicOr(p.flag, 1);
 }
 
-#undef DA_LOAD
 #undef DA_DMA
-#undef DA_PIN3
-#undef DA_PIN2
 #undef DA_STAGE
 #undef DA_MFMA_T
 #undef DA_MFMA_S

@@ -30,9 +30,6 @@
 
 namespace {
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int D = 256, NH = 8;
 constexpr int FRAG = 1024;
 constexpr int W_FRAGS = 32;
@@ -63,14 +60,6 @@ struct DecArgs2 {
     int ldp2, ldraw;
 };
 
-__device__ __forceinline__ f32x4 mfma16(const half8 a, const half8 b, const f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void dma_fragment(__amdgpu_buffer_rsrc_t rs, unsigned lane_off, unsigned frag_off, unsigned char* lds_frag) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_frag, 16, (int)lane_off, (int)frag_off, 0, 0);
-}
-
 // -DA2_STAMPS (tools/dec_attn2_variants.py only): s_memtime between the phases of every wave, summed per kind into a buffer set by
 // gom_dec_attn2_set_stamps -- [workgroup][wave][8] cycles: prologue, stage products, stage epilogues (+ exchange writes, stores),
 // end-of-stage waits + barriers, attention, the intra form's row reload, residual + LayerNorm, total
@@ -99,15 +88,6 @@ __device__ __forceinline__ float exp2_if(const float x, const unsigned long long
     float r;
     asm("v_exp_f32 %0, %1\n\ts_nop 0\n\tv_cndmask_b32 %0, 0, %0, %2" : "=&v"(r) : "v"(x), "s"(mask));
     return r;
-}
-
-// four fp32 values -> their fp16 planes: {hi01, hi23} and {lo01, lo23}
-__device__ __forceinline__ void split4(const f32x4 v, u32x2& hi, u32x2& lo) {
-    unsigned h0, l0, h1, l1;
-    gom_split2_f16(v[0], v[1], h0, l0);
-    gom_split2_f16(v[2], v[3], h1, l1);
-    hi = u32x2{h0, h1};
-    lo = u32x2{l0, l1};
 }
 
 // A wave's 16 rows x 256 fp32 in FRAGMENT order: consume(s, a, b) receives, for every 32-wide k-step s, lane (n = lane & 15, kg =
@@ -200,64 +180,53 @@ __device__ __forceinline__ void rows16_to_fragments(FA row_a, FB row_b, float* s
 // one weight stage: 32 fragments in eight groups of four (k-step g), group g + 1 read while the MFMAs of group g issue (four-fragment
 // groups: the two-deep register pipeline costs 32 VGPRs, not 64); this wave's four pieces of stage i + 2 are requested under every
 // other group
-#define A2_LOAD(dst, g)                                                                                       \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                          \
-        dst[i_] = *reinterpret_cast<const half8*>(base + ((g) * 4 + i_) * FRAG);
-#define A2_DMA(k) dma_fragment(rs_img, lane16, nsrc + (k) * WAVES * FRAG, ndst + (k) * WAVES * FRAG);
-#define A2_PIN()                                          \
-    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-#define A2_PIN0()                                         \
-    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+#define A2_DMA(k) gom_dma_fragment(rs_img, lane16, nsrc + (k) * WAVES * FRAG, ndst + (k) * WAVES * FRAG);
 #define A2_STAGE(MFMA)                                                                                        \
     {                                                                                                         \
         half8 fa[4], fb[4];                                                                                   \
-        A2_LOAD(fa, 0)                                                                                        \
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                                                    \
-        A2_LOAD(fb, 1) MFMA(fa, 0) A2_DMA(0) A2_PIN()                                                         \
-        A2_LOAD(fa, 2) MFMA(fb, 1) A2_PIN0()                                                                  \
-        A2_LOAD(fb, 3) MFMA(fa, 2) A2_DMA(1) A2_PIN()                                                         \
-        A2_LOAD(fa, 4) MFMA(fb, 3) A2_PIN0()                                                                  \
-        A2_LOAD(fb, 5) MFMA(fa, 4) A2_DMA(2) A2_PIN()                                                         \
-        A2_LOAD(fa, 6) MFMA(fb, 5) A2_PIN0()                                                                  \
-        A2_LOAD(fb, 7) MFMA(fa, 6) A2_DMA(3) A2_PIN()                                                         \
+        GOM_READ_FRAGS(fa, base, 0)                                                                           \
+        gom_pin<4, 0, 0, 0>();                                                                                \
+        GOM_READ_FRAGS(fb, base, 1) MFMA(fa, 0) A2_DMA(0) gom_pin<4, 1, 3, 3>();                              \
+        GOM_READ_FRAGS(fa, base, 2) MFMA(fb, 1) gom_pin<4, 0, 0, 6>(); \
+        GOM_READ_FRAGS(fb, base, 3) MFMA(fa, 2) A2_DMA(1) gom_pin<4, 1, 3, 3>(); \
+        GOM_READ_FRAGS(fa, base, 4) MFMA(fb, 3) gom_pin<4, 0, 0, 6>(); \
+        GOM_READ_FRAGS(fb, base, 5) MFMA(fa, 4) A2_DMA(2) gom_pin<4, 1, 3, 3>();                              \
+        GOM_READ_FRAGS(fa, base, 6) MFMA(fb, 5) gom_pin<4, 0, 0, 6>();                                        \
+        GOM_READ_FRAGS(fb, base, 7) MFMA(fa, 6) A2_DMA(3) gom_pin<4, 1, 3, 3>();                              \
         MFMA(fb, 7)                                                                                           \
         A2_T(1)                                                                                               \
     }
 #define A2_STAGE_LAST(MFMA)                                                                                   \
     {                                                                                                         \
         half8 fa[4], fb[4];                                                                                   \
-        A2_LOAD(fa, 0)                                                                                        \
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                                                    \
-        A2_LOAD(fb, 1) MFMA(fa, 0) A2_PIN0()                                                                  \
-        A2_LOAD(fa, 2) MFMA(fb, 1) A2_PIN0()                                                                  \
-        A2_LOAD(fb, 3) MFMA(fa, 2) A2_PIN0()                                                                  \
-        A2_LOAD(fa, 4) MFMA(fb, 3) A2_PIN0()                                                                  \
-        A2_LOAD(fb, 5) MFMA(fa, 4) A2_PIN0()                                                                  \
-        A2_LOAD(fa, 6) MFMA(fb, 5) A2_PIN0()                                                                  \
-        A2_LOAD(fb, 7) MFMA(fa, 6) A2_PIN0()                                                                  \
+        GOM_READ_FRAGS(fa, base, 0)                                                                           \
+        gom_pin<4, 0, 0, 0>();                                                                                \
+        GOM_READ_FRAGS(fb, base, 1) MFMA(fa, 0) gom_pin<4, 0, 0, 6>();                                        \
+        GOM_READ_FRAGS(fa, base, 2) MFMA(fb, 1) gom_pin<4, 0, 0, 6>(); \
+        GOM_READ_FRAGS(fb, base, 3) MFMA(fa, 2) gom_pin<4, 0, 0, 6>(); \
+        GOM_READ_FRAGS(fa, base, 4) MFMA(fb, 3) gom_pin<4, 0, 0, 6>(); \
+        GOM_READ_FRAGS(fb, base, 5) MFMA(fa, 4) gom_pin<4, 0, 0, 6>();                                        \
+        GOM_READ_FRAGS(fa, base, 6) MFMA(fb, 5) gom_pin<4, 0, 0, 6>();                                        \
+        GOM_READ_FRAGS(fb, base, 7) MFMA(fa, 6) gom_pin<4, 0, 0, 6>();                                        \
         MFMA(fb, 7)                                                                                           \
         A2_T(1)                                                                                               \
     }
 // fragment 2 Hh + p of a group = plane p of feature tile Hh at k-step g
 // transposed: acc[Hh][feature 16 Hh + 4 rg + e][token] += W . X^T   (A = weight fragment, B = the rows)
 #define A2_MFMA_T(src, g)                                                                                     \
-    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = mfma16(src[2 * h_ + 1], xf[0][g], acc[h_]);    \
-    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = mfma16(src[2 * h_], xf[1][g], acc[h_]);        \
-    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = mfma16(src[2 * h_], xf[0][g], acc[h_]);
+    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = gom_mfma16(src[2 * h_ + 1], xf[0][g], acc[h_]); \
+    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = gom_mfma16(src[2 * h_], xf[1][g], acc[h_]);    \
+    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = gom_mfma16(src[2 * h_], xf[0][g], acc[h_]);
 // straight: acc[Hh][token 4 rg + e][feature 16 Hh + n] += X . W^T   (A = the rows, B = weight fragment)
 #define A2_MFMA_S(src, g)                                                                                     \
-    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = mfma16(xf[0][g], src[2 * h_ + 1], acc[h_]);    \
-    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = mfma16(xf[1][g], src[2 * h_], acc[h_]);        \
-    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = mfma16(xf[0][g], src[2 * h_], acc[h_]);
+    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = gom_mfma16(xf[0][g], src[2 * h_ + 1], acc[h_]); \
+    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = gom_mfma16(xf[1][g], src[2 * h_], acc[h_]);    \
+    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) acc[h_] = gom_mfma16(xf[0][g], src[2 * h_], acc[h_]);
 // out_proj stage of a head: fragment 2 t + p = plane p of output tile t; group g = tiles 2 g, 2 g + 1
 #define A2_MFMA_O(src, g)                                                                                     \
-    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) yacc[(g) * 2 + i_] = mfma16(src[2 * i_ + 1], o_hi, yacc[(g) * 2 + i_]); \
-    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) yacc[(g) * 2 + i_] = mfma16(src[2 * i_], o_lo, yacc[(g) * 2 + i_]);     \
-    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) yacc[(g) * 2 + i_] = mfma16(src[2 * i_], o_hi, yacc[(g) * 2 + i_]);
+    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) yacc[(g) * 2 + i_] = gom_mfma16(src[2 * i_ + 1], o_hi, yacc[(g) * 2 + i_]); \
+    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) yacc[(g) * 2 + i_] = gom_mfma16(src[2 * i_], o_lo, yacc[(g) * 2 + i_]); \
+    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) yacc[(g) * 2 + i_] = gom_mfma16(src[2 * i_], o_hi, yacc[(g) * 2 + i_]);
 
 template <bool INTER, bool RAW = false>
 __global__ __launch_bounds__(512, 1) void dec_attn2_kernel(const DecArgs2 p) {
@@ -315,7 +284,7 @@ __global__ __launch_bounds__(512, 1) void dec_attn2_kernel(const DecArgs2 p) {
     const bool valid = fn < mine;
     const long row = slot_row(fn);
 
-    const __amdgpu_buffer_rsrc_t rs_img = __builtin_amdgcn_make_buffer_rsrc((void*)p.img, 0, VEC_BYTES + NST * CHUNK_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, VEC_BYTES + NST * CHUNK_BYTES);
     constexpr unsigned OOB = 0x7FFF0000u;
     const unsigned lane16 = lane * 16;
 
@@ -328,8 +297,8 @@ __global__ __launch_bounds__(512, 1) void dec_attn2_kernel(const DecArgs2 p) {
         // the ring's first two stages and the epilogue vectors are requested behind the first loads, slot 2 is the scratch
         float* scratch = reinterpret_cast<float*>(smem + 2 * CHUNK_BYTES) + wave * (16 * 64);
         rows16_to_fragments<false>(xrow, xrow, scratch, lane, xf, amax, [&]() {
-            for (int f = wave; f < 2 * CHUNK_FRAGS; f += WAVES) dma_fragment(rs_img, lane16, VEC_BYTES + f * FRAG, smem + f * FRAG);
-            if (wave < 4) dma_fragment(rs_img, lane16, wave * FRAG, smem + RING_BYTES + XCH_BYTES + wave * FRAG);
+            for (int f = wave; f < 2 * CHUNK_FRAGS; f += WAVES) gom_dma_fragment(rs_img, lane16, VEC_BYTES + f * FRAG, smem + f * FRAG);
+            if (wave < 4) gom_dma_fragment(rs_img, lane16, wave * FRAG, smem + RING_BYTES + XCH_BYTES + wave * FRAG);
             // the whole image towards this XCD's L2 (common.h gom_prefetch_image): between the layers of a step it (1.1 - 1.5 MB, last
             // read a step ago) is in HBM, and the ring's two stages of lookahead do not cover a miss per stage (tools/
             // dec_attn2_variants.py, a 768 MB fill in front of every launch: inter + raw 76 -> 99 us, 88 with this)
@@ -346,8 +315,8 @@ __global__ __launch_bounds__(512, 1) void dec_attn2_kernel(const DecArgs2 p) {
     const float* aux = reinterpret_cast<const float*>(smem + ((i) % SLOTS) * CHUNK_BYTES + W_FRAGS * FRAG);   \
     const unsigned nsrc = (i) + 2 < NST ? (unsigned)VEC_BYTES + (unsigned)((i) + 2) * CHUNK_BYTES + wave * FRAG : OOB; \
     unsigned char* ndst = smem + (((i) + 2) % SLOTS) * CHUNK_BYTES + wave * FRAG;                             \
-    if (wave == 0) dma_fragment(rs_img, lane16, (i) + 2 < NST ? (unsigned)VEC_BYTES + (unsigned)((i) + 2) * CHUNK_BYTES + W_FRAGS * FRAG : OOB, \
-                                smem + (((i) + 2) % SLOTS) * CHUNK_BYTES + W_FRAGS * FRAG);                   \
+    if (wave == 0) gom_dma_fragment(rs_img, lane16, (i) + 2 < NST ? (unsigned)VEC_BYTES + (unsigned)((i) + 2) * CHUNK_BYTES + W_FRAGS * FRAG : OOB, \
+                                    smem + (((i) + 2) % SLOTS) * CHUNK_BYTES + W_FRAGS * FRAG);                                    \
     __builtin_amdgcn_sched_barrier(0);
     // end of a stage: everything older than this stage's four (wave 0: five) requests has landed (= stage i + 1, requested a stage
     // ago; loads return in issue order); the LDS writes of the exchange are covered by the barrier's fence
@@ -427,11 +396,11 @@ __global__ __launch_bounds__(512, 1) void dec_attn2_kernel(const DecArgs2 p) {
                 k_lo[b] = *reinterpret_cast<const half8*>(xch_k + ((b0 + bb + b) * 2 + 1) * FRAG + lane * 16);
             }
 #pragma unroll
-            for (int b = 0; b < KB; ++b) s[bb + b] = mfma16(k_lo[b], q_hi, s[bb + b]);
+            for (int b = 0; b < KB; ++b) s[bb + b] = gom_mfma16(k_lo[b], q_hi, s[bb + b]);
 #pragma unroll
-            for (int b = 0; b < KB; ++b) s[bb + b] = mfma16(k_hi[b], q_lo, s[bb + b]);
+            for (int b = 0; b < KB; ++b) s[bb + b] = gom_mfma16(k_hi[b], q_lo, s[bb + b]);
 #pragma unroll
-            for (int b = 0; b < KB; ++b) s[bb + b] = mfma16(k_hi[b], q_hi, s[bb + b]);
+            for (int b = 0; b < KB; ++b) s[bb + b] = gom_mfma16(k_hi[b], q_hi, s[bb + b]);
         }
         // the first k-step's V fragments: on their way under the softmax
         half8 v[4];
@@ -480,11 +449,11 @@ __global__ __launch_bounds__(512, 1) void dec_attn2_kernel(const DecArgs2 p) {
                 for (int i = 0; i < 4; ++i) vn[i] = *reinterpret_cast<const half8*>(xch_v + ((t0 + t + 1) * 4 + i) * FRAG + lane * 16);
             }
 #pragma unroll
-            for (int hh = 0; hh < 2; ++hh) o[hh] = mfma16(v[2 * hh + 1], p_hi, o[hh]);
+            for (int hh = 0; hh < 2; ++hh) o[hh] = gom_mfma16(v[2 * hh + 1], p_hi, o[hh]);
 #pragma unroll
-            for (int hh = 0; hh < 2; ++hh) o[hh] = mfma16(v[2 * hh], p_lo, o[hh]);
+            for (int hh = 0; hh < 2; ++hh) o[hh] = gom_mfma16(v[2 * hh], p_lo, o[hh]);
 #pragma unroll
-            for (int hh = 0; hh < 2; ++hh) o[hh] = mfma16(v[2 * hh], p_hi, o[hh]);
+            for (int hh = 0; hh < 2; ++hh) o[hh] = gom_mfma16(v[2 * hh], p_hi, o[hh]);
             if (t + 1 < NB / 2) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = vn[i];
@@ -533,7 +502,7 @@ __global__ __launch_bounds__(512, 1) void dec_attn2_kernel(const DecArgs2 p) {
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
                 u32x2 hi, lo;
-                split4(acc[hh], hi, lo);
+                gom_split4_f16(acc[hh], hi, lo);
                 vo[h][hh] = u32x4{hi[0], hi[1], lo[0], lo[1]};
             }
             A2_STAGE_END()
@@ -611,8 +580,8 @@ __global__ __launch_bounds__(512, 1) void dec_attn2_kernel(const DecArgs2 p) {
                 A2_STAGE(A2_MFMA_S)
                 finish_s(acc, aux);
                 u32x2 hi0, lo0, hi1, lo1;
-                split4(acc[0], hi0, lo0);
-                split4(acc[1], hi1, lo1);
+                gom_split4_f16(acc[0], hi0, lo0);
+                gom_split4_f16(acc[1], hi1, lo1);
                 put_v(hi0, lo0, hi1, lo1);
                 A2_STAGE_END()
             }

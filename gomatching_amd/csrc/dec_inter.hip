@@ -22,9 +22,6 @@
 
 namespace {
 
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int D = 256, NH = 8;
 constexpr int FRAG = 1024;
 constexpr int W_FRAGS = 32;
@@ -45,24 +42,6 @@ struct InterArgs {
     int G, inner, nblk, per_blk;
 };
 
-__device__ __forceinline__ void dma_fragment(__amdgpu_buffer_rsrc_t rs, unsigned lane_off, unsigned frag_off, unsigned char* lds_frag) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_frag, 16, (int)lane_off, (int)frag_off, 0, 0);
-}
-
-__device__ __forceinline__ void acc_to_frags(const f32x16& a, half8 (&f)[2][2]) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-        gom_split8_f16(f32x4{a[8 * s], a[8 * s + 1], a[8 * s + 2], a[8 * s + 3]},
-                       f32x4{a[8 * s + 4], a[8 * s + 5], a[8 * s + 6], a[8 * s + 7]}, f[s][0], f[s][1]);
-}
-
-__device__ __forceinline__ f32x16 mfma_x3(const half8 a_hi, const half8 a_lo, const half8 b_hi, const half8 b_lo, f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_lo, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, c, 0, 0, 0);
-    return c;
-}
-
 __global__ __launch_bounds__(256, 1) void dec_inter_heads_kernel(const InterArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* wk = smem;                                // k weights, then q weights
@@ -75,11 +54,11 @@ __global__ __launch_bounds__(256, 1) void dec_inter_heads_kernel(const InterArgs
     const long gi = blockIdx.x / NH;
     const long b = gi / p.inner, pp = gi % p.inner;
 
-    const __amdgpu_buffer_rsrc_t rs_img = __builtin_amdgcn_make_buffer_rsrc((void*)p.img, 0, IMAGE_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, IMAGE_BYTES);
     const unsigned lane16 = lane * 16;
     // stage `st` of the image -> a 36 KB LDS region, the four waves sharing the 36 fragments
     auto request = [&](int st, unsigned char* dst) {
-        for (int f = wave; f < CHUNK_FRAGS; f += 4) dma_fragment(rs_img, lane16, (unsigned)st * CHUNK_BYTES + f * FRAG, dst + f * FRAG);
+        for (int f = wave; f < CHUNK_FRAGS; f += 4) gom_dma_fragment(rs_img, lane16, (unsigned)st * CHUNK_BYTES + f * FRAG, dst + f * FRAG);
     };
     request(3 * head + 1, wk);
     request(3 * head + 2, wv);
@@ -138,21 +117,21 @@ __global__ __launch_bounds__(256, 1) void dec_inter_heads_kernel(const InterArgs
         for (int s = 0; s < D / 16; ++s) {
             const half8 w_hi = *reinterpret_cast<const half8*>(wk + (2 * s) * FRAG + lane * 16);
             const half8 w_lo = *reinterpret_cast<const half8*>(wk + (2 * s + 1) * FRAG + lane * 16);
-            acc = mfma_x3(w_hi, w_lo, xf[0][s], xf[1][s], acc);
+            acc = gom_mfma_x3(w_hi, w_lo, xf[0][s], xf[1][s], acc);
         }
         finish_t(acc, reinterpret_cast<const float*>(wk + W_FRAGS * FRAG));
         half8 kf[2][2];
-        acc_to_frags(acc, kf);
+        gom_acc_to_frags(acc, kf);
         zero(acc);
 #pragma unroll
         for (int s = 0; s < D / 16; ++s) {
             const half8 w_hi = *reinterpret_cast<const half8*>(wv + (2 * s) * FRAG + lane * 16);
             const half8 w_lo = *reinterpret_cast<const half8*>(wv + (2 * s + 1) * FRAG + lane * 16);
-            acc = mfma_x3(xf[0][s], xf[1][s], w_hi, w_lo, acc);
+            acc = gom_mfma_x3(xf[0][s], xf[1][s], w_hi, w_lo, acc);
         }
         finish_s(acc, reinterpret_cast<const float*>(wv + W_FRAGS * FRAG));
         half8 vf[2][2];
-        acc_to_frags(acc, vf);
+        gom_acc_to_frags(acc, vf);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
@@ -183,10 +162,10 @@ __global__ __launch_bounds__(256, 1) void dec_inter_heads_kernel(const InterArgs
             for (int s = 0; s < D / 16; ++s) {
                 const half8 w_hi = *reinterpret_cast<const half8*>(wk + (2 * s) * FRAG + lane * 16);
                 const half8 w_lo = *reinterpret_cast<const half8*>(wk + (2 * s + 1) * FRAG + lane * 16);
-                acc = mfma_x3(w_hi, w_lo, xf[0][s], xf[1][s], acc);
+                acc = gom_mfma_x3(w_hi, w_lo, xf[0][s], xf[1][s], acc);
             }
             finish_t(acc, reinterpret_cast<const float*>(wk + W_FRAGS * FRAG));
-            acc_to_frags(acc, qf);
+            gom_acc_to_frags(acc, qf);
         }
         f32x16 o;
         zero(o);
@@ -200,7 +179,7 @@ __global__ __launch_bounds__(256, 1) void dec_inter_heads_kernel(const InterArgs
             for (int ks = 0; ks < 2; ++ks) {
                 const half8 k_hi = *reinterpret_cast<const half8*>(slot + (2 * ks) * FRAG);
                 const half8 k_lo = *reinterpret_cast<const half8*>(slot + (2 * ks + 1) * FRAG);
-                s = mfma_x3(k_hi, k_lo, qf[ks][0], qf[ks][1], s);
+                s = gom_mfma_x3(k_hi, k_lo, qf[ks][0], qf[ks][1], s);
             }
             float mb = -INFINITY;
 #pragma unroll
@@ -223,12 +202,12 @@ __global__ __launch_bounds__(256, 1) void dec_inter_heads_kernel(const InterArgs
 #pragma unroll
             for (int g = 0; g < 16; ++g) o[g] *= alpha;
             half8 pf[2][2];
-            acc_to_frags(s, pf);
+            gom_acc_to_frags(s, pf);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const half8 v_hi = *reinterpret_cast<const half8*>(slot + (4 + 2 * ks) * FRAG);
                 const half8 v_lo = *reinterpret_cast<const half8*>(slot + (4 + 2 * ks + 1) * FRAG);
-                o = mfma_x3(v_hi, v_lo, pf[ks][0], pf[ks][1], o);
+                o = gom_mfma_x3(v_hi, v_lo, pf[ks][0], pf[ks][1], o);
             }
         }
         l += __shfl_xor(l, 32, 64);

@@ -31,14 +31,6 @@
 
 namespace {
 
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma16(const half8 a, const half8 b, const f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 constexpr int D = 256;                                   // model width
 constexpr int CH = 32;                                   // hidden units per weight chunk
 constexpr int FRAG = 1024;
@@ -70,41 +62,6 @@ struct TailArgs {
     int ldr;
 };
 
-__device__ __forceinline__ void dma_fragment(__amdgpu_buffer_rsrc_t rs, unsigned byte_offset, unsigned char* lds_frag) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_frag, 16, (int)byte_offset, 0, 0, 0);
-}
-
-__device__ __forceinline__ float inv_sigmoid(float x) {   // adet/utils/misc.py:115-119, eps 1e-5 (as elementwise.hip)
-    x = fminf(fmaxf(x, 0.f), 1.f);
-    const float x1 = fmaxf(x, 1e-5f), x2 = fmaxf(1.f - x, 1e-5f);
-    return logf(x1 / x2);
-}
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
-
-// sin and cos of an angle in [0, 2 pi] (the sine embedding's range: a reference point in [0, 1] times 2 pi over dim_t >= 1):
-// quadrant by a two-term Cody-Waite reduction (exact with fma for q <= 4), then the cephes single-precision kernels on
-// [-pi/4, pi/4] -- within 1 ulp of 1 of the correctly rounded values.  Not ocml's sinf / cosf: their large-argument path keeps
-// the compiler from unrolling the embedding loop, and a dynamically indexed operand array goes to scratch.
-__device__ __forceinline__ void sincos_0_2pi(float a, float& sn, float& cs) {
-    const float q = rintf(a * 0.63661977236758134f);
-    float r = fmaf(q, -1.57079637050628662109375f, a);
-    r = fmaf(q, 4.37113900018624283e-8f, r);
-    const float z = r * r;
-    const float ps = fmaf(fmaf(fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f) * z, r, r);
-    const float pc = fmaf(fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f) * z, z, fmaf(-0.5f, z, 1.f));
-    const int qi = (int)q;
-    const float s0 = (qi & 1) ? pc : ps, c0 = (qi & 1) ? ps : pc;
-    sn = (qi & 2) ? -s0 : s0;
-    cs = ((qi + 1) & 2) ? -c0 : c0;
-}
-
-// sum over the four lane groups (lanes n, n + 16, n + 32, n + 48), result in all of them
-__device__ __forceinline__ float groups_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
 // (Measured, round 5: the FFN block ALONE on this kernel's register epilogue -- residual, LayerNorm and 16-byte stores in the
 // accumulator layout instead of ffn_fused.hip's LDS-staged whole-row pass -- is SLOWER: 884 vs 811 us at M = 297 368, 83 vs 79 us at
 // M = 20 000.  The register epilogue pays here only because it is what lets the blocks chain.)
@@ -121,12 +78,11 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
 
     unsigned pf[4];
     gom_prefetch_image(p.img, (unsigned)(total_chunks * STAGE_BYTES), tid, 256, pf);        // (common.h: a one-round launch, the image cold)
-    const __amdgpu_buffer_rsrc_t rs_img =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.img, 0, total_chunks * STAGE_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, total_chunks * STAGE_BYTES);
     auto dma_stage = [&](int c, int stage) {
         const unsigned src = (unsigned)c * STAGE_BYTES + lane * 16;
         unsigned char* dst = smem + stage * STAGE_BYTES;
-        for (int f = wave; f < STAGE_FRAGS; f += 4) dma_fragment(rs_img, src + f * FRAG, dst + f * FRAG);
+        for (int f = wave; f < STAGE_FRAGS; f += 4) gom_dma_fragment(rs_img, src + f * FRAG, dst + f * FRAG);
     };
 
     // this lane's two rows (row group r: row0 + 16 r + fn), clamped for loads; tail rows are never stored
@@ -160,48 +116,29 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
     constexpr unsigned OOB = 0x7FFF0000u;
 
     // ---- one weight chunk (global index c): H^T chunk = W1c . X^T, relu / scale / bias / split, Y^T += W2[:, c] . H^T ----
-    // (ffn_fused.hip's loop body: two-deep fragment pipeline pinned with sched_group_barrier, the next stage's LDS-DMA one per
+    // (ffn_fused.hip's loop body: two-deep fragment pipeline pinned with gom_pin, the next stage's LDS-DMA one per
     //  six MFMAs)
-#define DT_DMA(i) dma_fragment(rs_img, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
-#define DT_LOAD(dst, g)                                                                                       \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                          \
-        dst[i_] = *reinterpret_cast<const half8*>(base + ((g) * 8 + i_) * FRAG);
-#define DT_PIN3()                                         \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-#define DT_PIN1()                                         \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);   \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
-#define DT_PIN0()                                         \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 24, 0);
+#define DT_DMA(i) gom_dma_fragment(rs_img, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
 #define DT_GEMM1(src, g)                                                                                      \
     _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                        \
         const int s_ = (g) * 2 + i_;                                                                          \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                      \
             _Pragma("unroll") for (int r_ = 0; r_ < 2; ++r_)                                                  \
-                acc1[h_][r_] = mfma16(src[4 * i_ + 2 * h_ + 1], xf[0][8 * r_ + s_], acc1[h_][r_]);            \
+                acc1[h_][r_] = gom_mfma16(src[4 * i_ + 2 * h_ + 1], xf[0][8 * r_ + s_], acc1[h_][r_]);        \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                      \
             _Pragma("unroll") for (int r_ = 0; r_ < 2; ++r_)                                                  \
-                acc1[h_][r_] = mfma16(src[4 * i_ + 2 * h_], xf[1][8 * r_ + s_], acc1[h_][r_]);                \
+                acc1[h_][r_] = gom_mfma16(src[4 * i_ + 2 * h_], xf[1][8 * r_ + s_], acc1[h_][r_]);            \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                      \
             _Pragma("unroll") for (int r_ = 0; r_ < 2; ++r_)                                                  \
-                acc1[h_][r_] = mfma16(src[4 * i_ + 2 * h_], xf[0][8 * r_ + s_], acc1[h_][r_]);                \
+                acc1[h_][r_] = gom_mfma16(src[4 * i_ + 2 * h_], xf[0][8 * r_ + s_], acc1[h_][r_]);            \
     }
 #define DT_GEMM2(src, g)                                                                                      \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
         const int t_ = (g) * 4 + i_;                                                                          \
         _Pragma("unroll") for (int r_ = 0; r_ < 2; ++r_) {                                                    \
-            acc2[t_][r_] = mfma16(src[2 * i_ + 1], hf[0][r_], acc2[t_][r_]);                                  \
-            acc2[t_][r_] = mfma16(src[2 * i_], hf[1][r_], acc2[t_][r_]);                                      \
-            acc2[t_][r_] = mfma16(src[2 * i_], hf[0][r_], acc2[t_][r_]);                                      \
+            acc2[t_][r_] = gom_mfma16(src[2 * i_ + 1], hf[0][r_], acc2[t_][r_]);                              \
+            acc2[t_][r_] = gom_mfma16(src[2 * i_], hf[1][r_], acc2[t_][r_]);                                  \
+            acc2[t_][r_] = gom_mfma16(src[2 * i_], hf[0][r_], acc2[t_][r_]);                                  \
         }                                                                                                     \
     }
 #define DT_CHUNK(c)                                                                                           \
@@ -209,8 +146,8 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
         const int st = (c) & 1;                                                                               \
         const bool more = (c) + 1 < total_chunks;                                                             \
         if (more && wave == 0)                                                                                \
-            dma_fragment(rs_img, (unsigned)((c) + 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG + lane * 16,  \
-                         smem + (st ^ 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG);                       \
+            gom_dma_fragment(rs_img, (unsigned)((c) + 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG + lane * 16, \
+                             smem + (st ^ 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG);                   \
         const unsigned nsrc = more ? (unsigned)((c) + 1) * STAGE_BYTES + wave * FRAG + lane * 16 : OOB;       \
         unsigned char* ndst = smem + (st ^ 1) * STAGE_BYTES + wave * FRAG;                                    \
         const unsigned char* base = smem + st * STAGE_BYTES + lane * 16;                                      \
@@ -218,12 +155,12 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
         f32x4 acc1[2][2];                                                                                     \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                      \
             _Pragma("unroll") for (int r_ = 0; r_ < 2; ++r_) acc1[h_][r_] = f32x4{0.f, 0.f, 0.f, 0.f};        \
-        DT_LOAD(fa, 0)                                                                                        \
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);                                                    \
-        DT_LOAD(fb, 1) DT_GEMM1(fa, 0) DT_DMA(0) DT_DMA(1) DT_DMA(2) DT_PIN3()                                \
-        DT_LOAD(fa, 2) DT_GEMM1(fb, 1) DT_DMA(3) DT_DMA(4) DT_DMA(5) DT_PIN3()                                \
-        DT_LOAD(fb, 3) DT_GEMM1(fa, 2) DT_DMA(6) DT_DMA(7) DT_DMA(8) DT_PIN3()                                \
-        DT_LOAD(fa, 4) DT_GEMM1(fb, 3) DT_DMA(9) DT_DMA(10) DT_DMA(11) DT_PIN3()                              \
+        GOM_READ_FRAGS(fa, base, 0)                                                                           \
+        gom_pin<8, 0, 0, 0>();                                                                                \
+        GOM_READ_FRAGS(fb, base, 1) DT_GEMM1(fa, 0) DT_DMA(0) DT_DMA(1) DT_DMA(2) gom_pin<8, 3, 8, 0>();      \
+        GOM_READ_FRAGS(fa, base, 2) DT_GEMM1(fb, 1) DT_DMA(3) DT_DMA(4) DT_DMA(5) gom_pin<8, 3, 8, 0>();      \
+        GOM_READ_FRAGS(fb, base, 3) DT_GEMM1(fa, 2) DT_DMA(6) DT_DMA(7) DT_DMA(8) gom_pin<8, 3, 8, 0>();      \
+        GOM_READ_FRAGS(fa, base, 4) DT_GEMM1(fb, 3) DT_DMA(9) DT_DMA(10) DT_DMA(11) gom_pin<8, 3, 8, 0>();    \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
         const float* aux = reinterpret_cast<const float*>(smem + st * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG);  \
         half8 hf[2][2];                                                                                       \
@@ -244,9 +181,9 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
             }                                                                                                 \
         }                                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
-        DT_LOAD(fb, 5) DT_GEMM2(fa, 0) DT_DMA(12) DT_DMA(13) DT_DMA(14) DT_PIN3()                             \
-        DT_LOAD(fa, 6) DT_GEMM2(fb, 1) DT_DMA(15) DT_PIN1()                                                   \
-        DT_LOAD(fb, 7) DT_GEMM2(fa, 2) DT_PIN0()                                                              \
+        GOM_READ_FRAGS(fb, base, 5) DT_GEMM2(fa, 0) DT_DMA(12) DT_DMA(13) DT_DMA(14) gom_pin<8, 3, 8, 0>();   \
+        GOM_READ_FRAGS(fa, base, 6) DT_GEMM2(fb, 1) DT_DMA(15) gom_pin<8, 1, 12, 12>();                       \
+        GOM_READ_FRAGS(fb, base, 7) DT_GEMM2(fa, 2) gom_pin<8, 0, 0, 24>();                                   \
         DT_GEMM2(fb, 3)                                                                                       \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                      \
         __syncthreads();                                                                                      \
@@ -260,30 +197,30 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
         const int t_ = ((g) & 3) * 4 + i_;                                                                    \
         _Pragma("unroll") for (int r_ = 0; r_ < 2; ++r_) {                                                    \
-            acc2[t_][r_] = mfma16(src[2 * i_ + 1], xf[0][8 * r_ + (ks)], acc2[t_][r_]);                       \
-            acc2[t_][r_] = mfma16(src[2 * i_], xf[1][8 * r_ + (ks)], acc2[t_][r_]);                           \
-            acc2[t_][r_] = mfma16(src[2 * i_], xf[0][8 * r_ + (ks)], acc2[t_][r_]);                           \
+            acc2[t_][r_] = gom_mfma16(src[2 * i_ + 1], xf[0][8 * r_ + (ks)], acc2[t_][r_]);                   \
+            acc2[t_][r_] = gom_mfma16(src[2 * i_], xf[1][8 * r_ + (ks)], acc2[t_][r_]);                       \
+            acc2[t_][r_] = gom_mfma16(src[2 * i_], xf[0][8 * r_ + (ks)], acc2[t_][r_]);                       \
         }                                                                                                     \
     }
 #define DT_LIN(c)                                                                                             \
     {                                                                                                         \
         const int st = (c) & 1;                                                                               \
         if (wave == 0)                                                                                        \
-            dma_fragment(rs_img, (unsigned)((c) + 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG + lane * 16,  \
-                         smem + (st ^ 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG);                       \
+            gom_dma_fragment(rs_img, (unsigned)((c) + 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG + lane * 16, \
+                             smem + (st ^ 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG);                   \
         const unsigned nsrc = (unsigned)((c) + 1) * STAGE_BYTES + wave * FRAG + lane * 16;                    \
         unsigned char* ndst = smem + (st ^ 1) * STAGE_BYTES + wave * FRAG;                                    \
         const unsigned char* base = smem + st * STAGE_BYTES + lane * 16;                                      \
         half8 fa[8], fb[8];                                                                                   \
-        DT_LOAD(fa, 0)                                                                                        \
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);                                                    \
-        DT_LOAD(fb, 1) DT_GEMM2X(fa, 0, 2 * (c)) DT_DMA(0) DT_DMA(1) DT_DMA(2) DT_PIN3()                      \
-        DT_LOAD(fa, 2) DT_GEMM2X(fb, 1, 2 * (c)) DT_DMA(3) DT_DMA(4) DT_DMA(5) DT_PIN3()                      \
-        DT_LOAD(fb, 3) DT_GEMM2X(fa, 2, 2 * (c)) DT_DMA(6) DT_DMA(7) DT_DMA(8) DT_PIN3()                      \
-        DT_LOAD(fa, 4) DT_GEMM2X(fb, 3, 2 * (c)) DT_DMA(9) DT_DMA(10) DT_DMA(11) DT_PIN3()                    \
-        DT_LOAD(fb, 5) DT_GEMM2X(fa, 4, 2 * (c) + 1) DT_DMA(12) DT_DMA(13) DT_DMA(14) DT_PIN3()               \
-        DT_LOAD(fa, 6) DT_GEMM2X(fb, 5, 2 * (c) + 1) DT_DMA(15) DT_PIN1()                                     \
-        DT_LOAD(fb, 7) DT_GEMM2X(fa, 6, 2 * (c) + 1) DT_PIN0()                                                \
+        GOM_READ_FRAGS(fa, base, 0)                                                                           \
+        gom_pin<8, 0, 0, 0>();                                                                                \
+        GOM_READ_FRAGS(fb, base, 1) DT_GEMM2X(fa, 0, 2 * (c)) DT_DMA(0) DT_DMA(1) DT_DMA(2) gom_pin<8, 3, 8, 0>(); \
+        GOM_READ_FRAGS(fa, base, 2) DT_GEMM2X(fb, 1, 2 * (c)) DT_DMA(3) DT_DMA(4) DT_DMA(5) gom_pin<8, 3, 8, 0>(); \
+        GOM_READ_FRAGS(fb, base, 3) DT_GEMM2X(fa, 2, 2 * (c)) DT_DMA(6) DT_DMA(7) DT_DMA(8) gom_pin<8, 3, 8, 0>(); \
+        GOM_READ_FRAGS(fa, base, 4) DT_GEMM2X(fb, 3, 2 * (c)) DT_DMA(9) DT_DMA(10) DT_DMA(11) gom_pin<8, 3, 8, 0>(); \
+        GOM_READ_FRAGS(fb, base, 5) DT_GEMM2X(fa, 4, 2 * (c) + 1) DT_DMA(12) DT_DMA(13) DT_DMA(14) gom_pin<8, 3, 8, 0>(); \
+        GOM_READ_FRAGS(fa, base, 6) DT_GEMM2X(fb, 5, 2 * (c) + 1) DT_DMA(15) gom_pin<8, 1, 12, 12>();         \
+        GOM_READ_FRAGS(fb, base, 7) DT_GEMM2X(fa, 6, 2 * (c) + 1) gom_pin<8, 0, 0, 24>();                     \
         DT_GEMM2X(fb, 7, 2 * (c) + 1)                                                                         \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                      \
         __syncthreads();                                                                                      \
@@ -312,7 +249,7 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
         }
         float mean[2], rstd[2];
 #pragma unroll
-        for (int r = 0; r < 2; ++r) mean[r] = groups_sum(sum[r]) * (1.f / D);
+        for (int r = 0; r < 2; ++r) mean[r] = gom_groups_sum(sum[r]) * (1.f / D);
         float sq[2] = {0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < D / 16; ++t)
@@ -324,7 +261,7 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
                     sq[r] = fmaf(acc2[t][r][e], acc2[t][r][e], sq[r]);
                 }
 #pragma unroll
-        for (int r = 0; r < 2; ++r) rstd[r] = rsqrtf(groups_sum(sq[r]) * (1.f / D) + p.p_eps);
+        for (int r = 0; r < 2; ++r) rstd[r] = rsqrtf(gom_groups_sum(sq[r]) * (1.f / D) + p.p_eps);
 #pragma unroll
         for (int s = 0; s < D / 32; ++s) {
             f32x4 o[2][2];
@@ -385,7 +322,7 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
         }
         float mean[2], rstd[2];
 #pragma unroll
-        for (int r = 0; r < 2; ++r) mean[r] = groups_sum(sum[r]) * (1.f / D);
+        for (int r = 0; r < 2; ++r) mean[r] = gom_groups_sum(sum[r]) * (1.f / D);
         float sq[2] = {0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < D / 16; ++t)
@@ -397,7 +334,7 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
                     sq[r] = fmaf(acc2[t][r][e], acc2[t][r][e], sq[r]);
                 }
 #pragma unroll
-        for (int r = 0; r < 2; ++r) rstd[r] = rsqrtf(groups_sum(sq[r]) * (1.f / D) + p.eps);
+        for (int r = 0; r < 2; ++r) rstd[r] = rsqrtf(gom_groups_sum(sq[r]) * (1.f / D) + p.eps);
 #pragma unroll
         for (int s = 0; s < D / 32; ++s) {
             f32x4 o[2][2];                                       // [half of the k-step][row group]
@@ -453,10 +390,10 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
         const float bx = p.b3[0], by = p.b3[1];
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-            const float ddx = groups_sum(dx[r]) + bx, ddy = groups_sum(dy[r]) + by;
+            const float ddx = gom_groups_sum(dx[r]) + bx, ddy = gom_groups_sum(dy[r]) + by;
             const float rx0 = p.ref[mrow[r] * 2], ry0 = p.ref[mrow[r] * 2 + 1];
-            nref[r][0] = sigmoidf(ddx + inv_sigmoid(rx0));
-            nref[r][1] = sigmoidf(ddy + inv_sigmoid(ry0));
+            nref[r][0] = gom_sigmoid(ddx + gom_inv_sigmoid(rx0));
+            nref[r][1] = gom_sigmoid(ddy + gom_inv_sigmoid(ry0));
             if (live[r] && fg == 0) *reinterpret_cast<f32x2*>(p.new_ref + (row0 + 16 * r + fn) * 2) = f32x2{nref[r][0], nref[r][1]};
         }
         asm volatile("" : "+v"(chk));
@@ -480,7 +417,7 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
                     for (int k = 0; k < 2; ++k) {                // channels (4 g + 2 k, 4 g + 2 k + 1) of the quad: one angle
                         const float a = e / dt[hh][2 * k];
                         float sn, cs;
-                        sincos_0_2pi(a, sn, cs);
+                        gom_sincos_0_2pi(a, sn, cs);
                         o[hh][2 * k] = sn;
                         o[hh][2 * k + 1] = cs;
                     }
@@ -512,10 +449,6 @@ __global__ __launch_bounds__(256, 1) void dec_tail_kernel(const TailArgs p) {
         asm volatile("" : "+v"(chk));
     }
 #undef DT_DMA
-#undef DT_LOAD
-#undef DT_PIN3
-#undef DT_PIN1
-#undef DT_PIN0
 #undef DT_GEMM1
 #undef DT_GEMM2
 #undef DT_CHUNK

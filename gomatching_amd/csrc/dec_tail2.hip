@@ -37,9 +37,6 @@
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 // Range bookkeeping on what is SPLIT (gemm_f16x3.hip contract: an operand must stay within fp16's range, and a NaN must not pass):
@@ -55,10 +52,6 @@ __device__ __forceinline__ void t2_track_nonneg(u16x2& m, const half8 plane0) {
     const u32x4 w = __builtin_bit_cast(u32x4, plane0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) m = __builtin_elementwise_max(m, __builtin_bit_cast(u16x2, w[i]));
-}
-
-__device__ __forceinline__ f32x4 mfma16(const half8 a, const half8 b, const f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
 constexpr int D = 256;                                   // model width
@@ -90,34 +83,6 @@ struct T2Args {
     int ldx, ldr, ldy, ldq, M, ffn_chunks;
     unsigned wave_stride, img_bytes;
 };
-
-__device__ __forceinline__ float inv_sigmoid(float x) {   // adet/utils/misc.py:115-119, eps 1e-5 (as elementwise.hip)
-    x = fminf(fmaxf(x, 0.f), 1.f);
-    const float x1 = fmaxf(x, 1e-5f), x2 = fmaxf(1.f - x, 1e-5f);
-    return logf(x1 / x2);
-}
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
-
-// sin and cos of an angle in [0, 2 pi] (dec_tail.hip: Cody-Waite quadrant reduction + the cephes single-precision kernels)
-__device__ __forceinline__ void sincos_0_2pi(float a, float& sn, float& cs) {
-    const float q = rintf(a * 0.63661977236758134f);
-    float r = fmaf(q, -1.57079637050628662109375f, a);
-    r = fmaf(q, 4.37113900018624283e-8f, r);
-    const float z = r * r;
-    const float ps = fmaf(fmaf(fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f) * z, r, r);
-    const float pc = fmaf(fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f) * z, z, fmaf(-0.5f, z, 1.f));
-    const int qi = (int)q;
-    const float s0 = (qi & 1) ? pc : ps, c0 = (qi & 1) ? ps : pc;
-    sn = (qi & 2) ? -s0 : s0;
-    cs = ((qi + 1) & 2) ? -c0 : c0;
-}
-
-// sum over the four lane groups (lanes n, n + 16, n + 32, n + 48), result in all of them
-__device__ __forceinline__ float groups_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 // schedule knobs (tools/dec_tail2_variants.py builds the file with other values): MFMAs between two of a step's eight weight loads
 #ifndef T2_SPREAD1
@@ -169,7 +134,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dec_tail2_kernel(const T2Args p) {
 #endif
 
     // ---- the wave's weight stream ----
-    const __amdgpu_buffer_rsrc_t rs_img = __builtin_amdgcn_make_buffer_rsrc((void*)p.img, 0, (int)p.img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, (int)p.img_bytes);
     const int voff = lane * 16;
     int so = (int)(wave * p.wave_stride);                    // byte offset of the current block / chunk in the stream (uniform)
     half8 a0[GF], a1[GF], b0[10], b1[10];
@@ -255,22 +220,22 @@ __global__ __launch_bounds__(64 * NW, 1) void dec_tail2_kernel(const T2Args p) {
     // small products first (residual x main, main x residual, main x main), twenty accumulators between dependent ones
 #define T2_MM2(A, B)                                                                                                        \
     _Pragma("unroll") for (int cg = 0; cg < CGN; ++cg)                                                                        \
-        _Pragma("unroll") for (int rg = 0; rg < NRG; ++rg) acc2[cg][rg] = mfma16(A[2 * cg + 1], B[2 * rg], acc2[cg][rg]);   \
+        _Pragma("unroll") for (int rg = 0; rg < NRG; ++rg) acc2[cg][rg] = gom_mfma16(A[2 * cg + 1], B[2 * rg], acc2[cg][rg]); \
     _Pragma("unroll") for (int cg = 0; cg < CGN; ++cg)                                                                        \
-        _Pragma("unroll") for (int rg = 0; rg < NRG; ++rg) acc2[cg][rg] = mfma16(A[2 * cg], B[2 * rg + 1], acc2[cg][rg]);   \
+        _Pragma("unroll") for (int rg = 0; rg < NRG; ++rg) acc2[cg][rg] = gom_mfma16(A[2 * cg], B[2 * rg + 1], acc2[cg][rg]); \
     _Pragma("unroll") for (int cg = 0; cg < CGN; ++cg)                                                                        \
-        _Pragma("unroll") for (int rg = 0; rg < NRG; ++rg) acc2[cg][rg] = mfma16(A[2 * cg], B[2 * rg], acc2[cg][rg]);
+        _Pragma("unroll") for (int rg = 0; rg < NRG; ++rg) acc2[cg][rg] = gom_mfma16(A[2 * cg], B[2 * rg], acc2[cg][rg]);
     // 30 MFMAs: the wave's two hidden groups (fragments A[4 half + 2 hg + plane]) against the five row groups
 #define T2_MM1(A, half, B)                                                                                                  \
     _Pragma("unroll") for (int hg = 0; hg < HGN; ++hg)                                                                        \
         _Pragma("unroll") for (int rg = 0; rg < NRG; ++rg)                                                                  \
-            acc1[hg][rg] = mfma16(A[2 * HGN * (half) + 2 * hg + 1], B[2 * rg], acc1[hg][rg]);                                     \
+            acc1[hg][rg] = gom_mfma16(A[2 * HGN * (half) + 2 * hg + 1], B[2 * rg], acc1[hg][rg]);                             \
     _Pragma("unroll") for (int hg = 0; hg < HGN; ++hg)                                                                        \
         _Pragma("unroll") for (int rg = 0; rg < NRG; ++rg)                                                                  \
-            acc1[hg][rg] = mfma16(A[2 * HGN * (half) + 2 * hg], B[2 * rg + 1], acc1[hg][rg]);                                     \
+            acc1[hg][rg] = gom_mfma16(A[2 * HGN * (half) + 2 * hg], B[2 * rg + 1], acc1[hg][rg]);                             \
     _Pragma("unroll") for (int hg = 0; hg < HGN; ++hg)                                                                        \
         _Pragma("unroll") for (int rg = 0; rg < NRG; ++rg)                                                                  \
-            acc1[hg][rg] = mfma16(A[2 * HGN * (half) + 2 * hg], B[2 * rg], acc1[hg][rg]);
+            acc1[hg][rg] = gom_mfma16(A[2 * HGN * (half) + 2 * hg], B[2 * rg], acc1[hg][rg]);
     // schedule pins: the step's ten LDS reads first, then its MFMAs with the eight weight loads spread between them
 #define T2_PIN_B() __builtin_amdgcn_sched_group_barrier(0x100, 10, 0);
 #define T2_PIN_MA(n_mfma_per_load)                                                                                          \
@@ -325,7 +290,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dec_tail2_kernel(const T2Args p) {
                 } else {              /* 16 hidden units per wave: its half of k-step wave >> 1's fragment, 8 bytes per lane */ \
                     unsigned h0, l0, h1, l1;                                                                                \
                     gom_split2_f16(v[0][0], v[0][1], h0, l0);                                                               \
-                    gom_split2_f16(v[0][2], v[0][3], h1, l1);                                                               \
+                    gom_split2_f16(v[0][2], v[0][3], h1, l1);                                                                                        \
                     pmax = __builtin_elementwise_max(pmax, __builtin_elementwise_max(__builtin_bit_cast(u16x2, h0), __builtin_bit_cast(u16x2, h1))); \
                     unsigned char* dst = smem + HP_OFF + (((wave >> 1) * NRG + rg) * 2) * FRAG + lane * 16 + 8 * (wave & 1); \
                     *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};                                                         \
@@ -367,7 +332,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dec_tail2_kernel(const T2Args p) {
             for (int cg = 0; cg < CGN; ++cg)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) s += acc2[cg][rg][e];
-            const float mw = groups_sum(s) * (1.f / WCOLS);
+            const float mw = gom_groups_sum(s) * (1.f / WCOLS);
             float q = 0.f;
 #pragma unroll
             for (int cg = 0; cg < CGN; ++cg)
@@ -376,7 +341,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dec_tail2_kernel(const T2Args p) {
                     const float d = acc2[cg][rg][e] - mw;
                     q = fmaf(d, d, q);
                 }
-            q = groups_sum(q);
+            q = gom_groups_sum(q);
             if (fg == 0) red[wave * RB + 16 * rg + fn] = make_float2(mw, q);
         }
         T2_BARRIER_LDS();
@@ -527,7 +492,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dec_tail2_kernel(const T2Args p) {
         }
 #pragma unroll
         for (int rg = 0; rg < NRG; ++rg) {
-            const float sx = groups_sum(dx[rg]), sy = groups_sum(dy[rg]);
+            const float sx = gom_groups_sum(dx[rg]), sy = gom_groups_sum(dy[rg]);
             if (fg == 0) red[wave * RB + 16 * rg + fn] = make_float2(sx, sy);
         }
         T2_BARRIER_LDS();
@@ -543,8 +508,8 @@ __global__ __launch_bounds__(64 * NW, 1) void dec_tail2_kernel(const T2Args p) {
             }
             const float ddx = tree(wx) + bx, ddy = tree(wy) + by;
             const float rx0 = p.ref[mrow[rg] * 2], ry0 = p.ref[mrow[rg] * 2 + 1];
-            nref[rg][0] = sigmoidf(ddx + inv_sigmoid(rx0));
-            nref[rg][1] = sigmoidf(ddy + inv_sigmoid(ry0));
+            nref[rg][0] = gom_sigmoid(ddx + gom_inv_sigmoid(rx0));
+            nref[rg][1] = gom_sigmoid(ddy + gom_inv_sigmoid(ry0));
             if (live[rg] && fg == 0 && wave == 0) *reinterpret_cast<f32x2*>(p.new_ref + mrow[rg] * 2) = f32x2{nref[rg][0], nref[rg][1]};
         }
         asm volatile("" : "+v"(chk));
@@ -572,7 +537,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dec_tail2_kernel(const T2Args p) {
 #pragma unroll
                     for (int k = 0; k < 2; ++k) {            // channels (4 g + 2 k, 4 g + 2 k + 1) of the quad: one angle
                         float sn, cs;
-                        sincos_0_2pi(e * rdt[k], sn, cs);
+                        gom_sincos_0_2pi(e * rdt[k], sn, cs);
                         o[cg][rg][2 * k] = sn;
                         o[cg][rg][2 * k + 1] = cs;
                     }

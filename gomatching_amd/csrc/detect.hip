@@ -10,8 +10,6 @@ namespace {
 
 constexpr int MAXQ = 1024;
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 // one wave per row: index of the first maximum
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, int ld, int V, long rows,
                                                           int* __restrict__ out) {
@@ -52,11 +50,11 @@ __global__ __launch_bounds__(256) void detect_post_kernel(
         const long base = ((long)b * nq + q) * P;
         float sum = 0.f;
         for (int p = 0; p < P; ++p) sum += cls[(base + p) * ld_cls];
-        float sc = sigmoidf_(sum / (float)P);
+        float sc = gom_sigmoid(sum / (float)P);
         if (recls) {
             float rs = 0.f;
             for (int p = 0; p < P; ++p) rs += recls[(base + p) * ld_recls];
-            const float re = sigmoidf_(rs / (float)P);
+            const float re = gom_sigmoid(rs / (float)P);
             sc = (sc > re) ? sc : re;
         }
         s_score[q] = sc;

@@ -82,13 +82,6 @@ __global__ __launch_bounds__(256) void point_pos_kernel(const float* __restrict_
     out[i] = (j & 1) ? cosf(a) : sinf(a);
 }
 
-__device__ __forceinline__ float inv_sigmoid(float x) {   // adet/utils/misc.py:115-119, eps 1e-5
-    x = fminf(fmaxf(x, 0.f), 1.f);
-    const float x1 = fmaxf(x, 1e-5f), x2 = fmaxf(1.f - x, 1e-5f);
-    return logf(x1 / x2);
-}
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
-
 // out[q, c] = sigmoid(delta[q, c] + inverse_sigmoid(ref[q, c % 2]))   (C = 2: point refinement,
 // deformable_transformer.py:484-488 and detection_transformer_wobackbone.py:211-227; C = 4: boundary)
 __global__ __launch_bounds__(256) void ref_sigmoid_kernel(const float* __restrict__ delta, int ld_delta,
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(256) void ref_sigmoid_kernel(const float* __restric
     if (i >= Q * C) return;
     const long q = i / C;
     const int c = (int)(i % C);
-    out[i] = sigmoidf(delta[q * ld_delta + c] + inv_sigmoid(ref[q * 2 + (c & 1)]));
+    out[i] = gom_sigmoid(delta[q * ld_delta + c] + gom_inv_sigmoid(ref[q * 2 + (c & 1)]));
 }
 
 // The tail of a decoder layer's reference refinement and the head of the next layer's query position as ONE launch
@@ -125,7 +118,7 @@ __global__ __launch_bounds__(256) void ref_update_kernel(const float* __restrict
         }
         dx = wave_sum(dx) + bx;
         dy = wave_sum(dy) + by;
-        const float rx = sigmoidf(dx + inv_sigmoid(ref[q * 2])), ry = sigmoidf(dy + inv_sigmoid(ref[q * 2 + 1]));
+        const float rx = gom_sigmoid(dx + gom_inv_sigmoid(ref[q * 2])), ry = gom_sigmoid(dy + gom_inv_sigmoid(ref[q * 2 + 1]));
         if (lane == 0) {
             new_ref[q * 2] = rx;
             new_ref[q * 2 + 1] = ry;
@@ -190,7 +183,7 @@ __global__ __launch_bounds__(256) void bezier_refs_kernel(const float* __restric
     float ox = 0.f, oy = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float cx = sigmoidf(cr[2 * k] + px), cy = sigmoidf(cr[2 * k + 1] + py);
+        const float cx = gom_sigmoid(cr[2 * k] + px), cy = gom_sigmoid(cr[2 * k + 1] + py);
         ox = fmaf(bern[p * 4 + k], cx, ox);
         oy = fmaf(bern[p * 4 + k], cy, oy);
     }

@@ -35,15 +35,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma16(const half8 a, const half8 b, const f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 constexpr int D = 256;                                   // model width (fixed: every shipped config)
 constexpr int CH = 32;                                   // hidden units per weight chunk
 constexpr int FRAG = 1024;                               // bytes of one MFMA operand fragment (64 lanes x 8 fp16)
@@ -68,43 +59,6 @@ struct FfnArgs {
     long row_base;                                           // first row of this launch's tiles (the half-height tail launch)
     int relu_out;                                            // PLAIN form: ReLU behind the second layer
 };
-
-// sum over the 16 lanes of a DPP row, result in every lane: quad swaps (xor 1, xor 2), then the two mirrors
-__device__ __forceinline__ float row16_sum(float v) {
-    auto dpp = [](float x, int ctrl_tag) {
-        const int xi = __builtin_bit_cast(int, x);
-        int r;
-        if (ctrl_tag == 0) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, true);        // quad_perm [1,0,3,2]
-        else if (ctrl_tag == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
-        else if (ctrl_tag == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x141, 0xF, 0xF, true);  // row_half_mirror
-        else r = __builtin_amdgcn_update_dpp(0, xi, 0x140, 0xF, 0xF, true);                     // row_mirror
-        return __builtin_bit_cast(float, r);
-    };
-    v += dpp(v, 0);
-    v += dpp(v, 1);
-    v += dpp(v, 2);
-    v += dpp(v, 3);
-    return v;
-}
-
-__device__ __forceinline__ void split2(float x, float y, unsigned int& q0, unsigned int& q1) { gom_split2_f16(x, y, q0, q1); }
-
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, half8& p0, half8& p1) {
-    unsigned int l0, l1, l2, l3, h0, h1, h2, h3;
-    split2(a[0], a[1], l0, h0);
-    split2(a[2], a[3], l1, h1);
-    split2(b[0], b[1], l2, h2);
-    split2(b[2], b[3], l3, h3);
-    p0 = __builtin_bit_cast(half8, (u32x4{l0, l1, l2, l3}));
-    p1 = __builtin_bit_cast(half8, (u32x4{h0, h1, h2, h3}));
-}
-
-// One KB of the weight stream straight into LDS (buffer_load_dwordx4 ... lds).  The MUBUF form, not global_load_lds: hipcc
-// books a FLAT-segment LDS-DMA as "may return out of order" and from then on turns every counted s_waitcnt lgkmcnt(N) of the
-// loop into lgkmcnt(0), which serialises the fragment prefetch below (measured: no gain over three launches).
-__device__ __forceinline__ void dma_fragment(__amdgpu_buffer_rsrc_t rs, unsigned byte_offset, unsigned char* lds_frag) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_frag, 16, (int)byte_offset, 0, 0, 0);
-}
 
 // PLAIN = true: a two-layer perceptron  Y = [relu](relu(X W1^T + b1) W2^T + b2)  -- no residual, no LayerNorm -- on the same
 // pipeline: the decoder's ref_point_head (deformable_transformer.py:470-473, adet/modeling/model/utils.py MLP) and the first two
@@ -135,12 +89,11 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(const FfnArgs p) {
     if (gridDim.x <= 256) gom_prefetch_image(p.img, (unsigned)(p.chunks * STAGE_BYTES), tid, 256, pf);
     if (p.stagger > 0 && blockIdx.x < 256)
         for (int i = 0; i < (int)((blockIdx.x >> 3) & 7) * p.stagger; ++i) __builtin_amdgcn_s_sleep(16);
-    const __amdgpu_buffer_rsrc_t rs_img =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.img, 0, p.chunks * STAGE_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, p.chunks * STAGE_BYTES);
     auto dma_stage = [&](int c, int stage) {                 // 65 fragments, dealt to the four waves
         const unsigned src = (unsigned)c * STAGE_BYTES + lane * 16;
         unsigned char* dst = smem + stage * STAGE_BYTES;
-        for (int f = wave; f < STAGE_FRAGS; f += 4) dma_fragment(rs_img, src + f * FRAG, dst + f * FRAG);
+        for (int f = wave; f < STAGE_FRAGS; f += 4) gom_dma_fragment(rs_img, src + f * FRAG, dst + f * FRAG);
     };
 
     // ---- this wave's 32 rows of X as B-operand fragments: lane (n, kg) holds X[row 16 R + n][32 s + 8 kg .. + 7] in xf[.][8 R + s],
@@ -174,42 +127,22 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(const FfnArgs p) {
     for (int c = 0; c < p.chunks; ++c) {
         const int st = c & 1;
         // The next stage's 65 fragments: fragment 64 (scale | bias) by wave 0 here, fragments wave, wave + 4, ..., wave + 60 --
-        // sixteen per wave -- ONE PER SIX MFMAs inside the products below.  An LDS-DMA instruction costs its wave 100-140
-        // cycles of issue (s_memtime stamps, gemm_k256.hip); issued in a block in front of the MFMAs that was ~2200 cycles per
-        // chunk with the matrix pipe idle (one wave per SIMD), beside running MFMAs it is hidden.
+        // sixteen per wave -- ONE PER SIX MFMAs inside the products below (common.h gom_dma_fragment: the issue cost); issued in
+        // a block in front of the MFMAs that was ~2200 cycles per chunk with the matrix pipe idle (one wave per SIMD).
         const bool more = c + 1 < p.chunks;
         if (more && wave == 0)
-            dma_fragment(rs_img, (unsigned)(c + 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG + lane * 16,
-                         smem + (st ^ 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG);
+            gom_dma_fragment(rs_img, (unsigned)(c + 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG + lane * 16,
+                             smem + (st ^ 1) * STAGE_BYTES + (W1_FRAGS + W2_FRAGS) * FRAG);
         const unsigned nsrc = more ? (unsigned)(c + 1) * STAGE_BYTES + wave * FRAG + lane * 16 : OOB;
         unsigned char* ndst = smem + (st ^ 1) * STAGE_BYTES + wave * FRAG;
-#define FFN_DMA(i) dma_fragment(rs_img, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
+#define FFN_DMA(i) gom_dma_fragment(rs_img, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
         const unsigned char* base = smem + st * STAGE_BYTES + lane * 16;
 
         // The 64 weight fragments of the chunk are consumed in eight groups of eight; with ONE wave per SIMD nothing else hides
         // the LDS latency, so group g + 1 is read into the other register set BEFORE the 24 MFMAs of group g are issued
-        // (explicit two-deep software pipeline; the sched_group_barrier pairs pin that order -- left alone the compiler issues
+        // (explicit two-deep software pipeline; the gom_pin groups pin that order -- left alone the compiler issues
         // every fragment read right in front of its MFMAs: reads, wait, MFMAs, ... = 28 % MFMA busy).
         half8 fa[8], fb[8];
-#define FFN_LOAD(dst, g)                                                                                      \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                          \
-        dst[i_] = *reinterpret_cast<const half8*>(base + ((g) * 8 + i_) * FRAG);
-#define FFN_PIN3()                                        \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-#define FFN_PIN1()                                        \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);   \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
-#define FFN_PIN0()                                        \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 24, 0);
         // ---- H^T chunk = W1c . X^T : 2 hidden groups x 2 row groups of 16 x 16, 8 k-steps x 3 plane products (smallest first);
         //      fragment 4 i + 2 Hh + p of a group = plane p of hidden group Hh at the group's k-step i ----
         f32x4 acc1[2][RG];
@@ -222,20 +155,20 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(const FfnArgs p) {
         const int s_ = (g) * 2 + i_;                                                                          \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                      \
             _Pragma("unroll") for (int r_ = 0; r_ < RG; ++r_)                                                 \
-                acc1[h_][r_] = mfma16(src[4 * i_ + 2 * h_ + 1], xf[0][8 * r_ + s_], acc1[h_][r_]);            \
+                acc1[h_][r_] = gom_mfma16(src[4 * i_ + 2 * h_ + 1], xf[0][8 * r_ + s_], acc1[h_][r_]);        \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                      \
             _Pragma("unroll") for (int r_ = 0; r_ < RG; ++r_)                                                 \
-                acc1[h_][r_] = mfma16(src[4 * i_ + 2 * h_], xf[1][8 * r_ + s_], acc1[h_][r_]);                \
+                acc1[h_][r_] = gom_mfma16(src[4 * i_ + 2 * h_], xf[1][8 * r_ + s_], acc1[h_][r_]);            \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                      \
             _Pragma("unroll") for (int r_ = 0; r_ < RG; ++r_)                                                 \
-                acc1[h_][r_] = mfma16(src[4 * i_ + 2 * h_], xf[0][8 * r_ + s_], acc1[h_][r_]);                \
+                acc1[h_][r_] = gom_mfma16(src[4 * i_ + 2 * h_], xf[0][8 * r_ + s_], acc1[h_][r_]);            \
     }
-        FFN_LOAD(fa, 0)
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);       // group 0's reads come first, then (reads, MFMAs) pairs
-        FFN_LOAD(fb, 1) FFN_GEMM1(fa, 0) FFN_DMA(0) FFN_DMA(1) FFN_DMA(2) FFN_PIN3()
-        FFN_LOAD(fa, 2) FFN_GEMM1(fb, 1) FFN_DMA(3) FFN_DMA(4) FFN_DMA(5) FFN_PIN3()
-        FFN_LOAD(fb, 3) FFN_GEMM1(fa, 2) FFN_DMA(6) FFN_DMA(7) FFN_DMA(8) FFN_PIN3()
-        FFN_LOAD(fa, 4) FFN_GEMM1(fb, 3) FFN_DMA(9) FFN_DMA(10) FFN_DMA(11) FFN_PIN3()   // fa <- first group of W2 fragments
+        GOM_READ_FRAGS(fa, base, 0)
+        gom_pin<8, 0, 0, 0>();       // group 0's reads come first, then (reads, MFMAs) pairs
+        GOM_READ_FRAGS(fb, base, 1) FFN_GEMM1(fa, 0) FFN_DMA(0) FFN_DMA(1) FFN_DMA(2) gom_pin<8, 3, 8, 0>();
+        GOM_READ_FRAGS(fa, base, 2) FFN_GEMM1(fb, 1) FFN_DMA(3) FFN_DMA(4) FFN_DMA(5) gom_pin<8, 3, 8, 0>();
+        GOM_READ_FRAGS(fb, base, 3) FFN_GEMM1(fa, 2) FFN_DMA(6) FFN_DMA(7) FFN_DMA(8) gom_pin<8, 3, 8, 0>();
+        GOM_READ_FRAGS(fa, base, 4) FFN_GEMM1(fb, 3) FFN_DMA(9) FFN_DMA(10) FFN_DMA(11) gom_pin<8, 3, 8, 0>();   // fa <- first group of W2 fragments
         __builtin_amdgcn_sched_barrier(0);
         // ---- relu(acc / row scale + bias), split into two fp16 planes: the lane's 2 x 4 values of a row group are its eight
         //      k-slots of the second product's B fragment ----
@@ -258,7 +191,7 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(const FfnArgs p) {
                         v[h_][e] = fmaxf(fmaf(acc1[h_][r_][e], sc[h_][e], bi[h_][e]), 0.f);
                         hmax = fmaxf(hmax, v[h_][e]);          // (never NaN after the max with 0) checked once, after the loop
                     }
-                split8(v[0], v[1], hf[0][r_], hf[1][r_]);
+                gom_split8_f16(v[0], v[1], hf[0][r_], hf[1][r_]);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -268,20 +201,16 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(const FfnArgs p) {
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
         const int t_ = (g) * 4 + i_;                                                                          \
         _Pragma("unroll") for (int r_ = 0; r_ < RG; ++r_) {                                                   \
-            acc2[t_][r_] = mfma16(src[2 * i_ + 1], hf[0][r_], acc2[t_][r_]);                                  \
-            acc2[t_][r_] = mfma16(src[2 * i_], hf[1][r_], acc2[t_][r_]);                                      \
-            acc2[t_][r_] = mfma16(src[2 * i_], hf[0][r_], acc2[t_][r_]);                                      \
+            acc2[t_][r_] = gom_mfma16(src[2 * i_ + 1], hf[0][r_], acc2[t_][r_]);                              \
+            acc2[t_][r_] = gom_mfma16(src[2 * i_], hf[1][r_], acc2[t_][r_]);                                  \
+            acc2[t_][r_] = gom_mfma16(src[2 * i_], hf[0][r_], acc2[t_][r_]);                                  \
         }                                                                                                     \
     }
-        FFN_LOAD(fb, 5) FFN_GEMM2(fa, 0) FFN_DMA(12) FFN_DMA(13) FFN_DMA(14) FFN_PIN3()
-        FFN_LOAD(fa, 6) FFN_GEMM2(fb, 1) FFN_DMA(15) FFN_PIN1()
-        FFN_LOAD(fb, 7) FFN_GEMM2(fa, 2) FFN_PIN0()
+        GOM_READ_FRAGS(fb, base, 5) FFN_GEMM2(fa, 0) FFN_DMA(12) FFN_DMA(13) FFN_DMA(14) gom_pin<8, 3, 8, 0>();
+        GOM_READ_FRAGS(fa, base, 6) FFN_GEMM2(fb, 1) FFN_DMA(15) gom_pin<8, 1, 12, 12>();
+        GOM_READ_FRAGS(fb, base, 7) FFN_GEMM2(fa, 2) gom_pin<8, 0, 0, 24>();
         FFN_GEMM2(fb, 3)
 #undef FFN_DMA
-#undef FFN_LOAD
-#undef FFN_PIN3
-#undef FFN_PIN1
-#undef FFN_PIN0
 #undef FFN_GEMM1
 #undef FFN_GEMM2
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's share of the next stage has landed
@@ -368,14 +297,14 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(const FfnArgs p) {
                 v[gi][k] = v[gi][k] * s2[k] + b2[k] + xres[g][k];
                 sum += (v[gi][k][0] + v[gi][k][1]) + (v[gi][k][2] + v[gi][k][3]);
             }
-            const float mean = row16_sum(sum) * (1.f / D);
+            const float mean = gom_row16_sum(sum) * (1.f / D);
             float q = 0.f;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 v[gi][k] = v[gi][k] - mean;
                 q += (v[gi][k][0] * v[gi][k][0] + v[gi][k][1] * v[gi][k][1]) + (v[gi][k][2] * v[gi][k][2] + v[gi][k][3] * v[gi][k][3]);
             }
-            const float rstd = rsqrtf(row16_sum(q) * (1.f / D) + p.eps);
+            const float rstd = rsqrtf(gom_row16_sum(q) * (1.f / D) + p.eps);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const f32x4 o = v[gi][k] * rstd * ga[k] + be[k];

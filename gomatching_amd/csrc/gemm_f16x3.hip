@@ -23,11 +23,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BK = 32;
 constexpr int ROW_BYTES = 80;                    // 32 bf16 + 16 B pad: 5 sixteen-byte slots (odd) per row
 
@@ -52,19 +47,6 @@ struct Args {
     int kt_per_split;
     float* partial;                              // [splits][M][N] or nullptr
 };
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// two floats -> packed fp16 pair (v_cvt_pk_f16_f32, round to nearest even) and the exact residuals
-__device__ __forceinline__ void split2(float x, float y, unsigned int& q0, unsigned int& q1) { gom_split2_f16(x, y, q0, q1); }
-// split 4 floats into 2 planes of 4 fp16 (8 bytes each)
-__device__ __forceinline__ void split4(const f32x4 v, u32x2& p0, u32x2& p1) {
-    unsigned int a0, a1, b0, b1;
-    split2(v[0], v[1], a0, a1);
-    split2(v[2], v[3], b0, b1);
-    p0 = u32x2{a0, b0};
-    p1 = u32x2{a1, b1};
-}
 
 template <int BM, int BN, int KH, int KW, int OCC>
 __global__ __launch_bounds__(256, OCC) void gemm_f16x3_kernel(const Args p) {
@@ -95,8 +77,8 @@ __global__ __launch_bounds__(256, OCC) void gemm_f16x3_kernel(const Args p) {
 
     // ---- buffer descriptors: 32-bit byte offsets, out-of-range lanes read zeros (no select instructions) ----
     constexpr unsigned RANGE = 0x80000000u, INVALID = 0xC0000000u;       // offsets stay OOB after adding < 1 GiB
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)RANGE, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wp, 0, (int)RANGE, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = gom_buffer_rsrc(p.A, (int)RANGE);
+    const __amdgpu_buffer_rsrc_t rsW = gom_buffer_rsrc(p.Wp, (int)RANGE);
 
     // A: unit u = tid + i*256 -> row u>>3, k-quad u&7.  a_off = byte offset of (row, k = kq*4) or of the tap origin
     const int kq = tid & 7;
@@ -177,7 +159,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_f16x3_kernel(const Args p) {
         for (int i = 0; i < A_UNITS; ++i) {
             const int row = (tid >> 3) + i * 32;
             u32x2 p0, p1;
-            split4(a_reg[i], p0, p1);
+            gom_split4_f16(a_reg[i], p0, p1);
             unsigned char* d = As + row * ROW_BYTES + kq * 8;
             *reinterpret_cast<u32x2*>(d) = p0;
             *reinterpret_cast<u32x2*>(d + A_PLANE) = p1;

@@ -19,11 +19,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int KD = 256;                                  // K (fixed: d_model of every shipped config)
 constexpr int CW = 32;                                   // output columns per chunk
 constexpr int FRAG = 1024;                               // bytes of one MFMA operand fragment
@@ -64,27 +59,10 @@ __device__ __forceinline__ long tile_of(const RowArgs& p, unsigned i) {
     return t < p.tiles ? t : -1;
 }
 
-__device__ __forceinline__ void split2(float x, float y, unsigned int& q0, unsigned int& q1) { gom_split2_f16(x, y, q0, q1); }
-
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, half8& p0, half8& p1) {
-    unsigned int l0, l1, l2, l3, h0, h1, h2, h3;
-    split2(a[0], a[1], l0, h0);
-    split2(a[2], a[3], l1, h1);
-    split2(b[0], b[1], l2, h2);
-    split2(b[2], b[3], l3, h3);
-    p0 = __builtin_bit_cast(half8, (u32x4{l0, l1, l2, l3}));
-    p1 = __builtin_bit_cast(half8, (u32x4{h0, h1, h2, h3}));
-}
-
 template <bool ROWS_FIRST>
 __device__ __forceinline__ f32x16 mfma_either(const half8 w, const half8 x, const f32x16 acc) {
     if constexpr (ROWS_FIRST) return __builtin_amdgcn_mfma_f32_32x32x16_f16(x, w, acc, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_f16(w, x, acc, 0, 0, 0);
-}
-
-// MUBUF LDS-DMA (not global_load_lds: see ffn_fused.hip -- the FLAT form turns every counted lgkmcnt wait into lgkmcnt(0))
-__device__ __forceinline__ void dma_fragment(__amdgpu_buffer_rsrc_t rs, unsigned byte_offset, unsigned char* lds_frag) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_frag, 16, (int)byte_offset, 0, 0, 0);
 }
 
 // LINES = false: C^T chunk = Wc . A^T, the lane is the ROW (four 16-byte stores per chunk, each 32-byte pieces of 32 lines);
@@ -106,12 +84,11 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
     if (tile < 0) return;                                    // padding of the interleaved id space (whole workgroup)
     long row = tile * BM + wave * 32 + fr;
     if (row > p.M - 1) row = p.M - 1;                        // tail rows recompute AND re-store the last row (same bits)
-    const __amdgpu_buffer_rsrc_t rs_img =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.img, 0, p.chunks * CHUNK_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, p.chunks * CHUNK_BYTES);
     auto dma_stage = [&](int c, int stage) {                 // 33 fragments, dealt to the four waves
         const unsigned src = (unsigned)c * CHUNK_BYTES + lane * 16;
         unsigned char* dst = smem + stage * CHUNK_BYTES;
-        for (int f = wave; f < CHUNK_FRAGS; f += 4) dma_fragment(rs_img, src + f * FRAG, dst + f * FRAG);
+        for (int f = wave; f < CHUNK_FRAGS; f += 4) gom_dma_fragment(rs_img, src + f * FRAG, dst + f * FRAG);
     };
     constexpr unsigned OOB = 0x7FFF0000u;                    // beyond num_records: the DMA writes zeros (into an unused stage)
 
@@ -145,31 +122,12 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
     __syncthreads();
 
     // one chunk: 64 weight fragments in eight-fragment groups, group g + 1 read while the twelve MFMAs of group g issue
-    // (explicit two-deep pipeline pinned by sched_group_barrier, as in ffn_fused.hip)
+    // (explicit two-deep pipeline pinned by gom_pin, as in ffn_fused.hip)
     // `nsrc` / `ndst`: this wave's eight weight fragments of the NEXT stage (fragments wave, wave + 4, ...), issued one per
-    // four MFMAs: an LDS-DMA instruction costs its wave 100-140 cycles of issue (measured with s_memtime stamps: 1250 of the
-    // 4200 cycles of a chunk when all nine were issued in front of the MFMAs); beside running MFMAs that time is hidden.
+    // four MFMAs (the issue cost of LDS-DMA: common.h gom_dma_fragment).
     auto chunk_product = [&](const unsigned char* base, f32x16& acc, unsigned nsrc, unsigned char* ndst) {
         half8 fa[8], fb[8];
-#define K256_LOAD(dst, g)                                                                                     \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                          \
-        dst[i_] = *reinterpret_cast<const half8*>(base + ((g) * 8 + i_) * FRAG);
-#define K256_DMA(i) dma_fragment(rs_img, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
-#define K256_PIN3()                                       \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-#define K256_PIN2()                                       \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+#define K256_DMA(i) gom_dma_fragment(rs_img, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
         // C^T chunk [32 columns x 32 rows] = Wc . A^T: A operand = weight fragment (LDS), B operand = the rows in registers
 #define K256_MFMA(src, g)                                                                                     \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
@@ -180,16 +138,13 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
     }
 #pragma unroll
         for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-        K256_LOAD(fa, 0)
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-        K256_LOAD(fb, 1) K256_MFMA(fa, 0) K256_DMA(0) K256_DMA(1) K256_DMA(2) K256_PIN3()
-        K256_LOAD(fa, 2) K256_MFMA(fb, 1) K256_DMA(3) K256_DMA(4) K256_DMA(5) K256_PIN3()
-        K256_LOAD(fb, 3) K256_MFMA(fa, 2) K256_DMA(6) K256_DMA(7) K256_PIN2()
+        GOM_READ_FRAGS(fa, base, 0)
+        gom_pin<8, 0, 0, 0>();
+        GOM_READ_FRAGS(fb, base, 1) K256_MFMA(fa, 0) K256_DMA(0) K256_DMA(1) K256_DMA(2) gom_pin<8, 3, 4, 0>();
+        GOM_READ_FRAGS(fa, base, 2) K256_MFMA(fb, 1) K256_DMA(3) K256_DMA(4) K256_DMA(5) gom_pin<8, 3, 4, 0>();
+        GOM_READ_FRAGS(fb, base, 3) K256_MFMA(fa, 2) K256_DMA(6) K256_DMA(7) gom_pin<8, 2, 4, 4>();
         K256_MFMA(fb, 3)
-#undef K256_LOAD
 #undef K256_DMA
-#undef K256_PIN3
-#undef K256_PIN2
 #undef K256_MFMA
     };
 
@@ -204,12 +159,10 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
         const long tile0 = tile * BM;
         const unsigned rows_here = (unsigned)min((long)BM, (long)p.M - tile0);
         const unsigned c_row = (unsigned)p.ldc * 4u, r_row = (unsigned)p.ldr * 4u;
-        const __amdgpu_buffer_rsrc_t rs_c =
-            __builtin_amdgcn_make_buffer_rsrc((void*)(p.C + (size_t)tile0 * p.ldc), 0, (int)(rows_here * c_row), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_c = gom_buffer_rsrc(p.C + (size_t)tile0 * p.ldc, (int)(rows_here * c_row));
         const bool periodic = p.r_period > 0;
-        const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(!p.R ? p.C : periodic ? p.R : p.R + (size_t)tile0 * p.ldr), 0,
-            !p.R ? 0 : (int)((periodic ? (unsigned)p.r_period : rows_here) * r_row), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_r = gom_buffer_rsrc(!p.R ? p.C : periodic ? p.R : p.R + (size_t)tile0 * p.ldr,
+                                                              !p.R ? 0 : (int)((periodic ? (unsigned)p.r_period : rows_here) * r_row));
         const unsigned c_lane = (unsigned)(wave * 32 + 4 * fh) * c_row;
         const unsigned r_first = periodic ? (unsigned)((tile0 + wave * 32 + 4 * fh) % p.r_period) : (unsigned)(wave * 32 + 4 * fh);
         auto r_offset = [&](int k) {                         // byte offset of residual row (first + k), wrapped once (period >= 32)
@@ -221,8 +174,8 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
             const int st = (c - c0) & 1;
             const bool more = c + 1 < c1;
             if (more && wave == 0)                           // the (scale | bias) fragment of the next stage
-                dma_fragment(rs_img, (unsigned)(c + 1) * CHUNK_BYTES + W_FRAGS * FRAG + lane * 16,
-                             smem + (st ^ 1) * CHUNK_BYTES + W_FRAGS * FRAG);
+                gom_dma_fragment(rs_img, (unsigned)(c + 1) * CHUNK_BYTES + W_FRAGS * FRAG + lane * 16,
+                                 smem + (st ^ 1) * CHUNK_BYTES + W_FRAGS * FRAG);
             const unsigned nsrc = more ? (unsigned)(c + 1) * CHUNK_BYTES + wave * FRAG + lane * 16 : OOB;
             unsigned char* ndst = smem + (st ^ 1) * CHUNK_BYTES + wave * FRAG;
             const bool use_r = p.R && c < p.r_chunks;

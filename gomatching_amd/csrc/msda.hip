@@ -324,8 +324,7 @@ __global__ __launch_bounds__(256) void msda_fused_lanes_kernel(const float* __re
     }
 
     // ---- gather part: every lane, all 16 samples, 4 channels ----
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(value + (size_t)b * v_bs), 0, 0x7FFFFFFF, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = gom_buffer_rsrc(value + (size_t)b * v_bs, 0x7FFFFFFF);
     const unsigned mine = (unsigned)k * 16u;                 // this lane's 4 channels inside the head's 128-byte slice
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -439,8 +438,7 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
     const float Hf = (float)H, Wf = (float)W;
     const float rW = 1.f / Wf, rH = 1.f / Hf;
 
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(value + (size_t)b * v_bs), 0, 0x7FFFFFFF, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = gom_buffer_rsrc(value + (size_t)b * v_bs, 0x7FFFFFFF);
     const unsigned mine = (unsigned)k * 16u;                 // this lane's 4 channels inside a 128-byte line
     const unsigned head = (unsigned)(m * CH) * 4u;
 

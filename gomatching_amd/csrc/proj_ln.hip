@@ -14,11 +14,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int D = 256;                                   // model width = K = N (fixed: every shipped config)
 constexpr int FRAG = 1024;                               // bytes of one MFMA operand fragment
 
@@ -39,39 +34,6 @@ struct ProjArgs {
     float dot_b;
 };
 
-__device__ __forceinline__ float row16_sum(float v) {        // sum over the 16 lanes of a DPP row, result in every lane
-    auto dpp = [](float x, int ctrl_tag) {
-        const int xi = __builtin_bit_cast(int, x);
-        int r;
-        if (ctrl_tag == 0) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, true);        // quad_perm [1,0,3,2]
-        else if (ctrl_tag == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
-        else if (ctrl_tag == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x141, 0xF, 0xF, true);  // row_half_mirror
-        else r = __builtin_amdgcn_update_dpp(0, xi, 0x140, 0xF, 0xF, true);                     // row_mirror
-        return __builtin_bit_cast(float, r);
-    };
-    v += dpp(v, 0);
-    v += dpp(v, 1);
-    v += dpp(v, 2);
-    v += dpp(v, 3);
-    return v;
-}
-
-__device__ __forceinline__ void split2(float x, float y, unsigned int& q0, unsigned int& q1) { gom_split2_f16(x, y, q0, q1); }
-
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, half8& p0, half8& p1) {
-    unsigned int l0, l1, l2, l3, h0, h1, h2, h3;
-    split2(a[0], a[1], l0, h0);
-    split2(a[2], a[3], l1, h1);
-    split2(b[0], b[1], l2, h2);
-    split2(b[2], b[3], l3, h3);
-    p0 = __builtin_bit_cast(half8, (u32x4{l0, l1, l2, l3}));
-    p1 = __builtin_bit_cast(half8, (u32x4{h0, h1, h2, h3}));
-}
-
-__device__ __forceinline__ void dma_fragment(__amdgpu_buffer_rsrc_t rs, unsigned byte_offset, unsigned char* lds_frag) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_frag, 16, (int)byte_offset, 0, 0, 0);
-}
-
 // FORM 0: + residual, rows stored (the attention blocks); 1: no residual, rows stored; 2: no residual, only <row, dot_w> + dot_b
 // stored.  Compile-time: as run-time branches the residual loads of form 0 were no longer batched (268 -> 405 us at 297k rows).
 // ---- round 5: the TWO-WORKGROUPS-PER-CU form ----
@@ -91,10 +53,6 @@ constexpr int V2_STAGES = D / 32;                        // 8
 constexpr int V2_LDS_BYTES = 2 * V2_STAGE_BYTES;         // = 64 rows x 256 fp32: the staging area fits the ring exactly
 constexpr long V2_IMAGE_BYTES = (long)V2_STAGES * V2_STAGE_BYTES;
 
-__device__ __forceinline__ f32x4 mfma16(const half8 a, const half8 b, const f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 template <int FORM>
 __global__ __launch_bounds__(256, 2) void proj_ln2_kernel(const ProjArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -104,7 +62,7 @@ __global__ __launch_bounds__(256, 2) void proj_ln2_kernel(const ProjArgs p) {
     const long tile0 = (long)blockIdx.x * V2_BM;
     const long row0 = tile0 + wave * 16;
     const unsigned char* img = p.img;
-    const __amdgpu_buffer_rsrc_t rs_img = __builtin_amdgcn_make_buffer_rsrc((void*)img, 0, (int)V2_IMAGE_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(img, (int)V2_IMAGE_BYTES);
 
     // ---- this wave's 16 rows as B-operand fragments: lane (n, kg) holds X[row n][32 s + 8 kg .. + 7], two planes.  Whole-line loads
     // (a wave-instruction = 128 floats of 2 rows) + a layout change in a wave-private 8 KB of the ring's second slot ----
@@ -125,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void proj_ln2_kernel(const ProjArgs p) {
             }
             if (part == 0) {
                 __builtin_amdgcn_sched_barrier(0);
-                for (int f = wave; f < V2_STAGE_FRAGS; f += 4) dma_fragment(rs_img, f * FRAG + lane * 16, smem + f * FRAG);
+                for (int f = wave; f < V2_STAGE_FRAGS; f += 4) gom_dma_fragment(rs_img, f * FRAG + lane * 16, smem + f * FRAG);
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
@@ -141,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void proj_ln2_kernel(const ProjArgs p) {
                 const f32x4 b = *reinterpret_cast<const f32x4*>(scratch + fn * 128 + (((p0 + 1) ^ (fn & 31)) << 2));
 #pragma unroll
                 for (int e = 0; e < 4; ++e) xmax = fmaxf(xmax, fmaxf(fabsf(a[e]), fabsf(b[e])));
-                split8(a, b, xf[0][4 * part + s_], xf[1][4 * part + s_]);
+                gom_split8_f16(a, b, xf[0][4 * part + s_], xf[1][4 * part + s_]);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -163,37 +121,23 @@ __global__ __launch_bounds__(256, 2) void proj_ln2_kernel(const ProjArgs p) {
         unsigned char* ndst = smem + (st ^ 1) * V2_STAGE_BYTES + wave * FRAG;
         const unsigned char* base = smem + st * V2_STAGE_BYTES + lane * 16;
         half8 fa[8], fb[8];
-#define P2_DMA(i) dma_fragment(rs_img, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
-#define P2_LOAD(dst, g)                                                                                       \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                          \
-        dst[i_] = *reinterpret_cast<const half8*>(base + ((g) * 8 + i_) * FRAG);
-#define P2_PIN()                                          \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+#define P2_DMA(i) gom_dma_fragment(rs_img, nsrc + (i) * 4 * FRAG, ndst + (i) * 4 * FRAG);
         // group g of a stage: output groups 4 g .. 4 g + 3; fragment 2 i + p = plane p of output group 4 g + i
 #define P2_MFMA(src, g)                                                                                       \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                        \
         const int t_ = (g) * 4 + i_;                                                                          \
-        acc[t_] = mfma16(src[2 * i_ + 1], xf[0][c], acc[t_]);                                                 \
-        acc[t_] = mfma16(src[2 * i_], xf[1][c], acc[t_]);                                                     \
-        acc[t_] = mfma16(src[2 * i_], xf[0][c], acc[t_]);                                                     \
+        acc[t_] = gom_mfma16(src[2 * i_ + 1], xf[0][c], acc[t_]);                                             \
+        acc[t_] = gom_mfma16(src[2 * i_], xf[1][c], acc[t_]);                                                 \
+        acc[t_] = gom_mfma16(src[2 * i_], xf[0][c], acc[t_]);                                                 \
     }
-        P2_LOAD(fa, 0)
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-        P2_LOAD(fb, 1) P2_MFMA(fa, 0) P2_DMA(0) P2_DMA(1) P2_PIN()
-        P2_LOAD(fa, 2) P2_MFMA(fb, 1) P2_DMA(2) P2_DMA(3) P2_PIN()
-        P2_LOAD(fb, 3) P2_MFMA(fa, 2) P2_DMA(4) P2_DMA(5) P2_PIN()
+        GOM_READ_FRAGS(fa, base, 0)
+        gom_pin<8, 0, 0, 0>();
+        GOM_READ_FRAGS(fb, base, 1) P2_MFMA(fa, 0) P2_DMA(0) P2_DMA(1) gom_pin<8, 2, 6, 0>();
+        GOM_READ_FRAGS(fa, base, 2) P2_MFMA(fb, 1) P2_DMA(2) P2_DMA(3) gom_pin<8, 2, 6, 0>();
+        GOM_READ_FRAGS(fb, base, 3) P2_MFMA(fa, 2) P2_DMA(4) P2_DMA(5) gom_pin<8, 2, 6, 0>();
         P2_MFMA(fb, 3) P2_DMA(6) P2_DMA(7)
-        __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        gom_pin<0, 2, 6, 0>();
 #undef P2_DMA
-#undef P2_LOAD
-#undef P2_PIN
 #undef P2_MFMA
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -256,14 +200,14 @@ __global__ __launch_bounds__(256, 2) void proj_ln2_kernel(const ProjArgs p) {
             else v[g][k] = v[g][k] * sc[k] + bi[k];
             sum += (v[g][k][0] + v[g][k][1]) + (v[g][k][2] + v[g][k][3]);
         }
-        const float mean = row16_sum(sum) * (1.f / D);
+        const float mean = gom_row16_sum(sum) * (1.f / D);
         float q = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             v[g][k] = v[g][k] - mean;
             q += (v[g][k][0] * v[g][k][0] + v[g][k][1] * v[g][k][1]) + (v[g][k][2] * v[g][k][2] + v[g][k][3] * v[g][k][3]);
         }
-        const float rstd = rsqrtf(row16_sum(q) * (1.f / D) + p.eps);
+        const float rstd = rsqrtf(gom_row16_sum(q) * (1.f / D) + p.eps);
         float dot = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -273,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void proj_ln2_kernel(const ProjArgs p) {
             else if (m < p.M) *reinterpret_cast<f32x4*>(p.Y + (size_t)m * p.ldy + (sub + 16 * k) * 4) = o;
         }
         if constexpr (FORM == 2) {
-            dot = row16_sum(dot) + p.dot_b;
+            dot = gom_row16_sum(dot) + p.dot_b;
             if (sub == 0 && m < p.M) p.dot_out[m] = dot;
         }
     }

@@ -14,12 +14,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BK = 32;                            // k-tile: eight taps of four channels
 constexpr int ROW_BYTES = 80;                     // 32 fp16 + 16 B pad (odd number of 16-byte slots per row)
 constexpr int BM = 128, BN = 64;                  // tile: 128 convolution pixels (119 used) x 64 channels
@@ -43,15 +37,6 @@ struct StemArgs {
     int H, W, OH, OW, PH, PW, ldw, tiles_h, tiles_w;
 };
 
-__device__ __forceinline__ void split2(float x, float y, unsigned int& q0, unsigned int& q1) { gom_split2_f16(x, y, q0, q1); }
-__device__ __forceinline__ void split4(const f32x4 v, u32x2& p0, u32x2& p1) {
-    unsigned int a0, a1, b0, b1;
-    split2(v[0], v[1], a0, a1);
-    split2(v[2], v[3], b0, b1);
-    p0 = u32x2{a0, b0};
-    p1 = u32x2{a1, b1};
-}
-
 __global__ __launch_bounds__(256, 3) void stem_pool_kernel(const StemArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -65,8 +50,8 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(const StemArgs p) {
     const int oh0 = 2 * ph0 - 1, ow0 = 2 * pw0 - 1;          // convolution pixel of patch position (0, 0)
 
     constexpr unsigned RANGE = 0x80000000u, INVALID = 0xC0000000u;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.X, 0, (int)RANGE, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wp, 0, (int)RANGE, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = gom_buffer_rsrc(p.X, (int)RANGE);
+    const __amdgpu_buffer_rsrc_t rsW = gom_buffer_rsrc(p.Wp, (int)RANGE);
 
     // ---- the INPUT patch under the tile, staged once: 19 x 39 pixels x 4 channels as two fp16 planes (8 bytes per pixel and
     // plane; out-of-image pixels and one spare slot hold zeros).  The A operand of every tap is read straight from it: before,
@@ -87,7 +72,7 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(const StemArgs p) {
             if (t == ZERO_PIX || !(((unsigned)ih < (unsigned)p.H) && ((unsigned)iw < (unsigned)p.W))) off = INVALID;
             const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)off, 0, 0));
             u32x2 p0, p1;
-            split4(v, p0, p1);
+            gom_split4_f16(v, p0, p1);
             *reinterpret_cast<u32x2*>(PP + t * 8) = p0;
             *reinterpret_cast<u32x2*>(PP + PP_PLANE + t * 8) = p1;
         }
