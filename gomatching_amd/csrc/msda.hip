@@ -851,6 +851,7 @@ extern "C" int gom_msda_fused_forward_vr(const float* raw, int ld_raw, const flo
     GOM_CHECK_ARG(raw && ref && value && spatial_shapes && level_start_index && valid_ratios && output);
     GOM_CHECK_ARG(batch > 0 && num_query > 0 && ld_raw >= HEADS * LEVELS * 4 * 3 && (ld_raw % 4) == 0);
     GOM_CHECK_ARG(value_row_stride >= HEADS * CH && (value_row_stride % 4) == 0 && (value_batch_stride % 4) == 0);
+    GOM_CHECK_ARG(((uintptr_t)raw % 16) == 0 && ((uintptr_t)value % 16) == 0);
     const long nq = (long)batch * num_query;
     if (g_msda_lanes && value_batch_stride > 0 && value_batch_stride < (1L << 29))
         hipLaunchKernelGGL((msda_fused_lanes_kernel<true>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream,
