@@ -55,11 +55,15 @@ class ResNet50:
         # conv3 + residual + ReLU of block k fused with conv1 of block k + 1 (csrc/bneck_fused.hip) where the shapes are served
         # (res2, res3, inside res4) under the f16x3 back-end: block k's output is written once and never read back by conv1
         self.fused = {}
-        for (_, p, _, _, _), (_, pn, _, _, _) in zip(self.blocks[:-1], self.blocks[1:]):
+        # ... and, where that is built too (res2.0), the block's projection shortcut computed inside the same launch
+        for (_, p, s, has_sc, _), (_, pn, _, _, _) in zip(self.blocks[:-1], self.blocks[1:]):
             w3, sc3, sh3 = self.convs[p + "conv3"]
             w1, sc1, sh1 = self.convs[pn + "conv1"]
             if ops.BneckFused.serves(w3, w1):
-                self.fused[p] = ops.BneckFused(w3, sc3, sh3, w1, sc1, sh1)
+                shortcut = None
+                if has_sc and ops.BneckFused.serves_shortcut(w3, w1, self.convs[p + "shortcut"][0], s):
+                    shortcut = self.convs[p + "shortcut"] + (s,)
+                self.fused[p] = ops.BneckFused(w3, sc3, sh3, w1, sc1, sh1, shortcut=shortcut)
 
     def _conv(self, x, name, stride=1, pad=0, relu=False, R=None):
         w, sc, sh = self.convs[name]
@@ -76,10 +80,13 @@ class ResNet50:
         outs = {}
         y1 = None                                            # conv1 of this block, when the previous block's launch made it
         for stage, p, s, has_sc, last in self.blocks:
-            sc = self._conv(x, p + "shortcut", stride=s) if has_sc else x
+            blk = self.fused.get(p)
+            if blk is not None and blk.ks:
+                sc = x                                       # the fused launch computes the shortcut from the block's input
+            else:
+                sc = self._conv(x, p + "shortcut", stride=s) if has_sc else x
             y = y1 if y1 is not None else self._conv(x, p + "conv1", relu=True)
             y = self._conv(y, p + "conv2", stride=s, pad=1, relu=True)
-            blk = self.fused.get(p)
             if blk is not None:
                 x, y1 = ops.bneck_fused(y, blk, sc)                   # relu(conv3 + shortcut) and the next block's conv1
             else:

@@ -640,6 +640,9 @@ BNECK_FUSED = _switch("BNECK_FUSED")   # f16x3 back-end: a bottleneck block's co
 
 
 BNECK2 = _switch("BNECK2")           # res4's bottleneck tails + next heads (256 -> 1024 -> 256) fused on csrc/bneck2.hip (two workgroups per CU)
+# a stage's first block: its 1x1 projection shortcut computed inside the fused launch from the block's input (res2.0); off: the
+# shortcut is a launch of its own whose [M, c4] output the fused launch reads back
+BNECK_SHORTCUT = _switch("BNECK_SHORTCUT")
 
 
 class BneckFused:
@@ -647,12 +650,30 @@ class BneckFused:
     folded BatchNorm + ReLU of the NEXT block prepared for gom_bneck_f32 (csrc/bneck_fused.hip): the block's output is written once
     and never read back."""
 
-    def __init__(self, w3, scale3, shift3, w1, scale1, shift1):
+    def __init__(self, w3, scale3, shift3, w1, scale1, shift1, shortcut=None):
+        """shortcut = (SplitWeight [c4, ks], scale, shift, stride) of the block's 1x1 projection shortcut: the launch then computes
+        the residual from the block's input (`serves_shortcut` says whether the shapes are built)."""
         assert isinstance(w3, SplitWeight) and isinstance(w1, SplitWeight) and w3.kind == "f16x3" and w1.kind == "f16x3"
         self.k1, self.c4, self.mp = w3.K, w3.N, w1.N
         assert w1.K == self.c4
         _chk_f32(scale3, shift3, scale1, shift1)
         p3, p1 = w3.planes, w1.planes
+        self.ks, self.stride = 0, 1
+        if shortcut is not None:
+            ws, scale_s, shift_s, stride = shortcut
+            assert BneckFused.serves_shortcut(w3, w1, ws, stride), "fused bottleneck kernel does not serve this shortcut"
+            _chk_f32(scale_s, shift_s)
+            self.v2, self.ks, self.stride = False, ws.K, int(stride)
+            ps = ws.planes
+            nbytes = _L().gom_bneck_sc_image_bytes(self.k1, self.c4, self.mp, self.ks, self.stride)
+            self.image = torch.empty((nbytes,), dtype=torch.uint8, device=p3.device)
+            check(_L().gom_bneck_sc_image(_p(p3), p3.stride(0), p3.stride(1), _p(w3.inv_scale), _p(scale3), _p(shift3), _p(p1),
+                                          p1.stride(0), p1.stride(1), _p(ps), ps.stride(0), ps.stride(1), _p(ws.inv_scale),
+                                          _p(scale_s), _p(shift_s), self.k1, self.c4, self.mp, self.ks, self.stride, _p(self.image),
+                                          nbytes, _stream()), "gom_bneck_sc_image")
+            self.sc1 = (scale1 * w1.inv_scale).contiguous()
+            self.sh1 = shift1.contiguous()
+            return
         self.v2 = BneckFused._wide(self.k1, self.c4, self.mp)
         if self.v2:
             # res4 (256 -> 1024 -> 256) and the res3 -> res4 transition (128 -> 512 -> 256): csrc/bneck2.hip, 16-pixel waves, eight per
@@ -684,8 +705,42 @@ class BneckFused:
                 and (BneckFused._wide(w3.K, w3.N, w1.N) or _L().gom_bneck_image_bytes(w3.K, w3.N, w1.N) > 0))
 
 
+    @staticmethod
+    def serves_shortcut(w3, w1, ws, stride):
+        """By shapes only (never by row count: a frame's bits must not depend on what shares its step)."""
+        return (bool(BNECK_SHORTCUT) and BneckFused.serves(w3, w1) and isinstance(ws, SplitWeight) and ws.kind == "f16x3"
+                and ws.N == w3.N and _L().gom_bneck_sc_image_bytes(w3.K, w3.N, w1.N, ws.K, int(stride)) > 0)
+
+
+def _bneck_fused_sc(a, blk, S):
+    _chk_f32(a, S)
+    B, H, W, k1 = a.shape
+    Bs, Hs, Ws, ks = S.shape
+    st = blk.stride
+    assert k1 == blk.k1 and ks == blk.ks and Bs == B and (H, W) == ((Hs - 1) // st + 1, (Ws - 1) // st + 1)
+    assert a.is_contiguous() and S.is_contiguous()
+    M = B * H * W
+    X = torch.empty((B, H, W, blk.c4), dtype=_f32, device=a.device)
+    Y1 = torch.empty((B, H, W, blk.mp), dtype=_f32, device=a.device)
+    prof = _gemm_profile if (_gemm_profile is not None and M > 0) else None
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(_L().gom_bneck_sc_f32(_p(a), k1, _p(blk.image), _p(S), ks, B, Hs, Ws, st, _p(blk.sc1), _p(blk.sh1), _p(X), blk.c4, _p(Y1),
+                                blk.mp, blk.k1, blk.c4, blk.mp, blk.ks, _p(range_flag(a.device)), _stream()), "gom_bneck_sc_f32")
+    if prof is not None:
+        e1.record()
+        # A and the sampled rows of S in, X and Y1 out: no residual stream
+        prof.append((e0, e1, 2.0 * M * blk.c4 * (blk.k1 + blk.ks + blk.mp), 4.0 * M * (blk.k1 + blk.ks + blk.c4 + blk.mp) + blk.image.numel(),
+                     "bneck:%dx%dx%dx%d+sc%d/%d" % (M, blk.k1, blk.c4, blk.mp, blk.ks, st), _profile_scope))
+    return X, Y1
+
+
 def bneck_fused(a, blk, R):
-    """(X, Y1) = (relu(bn3(conv3(a)) + R), relu(bn1'(conv1'(X)))) in one launch; a [B, H, W, k1], R [B, H, W, c4] NHWC."""
+    """(X, Y1) = (relu(bn3(conv3(a)) + R), relu(bn1'(conv1'(X)))) in one launch; a [B, H, W, k1], R [B, H, W, c4] NHWC.  A block
+    prepared with its projection shortcut takes the block's INPUT [B, Hs, Ws, ks] in R's place and computes the residual itself."""
+    if blk.ks:
+        return _bneck_fused_sc(a, blk, R)
     _chk_f32(a, R)
     B, H, W, k1 = a.shape
     assert k1 == blk.k1 and tuple(R.shape) == (B, H, W, blk.c4) and a.is_contiguous() and R.is_contiguous()

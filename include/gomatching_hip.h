@@ -222,6 +222,22 @@ int gom_bneck_image(const void* w3_planes, long w3_plane_stride, int ld3, const 
                     long image_bytes, void* stream);
 int gom_bneck_f32(const float* A, int lda, const void* image, const float* R, int ldr, const float* scale1, const float* shift1,
                   float* X, int ldx, float* Y1, int ldy, int M, int k1, int c4, int mp, int* flag, void* stream);
+/* Shortcut form, for the FIRST block of a stage: the residual is the block's 1x1 projection shortcut, computed inside the launch
+ * from the block's input instead of being read ([M, c4] written by one launch to be read by the next, gone):
+ *     R  = fl32(scale_s * (S Wsc^T) + shift_s)        S [B, Hs, Ws, ks] NHWC (pixel stride lds floats), sampled at (b, stride y, stride x)
+ *     X  = relu((scale3 * (A W3^T) + shift3) + R),  Y1 as above;   A / X / Y1 have B x OH x OW rows, OH = (Hs - 1) / stride + 1
+ * i.e. the arithmetic of the shortcut's own launch followed by gom_bneck_f32's.  S is split into fp16 planes like A (range contract,
+ * *flag).  Served (k1, c4, mp, ks, stride): (64, 256, 64, 64, 1) = res2.0; gom_bneck_sc_image_bytes returns -1 otherwise.
+ * gom_bneck_sc_image: gom_bneck_image's arguments plus the gom_split_f16x2 planes of the shortcut's [c4, ks] matrix, its inverse
+ * row scales and its folded BatchNorm. */
+long gom_bneck_sc_image_bytes(int k1, int c4, int mp, int ks, int stride);
+int gom_bneck_sc_image(const void* w3_planes, long w3_plane_stride, int ld3, const float* w3_inv_scale, const float* scale3,
+                       const float* shift3, const void* w1_planes, long w1_plane_stride, int ld1, const void* ws_planes,
+                       long ws_plane_stride, int lds, const float* ws_inv_scale, const float* scale_s, const float* shift_s, int k1,
+                       int c4, int mp, int ks, int stride, void* image, long image_bytes, void* stream);
+int gom_bneck_sc_f32(const float* A, int lda, const void* image, const float* S, int lds, int B, int Hs, int Ws, int stride,
+                     const float* scale1, const float* shift1, float* X, int ldx, float* Y1, int ldy, int k1, int c4, int mp, int ks,
+                     int* flag, void* stream);
 /* The same pair for the wide shapes (res4: k1 = 256, c4 = 1024, mp = 256; the res3 -> res4 transition: 128, 512, 256) on
  * csrc/bneck2.hip: 16-pixel waves on the 16x16x32 MFMA shape, eight per workgroup (two per SIMD) sharing one weight ring.
  * gom_bneck2_image / gom_bneck2_f32: arguments as gom_bneck_image / gom_bneck_f32 (gom_bneck2_image_bytes: -1 = shape not served). */
