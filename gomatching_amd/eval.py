@@ -1,0 +1,181 @@
+"""`python -m gomatching_amd.eval`: run the spotter over a dataset directory and write the result files the reference's
+offline evaluation protocols consume -- the counterpart of the reference's measured entry point (eval.py:212-383)
+without drawing.
+
+    python -m gomatching_amd.eval --config-file FILE --input DIR --output OUT --opts MODEL.WEIGHTS W
+      -> OUT/preds/res_<video>.xml, OUT/preds/res_<video>.txt, OUT/jsons/<video>.json
+
+What it keeps of the reference: `setup_cfg` (with the ASSO_THRESH_TEST override of :220), the data type taken from the
+input path (DSText / ICDAR15 / BOVText / OTHER), video directories one level deeper for DSText and BOVText (:290-295),
+frames sorted by the integer stem of the file name (:309), 100-frame chunks, skipping of videos whose XML exists and of
+the damaged `Cls1_Livestreaming_video40` (:275-277, :316), the ICDAR15 XML naming (:372-378), the per-track
+transcription files (:381) and the wording of the timing lines.
+
+Deliberate differences:
+  * the "already written" check compares the XML stem `results.result_names` returns; the reference compares the raw
+    video name, which never matches an ICDAR15 stem ('Video_35_2_3' is written as res_video_35.xml), so it never
+    resumes on ICDAR15;
+  * no `--cpu` (there is no CPU path), no `--webcam`, no `--show` (nothing is drawn);
+  * frames are decoded with Pillow (`convert("RGB")`, reversed to the BGR order `read_image(format="BGR")` yields).
+    OpenCV is not available here, so the parity of the decoded pixels with `cv2.imread` (JPEG decoders differ in their
+    IDCT and chroma upsampling) is UNPINNED, as is the parity of `results.min_area_rect` with `cv2.minAreaRect`.
+"""
+import argparse
+import os
+import shutil
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from . import config as _config
+from . import results as _results
+
+DAMAGED_VIDEOS = ("Cls1_Livestreaming_video40",)          # eval.py:316 "filter bovtext damaged video"
+DECODE_THREADS = 4                                        # a small fixed pool that decodes frames ahead (never sized by the host)
+
+
+def get_parser():
+    p = argparse.ArgumentParser(
+        prog="python -m gomatching_amd.eval",
+        description="Video text spotting over a dataset directory on an MI355X; writes preds/res_*.xml, preds/res_*.txt and "
+                    "jsons/*.json under --output.  There is no --cpu, --webcam or --show: the package has no CPU path and "
+                    "draws nothing.")
+    p.add_argument("--config-file", default=None, metavar="FILE", help="path to config file")
+    p.add_argument("--builtin", default=None, choices=sorted(_config.BUILTIN), metavar="NAME",
+                   help="a packaged config instead of --config-file: " + ", ".join(sorted(_config.BUILTIN)))
+    p.add_argument("--input", required=True, metavar="DIR",
+                   help="dataset directory: one directory of frames per video (one level deeper for DSText / BOVText)")
+    p.add_argument("--output", required=True, metavar="DIR", help="directory for preds/ and jsons/")
+    p.add_argument("--frames-per-step", type=int, default=8, metavar="N", help="frames per detector step (default 8)")
+    p.add_argument("--host-ingest", action="store_true",
+                   help="resize and normalise frames on the host (default: on the GPU, bit-exact with the host path)")
+    p.add_argument("--host-rows", action="store_true",
+                   help="build result rows per frame on the host (default: one kernel launch and one copy per clip)")
+    p.add_argument("--opts", default=[], nargs=argparse.REMAINDER,
+                   help="modify config options using the command-line 'KEY VALUE' pairs")
+    return p
+
+
+def data_type_of(input_dir):
+    for name in ("DSText", "ICDAR15", "BOVText"):
+        if name in input_dir:
+            return name
+    return "OTHER"
+
+
+def list_videos(input_dir, done=()):
+    """-> (data type, [(video name, video directory)]) in listing order; videos whose XML stem is in `done` and the damaged
+    BOVText video are left out."""
+    data_type = data_type_of(input_dir)
+    dirs = []
+    for video in sorted(os.listdir(input_dir)):
+        path = os.path.join(input_dir, video)
+        if data_type in ("DSText", "BOVText"):
+            dirs.extend(os.path.join(path, v) for v in sorted(os.listdir(path)))
+        else:
+            dirs.append(path)
+    out = []
+    for d in dirs:
+        name = os.path.basename(d).split(".")[0]
+        if name in DAMAGED_VIDEOS or _results.result_names(name, data_type)[0] in done:
+            continue
+        out.append((name, d))
+    return data_type, out
+
+
+def written_videos(xml_dir):
+    """XML stems already present under preds/ (eval.py:275-277)."""
+    if not os.path.isdir(xml_dir):
+        return set()
+    return set(f[len("res_"):-len(".xml")] for f in os.listdir(xml_dir) if f.startswith("res_") and f.endswith(".xml"))
+
+
+def frame_paths(video_dir):
+    """Frame files of one video, sorted by the integer stem of the file name (2.jpg before 10.jpg)."""
+    return sorted((os.path.join(video_dir, f) for f in os.listdir(video_dir)),
+                  key=lambda p: int(os.path.basename(p).split(".")[0]))
+
+
+def read_frame(path):
+    """HxWx3 uint8 in BGR order, as `read_image(path, format="BGR")`."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
+
+
+def load_weights(path):
+    """-> canonical state dict, or None when `path` is empty or no file."""
+    if not path or not os.path.isfile(path):
+        return None
+    import torch
+    from .weights import normalize_state_dict
+    return normalize_state_dict(torch.load(path, map_location="cpu"))
+
+
+def main(argv=None):
+    args = get_parser().parse_args(argv)
+    if (args.config_file is None) == (args.builtin is None):
+        sys.stderr.write("error: give exactly one of --config-file and --builtin\n")
+        return 2
+    if args.config_file is not None and not os.path.isfile(args.config_file):
+        sys.stderr.write("error: config file %r not found\n" % args.config_file)
+        return 2
+    if len(args.opts) % 2:
+        sys.stderr.write("error: --opts takes KEY VALUE pairs\n")
+        return 2
+    if not os.path.isdir(args.input):
+        sys.stderr.write("error: input directory %r not found\n" % args.input)
+        return 2
+    cfg = _config.setup_cfg(config_file=args.config_file, opts=args.opts, builtin=args.builtin)
+    state_dict = load_weights(cfg.MODEL.WEIGHTS)
+    if state_dict is None:
+        sys.stderr.write("error: MODEL.WEIGHTS %r is not a file (set it with --opts MODEL.WEIGHTS PATH)\n"
+                         % (cfg.MODEL.WEIGHTS,))
+        return 2
+
+    xml_dir, json_dir = os.path.join(args.output, "preds"), os.path.join(args.output, "jsons")
+    os.makedirs(xml_dir, exist_ok=True)
+    os.makedirs(json_dir, exist_ok=True)
+    config_file = args.config_file or _config.BUILTIN[args.builtin]
+    shutil.copy(config_file, args.output)
+    data_type, videos = list_videos(args.input, done=written_videos(xml_dir))
+
+    from .predictor import GoMBatchPredictor, TextDecoder, new_time_cost
+    time_cost = new_time_cost()
+    if videos:                                              # a resumed run with nothing left builds no model
+        from .modeling import GoMatching
+        model = GoMatching(cfg, state_dict, frames_per_step=args.frames_per_step)
+        spotter = GoMBatchPredictor(cfg, model, device_ingest=not args.host_ingest)
+        decoder = TextDecoder(cfg.MODEL.TRANSFORMER.VOC_SIZE, cfg.MODEL.TRANSFORMER.CUSTOM_DICT)
+    total_frame, read_seconds, rows_seconds = 0, 0.0, 0.0
+    with ThreadPoolExecutor(max_workers=DECODE_THREADS) as pool:
+        for video_name, video_dir in videos:
+            print("processing {}...".format(video_name))
+            t0 = time.time()
+            frames = list(pool.map(read_frame, frame_paths(video_dir)))
+            read_seconds += time.time() - t0
+            if not frames:
+                continue
+            preds, per_video_time = _results.spot_video(spotter, frames, time_cost)
+            total_frame += len(frames)
+            t0 = time.time()
+            _results.write_video(preds, video_name, data_type, args.output, decoder, device_rows=not args.host_rows)
+            rows_seconds += time.time() - t0
+            print("Video: ", video_name, "per_img_time: ", per_video_time / len(frames), ", FPS: ",
+                  len(frames) / per_video_time)
+    t0 = time.time()
+    _results.write_track_transcriptions(xml_dir)
+    rows_seconds += time.time() - t0
+    if total_frame:
+        print("total_time: ", time_cost["total_time"], ", per_video_time: ", time_cost["total_time"] / len(videos),
+              ", per_img_time: ", time_cost["total_time"] / total_frame, ", FPS: ", total_frame / time_cost["total_time"])
+    print(time_cost)
+    print("host seconds outside the timed window: reading frames ", read_seconds, ", building rows and writing files ",
+          rows_seconds, ", videos processed: ", len(videos))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

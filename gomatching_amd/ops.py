@@ -1432,6 +1432,30 @@ def ingest(frames, out_h, out_w, mean, std, flip):
     return out
 
 
+RESULT_ROWS_WORDS = 234             # GOM_RESULT_ROWS_WORDS (include/gomatching_hip.h)
+
+
+def result_rows(bd, recs, voc_size, track_ids=None):
+    """bd [n,25,4] f32, recs [n,25] int64 (CUDA) -> int32 [n, RESULT_ROWS_WORDS]: integer polygon, its fp32 bits, recs,
+    CTC emit mask, convex-hull membership and the minimum-area-rectangle edge of every instance, one launch
+    (csrc/result_rows.hip; layout in include/gomatching_hip.h)."""
+    if not bd.is_cuda or bd.dtype != _f32 or bd.dim() != 3 or tuple(bd.shape[1:]) != (25, 4):
+        raise ValueError("bd must be a CUDA float32 [n,25,4] tensor")
+    n = bd.shape[0]
+    if recs.dtype != torch.int64 or tuple(recs.shape) != (n, 25) or recs.device != bd.device:
+        raise ValueError("recs must be an int64 [n,25] tensor on bd's device")
+    if track_ids is not None and (track_ids.dtype != torch.int64 or tuple(track_ids.shape) != (n,)
+                                  or track_ids.device != bd.device):
+        raise ValueError("track_ids must be an int64 [n] tensor on bd's device")
+    bd, recs = bd.contiguous(), recs.contiguous()
+    track_ids = None if track_ids is None else track_ids.contiguous()
+    out = torch.empty((n, RESULT_ROWS_WORDS), dtype=torch.int32, device=bd.device)
+    with torch.cuda.device(bd.device):
+        check(_L().gom_result_rows_i32(_p(bd), _p(recs), _p(track_ids), n, int(voc_size), _p(out), RESULT_ROWS_WORDS,
+                                       _stream()), "gom_result_rows_i32")
+    return out
+
+
 STEM_POOL = _switch("STEM_POOL")     # f16x3 back-end: the ResNet stem (conv 7x7 / 2 + BN + ReLU + max-pool 3x3 / 2) as one launch
 
 

@@ -460,6 +460,38 @@ int gom_resize_bilinear_u8_hwc3(const uint8_t* src, int B, int H, int W, const i
 int gom_ingest_u8_hwc3_to_nhwc4(const uint8_t* src, int B, int H, int W, const int* xbounds, const int* xkk,
                                 int xksize, const int* ybounds, const int* ykk, int yksize, const float* mean3,
                                 const float* std3, float* dst, int OH, int OW, int flip_channels, void* stream);
+/* ---- f1: result rows (eval.py:346-363, the per-instance conversion in front of the XML / JSON writers) --------
+ * The per-instance work of the host's `frame_lines` for all n instances of a clip in ONE launch (one wave64 per instance):
+ *   bd [n,25,4] fp32 (top x, top y, bottom x, bottom y per point, frame pixels), recs [n,25] int64 class ids,
+ *   track_ids [n] int64 (may be NULL: the two id words are then 0), out [n, ld] int32, ld >= GOM_RESULT_ROWS_WORDS.
+ * Words of one output row (polygon point p = top point p for p < 25, bottom point 49 - p otherwise):
+ *   GOM_RR_POLY_I32  + 2p, +2p+1 : the polygon point truncated toward zero (numpy astype(int)), x then y
+ *   GOM_RR_POLY_F32  + 2p, +2p+1 : the same point's fp32 bit patterns (the host finishes the rectangle from them)
+ *   GOM_RR_RECS      + c         : recs[c] as int32 (saturated), c < 25
+ *   GOM_RR_EMIT                  : bit c set iff character c is emitted by the CTC collapse: id < voc_size - 1 and
+ *                                  (c == 0 or id[c-1] is a blank or id[c] != id[c-1])
+ *   GOM_RR_NHULL                 : number of convex-hull points (de-duplicated points, sorted by (x, y), monotone chain
+ *                                  popping on cross <= 0, order lower[:-1] + upper[:-1]; <= 2 distinct points are their hull)
+ *   GOM_RR_HULL_MASK, +1         : bit p (low word: p < 32) set iff polygon point p is a hull point (first occurrence
+ *                                  of a repeated point)
+ *   GOM_RR_EDGE, +1              : polygon indices of the two ends (hull order) of the hull edge whose enclosing rectangle
+ *                                  has the smallest area, first hull index winning ties, zero-length edges skipped;
+ *                                  -1, -1 with fewer than 2 hull points.  GOM_RR_EDGE + 2 is 0 (padding).
+ *   GOM_RR_TRACK_ID, +1          : track_ids[i], low word then high word (8-byte aligned for ld even)
+ * The search is fp64 with the host code's operations in its order, each rounded once (no contraction; edge length
+ * sqrt(ex*ex + ey*ey)); centre, size, angle and corners are left to the host (their libm calls differ in the last bit).
+ * n == 0 is GOM_OK without a launch.  Coordinates are expected finite. */
+#define GOM_RR_POLY_I32 0
+#define GOM_RR_POLY_F32 100
+#define GOM_RR_RECS 200
+#define GOM_RR_EMIT 225
+#define GOM_RR_NHULL 226
+#define GOM_RR_HULL_MASK 227
+#define GOM_RR_EDGE 229
+#define GOM_RR_TRACK_ID 232
+#define GOM_RESULT_ROWS_WORDS 234
+int gom_result_rows_i32(const float* bd, const int64_t* recs, const int64_t* track_ids, int n, int voc_size,
+                        int32_t* out, int ld, void* stream);
 int gom_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 /* out [H*W, 256] = PositionalEncoding2D(normalize=True) + level_embed, for an unpadded H x W level. */
 int gom_pos_encoding_2d_f32(const float* dim_t128, const float* level_embed256, float* out, int H, int W,
