@@ -17,6 +17,14 @@ P = c_void_p
 I = c_int
 L = c_long
 F = c_float
+D = ctypes.c_double
+
+
+class OptimTensor(ctypes.Structure):
+    """`gom_optim_tensor` of include/gomatching_hip.h: one row of the clipped-AdamW table."""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("n", c_long), ("step", c_long), ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double)]
+
 
 # name -> (restype, argtypes); must list every symbol declared in include/gomatching_hip.h
 SIGNATURES = {
@@ -105,6 +113,8 @@ SIGNATURES = {
     "gom_softmax_rows_backward_f32": (I, [P, P, P, L, I, L, F, P]),
     "gom_asso_ce_f32": (I, [P, I, P, I, P, L, P, P, P, P]),
     "gom_sigmoid_focal_f32": (I, [P, P, F, F, L, P, P, P]),
+    "gom_clipped_adamw_partials": (L, [P, I]),
+    "gom_clipped_adamw_step": (I, [P, I, D, D, D, D, P, L, P, P]),
     "gom_layernorm_f32": (I, [P, P, P, P, P, L, I, F, P]),
     "gom_groupnorm32_nhwc_f32": (I, [P, P, P, P, P, L, I, I, I, F, P]),
     "gom_mha_core_f32": (I, [P, P, P, P, I, I, I, I, I, I, ctypes.POINTER(c_long), P]),

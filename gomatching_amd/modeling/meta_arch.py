@@ -130,11 +130,43 @@ class GoMatching:
 
     def trainable_parameters(self):
         """{state-dict key: leaf tensor with requires_grad} of the trainable head, created from the loaded weights on first use.
-        Inference keeps using the weights the model was built with; rebuild the model to run inference with updated ones."""
+        Inference keeps using the weights the head was last built with: `load_head` (or `solver.Trainer.sync_inference`) hands
+        updated ones to the inference path without rebuilding the detector."""
         if getattr(self, "_train_params", None) is None:
             self._train_params = {k: torch.as_tensor(v).detach().float().to(self.device).clone().requires_grad_(True)
                                   for k, v in self._head_state.items()}
         return self._train_params
+
+    def set_score_threshold(self, threshold):
+        """Change the detection score threshold (`INFERENCE_TH_TEST`) of a built model.  The threshold is a kernel argument of
+        `gom_detect_post`, so captured detector graphs hold the old one: they are dropped and re-captured on their next use."""
+        self.test_score_threshold = float(threshold)
+        for k in [k for k, v in self._graphs.items() if isinstance(v, dict)]:
+            self._graphs[k] = "warm"
+
+    def load_head(self, head_state):
+        """Run inference with another set of head weights ({`roi_heads.*` key: tensor}, every key of the current head, same
+        shapes) WITHOUT touching the backbone and DeepSolo preparation: replaces the retained head state, rebuilds
+        `self.roi_heads` (FC head, matcher layers, rescoring weights), releases the native tracker handle (created with the old
+        layer pointers), forgets the hoisted matcher projections of the old weights, and drops captured detector graphs when
+        the rescoring product is part of them (they hold the old weight pointers; they are re-captured on their next use).
+        `trainable_parameters()` are left alone: they are the training copies."""
+        hs = {k: torch.as_tensor(v).detach().float().cpu().clone() for k, v in head_state.items() if k.startswith("roi_heads.")}
+        if set(hs) != set(self._head_state):
+            raise KeyError("load_head: key set differs from the model's head (missing %s, unexpected %s)" % (
+                sorted(set(self._head_state) - set(hs))[:3], sorted(set(hs) - set(self._head_state))[:3]))
+        for k, v in hs.items():
+            if tuple(v.shape) != tuple(self._head_state[k].shape):
+                raise ValueError("load_head: %s has shape %s, the model's is %s" % (k, tuple(v.shape), tuple(self._head_state[k].shape)))
+        self.close()
+        torch.cuda.synchronize(self.device)                      # queued kernels may still read the old weights
+        self._head_state = hs
+        self.roi_heads = build_roi_heads(self.cfg, hs, self.device)
+        self._proj, self._proj_pool, self._proj_done = None, None, 0
+        if self.with_rescore:
+            for k in [k for k, v in self._graphs.items() if isinstance(v, dict)]:
+                self._graphs[k] = "warm"
+        return self
 
     # ------------------------------------------------------------------------------------ detection
     def _raw_input(self, batched_inputs, out=None):

@@ -1827,6 +1827,36 @@ def sigmoid_focal(x, target, alpha, gamma, want_loss=True, want_grad=True):
     return loss, dx
 
 
+def clipped_adamw_step(rows, beta1, beta2, eps, clip_value, workspace=None, norm_out=None):
+    """One full-model-clipped AdamW step (`gom_clipped_adamw_step`, csrc/optim.hip) over rows = [(param, grad, exp_avg,
+    exp_avg_sq, step, lr, weight_decay)]: dense fp32 CUDA tensors of one size per row, `step` the count including this step.
+    Updates param / exp_avg / exp_avg_sq in place, leaves grad as it is.  Returns (norm_out, workspace): norm_out = device
+    [2] {total gradient norm, clip coefficient}; pass both back in to reuse them.  Launches only: nothing is read back."""
+    table = (_lib_mod.OptimTensor * max(len(rows), 1))()
+    for i, (p, g, m, v, step, lr, wd) in enumerate(rows):
+        _chk_f32(p, g, m, v)
+        if any(t.device != rows[0][0].device for t in (p, g, m, v)):
+            raise ValueError("clipped_adamw_step: every tensor of the table must be on one device")
+        for t in (g, m, v):
+            if t.numel() != p.numel() or not t.is_contiguous():
+                raise ValueError("clipped_adamw_step: param, grad and both moments must be contiguous and of one size")
+        if not p.is_contiguous():
+            raise ValueError("clipped_adamw_step: non-contiguous parameter")
+        table[i] = _lib_mod.OptimTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), int(step), float(lr),
+                                        float(wd))
+    n = _L().gom_clipped_adamw_partials(table, len(rows))
+    if n < 0:
+        raise _lib_mod.GomError("gom_clipped_adamw_partials failed: GOM_ERR_INVALID_ARG (violated precondition)")
+    dev = rows[0][0].device
+    if workspace is None or workspace.numel() < n or workspace.device != dev:
+        workspace = torch.empty((max(n, 1),), dtype=_f32, device=dev)
+    if norm_out is None or norm_out.device != dev:
+        norm_out = torch.empty((2,), dtype=_f32, device=dev)
+    check(_L().gom_clipped_adamw_step(table, len(rows), float(beta1), float(beta2), float(eps), float(clip_value), _p(workspace),
+                                      workspace.numel(), _p(norm_out), _stream()), "gom_clipped_adamw_step")
+    return norm_out, workspace
+
+
 def transpose_into(x, out):
     """out[c, r] = x[r, c] for 2-D row-strided views (out may be wider than x has rows)."""
     assert x.dim() == 2 and out.dim() == 2 and x.stride(1) == 1 and out.stride(1) == 1

@@ -37,3 +37,22 @@ def make_clip(num_frames, height, width, clip_id=0, num_rects=6):
                 img[y0 + h // 5: y0 + h - h // 5, s:s + max(2, w // 16)] = fg
         frames.append(np.clip(img, 0, 255).astype(np.uint8))
     return frames
+
+
+# Calibration of the synthetic weights for the training clip below: detector and rescoring biases that let detections pass
+TRAINING_CLS_BIAS = {"detection_transformer.ctrl_point_class.0.bias": 0.8, "roi_heads.rescoring_head.bias": 0.8}
+
+
+def make_training_clip(num_frames=4, height=96, width=128, clip_id=2):
+    """`make_clip` frames as mapped training inputs: per frame {"image" [3,H,W] float32 tensor, "instances": two moving
+    ground-truth boxes with instance ids 1 and 2 and their 25 control points (pixels)}.  The ONE clip that the trainer test,
+    tools/solver_rehearsal.py and tools/solver_bench.py use, so that the rehearsal's chosen learning rate stays valid."""
+    import torch
+    batch = []
+    for t, fr in enumerate(make_clip(num_frames, height, width, clip_id=clip_id)):
+        boxes = np.array([[10 + 3 * t, 12, 40 + 3 * t, 30], [60, 40 + 2 * t, 100, 62 + 2 * t]], np.float32)
+        ctrl = np.stack([np.stack([np.linspace(b[0], b[2], 25), np.full(25, (b[1] + b[3]) / 2)], -1) for b in boxes]).astype(np.float32)
+        batch.append({"image": torch.as_tensor(fr.astype("float32").transpose(2, 0, 1)),
+                      "instances": {"gt_boxes": torch.as_tensor(boxes), "gt_instance_ids": torch.tensor([1, 2]),
+                                    "ctrl_points": torch.as_tensor(ctrl)}})
+    return batch

@@ -6,6 +6,8 @@
  * stock torch.nn in the reference; here those ops are hand-written HIP kernels behind the remaining entry
  * points, which the Python mirror of the reference's META_ARCH / ROI_HEADS classes
  * (gomatching_amd/modeling) binds through ctypes.  INTEGRATION.md shows the reference-side stubs.
+ * Training of the association head adds gom_relu_backward_f32 ... gom_sigmoid_focal_f32 (losses and backward pieces) and
+ * gom_clipped_adamw_partials / gom_clipped_adamw_step (the optimizer step), at the end of this file.
  *
  * Conventions
  *   - plain pointers and sizes only; every tensor pointer is DEVICE memory unless marked [host];
@@ -727,6 +729,36 @@ int gom_asso_ce_f32(const float* logits, int ld, const int* frame_offsets, int n
                     float* loss, const float* grad_scale, float* dlogits, void* stream);
 int gom_sigmoid_focal_f32(const float* x, const float* target, float alpha, float gamma, long n, float* loss, float* dx,
                           void* stream);
+
+/* The optimizer step of that training (csrc/optim.hip): AdamW with FULL-MODEL gradient clipping over a table of fp32 tensors,
+ * the fp32 arithmetic of the reference's FullModelGradientClippingOptimizer(torch.optim.AdamW) (costom_solver.py:55-73):
+ *   total = || all gradients ||_2 ;  coef = min(1, clip_value / (total + 1e-6))  (clip_value <= 0: coef = 1) ;  g' = coef g ;
+ *   per tensor, with ITS step count t, lr and weight_decay:  p *= 1 - lr wd ;  m = m + (1 - beta1) (g' - m) ;
+ *   v = beta2 v + (1 - beta2) g' g' ;  p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).
+ * The table [host] lists the tensors that HAVE a gradient in this iteration; `step` is the count INCLUDING this step (>= 1).  A
+ * tensor that is not listed is not touched.  n = 0 is allowed (nothing happens); pointers need 4-byte alignment only: a tensor
+ * whose four arrays share one offset from the 16-byte grid gets 16-byte accesses on its aligned body, any other 4-byte ones.
+ * The gradients are read twice and NOT modified (the clipped gradient exists in registers only).
+ * No host synchronisation, no allocation on the device, no atomics; the table travels in kernel arguments, so the call is
+ * capture-safe.  Bitwise reproducible: the same inputs give the same bits whatever the alignment of the arrays.
+ *   partials [device, n_partials floats]  workspace, n_partials >= gom_clipped_adamw_partials(tensors, n_tensors);
+ *   norm_out [device, 2 floats]           {total, coef} of this step, readable afterwards (logging).
+ * gom_clipped_adamw_partials returns -1 for a table the step would reject.  Both check their arguments before any HIP call:
+ * null table, n_tensors < 1, a negative size, a null or non-4-byte-aligned array of a non-empty tensor, step < 1 ->
+ * GOM_ERR_INVALID_ARG. */
+typedef struct gom_optim_tensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    long n;
+    long step;
+    double lr;
+    double weight_decay;
+} gom_optim_tensor;
+long gom_clipped_adamw_partials(const gom_optim_tensor* tensors, int n_tensors);
+int gom_clipped_adamw_step(const gom_optim_tensor* tensors, int n_tensors, double beta1, double beta2, double eps,
+                           double clip_value, float* partials, long n_partials, float* norm_out, void* stream);
 
 #ifdef __cplusplus
 }
