@@ -167,3 +167,219 @@ def msda64_fused(value, shapes, lsi, raw, ref, B, Lq, vr=None):
     loc = torch.from_numpy(msda_locations32(raw, ref, shapes, vr)).view(B, Lq, 8, 4, 4, 2)
     w = torch.from_numpy(msda_softmax64(raw)[0]).view(B, Lq, 8, 4, 4)
     return msda64(value, shapes, lsi, loc, w).view(B * Lq, 256)
+
+
+# ------------------------------------------------------------------------------------------ attention statement
+ATTN_U = 2.0 ** -24
+
+
+def attention64(q, k, v, head_dim):
+    """fp64 statement of the softmax attention core (csrc/attn.hip, mha_tiny128_task of csrc/tracker_tasks.h) with its element-wise
+    error bound.  q [..., Lq, hd], k and v [..., Lk, hd] float32 (leading dimensions = independent (batch, head) problems) ->
+    (exp, bound) float64 [..., Lq, hd].
+
+        qs = fp32(q * fp32(1 / sqrt(head_dim))), widened  (the kernels pre-scale q in fp32; for 32 and 128 that constant has the
+             bits of the kernels' 1.0f / sqrtf(head_dim))
+        s = qs k^T,  m = rowmax(s),  p = exp(s - m) / sum,  exp = p v                      all float64
+
+        bound[i,d] = sum_j p_ij |v_jd| (2 E_i + (|s_ij - m_i| + 2 Lk + 16) U) + Lk 2^-126 max|v|,      U = 2^-24
+        E_i = (head_dim + 2) U max_j sum_d |qs_id k_jd|
+
+    E_i: one fmaf chain of head_dim terms plus the pre-scale rounding -- an absolute error of a logit, which enters every p_j once
+    directly and once through the normaliser (2 E_i).  |s - m| U: the rounding of expf's argument.  2 Lk: the sequential sum of
+    the exponentials (the row-per-lane kernel's) plus the sequential P V fmaf chain.  16: expf, the reciprocal, the product, the
+    butterflies.  Last term: weights below fp32's normal range.  Derived from the operation count; nothing in it was measured."""
+    q, k, v = torch.as_tensor(q), torch.as_tensor(k), torch.as_tensor(v)
+    assert q.dtype == k.dtype == v.dtype == torch.float32, "the pre-scale is an fp32 computation: inputs must be float32"
+    Lk = k.shape[-2]
+    qs = (q * torch.tensor(1.0 / np.sqrt(head_dim), dtype=torch.float32)).double()
+    k64, va = k.double(), v.double().abs()
+    s = qs @ k64.transpose(-1, -2)
+    d = s - s.max(-1, keepdim=True).values
+    e = torch.exp(d)
+    p = e / e.sum(-1, keepdim=True)
+    exp = p @ v.double()
+    E = (head_dim + 2) * ATTN_U * (qs.abs() @ k64.abs().transpose(-1, -2)).max(-1, keepdim=True).values      # [..., Lq, 1]
+    bound = 2 * E * (p @ va) + ATTN_U * ((p * (d.abs() + 2 * Lk + 16)) @ va) + Lk * 2.0 ** -126 * va.amax((-1, -2), keepdim=True)
+    return exp, bound
+
+
+def attn_index(offset, bo, bi, ss, outer, inner, heads, hd, L, size=None):
+    """Element indices [outer * inner, heads, L, hd] of one operand of the op: batch b = (b // inner, b % inner) with strides
+    (bo, bi), sequence stride ss, head h at column h * hd.  `size`: wrap the indices into a buffer of that many elements (only
+    the planted stride mistake of the CPU file walks out of its buffer)."""
+    b = torch.arange(outer * inner)
+    idx = (offset + (b // inner) * bo + (b % inner) * bi).view(-1, 1, 1, 1) + (torch.arange(heads) * hd).view(1, -1, 1, 1) \
+        + (torch.arange(L) * ss).view(1, 1, -1, 1) + torch.arange(hd).view(1, 1, 1, -1)
+    return idx if size is None else idx % size
+
+
+def attention64_views(qbuf, kbuf, vbuf, outer, inner, heads, hd, Lq, Lk, strides, offsets=(0, 0, 0)):
+    """attention64 over batch and heads on the op's own views: flat float32 buffers, the 12 strides gom_mha_core_f32 takes (q, k, v,
+    o x (outer, inner, sequence)) and the element offset of each operand in its buffer -> (exp, bound) [outer*inner, heads, Lq, hd].
+    What the views address must be finite: the statement reads exactly the elements the op may read."""
+    got = []
+    for buf, off, st, L in ((qbuf, offsets[0], strides[0:3], Lq), (kbuf, offsets[1], strides[3:6], Lk), (vbuf, offsets[2], strides[6:9], Lk)):
+        x = buf[attn_index(off, st[0], st[1], st[2], outer, inner, heads, hd, L)]
+        assert bool(torch.isfinite(x).all())
+        got.append(x)
+    return attention64(got[0], got[1], got[2], hd)
+
+
+# ---- inputs of tests/test_attn_forms_gpu.py, shared with tests/test_attn_statement_cpu.py (same generators, same seeds, same bits)
+ATTN_KINDS = ("randn", "peaked", "overflow", "same", "widev", "edge")
+
+
+def attn_edges(Lk):
+    """Keys on which a tail tile, a 64-key tile edge or the first / last key goes wrong, the ones a planted mistake needs first."""
+    out = []
+    for e in (Lk - 1, 63, 64, 0, 65, Lk - 65, Lk - 64):
+        if 0 <= e < Lk and e not in out:
+            out.append(e)
+    return out
+
+
+def attn_inputs(kind, nb, heads, hd, Lq, Lk, seed):
+    """q [nb, heads, Lq, hd], k and v [nb, heads, Lk, hd] float32.
+      randn     unit normal
+      peaked    q x 8: a few keys hold a row's weight
+      overflow  q x 40, k x 3: logits in the hundreds -- exp without the max subtraction overflows
+      same      every key of a (batch, head) identical: the output is the mean of v
+      widev     v x e^U(-10, 10), element-wise: nine decades of magnitude in one sum
+      edge      randn, then the first rows of every (batch, head) each own one key of attn_edges(Lk), cycling over (batch, head,
+                row) so that every edge key is owned somewhere: the key is set to alpha q_i sqrt(hd) / |q_i|^2, its logit alpha =
+                the log-sum-exp of the row's other randn logits, so that it holds about half of the row's weight (about: the
+                keys that other rows of the same (batch, head) own are set afterwards and take a little of it).  Dropping, misplacing or
+                mis-scaling that key then moves the row by a large part of |v| -- where a one-hot row or a row of Lk equal weights
+                moves by nothing, or by 1 / Lk."""
+    assert kind in ATTN_KINDS
+    g = torch.Generator().manual_seed(seed)
+    q = torch.randn(nb, heads, Lq, hd, generator=g)
+    k = torch.randn(nb, heads, Lk, hd, generator=g)
+    v = torch.randn(nb, heads, Lk, hd, generator=g)
+    if kind == "peaked":
+        q = q * 8
+    elif kind == "overflow":
+        q, k = q * 40, k * 3
+    elif kind == "same":
+        k = k[:, :, :1].expand(nb, heads, Lk, hd).contiguous()
+    elif kind == "widev":
+        v = v * torch.exp(torch.rand(nb, heads, Lk, hd, generator=g) * 20 - 10)
+    elif kind == "edge" and Lk >= 2:
+        edges = attn_edges(Lk)
+        n = min(Lq, len(edges))
+        qs = (q[:, :, :n] * torch.tensor(1.0 / np.sqrt(hd), dtype=torch.float32)).double()
+        s = qs @ k.double().transpose(-1, -2)                             # the randn keys' logits [nb, heads, n, Lk]
+        own = (torch.arange(n).view(1, 1, n) + (torch.arange(nb).view(nb, 1, 1) * heads + torch.arange(heads).view(1, heads, 1)) * n) % len(edges)
+        own = torch.tensor(edges)[own]                                    # [nb, heads, n] the key row i owns
+        alpha = torch.logsumexp(s.scatter(-1, own.unsqueeze(-1), float("-inf")), -1)
+        q64 = q[:, :, :n].double()
+        new = (alpha * np.sqrt(hd) / (q64 * q64).sum(-1)).unsqueeze(-1) * q64                      # [nb, heads, n, hd]
+        k = k.scatter(2, own.unsqueeze(-1).expand(nb, heads, n, hd), new.float())
+    return q.contiguous(), k.contiguous(), v.contiguous()
+
+
+def attn_layout(view, outer, inner, heads, hd, Lq, Lk, odd_out=False):
+    """Where q, k, v and the output live for one call.  -> dict: sizes {buffer: floats}, where {q|k|v: (buffer, offset)}, strides
+    (the op's 12), out_size.  Everything a buffer holds beside the operands is NaN (attn_pack), everything the output buffer holds
+    beside the [Lq, heads * hd] block of each batch a sentinel: gap columns, and rows past Lq / Lk inside the allocation.
+      plain    q [nb, Lq, E], k and v [nb, Lk, E], contiguous
+      wide     the same three, each inside wider rows (ld = E + 8 | E + 4 | E + 12, at column 4 | 0 | 8) with 2 | 2 | 1 rows past the end
+      qkv      packed [nb, Lk + 1, 3 E]: q = f, k = f[E:], v = f[2E:], ld 3 E (roi_heads._attend); the queries are the first Lq rows
+      kv       q [nb, Lq, E]; k = f, v = f[E:] of [nb, Lk, 2 E] (the matcher decoder's cross attention)
+      swapped  packed [outer, Lk, inner, 3 E]: sequences run over dim 1, batched over (outer, inner) with different strides and no
+               transpose (the DeepSolo decoder's inter-instance attention); the output likewise
+    The output has rows of E + 4 floats (E + 1 with odd_out) and one row past Lq per batch."""
+    E, nb = heads * hd, outer * inner
+    if view in ("plain", "wide"):
+        ld, col, extra = ((E, E, E), (0, 0, 0), (0, 0, 0)) if view == "plain" else ((E + 8, E + 4, E + 12), (4, 0, 8), (2, 2, 1))
+        rows = (Lq + extra[0], Lk + extra[1], Lk + extra[2])
+        sizes = {n: nb * r * l for n, r, l in zip("qkv", rows, ld)}
+        where = {n: (n, c) for n, c in zip("qkv", col)}
+        st = [x for r, l in zip(rows, ld) for x in (inner * r * l, r * l, l)]
+    elif view == "kv":
+        sizes = {"q": nb * Lq * E, "f": nb * Lk * 2 * E}
+        where = {"q": ("q", 0), "k": ("f", 0), "v": ("f", E)}
+        st = [inner * Lq * E, Lq * E, E] + [inner * Lk * 2 * E, Lk * 2 * E, 2 * E] * 2
+    elif view == "qkv":
+        assert Lq <= Lk
+        ld, R = 3 * E, Lk + 1
+        sizes = {"f": nb * R * ld}
+        where = {"q": ("f", 0), "k": ("f", E), "v": ("f", 2 * E)}
+        st = [inner * R * ld, R * ld, ld] * 3
+    else:
+        assert view == "swapped" and Lq <= Lk
+        ld = 3 * E
+        sizes = {"f": outer * Lk * inner * ld}
+        where = {"q": ("f", 0), "k": ("f", E), "v": ("f", 2 * E)}
+        st = [Lk * inner * ld, ld, inner * ld] * 3
+    ldo, Ro = E + (1 if odd_out else 4), Lq + 1
+    st += [Ro * inner * ldo, ldo, inner * ldo] if view == "swapped" else [inner * Ro * ldo, Ro * ldo, ldo]
+    return {"sizes": sizes, "where": where, "strides": st, "out_size": nb * Ro * ldo}
+
+
+def attn_pack(lay, q, k, v, outer, inner):
+    """The layout's buffers {name: flat float32}, NaN outside the operands."""
+    bufs = {n: torch.full((s,), float("nan")) for n, s in lay["sizes"].items()}
+    for i, (n, x) in enumerate((("q", q), ("k", k), ("v", v))):
+        name, off = lay["where"][n]
+        st = lay["strides"][3 * i:3 * i + 3]
+        _, heads, L, hd = x.shape
+        bufs[name][attn_index(off, st[0], st[1], st[2], outer, inner, heads, hd, L).reshape(-1)] = x.reshape(-1)
+    return bufs
+
+
+class AttnCase:
+    """One call of the GPU file: `form` is the kernel the shape is meant to reach (csrc/attn.hip, gom_mha_core_f32)."""
+
+    def __init__(self, form, hd, Lq, Lk, view, heads=2, outer=2, inner=1, odd_out=False, kinds=ATTN_KINDS):
+        if view == "swapped":                                             # the decoder's view: batch = outer x inner = 2 x 3
+            outer, inner = 2, 3
+        self.form, self.hd, self.Lq, self.Lk, self.view, self.heads = form, hd, Lq, Lk, view, heads
+        self.outer, self.inner, self.odd_out, self.kinds = outer, inner, odd_out, kinds
+        self.id = "%s-%dx%d-%s%s%s" % (form, Lq, Lk, view, "-odd" if odd_out else "", "-b%d" % outer if outer != 2 else "")
+
+    def inputs(self, kind):
+        seed = 1000 * ATTN_KINDS.index(kind) + 7 * self.Lq + 13 * self.Lk + self.hd + len(self.view)
+        return attn_inputs(kind, self.outer * self.inner, self.heads, self.hd, self.Lq, self.Lk, seed)
+
+    def layout(self):
+        return attn_layout(self.view, self.outer, self.inner, self.heads, self.hd, self.Lq, self.Lk, self.odd_out)
+
+
+def _attn_cases():
+    """Per form, the smallest shapes on either side of every limit of gom_mha_core_f32's choice (launch<HD, QT>'s LDS formula
+    4 (QT HD + 64 (HD + 4) + QT Lkp) <= 160 KiB, Lkp = Lk rounded up to 64: <32,32> to Lk 1152, <32,8> to 4800, <128,32> to 832,
+    <128,8> to 3904; the row-per-lane kernel to Lq 512 and Lk 512, its 64 KiB attribute call from Lk 257), on the tile edges
+    63 / 64 / 65, and on every view of attn_layout at least once per form."""
+    C = AttnCase
+    rows = [C("rows32", 32, 1, 1, "swapped"), C("rows32", 32, 25, 25, "qkv"), C("rows32", 32, 25, 25, "swapped"),
+            C("rows32", 32, 63, 5, "kv"), C("rows32", 32, 64, 64, "wide"), C("rows32", 32, 65, 65, "swapped"),
+            C("rows32", 32, 512, 7, "plain"), C("rows32", 32, 7, 256, "wide"), C("rows32", 32, 7, 257, "qkv"),
+            C("rows32", 32, 3, 512, "kv")]
+    t3232 = [C("tile32x32", 32, 513, 5, "kv"), C("tile32x32", 32, 3, 513, "wide"), C("tile32x32", 32, 33, 1152, "qkv"),
+             C("tile32x32", 32, 25, 25, "plain", odd_out=True), C("tile32x32", 32, 25, 25, "swapped", odd_out=True)]
+    t328 = [C("tile32x8", 32, 9, 1153, "wide"), C("tile32x8", 32, 9, 1153, "swapped"), C("tile32x8", 32, 3, 4800, "kv"),
+            C("tile32x8", 32, 3, 4800, "qkv")]
+    tiny = [C("tiny128", 128, 1, 1, "swapped", heads=8), C("tiny128", 128, 9, 9, "qkv", heads=8),
+            C("tiny128", 128, 53, 53, "swapped", heads=8), C("tiny128", 128, 5, 63, "kv", heads=8),
+            C("tiny128", 128, 5, 64, "wide", heads=8), C("tiny128", 128, 70, 64, "plain", heads=8),
+            C("tiny128", 128, 64, 64, "plain", heads=8, outer=128, kinds=("randn", "edge"))]          # 65536 waves: the last tiny
+    t12832 = [C("tile128x32", 128, 5, 65, "kv"), C("tile128x32", 128, 33, 128, "qkv"), C("tile128x32", 128, 31, 129, "swapped"),
+              C("tile128x32", 128, 3, 832, "wide"),
+              C("tile128x32", 128, 64, 64, "plain", heads=8, outer=129, kinds=("randn", "edge"))]    # 66048 waves > 65536
+    t1288 = [C("tile128x8", 128, 9, 833, "wide"), C("tile128x8", 128, 9, 833, "swapped"), C("tile128x8", 128, 3, 3904, "kv"),
+             C("tile128x8", 128, 3, 3904, "qkv")]
+    return rows + t3232 + t328 + tiny + t12832 + t1288
+
+
+ATTN_CASES = _attn_cases()
+# gom_mha_core_segments_f32: (Lq, Lk) of the ragged call's segments; an empty query range and an empty key range among them
+ATTN_SEGMENTS = [(14, 14), (1, 10), (71, 103), (33, 33), (0, 5), (4, 0)]
+ATTN_SEGMENT_KINDS = ("randn", "overflow", "edge")
+
+
+def attn_segment_inputs(kind, s):
+    """Segment s of ATTN_SEGMENTS: attn_inputs for one batch, 2 heads x 128."""
+    Lq, Lk = ATTN_SEGMENTS[s]
+    return attn_inputs(kind, 1, 2, 128, Lq, Lk, 500 + 10 * s + ATTN_KINDS.index(kind))
