@@ -16,7 +16,9 @@ the call sites that walk the module tree keep working unchanged --
 Inference calls (`batch_inference`, `inference`, `_remove_short_track`, `batch_postprocess`, `run_*_match`, `min_track_len`)
 go to the HIP implementation, which is (re)built from the CURRENT parameter values whenever they changed since the last
 build.  `forward(batched_inputs)` is the reference's training entry (gom_lstmatcher.py:213-266): losses of the trainable
-head (`gomatching_amd/training.py`)."""
+head (`gomatching_amd/training.py`).  In train() mode with MODEL.ASSO_HEAD.DROPOUT > 0 the model owns the dropout mask stream
+(`training.DropoutState`): seed = cfg.SEED (drawn once and printed when absent or negative), rank = torch.distributed's, and
+an iteration count that advances once per `forward`.  eval() mode never drops."""
 import torch
 from torch import nn
 
@@ -86,6 +88,23 @@ class GoMatchingMI355X(nn.Module):
         self._impl = None
         self._impl_version = None
         self._device = torch.device(self.cfg.MODEL.DEVICE if self.cfg.MODEL.DEVICE != "cpu" else "cpu")
+        self._dropout = None                                     # made by the first training forward
+        self._forwards = 0
+
+    @property
+    def dropout_state(self):
+        """The mask stream of the training forward (what `training.forward_losses` reads); None in eval() mode or at DROPOUT 0."""
+        p = self.cfg.MODEL.ASSO_HEAD.DROPOUT
+        if not self.training or not p > 0:
+            return None
+        from .. import training
+        if self._dropout is None:
+            seed = self.cfg.get("SEED", -1)
+            if seed is None or int(seed) < 0:
+                seed = training.new_dropout_seed()
+                print("MODEL.ASSO_HEAD.DROPOUT = %g, dropout seed %d" % (p, seed))
+            self._dropout = training.DropoutState(p, int(seed), self._forwards, training.distributed_rank())
+        return self._dropout
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, state_dict, strict=False, assign=False):
@@ -149,6 +168,11 @@ class GoMatchingMI355X(nn.Module):
             raise RuntimeError("inference goes through batch_inference / inference (gom_lstmatcher.py:268,366), as in the "
                                "reference; forward() is the training entry")
         from .. import training
+        state = self.dropout_state
+        if state is not None:
+            state.rank = training.distributed_rank()             # the process group may have come up after construction
+            state.begin_forward(self._forwards)
+        self._forwards += 1
         return training.forward_losses(self, batched_inputs)
 
 

@@ -18,6 +18,8 @@ I = c_int
 L = c_long
 F = c_float
 D = ctypes.c_double
+U = ctypes.c_uint
+U64 = ctypes.c_ulonglong
 
 
 class OptimTensor(ctypes.Structure):
@@ -113,6 +115,10 @@ SIGNATURES = {
     "gom_softmax_rows_backward_f32": (I, [P, P, P, L, I, L, F, P]),
     "gom_asso_ce_f32": (I, [P, I, P, I, P, L, P, P, P, P]),
     "gom_sigmoid_focal_f32": (I, [P, P, F, F, L, P, P, P]),
+    "gom_dropout_f32": (I, [P, L, P, L, P, L, L, L, U64, U, U, U, L, F, P]),
+    "gom_relu_backward_scaled_f32": (I, [P, P, P, L, F, P]),
+    "gom_softmax_dropout_rows_f32": (I, [P, P, L, I, L, F, L, U64, U, U, U, L, F, P]),
+    "gom_softmax_dropout_rows_backward_f32": (I, [P, P, P, L, I, L, F, L, U64, U, U, U, L, F, P]),
     "gom_clipped_adamw_partials": (L, [P, I]),
     "gom_clipped_adamw_step": (I, [P, I, D, D, D, D, P, L, P, P]),
     "gom_layernorm_f32": (I, [P, P, P, P, P, L, I, F, P]),

@@ -1805,6 +1805,73 @@ def softmax_rows_backward(P, dP, cols, scale):
     return dS
 
 
+def dropout_args(p, seed, site, iteration, rank):
+    """The stream arguments every dropout entry point takes, from (p, seed, site, iteration, rank): threshold = floor(p 2^32) in
+    double and scale = float(1 / (1 - p)), formed here once (include/gomatching_hip.h; the library refuses p outside [0, 1))."""
+    p = float(p)
+    scale = 1.0 / (1.0 - p) if p < 1.0 else float("inf")
+    return (int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), int(iteration), int(rank), int(math.floor(p * 4294967296.0)), scale)
+
+
+def _row_view(t):
+    """A 2-D row-strided fp32 view of `t` for the dropout kernels: 1-D and contiguous tensors as they are laid out."""
+    assert t.dtype == _f32 and t.is_cuda
+    if t.dim() != 2:
+        assert t.is_contiguous()
+        t = t.view(1, -1) if t.dim() < 2 else t.view(-1, t.shape[-1])
+    assert t.stride(1) == 1 or t.shape[1] <= 1
+    return t
+
+
+def dropout(x, stream, residual=None, out=None):
+    """out = [residual +] mask * scale * x with the mask of `stream` = (p, seed, site, iteration, rank) over the LOGICAL elements
+    of x (row * cols + col): 2-D row-strided views of any leading dimension and alignment give the same bits.  Also the backward:
+    dx = dropout(dy, same stream).  `out` may be x."""
+    xv = _row_view(x)
+    rows, cols = xv.shape
+    if out is None:
+        out = torch.empty(x.shape, dtype=_f32, device=x.device)
+    ov = _row_view(out)
+    rv = None if residual is None else _row_view(residual)
+    assert ov.shape == xv.shape and (rv is None or rv.shape == xv.shape)
+    ld = lambda t: max(t.stride(0), cols) if rows > 1 else cols
+    check(_L().gom_dropout_f32(_p(xv), ld(xv), _p(rv), 0 if rv is None else ld(rv), _p(ov), ld(ov), rows, cols,
+                               *dropout_args(*stream), _stream()), "gom_dropout_f32")
+    return out
+
+
+def relu_backward_scaled(dy, y, scale):
+    """dx = y > 0 ? dy * scale : 0 (ReLU's backward behind a dropout whose output y was saved)."""
+    _chk_f32(dy, y)
+    dx = torch.empty_like(dy)
+    check(_L().gom_relu_backward_scaled_f32(_p(dy), _p(y), _p(dx), dy.numel(), float(scale), _stream()),
+          "gom_relu_backward_scaled_f32")
+    return dx
+
+
+def softmax_dropout_rows_(x, cols, scale, stream, elem0=0):
+    """In place over the first `cols` columns of a 2-D row-strided view: x <- P = softmax(scale x) (the bits of
+    `softmax_rows_scaled_`); returns the dropped weights mask * scale_p * P in a tensor of x's shape whose other columns are
+    zero.  Row r covers the logical elements elem0 + r cols ... of `stream` = (p, seed, site, iteration, rank)."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == _f32
+    pd = torch.zeros_like(x)
+    assert pd.stride() == x.stride()
+    check(_L().gom_softmax_dropout_rows_f32(_p(x), _p(pd), x.shape[0], cols, x.stride(0), float(scale), int(elem0),
+                                            *dropout_args(*stream), _stream()), "gom_softmax_dropout_rows_f32")
+    return pd
+
+
+def softmax_dropout_rows_backward(P, dPd, cols, scale, stream, elem0=0):
+    """dS = scale * P * (G - rowsum(G * P)) with G = mask * scale_p * dPd, the mask of `stream` regenerated in the kernel."""
+    assert P.shape == dPd.shape and P.stride() == dPd.stride() and P.stride(1) == 1
+    dS = torch.zeros_like(P)
+    assert dS.stride() == P.stride()
+    check(_L().gom_softmax_dropout_rows_backward_f32(_p(P), _p(dPd), _p(dS), P.shape[0], cols, P.stride(0), float(scale),
+                                                     int(elem0), *dropout_args(*stream), _stream()),
+          "gom_softmax_dropout_rows_backward_f32")
+    return dS
+
+
 def asso_ce(logits, frame_offsets, gt, want_loss=True, grad_scale=None):
     """Per (row, frame) cross entropy with a zero background logit (lstmatcher.py:436-475) -> loss [rows, T] and / or
     dlogits = grad_scale * (softmax - onehot); gt int32 [rows, T] (index in frame | n_t = background | -1 = not counted)."""

@@ -17,8 +17,11 @@ detectron2/solver/build.py, fvcore/common/param_scheduler.py), as `Boxes` / `nms
 compares them with a Detectron2 run.  The optimizer arithmetic IS pinned: tests/golden/solver_adamw.npz holds what the
 reference's own optimizer class computes (tools/gen_golden_solver.py).
 
-The training forward runs with eval-mode dropout (training.py, `_mha`) while the configs train with `ASSO_HEAD.DROPOUT 0.1`:
-`Trainer` says so once.
+`MODEL.ASSO_HEAD.DROPOUT` (0.1 in every shipped config) is applied by the training forward at the reference's sites
+(training.py, `matcher_transformer`; csrc/dropout.hip).  The mask stream is this project's own -- the reference's distribution,
+not torch's bits: a counter-based generator keyed by the trainer's `seed` and indexed by (site, iteration, rank), so a resumed
+run reproduces an uninterrupted one and ranks draw different masks.  `Trainer` prints p and the seed once and keeps the seed
+in its checkpoints ("dropout_seed").
 """
 import math
 import os
@@ -192,8 +195,9 @@ def build_optimizer(cfg, named_parameters):
     return ClippedAdamW(groups, S.BASE_LR, weight_decay=S.WEIGHT_DECAY, clip_value=clip)
 
 
-def save_checkpoint(path, model_state, optimizer_state=None, iteration=0):
-    """Write {"model", "optimizer", "iteration"} with torch.save: `model_state` = the FULL state dict (frozen detector + current
+def save_checkpoint(path, model_state, optimizer_state=None, iteration=0, dropout_seed=None):
+    """Write {"model", "optimizer", "iteration"} (and "dropout_seed" when the run drops) with torch.save: `model_state` = the
+    FULL state dict (frozen detector + current
     head) as {canonical key: tensor or array}, stored as CPU tensors -- what `eval.load_weights` / `normalize_state_dict` read,
     and the layout Detectron2's checkpointer writes."""
     import numpy as np
@@ -203,7 +207,10 @@ def save_checkpoint(path, model_state, optimizer_state=None, iteration=0):
         model[k] = t.detach().cpu().clone()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = path + ".tmp"
-    torch.save({"model": model, "optimizer": optimizer_state, "iteration": int(iteration)}, tmp)
+    ck = {"model": model, "optimizer": optimizer_state, "iteration": int(iteration)}
+    if dropout_seed is not None:
+        ck["dropout_seed"] = int(dropout_seed)
+    torch.save(ck, tmp)
     os.replace(tmp, path)
     return path
 
@@ -219,9 +226,13 @@ class Trainer:
 
     Mirrored: the rescoring-head rule of :97-105 (the head starts from the detector's `ctrl_point_class` unless '_rescore' is
     in MODEL.WEIGHTS, in which case it is frozen), INFERENCE_TH_TEST = INFERENCE_TH_TRAIN (:167), the finite check (:125),
-    a checkpoint every CHECKPOINT_PERIOD iterations and at the end, `max_iter` = TRAIN_ITER when >= 0."""
+    a checkpoint every CHECKPOINT_PERIOD iterations and at the end, `max_iter` = TRAIN_ITER when >= 0.
 
-    def __init__(self, cfg, model, output_dir, inference_th_train=0.3):
+    `seed`: the seed of the dropout mask stream (MODEL.ASSO_HEAD.DROPOUT > 0; training.DropoutState).  None = `cfg.SEED` when
+    the config has one >= 0, else drawn once from the operating system and printed.  It is written into every checkpoint and
+    restored by `resume()`, so that iteration i of a resumed run draws the masks iteration i of the uninterrupted run drew."""
+
+    def __init__(self, cfg, model, output_dir, inference_th_train=0.3, seed=None):
         self.cfg, self.model, self.output_dir = cfg, model, output_dir
         self.solver = S = solver_cfg(cfg)
         self.max_iter = S.MAX_ITER if S.TRAIN_ITER < 0 else S.TRAIN_ITER
@@ -244,9 +255,16 @@ class Trainer:
                     params["roi_heads.rescoring_head." + leaf].requires_grad_(False)
                     self.frozen_keys.add("roi_heads.rescoring_head." + leaf)
                 print("using trained rescoring head")
+        self.seed, self.dropout = seed, None
         if cfg.MODEL.ASSO_HEAD.DROPOUT > 0:
-            print("note: MODEL.ASSO_HEAD.DROPOUT = %g, but the training forward of the head runs with eval-mode dropout "
-                  "(no dropout kernels yet)" % cfg.MODEL.ASSO_HEAD.DROPOUT)
+            from . import training
+            if seed is None:
+                seed = cfg.get("SEED", -1)
+                seed = training.new_dropout_seed() if seed is None or int(seed) < 0 else seed
+            self.seed = int(seed)
+            self.dropout = training.DropoutState(cfg.MODEL.ASSO_HEAD.DROPOUT, self.seed, 0, training.distributed_rank())
+            print("MODEL.ASSO_HEAD.DROPOUT = %g, dropout seed %d" % (self.dropout.p, self.seed))
+        model.dropout_state = self.dropout                       # what training.forward_losses reads
         self.params = params
         self.optimizer = build_optimizer(cfg, params.items())
         for g in self.optimizer.param_groups:
@@ -263,6 +281,8 @@ class Trainer:
 
     def step(self, batched_inputs):
         from . import training
+        if self.dropout is not None:
+            self.dropout.begin_forward(self.iteration)
         losses = training.forward_losses(self.model, batched_inputs)
         total = sum(v for k, v in losses.items() if "loss" in k)
         if not bool(torch.isfinite(total).all()):
@@ -292,14 +312,16 @@ class Trainer:
 
     def save(self, name="model_final.pth"):
         path = name if os.path.isabs(name) else os.path.join(self.output_dir, name)
-        save_checkpoint(path, self.state_dict(), self.optimizer.state_dict(), self.iteration - 1)
+        save_checkpoint(path, self.state_dict(), self.optimizer.state_dict(), self.iteration - 1,
+                        self.seed if self.dropout is not None else None)
         with open(os.path.join(os.path.dirname(path), "last_checkpoint"), "w") as f:
             f.write(os.path.basename(path))
         return path
 
     def resume(self, path=None):
         """Continue from a checkpoint written by `save()` (default: the one `last_checkpoint` names): head weights, optimizer
-        state and the iteration count.  Returns the iteration training continues at."""
+        state, the iteration count and the dropout seed (a checkpoint without one keeps this trainer's own).  Returns the iteration
+        training continues at."""
         if path is None:
             with open(os.path.join(self.output_dir, "last_checkpoint")) as f:
                 path = os.path.join(self.output_dir, f.read().strip())
@@ -311,6 +333,10 @@ class Trainer:
         for g in self.optimizer.param_groups:
             g.setdefault("initial_lr", g["lr"])
         self.iteration = int(ck.get("iteration", -1)) + 1
+        if ck.get("dropout_seed") is not None:
+            self.seed = int(ck["dropout_seed"])
+            if self.dropout is not None:
+                self.dropout.seed = self.seed
         self._set_lr()
         return self.iteration
 

@@ -3,7 +3,9 @@
 Two halves.  Host: the integer ground-truth logic that turns proposals + annotated instances into association targets and the
 Hungarian matching of `loss_res` (numpy + the library's LSA).  Device (second half of this file): the training forward of
 the trainable head with saved activations, its backward on HIP kernels, the loss dict of `GoMatching.forward`, and the
-gradient all-reduce.  Losses AND gradients are pinned against the reference's own (`tests/golden/train_*.npz`).
+gradient all-reduce.  Losses AND gradients are pinned against the reference's own (`tests/golden/train_*.npz`), at
+`MODEL.ASSO_HEAD.DROPOUT 0`; with dropout the forward follows the reference's sites and torch's semantics on a mask stream of its
+own (`DropoutState`, csrc/dropout.hip; INTEGRATION.md "Dropout"), pinned by a float64 restatement (tests/dropout_statement.py).
 
 `association_targets` mirrors `LSTMatcher._get_asso_gt` (lstmatcher.py:388-433; identical in shared_ffn_crsattn.py) on
 numpy arrays: it is bookkeeping over at most a few hundred boxes per clip and stays on the host, as the id logic of the
@@ -96,8 +98,9 @@ def point_matching(re_logits, pred_ctrl_points, target_ctrl_points, focal_alpha=
 # the matcher transformer(s) and the rescoring head.  Every contraction of the forward AND of the backward (dgrad = dY W,
 # wgrad = dY^T X, bias grad = dY^T 1) runs on the library's exact-fp32 MFMA GEMM (`gom_gemm_f32` / its split-K form) with
 # transposed operands made by `gom_transpose_f32`; attention is the same GEMM per head around `gom_softmax_rows_scaled_f32`
-# and its backward kernel; the losses are `gom_asso_ce_f32` / `gom_sigmoid_focal_f32` (csrc/train.hip).  torch supplies
-# device memory, the autograd tape that strings the kernels together, and the glue around them (concatenation, zero-padded
+# and its backward kernel; MODEL.ASSO_HEAD.DROPOUT is applied at the reference's sites by the kernels of csrc/dropout.hip on
+# a counter-based mask stream (`DropoutState`: the reference's distribution, a stream of our own); the losses are
+# `gom_asso_ce_f32` / `gom_sigmoid_focal_f32` (csrc/train.hip).  torch supplies device memory, the autograd tape that strings the kernels together, and the glue around them (concatenation, zero-padded
 # copies, the arithmetic on the 0-d loss values).
 # Pinned by the reference's own losses AND gradients (tests/golden/train_asso_*.npz, train_res_ic15.npz;
 # tests/test_training_gpu.py).
@@ -105,6 +108,53 @@ def point_matching(re_logits, pred_ctrl_points, target_ctrl_points, focal_alpha=
 def _torch():
     import torch
     return torch
+
+
+class DropoutState:
+    """Where the training forward is in the dropout mask stream ("Dropout"; csrc/dropout.hip).  The mask of a
+    dropout application is a pure function of (seed, site, iteration, rank) and the logical element index: `site` counts the
+    applications of one `forward_losses` call in call order, from 0; `iteration` is the trainer's; `rank` is
+    torch.distributed's (0 in a single process).  Nothing is stored: the backward regenerates each mask from the tuple that
+    the forward kept, a resumed run (same seed, same iteration) reproduces an uninterrupted one, ranks draw different masks."""
+
+    def __init__(self, p, seed, iteration=0, rank=0):
+        p = float(p)
+        if not 0.0 <= p < 1.0:
+            raise ValueError("DropoutState: p = %r is not in [0, 1)" % (p,))
+        self.p, self.seed, self.rank = p, int(seed) & 0xFFFFFFFFFFFFFFFF, int(rank)
+        self.begin_forward(iteration)
+
+    def begin_forward(self, iteration):
+        """Start the sites of a forward at 0, in iteration `iteration`."""
+        self.iteration, self.site = int(iteration), 0
+
+    def next_site(self):
+        site = self.site
+        self.site += 1
+        return site
+
+    def next_stream(self):
+        """(p, seed, site, iteration, rank) of the next dropout application: what `ops.dropout` and its kin take."""
+        return (self.p, self.seed, self.next_site(), self.iteration, self.rank)
+
+    @property
+    def active(self):
+        return self.p > 0.0
+
+
+def _active(dropout):
+    return dropout if (dropout is not None and dropout.active) else None
+
+
+def new_dropout_seed():
+    """A seed for a run whose config gives none (SEED < 0 or absent): 63 bits from the operating system, drawn once."""
+    import os
+    return int.from_bytes(os.urandom(8), "little") >> 1
+
+
+def distributed_rank():
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
 def _pad4(n):
@@ -127,6 +177,27 @@ def _make_functions():
     torch = _torch()
     from . import ops
 
+    def linear_grads(ctx, x, w, dy, extra):
+        """dgrad / wgrad / bias grad of y = x W^T + b for the incoming (activation-corrected) dy; `extra` Nones follow."""
+        M, N = dy.shape
+        dx = dw = db = None
+        if M == 0:
+            return (torch.zeros_like(x), torch.zeros_like(w), (torch.zeros((N,), device=w.device) if ctx.has_b else None)) + extra
+        if ctx.needs_input_grad[0]:
+            dyp = dy
+            if N % 4:                                                                             # the GEMM wants K % 4 == 0
+                dyp = torch.zeros((M, _pad4(N)), dtype=torch.float32, device=dy.device)
+                dyp[:, :N] = dy
+            dx = ops.gemm(dyp, _transpose_padded(w))                                              # dY W   (K = pad4(N))
+        dyT = _transpose_padded(dy)                                                               # [N, Mp]
+        if ctx.needs_input_grad[1]:
+            dw = ops.gemm(dyT, _transpose_padded(x))                                              # dY^T X (K = Mp)
+        if ctx.has_b and ctx.needs_input_grad[2]:
+            ones = torch.zeros((1, dyT.shape[1]), dtype=torch.float32, device=dy.device)
+            ones[:, :M] = 1.0
+            db = ops.gemm(dyT, ones).view(N)
+        return (dx, dw, db) + extra
+
     class Linear(torch.autograd.Function):
         """y = act(x W^T + b); x [M, K] row-strided, W [N, K]."""
 
@@ -143,24 +214,45 @@ def _make_functions():
             dy = dy.contiguous()
             if ctx.relu:
                 dy = ops.relu_backward(dy, y)
-            M, N = dy.shape
-            dx = dw = db = None
-            if M == 0:
-                return torch.zeros_like(x), torch.zeros_like(w), (torch.zeros((N,), device=w.device) if ctx.has_b else None), None
-            if ctx.needs_input_grad[0]:
-                dyp = dy
-                if N % 4:                                                                             # the GEMM wants K % 4 == 0
-                    dyp = torch.zeros((M, _pad4(N)), dtype=torch.float32, device=dy.device)
-                    dyp[:, :N] = dy
-                dx = ops.gemm(dyp, _transpose_padded(w))                                              # dY W   (K = pad4(N))
-            dyT = _transpose_padded(dy)                                                               # [N, Mp]
-            if ctx.needs_input_grad[1]:
-                dw = ops.gemm(dyT, _transpose_padded(x))                                              # dY^T X (K = Mp)
-            if ctx.has_b and ctx.needs_input_grad[2]:
-                ones = torch.zeros((1, dyT.shape[1]), dtype=torch.float32, device=dy.device)
-                ones[:, :M] = 1.0
-                db = ops.gemm(dyT, ones).view(N)
-            return dx, dw, db, None
+            return linear_grads(ctx, x, w, dy, (None,))
+
+    class LinearReluDrop(torch.autograd.Function):
+        """y = dropout(relu(x W^T + b)) (the FFN's `dropout(activation(linear1(.)))`): the dropout runs in place on the GEMM's
+        output, and that DROPPED y is all the backward needs -- it is positive exactly where the unit was active and kept, so
+        d = dy * scale * (y > 0) regenerates no mask."""
+
+        @staticmethod
+        def forward(ctx, x, w, b, stream):
+            y = ops.gemm(x, w, bias=b, relu=True)
+            if y.numel():
+                ops.dropout(y, stream, out=y)
+            ctx.save_for_backward(x, w, y)
+            ctx.has_b, ctx.drop_scale = b is not None, ops.dropout_args(*stream)[5]
+            return y
+
+        @staticmethod
+        def backward(ctx, dy):
+            x, w, y = ctx.saved_tensors
+            dy = ops.relu_backward_scaled(dy.contiguous(), y, ctx.drop_scale)
+            return linear_grads(ctx, x, w, dy, (None,))
+
+    class DropAdd(torch.autograd.Function):
+        """r + dropout(x) in one pass (`src + dropoutN(x)`; r = None: dropout(x) alone); the backward hands dy to r and
+        mask * scale * dy, the mask regenerated from the stream tuple, to x."""
+
+        @staticmethod
+        def forward(ctx, r, x, stream):
+            ctx.stream = stream
+            x = x.contiguous()
+            r = None if r is None else r.contiguous()
+            if x.numel() == 0:
+                return x.clone() if r is None else r.clone()
+            return ops.dropout(x, stream, residual=r)
+
+        @staticmethod
+        def backward(ctx, g):
+            g = g.contiguous()
+            return (g if ctx.needs_input_grad[0] else None), (ops.dropout(g, ctx.stream) if g.numel() else g), None
 
     class Attention(torch.autograd.Function):
         """softmax(q k^T / sqrt(hd)) v per head for ONE sequence pair: q [Lq, E], k, v [Lk, E] (nn.MultiheadAttention core,
@@ -207,6 +299,60 @@ def _make_functions():
                 ops.gemm(_transpose_padded(dS[:, :Lk]), _transpose_padded(q[:, c]), out=dk[:, c])     # dS^T q_h (K = Lqp)
             return dq, dk, dv, None
 
+    class AttentionDrop(torch.autograd.Function):
+        """`Attention` with dropout on the weights after the softmax (inside nn.MultiheadAttention): out = P~ v with
+        P~ = mask * scale * P over the logical [heads, Lq, Lk] tensor -- ONE stream for all heads, each head its own slice of
+        it.  The softmax of all heads is one launch that leaves both P (saved: the softmax backward needs the undropped
+        weights) and P~; the backward regenerates P~ from P and applies the mask to the incoming dP~ inside its kernel."""
+
+        @staticmethod
+        def forward(ctx, q, k, v, heads, stream):
+            Lq, E = q.shape
+            Lk = k.shape[0]
+            hd = E // heads
+            Lkp = _pad4(Lk)
+            out = torch.zeros((Lq, E), dtype=torch.float32, device=q.device)
+            P = torch.zeros((heads, Lq, Lkp), dtype=torch.float32, device=q.device)
+            scale = 1.0 / math.sqrt(hd)
+            if Lq and Lk:
+                for h in range(heads):
+                    c = slice(h * hd, (h + 1) * hd)
+                    ops.gemm(q[:, c], k[:, c], out=P[h][:, :Lk])                                       # q_h k_h^T
+                Pd = ops.softmax_dropout_rows_(P.view(heads * Lq, Lkp), Lk, scale, stream).view(heads, Lq, Lkp)
+                for h in range(heads):
+                    c = slice(h * hd, (h + 1) * hd)
+                    ops.gemm(Pd[h], _transpose_padded(v[:, c]), out=out[:, c])                        # P~ v_h  (K = Lkp)
+            ctx.save_for_backward(q, k, v, P)
+            ctx.heads, ctx.scale, ctx.stream = heads, scale, stream
+            return out
+
+        @staticmethod
+        def backward(ctx, do):
+            q, k, v, P = ctx.saved_tensors
+            heads, scale = ctx.heads, ctx.scale
+            Lq, E = q.shape
+            Lk = k.shape[0]
+            hd = E // heads
+            Lkp = _pad4(Lk)
+            dq, dk, dv = torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v)
+            if Lq == 0 or Lk == 0:
+                return dq, dk, dv, None, None
+            do = do.contiguous()
+            P2 = P.view(heads * Lq, Lkp)
+            Pd = torch.zeros_like(P)
+            ops.dropout(P2[:, :Lk], ctx.stream, out=Pd.view(heads * Lq, Lkp)[:, :Lk])                 # P~ again, from P
+            dPd = torch.zeros_like(P)
+            for h in range(heads):
+                c = slice(h * hd, (h + 1) * hd)
+                ops.gemm(_transpose_padded(Pd[h][:, :Lk]), _transpose_padded(do[:, c]), out=dv[:, c])  # P~^T dO (K = Lqp)
+                ops.gemm(do[:, c], v[:, c], out=dPd[h][:, :Lk])                                       # dO v_h^T
+            dS = ops.softmax_dropout_rows_backward(P2, dPd.view(heads * Lq, Lkp), Lk, scale, ctx.stream).view(heads, Lq, Lkp)
+            for h in range(heads):
+                c = slice(h * hd, (h + 1) * hd)
+                ops.gemm(dS[h], _transpose_padded(k[:, c]), out=dq[:, c])                             # dS k_h   (K = Lkp)
+                ops.gemm(_transpose_padded(dS[h][:, :Lk]), _transpose_padded(q[:, c]), out=dk[:, c])  # dS^T q_h (K = Lqp)
+            return dq, dk, dv, None, None
+
     class Add(torch.autograd.Function):
         @staticmethod
         def forward(ctx, a, b):
@@ -250,7 +396,8 @@ def _make_functions():
             (dx,) = ctx.saved_tensors
             return dx * g, None, None, None
 
-    return {"Linear": Linear, "Attention": Attention, "Add": Add, "AssoCE": AssoCE, "FocalSum": FocalSum}
+    return {"Linear": Linear, "Attention": Attention, "Add": Add, "AssoCE": AssoCE, "FocalSum": FocalSum,
+            "LinearReluDrop": LinearReluDrop, "DropAdd": DropAdd, "AttentionDrop": AttentionDrop}
 
 
 _FN = None
@@ -270,38 +417,58 @@ def _linear(x, params, name, relu=False):
     return _fn()["Linear"].apply(x, params[name + ".weight"], params.get(name + ".bias"), relu)
 
 
-def _mha(q_in, kv_in, params, name, heads):
-    """nn.MultiheadAttention(q, k = v = kv_in) with packed in_proj (transformer.py:208,287; eval-mode dropout)."""
+def _mha(q_in, kv_in, params, name, heads, dropout=None):
+    """nn.MultiheadAttention(q, k = v = kv_in) with packed in_proj (transformer.py:208,287).  `dropout`: a DropoutState that
+    drops the attention weights after the softmax (one site); None or p = 0: the eval-mode path, launch for launch."""
     E = q_in.shape[1]
     w, b = params[name + ".in_proj_weight"], params[name + ".in_proj_bias"]
     L = _fn()["Linear"]
     q = L.apply(q_in, w[:E], b[:E], False)
     kv = L.apply(kv_in, w[E:], b[E:], False)
-    a = _fn()["Attention"].apply(q, kv[:, :E], kv[:, E:], heads)
+    dropout = _active(dropout)
+    if dropout is None:
+        a = _fn()["Attention"].apply(q, kv[:, :E], kv[:, E:], heads)
+    else:
+        a = _fn()["AttentionDrop"].apply(q, kv[:, :E], kv[:, E:], heads, dropout.next_stream())
     return L.apply(a, params[name + ".out_proj.weight"], params[name + ".out_proj.bias"], False)
 
 
-def matcher_transformer(params, cfg, reid, short_term, prefix="roi_heads."):
+def _ffn(x, params, p, dropout):
+    """linear2(dropout(relu(linear1(x)))) (transformer.py:203, 283); without dropout: the two Linear launches as before."""
+    if dropout is None:
+        h = _linear(x, params, p + "linear1", relu=True)
+    else:
+        h = _fn()["LinearReluDrop"].apply(x, params[p + "linear1.weight"], params.get(p + "linear1.bias"), dropout.next_stream())
+    return _linear(h, params, p + "linear2")
+
+
+def matcher_transformer(params, cfg, reid, short_term, prefix="roi_heads.", dropout=None):
     """Training forward of the matcher (roi_heads/transformer.py:60-96 with norm = Identity, every proposal a query):
-    returns (feats [N, F], memory [N, F])."""
+    returns (feats [N, F], memory [N, F]).  `dropout`: a DropoutState (MODEL.ASSO_HEAD.DROPOUT in training mode) -- the sites of
+    the reference's `forward_post` layers, in call order: per encoder layer the attention weights, `src + dropout1(attn)`, the
+    FFN's inner dropout, `src + dropout2(ffn)`; per decoder layer the cross-attention weights, `tgt + dropout2(attn)` and, unless
+    the head is SHA_FFN_CRSATTN (`only_dec_crs_attn`), the FFN's inner dropout and `tgt + dropout3(ffn)`.  None or p = 0 takes
+    the path without dropout exactly: the same launches, the same bits."""
     A = cfg.MODEL.ASSO_HEAD
     shared = cfg.MODEL.ROI_HEADS.NAME == "SHA_FFN_CRSATTN"
     name = prefix + ("shared_matcher" if shared else ("short_term_matcher" if short_term else "long_term_matcher"))
-    add = _fn()["Add"].apply
+    dropout = _active(dropout)
+    if dropout is None:
+        add = _fn()["Add"].apply
+    else:
+        add = lambda r, x: _fn()["DropAdd"].apply(r, x, dropout.next_stream())
     memory = reid
     n_enc = 0 if shared else A.NUM_ENCODER_LAYERS
     for i in range(n_enc):
         p = "%s.encoder.layers.%d." % (name, i)
-        memory = add(memory, _mha(memory, memory, params, p + "self_attn", A.NUM_HEADS))
-        h = _linear(memory, params, p + "linear1", relu=True)
-        memory = add(memory, _linear(h, params, p + "linear2"))
+        memory = add(memory, _mha(memory, memory, params, p + "self_attn", A.NUM_HEADS, dropout))
+        memory = add(memory, _ffn(memory, params, p, dropout))
     tgt = reid
     for i in range(A.NUM_DECODER_LAYERS):
         p = "%s.decoder.layers.%d." % (name, i)
-        tgt = add(tgt, _mha(tgt, memory, params, p + "multihead_attn", A.NUM_HEADS))
+        tgt = add(tgt, _mha(tgt, memory, params, p + "multihead_attn", A.NUM_HEADS, dropout))
         if not shared:
-            h = _linear(tgt, params, p + "linear1", relu=True)
-            tgt = add(tgt, _linear(h, params, p + "linear2"))
+            tgt = add(tgt, _ffn(tgt, params, p, dropout))
     return tgt, memory
 
 
@@ -323,11 +490,12 @@ def _detr_asso_loss(logits, gt, cues, n_t, neg_unmatched):
     return total / (num + 1e-4)
 
 
-def asso_losses(params, cfg, frames, targets, prefix="roi_heads."):
+def asso_losses(params, cfg, frames, targets, prefix="roi_heads.", dropout=None):
     """`_forward_asso`, training branch (lstmatcher.py:271-330 = shared_ffn_crsattn.py), on the device.
     params: {state-dict key: CUDA tensor (nn.Parameter)}; frames: per frame {"image_size", "proposal_boxes" [n,4] px,
     "objectness_logits" [n], "query_features" [n,25,256]} (CUDA); targets: per frame {"image_size", "gt_boxes" [g,4] px,
-    "gt_instance_ids" [g]} (host or device).  Returns {"loss_long_asso", "loss_short_asso"} with autograd history."""
+    "gt_instance_ids" [g]} (host or device).  Returns {"loss_long_asso", "loss_short_asso"} with autograd history.
+    `dropout`: the DropoutState of the matchers (`matcher_transformer`); FCHead4Query and ATTWeightHead have no dropout."""
     torch = _torch()
     A = cfg.MODEL.ASSO_HEAD
     dev = params[prefix + "asso_head.fc1.weight"].device
@@ -350,7 +518,7 @@ def asso_losses(params, cfg, frames, targets, prefix="roi_heads."):
         return {"loss_long_asso": zero, "loss_short_asso": zero}
 
     def one(lo_f, hi_f, reid_sl, short):
-        feats, memory = matcher_transformer(params, cfg, reid_sl, short, prefix)
+        feats, memory = matcher_transformer(params, cfg, reid_sl, short, prefix, dropout)
         logits = _fn()["Linear"].apply(feats, memory, None, False)                 # ATTWeightHead, 0 layers: q . k^T
         pb, pt = normalised_boxes_and_times(boxes[lo_f:hi_f], sizes[lo_f:hi_f])
         gb, gtime = normalised_boxes_and_times(tb[lo_f:hi_f], [tuple(t["image_size"]) for t in targets[lo_f:hi_f]])
@@ -487,7 +655,10 @@ def forward_losses(model, batched_inputs):
                 else get("polyline")
             pts = torch.as_tensor(pts).float().reshape(-1, P, 2) / torch.tensor([kind[1][1], kind[1][0]], dtype=torch.float32)
             res_targets.append({"labels": np.zeros((pts.shape[0],), np.int64), "ctrl_points": pts})
-    losses = asso_losses(params, cfg, frames, targets)
+    dropout = _active(getattr(model, "dropout_state", None))    # Trainer / the META_ARCH wrapper attach it when DROPOUT > 0
+    if dropout is not None:
+        dropout.begin_forward(dropout.iteration)                # sites count from 0 in every forward
+    losses = asso_losses(params, cfg, frames, targets, dropout=dropout)
     if impl.with_rescore:
         losses.update(loss_res(params, cfg, qf, out["pred_ctrl_points"].view(B, nq, P, 2), res_targets))
     return losses

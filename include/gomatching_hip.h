@@ -6,8 +6,9 @@
  * stock torch.nn in the reference; here those ops are hand-written HIP kernels behind the remaining entry
  * points, which the Python mirror of the reference's META_ARCH / ROI_HEADS classes
  * (gomatching_amd/modeling) binds through ctypes.  INTEGRATION.md shows the reference-side stubs.
- * Training of the association head adds gom_relu_backward_f32 ... gom_sigmoid_focal_f32 (losses and backward pieces) and
- * gom_clipped_adamw_partials / gom_clipped_adamw_step (the optimizer step), at the end of this file.
+ * Training of the association head adds gom_relu_backward_f32 ... gom_sigmoid_focal_f32 (losses and backward pieces),
+ * gom_dropout_f32 ... gom_softmax_dropout_rows_backward_f32 (training-mode dropout) and gom_clipped_adamw_partials /
+ * gom_clipped_adamw_step (the optimizer step), at the end of this file.
  *
  * Conventions
  *   - plain pointers and sizes only; every tensor pointer is DEVICE memory unless marked [host];
@@ -729,6 +730,34 @@ int gom_asso_ce_f32(const float* logits, int ld, const int* frame_offsets, int n
                     float* loss, const float* grad_scale, float* dlogits, void* stream);
 int gom_sigmoid_focal_f32(const float* x, const float* target, float alpha, float gamma, long n, float* loss, float* dx,
                           void* stream);
+
+/* Training-mode dropout of that head (MODEL.ASSO_HEAD.DROPOUT; csrc/dropout.hip).  torch's semantics -- keep with probability
+ * 1 - p, kept values times 1 / (1 - p), the backward uses the forward's mask -- on a counter-based mask stream, so that nothing
+ * is stored and the backward regenerates the mask:
+ *   Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (e >> 2, site, iteration, rank) for LOGICAL element e, which
+ *   uses output word e & 3 and is kept iff word >= threshold;  e = row * cols + col of the logical [rows, cols] tensor,
+ *   whatever the leading dimensions, padding columns and pointer alignment (16-byte accesses where those allow, 4-byte ones
+ *   otherwise: the same bits).  e >> 2 must stay below 2^32.
+ * The host forms threshold = floor(p * 2^32) (in double) and scale = (float)(1.0 / (1.0 - p)) once; a pair that is not that of
+ * one p in [0, 1), a null pointer or a negative size -> GOM_ERR_INVALID_ARG before any HIP call.  Launches only, no atomics.
+ *   gom_dropout_f32                 y = [r +] mask * scale * x over [rows, cols] views (r may be NULL; y may be x).  Serves the
+ *                                   backward as well: dx = mask * scale * dy.
+ *   gom_relu_backward_scaled_f32    dx = y > 0 ? dy * scale : 0 -- ReLU's backward behind a dropout whose OUTPUT y was saved
+ *   gom_softmax_dropout_rows_f32    x [rows, ld] in place: P = softmax(scale_qk * x[:, :cols]) with the bits of
+ *                                   gom_softmax_rows_scaled_f32, and pd[:, :cols] = mask * scale * P; row r covers logical
+ *                                   elements elem0 + r * cols ...; columns cols..ld of pd are not written.  cols <= 8192.
+ *   gom_softmax_dropout_rows_backward_f32   dS = scale_qk * P * (G - rowsum(G * P)), G = mask * scale * dPd (the gradient of
+ *                                   the DROPPED weights; the mask is applied inside); columns cols..ld of dS are not written */
+int gom_dropout_f32(const float* x, long ldx, const float* r, long ldr, float* y, long ldy, long rows, long cols,
+                    unsigned long long seed, unsigned site, unsigned iteration, unsigned rank, long threshold, float scale,
+                    void* stream);
+int gom_relu_backward_scaled_f32(const float* dy, const float* y, float* dx, long n, float scale, void* stream);
+int gom_softmax_dropout_rows_f32(float* x, float* pd, long rows, int cols, long ld, float scale_qk, long elem0,
+                                 unsigned long long seed, unsigned site, unsigned iteration, unsigned rank, long threshold,
+                                 float scale, void* stream);
+int gom_softmax_dropout_rows_backward_f32(const float* P, const float* dPd, float* dS, long rows, int cols, long ld,
+                                          float scale_qk, long elem0, unsigned long long seed, unsigned site,
+                                          unsigned iteration, unsigned rank, long threshold, float scale, void* stream);
 
 /* The optimizer step of that training (csrc/optim.hip): AdamW with FULL-MODEL gradient clipping over a table of fp32 tensors,
  * the fp32 arithmetic of the reference's FullModelGradientClippingOptimizer(torch.optim.AdamW) (costom_solver.py:55-73):

@@ -5,6 +5,12 @@ step (median and min..max over the repeats) and the fused step's achieved bytes 
 (g twice, p m v read and written) against 8 TB/s.  Then the split of one `Trainer.step` on the test suite's small clip.
 
     python tools/solver_bench.py [--steps 300] [--repeats 5] > profiles/solver_bench.log
+
+`--dropout P`: instead of all that, the cost of MODEL.ASSO_HEAD.DROPOUT = P in the head's forward and backward on that clip:
+one process, one model, the trainer's dropout state switched between 0 and P from repeat to repeat (alternating), the split's
+own repeats, with the bytes the dropout passes move.
+
+    python tools/solver_bench.py --dropout 0.1 > profiles/dropout_bench.log
 """
 import argparse
 import os
@@ -114,13 +120,92 @@ def trainer_split():
     model.close()
 
 
+def dropout_cost(p, repeats=10, rounds=5):
+    """Head forward and backward of the split's clip with dropout 0 and `p`, alternating in one process on one model."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import mini_cfg
+    from gomatching_amd import ops, training
+    from gomatching_amd.modeling import GoMatching
+    from gomatching_amd.synth import TRAINING_CLS_BIAS, make_training_clip
+    cfg = mini_cfg("icdar15", device="cuda")
+    cfg.MODEL.ASSO_HEAD.DROPOUT = p
+    cfg.SOLVER.WARMUP_ITERS = 0
+    sd = synth_state_dict(cfg, seed=7, cls_bias=TRAINING_CLS_BIAS)
+    model = GoMatching(cfg, sd, device=DEV)
+    batch = make_training_clip()
+    tr = solver.Trainer(cfg, model, None, seed=7)
+    state = tr.dropout
+    sync = torch.cuda.synchronize
+    # bytes of the dropout passes, counted where they are launched (fp32; forward and backward)
+    count = {"bytes": 0, "launches": 0}
+    orig = (ops.dropout, ops.softmax_dropout_rows_, ops.softmax_dropout_rows_backward, ops.relu_backward_scaled)
+
+    def counted(fn, per_element):
+        def run(x, *a, **k):
+            count["bytes"] += 4 * per_element(x, k) * x.numel()
+            count["launches"] += 1
+            return fn(x, *a, **k)
+        return run
+    ops.dropout = counted(orig[0], lambda x, k: 3 if k.get("residual") is not None else 2)
+    ops.softmax_dropout_rows_ = counted(orig[1], lambda x, k: 3)             # read scores, write P and P~ (the softmax alone: 2)
+    ops.softmax_dropout_rows_backward = counted(orig[2], lambda x, k: 5)     # P and dP~ read in both passes, dS written (as without)
+    ops.relu_backward_scaled = counted(orig[3], lambda x, k: 3)              # as relu_backward
+
+    def one(with_dropout):
+        model.dropout_state = state if with_dropout else None
+        if with_dropout:
+            state.begin_forward(0)
+        sync(); t0 = time.perf_counter()
+        with torch.no_grad():
+            raw, kind = model._raw_input(batch)
+            feats = model.backbone.forward(model._normalise(raw, kind))
+            model.detection_transformer.forward([feats[k] for k in model.feature_names])
+        sync(); t1 = time.perf_counter()
+        losses = training.forward_losses(model, batch)
+        total = sum(losses.values())
+        sync(); t2 = time.perf_counter()
+        tr.optimizer.zero_grad()
+        total.backward()
+        sync(); t3 = time.perf_counter()
+        return 1e3 * (t2 - t1 - (t1 - t0)), 1e3 * (t3 - t2)
+    for _ in range(3):
+        one(False), one(True)
+    count["bytes"] = count["launches"] = 0
+    one(True)
+    nbytes, launches = count["bytes"], count["launches"]
+    ops.dropout, ops.softmax_dropout_rows_, ops.softmax_dropout_rows_backward, ops.relu_backward_scaled = orig
+    print("dropout cost, head forward + losses | backward on 4 frames of 96x128, %d queries (median of %d, host-synchronised), "
+          "%d rounds alternating P = 0 / P = %g:" % (cfg.MODEL.TRANSFORMER.NUM_QUERIES, repeats, rounds, p))
+    meds = {False: [], True: []}
+    for r in range(rounds):
+        for flag in (False, True):
+            runs = [one(flag) for _ in range(repeats)]
+            f, b = statistics.median(x[0] for x in runs), statistics.median(x[1] for x in runs)
+            meds[flag].append((f, b))
+            print("  round %d  P = %-4g forward %.2f ms   backward %.2f ms" % (r, p if flag else 0, f, b))
+    for flag in (False, True):
+        f, b = [x[0] for x in meds[flag]], [x[1] for x in meds[flag]]
+        print("  P = %-4g forward %.2f ms (%.2f .. %.2f)   backward %.2f ms (%.2f .. %.2f)" % (
+            p if flag else 0, statistics.median(f), min(f), max(f), statistics.median(b), min(b), max(b)))
+    df = statistics.median(x[0] for x in meds[True]) - statistics.median(x[0] for x in meds[False])
+    db = statistics.median(x[1] for x in meds[True]) - statistics.median(x[1] for x in meds[False])
+    print("  added by P = %g: forward %+.2f ms, backward %+.2f ms; the dropout launches of one step (%d) move %.2f MB, "
+          "%.1f us at 5.7 TB/s" % (p, df, db, launches, nbytes / 1e6, nbytes / 5.7e6))
+    model.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--no-split", action="store_true")
+    ap.add_argument("--dropout", type=float, default=None, metavar="P",
+                    help="measure the head's forward / backward with MODEL.ASSO_HEAD.DROPOUT 0 and P, alternating, and nothing else")
     a = ap.parse_args()
     print("solver_bench: %s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    if a.dropout is not None:
+        dropout_cost(a.dropout)
+        return
     for builtin in ("icdar15", "pp_dstext"):
         bench_head(builtin, a.steps, a.repeats)
     if not a.no_split:
