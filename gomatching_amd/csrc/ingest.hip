@@ -73,22 +73,25 @@ __device__ __forceinline__ int clip8(int v) {
 }
 
 // One thread per output pixel (3 channels).  F32OUT: write (v[perm] - mean) / std as NHWC4; else uint8 HWC.
+// The OH x OW output is the window at (y0, x0) of the resized image the tables describe (the whole of it for
+// x0 = y0 = 0): pixel (oy, ox) reads table rows oy + y0 and ox + x0, nothing outside the window is computed.
 template <bool F32OUT>
 __global__ __launch_bounds__(256) void resample_kernel(const uint8_t* __restrict__ src, int H, int W,
                                                        const int* __restrict__ xb, const int* __restrict__ xk, int xks,
                                                        const int* __restrict__ yb, const int* __restrict__ yk, int yks,
-                                                       void* __restrict__ dst, int OH, int OW, long total, int flip,
-                                                       float m0, float m1, float m2, float s0, float s1, float s2) {
+                                                       void* __restrict__ dst, int OH, int OW, int y0, int x0, long total,
+                                                       int flip, float m0, float m1, float m2, float s0, float s1, float s2) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int ox = (int)(i % OW);
     const long t = i / OW;
     const int oy = (int)(t % OH);
     const long b = t / OH;
-    const int xmin = xb[2 * ox], xn = xb[2 * ox + 1];
-    const int ymin = yb[2 * oy], yn = yb[2 * oy + 1];
-    const int* kx = xk + (long)ox * xks;
-    const int* ky = yk + (long)oy * yks;
+    const int rx = ox + x0, ry = oy + y0;
+    const int xmin = xb[2 * rx], xn = xb[2 * rx + 1];
+    const int ymin = yb[2 * ry], yn = yb[2 * ry + 1];
+    const int* kx = xk + (long)rx * xks;
+    const int* ky = yk + (long)ry * yks;
     const uint8_t* frame = src + b * (long)H * W * 3;
     const int half = 1 << (GOM_RESAMPLE_BITS - 1);
     int v0 = half, v1 = half, v2 = half;
@@ -139,7 +142,7 @@ extern "C" int gom_resize_bilinear_u8_hwc3(const uint8_t* src, int B, int H, int
     GOM_CHECK_ARG(GOM_RESAMPLE_ARGS_OK);
     const long total = (long)B * OH * OW;
     hipLaunchKernelGGL(resample_kernel<false>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src,
-                       H, W, xbounds, xkk, xksize, ybounds, ykk, yksize, (void*)dst, OH, OW, total, flip_channels, 0.f,
+                       H, W, xbounds, xkk, xksize, ybounds, ykk, yksize, (void*)dst, OH, OW, 0, 0, total, flip_channels, 0.f,
                        0.f, 0.f, 1.f, 1.f, 1.f);
     return gom_launch_status();
 }
@@ -151,7 +154,37 @@ extern "C" int gom_ingest_u8_hwc3_to_nhwc4(const uint8_t* src, int B, int H, int
     GOM_CHECK_ARG(GOM_RESAMPLE_ARGS_OK && mean3 && std3);
     const long total = (long)B * OH * OW;
     hipLaunchKernelGGL(resample_kernel<true>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src,
-                       H, W, xbounds, xkk, xksize, ybounds, ykk, yksize, (void*)dst, OH, OW, total, flip_channels,
+                       H, W, xbounds, xkk, xksize, ybounds, ykk, yksize, (void*)dst, OH, OW, 0, 0, total, flip_channels,
                        mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    return gom_launch_status();
+}
+
+// Resize to SH x SW, then keep the OH x OW window at (y0, x0): EfficientDetResizeCropTransform.apply_image
+// (custom_transform.py:46-59) without the SH x SW intermediate.  Tables are those of H -> SH and W -> SW.
+#define GOM_RESAMPLE_WINDOW_OK \
+    (SH > 0 && SW > 0 && y0 >= 0 && x0 >= 0 && OH <= SH - y0 && OW <= SW - x0)
+
+extern "C" int gom_resize_crop_bilinear_u8_hwc3(const uint8_t* src, int B, int H, int W, const int* xbounds,
+                                                const int* xkk, int xksize, const int* ybounds, const int* ykk,
+                                                int yksize, uint8_t* dst, int SH, int SW, int y0, int x0, int OH, int OW,
+                                                int flip_channels, void* stream) {
+    GOM_CHECK_ARG(GOM_RESAMPLE_ARGS_OK && GOM_RESAMPLE_WINDOW_OK);
+    const long total = (long)B * OH * OW;
+    hipLaunchKernelGGL(resample_kernel<false>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src,
+                       H, W, xbounds, xkk, xksize, ybounds, ykk, yksize, (void*)dst, OH, OW, y0, x0, total,
+                       flip_channels, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f);
+    return gom_launch_status();
+}
+
+extern "C" int gom_ingest_crop_u8_hwc3_to_nhwc4(const uint8_t* src, int B, int H, int W, const int* xbounds,
+                                                const int* xkk, int xksize, const int* ybounds, const int* ykk,
+                                                int yksize, const float* mean3, const float* std3, float* dst, int SH,
+                                                int SW, int y0, int x0, int OH, int OW, int flip_channels,
+                                                void* stream) {
+    GOM_CHECK_ARG(GOM_RESAMPLE_ARGS_OK && GOM_RESAMPLE_WINDOW_OK && mean3 && std3);
+    const long total = (long)B * OH * OW;
+    hipLaunchKernelGGL(resample_kernel<true>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src,
+                       H, W, xbounds, xkk, xksize, ybounds, ykk, yksize, (void*)dst, OH, OW, y0, x0, total,
+                       flip_channels, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
     return gom_launch_status();
 }

@@ -129,6 +129,9 @@ SIGNATURES = {
     "gom_resize_bilinear_u8_hwc3": (I, [P, I, I, I, P, P, I, P, P, I, P, I, I, I, P]),
     "gom_ingest_u8_hwc3_to_nhwc4": (I, [P, I, I, I, P, P, I, P, P, I, ctypes.POINTER(c_float),
                                         ctypes.POINTER(c_float), P, I, I, I, P]),
+    "gom_resize_crop_bilinear_u8_hwc3": (I, [P, I, I, I, P, P, I, P, P, I, P, I, I, I, I, I, I, I, P]),
+    "gom_ingest_crop_u8_hwc3_to_nhwc4": (I, [P, I, I, I, P, P, I, P, P, I, ctypes.POINTER(c_float),
+                                             ctypes.POINTER(c_float), P, I, I, I, I, I, I, I, P]),
     "gom_preprocess_nchw_to_nhwc4": (I, [P, ctypes.POINTER(c_float), ctypes.POINTER(c_float), P, I, I, I, P]),
     "gom_result_rows_i32": (I, [P, P, P, I, I, P, I, P]),
     "gom_maxpool3x3s2_nhwc_f32": (I, [P, P, I, I, I, I, P]),

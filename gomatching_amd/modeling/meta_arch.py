@@ -172,10 +172,23 @@ class GoMatching:
     def _raw_input(self, batched_inputs, out=None):
         """The step's frames as ONE device tensor (`out` = a static buffer to fill, for graph replay) + how to
         normalise it: ("u8", net hw, flip) for the device ingest of SURVEY §8-f2 -- `frame_u8` (u8 [H0,W0,3] as read
-        from disk) + `resize_hw` (+ `flip_channels`) -- or ("f32", hw, None) for the reference's `image` (f32 [3,H,W],
-        already resized).  gom_lstmatcher.py:164-170 for same-size frames (no padding needed)."""
+        from disk) + `resize_hw` (+ `flip_channels`) --, ("u8crop", crop hw, flip, resized hw, crop) when a `crop` =
+        (y0, x0, OH, OW) comes with them (the training augmentation), or ("f32", hw, None) for the reference's `image`
+        (f32 [3,H,W], already resized).  gom_lstmatcher.py:164-170 for same-size frames (no padding needed)."""
         first = batched_inputs[0]
-        if "frame_u8" in first:
+        if "frame_u8" in first and first.get("crop") is not None:
+            # the training augmentation (data.GoMDatasetMapper, device_ingest): resize to `resize_hw`, keep the window
+            # `crop` = (y0, x0, OH, OW).  kind[1] is the CROP's size, the reference's `image_shape` after apply_image.
+            shw, flip = tuple(int(v) for v in first["resize_hw"]), bool(first.get("flip_channels", False))
+            crop = tuple(int(v) for v in first["crop"])
+            frames = [x["frame_u8"] for x in batched_inputs]
+            for x in batched_inputs:
+                if tuple(x["resize_hw"]) != shw or x.get("crop") is None or tuple(x["crop"]) != crop \
+                        or tuple(x["frame_u8"].shape) != tuple(frames[0].shape) \
+                        or bool(x.get("flip_channels", False)) != flip:
+                    raise ValueError("frames of one step must share source size, target size, crop and channel order")
+            kind, dtype = ("u8crop", crop[2:], flip, shw, crop), torch.uint8
+        elif "frame_u8" in first:
             hw, flip = tuple(first["resize_hw"]), bool(first.get("flip_channels", False))
             frames = [x["frame_u8"] for x in batched_inputs]
             for x in batched_inputs:
@@ -244,6 +257,8 @@ class GoMatching:
     def _normalise(self, raw, kind):
         if kind[0] == "u8":
             return ops.ingest(raw, kind[1][0], kind[1][1], self.pixel_mean, self.pixel_std, kind[2])
+        if kind[0] == "u8crop":
+            return ops.ingest_crop(raw, kind[3], kind[4], self.pixel_mean, self.pixel_std, kind[2])
         return ops.preprocess(raw, self.pixel_mean, self.pixel_std)
 
     def preprocess_image(self, batched_inputs):
@@ -917,7 +932,8 @@ class GoMatching:
         BASELINE config #5, simply start a new step at every size change)."""
         def size(x):
             if "frame_u8" in x:
-                return tuple(x["frame_u8"].shape[:2]) + tuple(x["resize_hw"]) + (bool(x.get("flip_channels", False)),)
+                return tuple(x["frame_u8"].shape[:2]) + tuple(x["resize_hw"]) + (bool(x.get("flip_channels", False)),) \
+                    + tuple(x.get("crop") or ())
             return tuple(x["image"].shape[-2:]) if "image" in x else None
 
         steps, s0, n = [], 0, len(batched_inputs)

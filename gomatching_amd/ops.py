@@ -3,6 +3,7 @@
 Every function launches hand-written HIP kernels from libgomatching_hip.so on torch's current stream;
 none has a CPU or torch-op fallback.
 """
+import collections
 import contextlib
 import ctypes
 import math
@@ -1384,18 +1385,22 @@ def preprocess(images, mean, std):
 _resample_tables = {}
 
 
+def _build_resample_tables(in_size, out_size, device):
+    ks = _L().gom_resample_ksize_bilinear(in_size, out_size)
+    if ks <= 0:
+        raise ValueError("bad resample sizes %d -> %d" % (in_size, out_size))
+    bounds = torch.empty((out_size, 2), dtype=torch.int32)
+    kk = torch.empty((out_size, ks), dtype=torch.int32)
+    check(_L().gom_resample_coeffs_bilinear(in_size, out_size, _p(bounds), _p(kk), ks), "gom_resample_coeffs")
+    return (bounds.to(device), kk.to(device), ks)
+
+
 def resample_tables(in_size, out_size, device):
     """Pillow-bilinear coefficient tables of one axis on `device` (cached): (bounds i32 [out,2], kk i32 [out,ks], ks)."""
     key = (in_size, out_size, str(device))
     hit = _resample_tables.get(key)
     if hit is None:
-        ks = _L().gom_resample_ksize_bilinear(in_size, out_size)
-        if ks <= 0:
-            raise ValueError("bad resample sizes %d -> %d" % (in_size, out_size))
-        bounds = torch.empty((out_size, 2), dtype=torch.int32)
-        kk = torch.empty((out_size, ks), dtype=torch.int32)
-        check(_L().gom_resample_coeffs_bilinear(in_size, out_size, _p(bounds), _p(kk), ks), "gom_resample_coeffs")
-        hit = (bounds.to(device), kk.to(device), ks)
+        hit = _build_resample_tables(in_size, out_size, device)
         _resample_tables[key] = hit
     return hit
 
@@ -1429,6 +1434,68 @@ def ingest(frames, out_h, out_w, mean, std, flip):
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
     check(_L().gom_ingest_u8_hwc3_to_nhwc4(_p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, m, s,
                                            _p(out), out_h, out_w, int(flip), _stream()), "gom_ingest_u8_hwc3_to_nhwc4")
+    return out
+
+
+CROP_TABLES_MAX = 16               # per-axis tables the crop ops keep: random scales give a new size almost every clip
+_crop_tables = collections.OrderedDict()
+
+
+def _crop_resample_tables(in_size, out_size, device):
+    """`resample_tables` behind a small LRU of its own (the unbounded cache above serves inference's few fixed sizes, and is
+    read but never filled from here).  An evicted table may still be read by a queued launch: its memory goes back to torch's
+    allocator, which hands it out again in the order of the stream it was allocated on.  That is safe only while every table is
+    built and every crop launch is issued on ONE stream (no `record_stream` is called) -- true of `forward_losses`, the only
+    caller; a caller that launches crops on several streams must keep its tables alive itself."""
+    key = (in_size, out_size, str(device))
+    hit = _crop_tables.pop(key, None)
+    if hit is None:
+        hit = _resample_tables.get(key)
+    if hit is None:
+        hit = _build_resample_tables(in_size, out_size, device)
+    _crop_tables[key] = hit
+    while len(_crop_tables) > CROP_TABLES_MAX:
+        _crop_tables.popitem(last=False)
+    return hit
+
+
+def _chk_window(scaled_hw, window):
+    SH, SW = (int(v) for v in scaled_hw)
+    y0, x0, OH, OW = (int(v) for v in window)
+    if min(SH, SW, OH, OW) <= 0 or y0 < 0 or x0 < 0 or y0 + OH > SH or x0 + OW > SW:
+        raise ValueError("window (y0=%d, x0=%d, %dx%d) is not inside the %dx%d resized image" % (y0, x0, OH, OW, SH, SW))
+    return SH, SW, y0, x0, OH, OW
+
+
+def resize_crop_u8(frames, scaled_hw, window, flip=False):
+    """[B,H,W,3] u8 -> [B,OH,OW,3] u8: `PIL.Image.resize((SW,SH), BILINEAR)` then `[y0:y0+OH, x0:x0+OW]`, bit-exact, one
+    launch, no SH x SW intermediate.  scaled_hw = (SH, SW), window = (y0, x0, OH, OW)."""
+    SH, SW, y0, x0, OH, OW = _chk_window(scaled_hw, window)
+    _chk_frames(frames)
+    B, H, W, _ = frames.shape
+    xb, xk, xks = _crop_resample_tables(W, SW, frames.device)
+    yb, yk, yks = _crop_resample_tables(H, SH, frames.device)
+    out = torch.empty((B, OH, OW, 3), dtype=torch.uint8, device=frames.device)
+    check(_L().gom_resize_crop_bilinear_u8_hwc3(_p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, _p(out),
+                                                SH, SW, y0, x0, OH, OW, int(flip), _stream()),
+          "gom_resize_crop_bilinear_u8_hwc3")
+    return out
+
+
+def ingest_crop(frames, scaled_hw, window, mean, std, flip):
+    """[B,H,W,3] u8 frames -> normalised [B,OH,OW,4] f32 backbone input of the training augmentation: resize to scaled_hw,
+    keep `window`, flip, (x-mean)/std (custom_transform.py:46-59 + gom_lstmatcher.py:159-170), one launch."""
+    SH, SW, y0, x0, OH, OW = _chk_window(scaled_hw, window)
+    _chk_frames(frames)
+    B, H, W, _ = frames.shape
+    xb, xk, xks = _crop_resample_tables(W, SW, frames.device)
+    yb, yk, yks = _crop_resample_tables(H, SH, frames.device)
+    out = torch.empty((B, OH, OW, 4), dtype=_f32, device=frames.device)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    check(_L().gom_ingest_crop_u8_hwc3_to_nhwc4(_p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, m, s,
+                                                _p(out), SH, SW, y0, x0, OH, OW, int(flip), _stream()),
+          "gom_ingest_crop_u8_hwc3_to_nhwc4")
     return out
 
 

@@ -195,8 +195,9 @@ def build_optimizer(cfg, named_parameters):
     return ClippedAdamW(groups, S.BASE_LR, weight_decay=S.WEIGHT_DECAY, clip_value=clip)
 
 
-def save_checkpoint(path, model_state, optimizer_state=None, iteration=0, dropout_seed=None):
-    """Write {"model", "optimizer", "iteration"} (and "dropout_seed" when the run drops) with torch.save: `model_state` = the
+def save_checkpoint(path, model_state, optimizer_state=None, iteration=0, dropout_seed=None, data_seed=None):
+    """Write {"model", "optimizer", "iteration"} (and "dropout_seed" when the run drops, "data_seed" when the run's clips come
+    from `data.build_vts_train_loader`) with torch.save: `model_state` = the
     FULL state dict (frozen detector + current
     head) as {canonical key: tensor or array}, stored as CPU tensors -- what `eval.load_weights` / `normalize_state_dict` read,
     and the layout Detectron2's checkpointer writes."""
@@ -210,6 +211,8 @@ def save_checkpoint(path, model_state, optimizer_state=None, iteration=0, dropou
     ck = {"model": model, "optimizer": optimizer_state, "iteration": int(iteration)}
     if dropout_seed is not None:
         ck["dropout_seed"] = int(dropout_seed)
+    if data_seed is not None:
+        ck["data_seed"] = int(data_seed)
     torch.save(ck, tmp)
     os.replace(tmp, path)
     return path
@@ -220,7 +223,7 @@ class Trainer:
     (the head) trains.
 
         trainer = Trainer(cfg, model, "out")
-        for clip in clips:                      # what `forward_losses` takes: the reference's GoMDatasetMapper output
+        for clip in clips:                      # what `forward_losses` takes: the mapper's output (data.build_vts_train_loader)
             metrics = trainer.step(clip)        # {"loss_...": float, "total_loss", "lr", "grad_norm", "iteration"}
         trainer.save("model_final.pth")         # python -m gomatching_amd.eval --opts MODEL.WEIGHTS out/model_final.pth
 
@@ -256,6 +259,7 @@ class Trainer:
                     self.frozen_keys.add("roi_heads.rescoring_head." + leaf)
                 print("using trained rescoring head")
         self.seed, self.dropout = seed, None
+        self.data_seed = None                                    # set by whoever feeds `step` from a seeded loader (train.py)
         if cfg.MODEL.ASSO_HEAD.DROPOUT > 0:
             from . import training
             if seed is None:
@@ -313,14 +317,14 @@ class Trainer:
     def save(self, name="model_final.pth"):
         path = name if os.path.isabs(name) else os.path.join(self.output_dir, name)
         save_checkpoint(path, self.state_dict(), self.optimizer.state_dict(), self.iteration - 1,
-                        self.seed if self.dropout is not None else None)
+                        self.seed if self.dropout is not None else None, data_seed=self.data_seed)
         with open(os.path.join(os.path.dirname(path), "last_checkpoint"), "w") as f:
             f.write(os.path.basename(path))
         return path
 
     def resume(self, path=None):
         """Continue from a checkpoint written by `save()` (default: the one `last_checkpoint` names): head weights, optimizer
-        state, the iteration count and the dropout seed (a checkpoint without one keeps this trainer's own).  Returns the iteration
+        state, the iteration count, the dropout seed and the data seed (a checkpoint without one keeps this trainer's own).  Returns the iteration
         training continues at."""
         if path is None:
             with open(os.path.join(self.output_dir, "last_checkpoint")) as f:
@@ -337,6 +341,8 @@ class Trainer:
             self.seed = int(ck["dropout_seed"])
             if self.dropout is not None:
                 self.dropout.seed = self.seed
+        if ck.get("data_seed") is not None:
+            self.data_seed = int(ck["data_seed"])
         self._set_lr()
         return self.iteration
 

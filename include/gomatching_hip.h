@@ -463,6 +463,20 @@ int gom_resize_bilinear_u8_hwc3(const uint8_t* src, int B, int H, int W, const i
 int gom_ingest_u8_hwc3_to_nhwc4(const uint8_t* src, int B, int H, int W, const int* xbounds, const int* xkk,
                                 int xksize, const int* ybounds, const int* ykk, int yksize, const float* mean3,
                                 const float* std3, float* dst, int OH, int OW, int flip_channels, void* stream);
+/* Training augmentation (custom_transform.py:46-59, EfficientDetResizeCropTransform.apply_image): Pillow resize to
+ * SH x SW followed by the slice [y0 : y0+OH, x0 : x0+OW], in one launch and without the SH x SW intermediate.  The tables
+ * are those of H -> SH (ybounds/ykk) and W -> SW (xbounds/xkk); output pixel (oy, ox) is pixel (oy+y0, ox+x0) of the
+ * resized image, with the arithmetic of the two entry points above.  GOM_ERR_INVALID_ARG, before any HIP call, when a
+ * size is non-positive or the window leaves the resized image (x0 < 0, x0+OW > SW, likewise y).
+ * src [B,H,W,3] u8 -> dst [B,OH,OW,3] u8. */
+int gom_resize_crop_bilinear_u8_hwc3(const uint8_t* src, int B, int H, int W, const int* xbounds, const int* xkk,
+                                     int xksize, const int* ybounds, const int* ykk, int yksize, uint8_t* dst, int SH,
+                                     int SW, int y0, int x0, int OH, int OW, int flip_channels, void* stream);
+/* src [B,H,W,3] u8 -> dst [B,OH,OW,4] f32 = (window[flipped] - mean) / std, 4th channel 0. */
+int gom_ingest_crop_u8_hwc3_to_nhwc4(const uint8_t* src, int B, int H, int W, const int* xbounds, const int* xkk,
+                                     int xksize, const int* ybounds, const int* ykk, int yksize, const float* mean3,
+                                     const float* std3, float* dst, int SH, int SW, int y0, int x0, int OH, int OW,
+                                     int flip_channels, void* stream);
 /* ---- f1: result rows (eval.py:346-363, the per-instance conversion in front of the XML / JSON writers) --------
  * The per-instance work of the host's `frame_lines` for all n instances of a clip in ONE launch (one wave64 per instance):
  *   bd [n,25,4] fp32 (top x, top y, bottom x, bottom y per point, frame pixels), recs [n,25] int64 class ids,
