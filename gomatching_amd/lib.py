@@ -134,6 +134,8 @@ SIGNATURES = {
                                              ctypes.POINTER(c_float), P, I, I, I, I, I, I, I, P]),
     "gom_preprocess_nchw_to_nhwc4": (I, [P, ctypes.POINTER(c_float), ctypes.POINTER(c_float), P, I, I, I, P]),
     "gom_result_rows_i32": (I, [P, P, P, I, I, P, I, P]),
+    "gom_quad_pairs_count_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, P]),
+    "gom_quad_pairs_emit_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, L, P, P, P]),
     "gom_maxpool3x3s2_nhwc_f32": (I, [P, P, I, I, I, I, P]),
     "gom_pos_encoding_2d_f32": (I, [P, P, P, I, I, P]),
     "gom_point_pos_embed_f32": (I, [P, P, P, L, P]),

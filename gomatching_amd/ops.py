@@ -1523,7 +1523,39 @@ def result_rows(bd, recs, voc_size, track_ids=None):
     return out
 
 
-STEM_POOL = _switch("STEM_POOL")     # f16x3 back-end: the ResNet stem (conv 7x7 / 2 + BN + ReLU + max-pool 3x3 / 2) as one launch
+def quad_pairs(gt_quads, det_quads, gt_off, det_off, gt_key, det_key, measure, threshold, pairs=None):
+    """The (ground truth, detection) pairs of one video whose measure is above `threshold` (csrc/score.hip; contract in
+    include/gomatching_hip.h).  gt_quads [G,8] / det_quads [D,8] int32, gt_off / det_off [F+1] int32 (first object of each
+    frame), gt_key [G] / det_key [D] int32 (only equal keys pair), all CUDA; measure 0 = IoU, 1 = intersection over the
+    detection's area.  -> (counts int32 [G], det int32 [K], value fp64 [K]): kept detections per ground-truth object, then
+    per kept pair the detection's index within its frame and the value, ordered by ground truth, then detection.  Two
+    launches (count, emit) around the prefix sum of the counts; `pairs` = the per-frame G x D total, if the caller has it."""
+    dev = gt_quads.device
+    for name, t, shape in (("gt_quads", gt_quads, (None, 8)), ("det_quads", det_quads, (None, 8)), ("gt_off", gt_off, (None,)),
+                           ("det_off", det_off, (None,)), ("gt_key", gt_key, (None,)), ("det_key", det_key, (None,))):
+        if not t.is_cuda or t.device != dev or t.dtype != torch.int32 or t.dim() != len(shape) or \
+                any(s is not None and t.shape[i] != s for i, s in enumerate(shape)) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous CUDA int32 tensor of shape %s" % (name, list(shape)))
+    G, D, F = gt_quads.shape[0], det_quads.shape[0], gt_off.shape[0] - 1
+    if F < 0 or det_off.shape[0] != F + 1 or gt_key.shape[0] != G or det_key.shape[0] != D:
+        raise ValueError("offsets must be [F+1] and keys [G] / [D]")
+    if pairs is None:
+        pairs = 0 if F == 0 else int(((gt_off[1:] - gt_off[:-1]).to(torch.int64) * (det_off[1:] - det_off[:-1]).to(torch.int64)).sum())
+    counts = torch.empty((G,), dtype=torch.int32, device=dev)
+    args = (_p(gt_quads), _p(det_quads), _p(gt_off), _p(det_off), _p(gt_key), _p(det_key), G, D, F, int(pairs), int(measure),
+            float(threshold))
+    with torch.cuda.device(dev):
+        check(_L().gom_quad_pairs_count_f64(*args, _p(counts), _stream()), "gom_quad_pairs_count_f64")
+        ends = torch.cumsum(counts, 0, dtype=torch.int64)
+        total = int(ends[-1]) if G else 0
+        scan = ends - counts
+        det = torch.empty((total,), dtype=torch.int32, device=dev)
+        val = torch.empty((total,), dtype=torch.float64, device=dev)
+        check(_L().gom_quad_pairs_emit_f64(*args, _p(scan), total, _p(det), _p(val), _stream()), "gom_quad_pairs_emit_f64")
+    return counts, det, val
+
+
+STEM_POOL = _switch("STEM_POOL")    # f16x3 back-end: the ResNet stem (conv 7x7 / 2 + BN + ReLU + max-pool 3x3 / 2) as one launch
 
 
 def stem_conv_pool(x, w, scale=None, shift=None):

@@ -509,6 +509,34 @@ int gom_ingest_crop_u8_hwc3_to_nhwc4(const uint8_t* src, int B, int H, int W, co
 #define GOM_RESULT_ROWS_WORDS 234
 int gom_result_rows_i32(const float* bd, const int64_t* recs, const int64_t* track_ids, int n, int voc_size,
                         int32_t* out, int ld, void* stream);
+/* Scoring (csrc/score.hip): the pairwise convex-quadrilateral measure of one video's objects, as the count pass and the
+ * emit pass of a stream compaction over the (ground truth, detection) pairs of every frame.
+ *   gt_quads [G,8], det_quads [D,8] int32 : x1,y1,..,x4,y4 in any point order (the convex hull is taken)
+ *   gt_off [F+1], det_off [F+1] int32      : first object of each frame (CSR, gt_off[F] = G, det_off[F] = D); pairs exist
+ *                                            only within a frame
+ *   gt_key [G], det_key [D] int32          : a pair is eligible only when its two keys are equal
+ *   pairs                                  : the sum over the frames of (ground truth) x (detections), as the caller counts it
+ *   measure                                : 0 = IoU of the two hulls, 1 = overlap = intersection / area(detection hull)
+ *   threshold                              : a pair is kept when its value is STRICTLY greater
+ * Per pair: hull of each 4-gon (64-bit integer cross products; duplicate and collinear points collapse); 0 when either
+ * hull has no area; otherwise the detection hull clipped by the ground-truth hull (Sutherland-Hodgman, <= 8 vertices) and
+ * the shoelace area, in fp64 with every operation rounded once (side tests are fp64 cross products, exact on integer
+ * vertices below 2^25).
+ * gom_quad_pairs_count_f64: counts[g] = kept detections of ground-truth object g.
+ * gom_quad_pairs_emit_f64 : scan [G] int64 = exclusive prefix sum of counts, total = their sum; writes, per kept pair, the
+ *   detection's index within its frame (out_det, int32 [total]) and the value (out_val, fp64 [total]), ordered by ground
+ *   truth, then detection.  One wavefront per ground-truth object, ballot + popcount prefix, no atomics: the output is
+ *   bitwise reproducible and does not depend on the launch geometry.
+ * GOM_ERR_INVALID_ARG before any HIP call: null pointers, negative sizes, F == 0 with objects, measure outside {0, 1},
+ * threshold outside (0, 1), pairs negative, above G * D or above INT32_MAX, total negative or above pairs.  G == 0 (and
+ * for the emit pass total == 0) is GOM_OK without a launch; frames without ground truth or detections are valid. */
+int gom_quad_pairs_count_f64(const int32_t* gt_quads, const int32_t* det_quads, const int32_t* gt_off,
+                             const int32_t* det_off, const int32_t* gt_key, const int32_t* det_key, int G, int D, int F,
+                             long pairs, int measure, double threshold, int32_t* counts, void* stream);
+int gom_quad_pairs_emit_f64(const int32_t* gt_quads, const int32_t* det_quads, const int32_t* gt_off,
+                            const int32_t* det_off, const int32_t* gt_key, const int32_t* det_key, int G, int D, int F,
+                            long pairs, int measure, double threshold, const int64_t* scan, long total, int32_t* out_det,
+                            double* out_val, void* stream);
 int gom_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 /* out [H*W, 256] = PositionalEncoding2D(normalize=True) + level_embed, for an unpadded H x W level. */
 int gom_pos_encoding_2d_f32(const float* dim_t128, const float* level_embed256, float* out, int H, int W,
