@@ -2053,19 +2053,36 @@ def gather_rows(src, rows):
     return out
 
 
-def asso_activate(logits, offsets, T):
+def _ld(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def asso_activate(logits, offsets, T, out=None):
+    """logits [n_k, N], rows `logits.stride(0)` apart (a column slice of a wider buffer is fine); out: a caller's [n_k, >= N]
+    buffer (rows `out.stride(0)` apart) instead of a new one."""
     n_k, N = logits.shape
-    out = torch.empty_like(logits)
-    check(_L().gom_asso_activate_f32(_p(logits), logits.stride(0) if n_k > 1 else N, _p(offsets), T, n_k, _p(out),
-                                     N, _stream()), "gom_asso_activate_f32")
+    if out is None:
+        out = torch.empty((n_k, N), dtype=_f32, device=logits.device)
+    check(_L().gom_asso_activate_f32(_p(logits), _ld(logits), _p(offsets), T, n_k, _p(out), _ld(out), _stream()),
+          "gom_asso_activate_f32")
     return out
 
 
-def track_score(act, meta, decay, boxes, img_w, img_h, n_k, Np, M, with_iou, max_center_dist):
-    traj = torch.empty((n_k, M), dtype=_f32, device=act.device)
-    check(_L().gom_track_score_f32(_p(act), act.shape[1], _p(meta), _p(decay), _p(boxes), float(img_w), float(img_h),
+def track_score(act, meta, decay, boxes, img_w, img_h, n_k, Np, M, with_iou, max_center_dist, out=None):
+    traj = torch.empty((n_k, M), dtype=_f32, device=act.device) if out is None else out
+    check(_L().gom_track_score_f32(_p(act), _ld(act), _p(meta), _p(decay), _p(boxes), float(img_w), float(img_h),
                                    n_k, Np, M, 1 if with_iou else 0, float(max_center_dist), _p(traj), _stream()),
           "gom_track_score_f32")
+    return traj
+
+
+def asso_score(logits, offsets, T, meta, decay, boxes, img_w, img_h, n_k, Np, M, with_iou, max_center_dist, out=None):
+    """asso_activate + track_score of one match as ONE launch (the form the native matcher runs for N <= 16 384): logits
+    [n_k, N = Np + n_k], rows `logits.stride(0)` apart -> traj [n_k, M], the same values as the two launches."""
+    traj = torch.empty((n_k, M), dtype=_f32, device=logits.device) if out is None else out
+    check(_L().gom_asso_score_f32(_p(logits), _ld(logits), _p(offsets), T, _p(meta), _p(decay), _p(boxes), float(img_w),
+                                  float(img_h), n_k, Np, M, 1 if with_iou else 0, float(max_center_dist), _p(traj), _stream()),
+          "gom_asso_score_f32")
     return traj
 
 
@@ -2086,9 +2103,9 @@ BATCHED_SHORT_TERM = True  # False: per-pair kernels (kept for the A/B parity te
 SHORT_TERM_MAX_PREV = 320
 
 
-def short_term_pairs(tgt, memory, pairs, row_pair, boxes, img_w, img_h, with_iou, total_rows, max_prev, s_floats):
-    """All pairs' S = max(softmax-with-background(q.k^T), IoU) in one launch; returns the packed fp32 buffer."""
-    S = torch.empty((max(s_floats, 1),), dtype=_f32, device=tgt.device)
+def short_term_pairs(tgt, memory, pairs, row_pair, boxes, img_w, img_h, with_iou, total_rows, max_prev, s_floats, out=None):
+    """All pairs' S = max(softmax-with-background(q.k^T), IoU) in one launch; returns the packed fp32 buffer (`out`: a caller's)."""
+    S = torch.empty((max(s_floats, 1),), dtype=_f32, device=tgt.device) if out is None else out
     check(_L().gom_short_term_pairs_f32(_p(tgt), _p(memory), tgt.shape[1], _p(pairs), _p(row_pair), _p(boxes),
                                         float(img_w), float(img_h), 1 if with_iou else 0, total_rows, max_prev, _p(S),
                                         _stream()), "gom_short_term_pairs_f32")
