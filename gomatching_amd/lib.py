@@ -136,6 +136,10 @@ SIGNATURES = {
     "gom_result_rows_i32": (I, [P, P, P, I, I, P, I, P]),
     "gom_quad_pairs_count_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, P]),
     "gom_quad_pairs_emit_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, L, P, P, P]),
+    "gom_mask_fill_polygons_u32": (I, [P, I, P, I, P, P, P, I, L, P, I, I, I, P, P, P]),
+    "gom_mask_fill_rle_u32": (I, [P, I, P, P, P, I, L, P, I, I, I, P, P, P]),
+    "gom_mask_pairs_count_f64": (I, [P, P, P, P, L, P, P, P, P, L, P, P, P, P, I, I, I, L, D, P, P]),
+    "gom_mask_pairs_emit_f64": (I, [P, P, P, P, L, P, P, P, P, L, P, P, P, P, I, I, I, L, D, P, L, P, P, P]),
     "gom_maxpool3x3s2_nhwc_f32": (I, [P, P, I, I, I, I, P]),
     "gom_pos_encoding_2d_f32": (I, [P, P, P, I, I, P]),
     "gom_point_pos_embed_f32": (I, [P, P, P, L, P]),

@@ -1555,6 +1555,97 @@ def quad_pairs(gt_quads, det_quads, gt_off, det_off, gt_key, det_key, measure, t
     return counts, det, val
 
 
+def _chk_i(dev, *named):
+    for name, t, dtype, shape in named:
+        if not t.is_cuda or t.device != dev or t.dtype != dtype or t.dim() != len(shape) or \
+                any(s is not None and t.shape[i] != s for i, s in enumerate(shape)) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous CUDA %s tensor of shape %s" % (name, dtype, list(shape)))
+
+
+def _mask_fill_common(boxes, word_off, H, W, words, area, sel):
+    """Checks shared by the two fill calls -> (N, nwords, M): masks, words of the buffer, masks to fill."""
+    dev = boxes.device
+    _chk_i(dev, ("boxes", boxes, torch.int32, (None, 4)), ("word_off", word_off, torch.int64, (None,)),
+           ("words", words, torch.int32, (None,)), ("area", area, torch.int32, (None,)))
+    N = boxes.shape[0]
+    if word_off.shape[0] != N + 1 or area.shape[0] != N:
+        raise ValueError("word_off must be [N+1] and area [N]")
+    if sel is not None:
+        _chk_i(dev, ("sel", sel, torch.int32, (None,)))
+        if sel.shape[0] > N:
+            raise ValueError("sel names more masks than there are")
+    if boxes.data_ptr() % 16:
+        raise ValueError("boxes must be 16-byte aligned")
+    if int(H) < 1 or int(W) < 1 or int(H) * int(W) > 2 ** 31 - 1:
+        raise ValueError("H x W must lie in [1, 2^31 - 1]")
+    return N, words.shape[0], (N if sel is None else sel.shape[0])
+
+
+def mask_fill_polygons(points, contour_off, mask_coff, boxes, word_off, H, W, words, area, sel=None):
+    """Rasterise polygon masks into their bit rows (csrc/mask_pairs.hip; the rule and the representation are in
+    include/gomatching_hip.h).  points int32 [P,2], contour_off int32 [C+1], mask_coff int32 [N+1], boxes int32 [N,4] =
+    (y0, y1, wx0, wx1), word_off int64 [N+1], all CUDA; fills `words` (int32 [nwords], the uint32 bit rows) and `area`
+    (int32 [N], the popcounts) in place for every mask, or for the masks `sel` (int32 [M]) names.  -> (words, area)."""
+    N, nwords, M = _mask_fill_common(boxes, word_off, H, W, words, area, sel)
+    _chk_i(boxes.device, ("points", points, torch.int32, (None, 2)), ("contour_off", contour_off, torch.int32, (None,)),
+           ("mask_coff", mask_coff, torch.int32, (None,)))
+    P, C = points.shape[0], contour_off.shape[0] - 1
+    if C < 0 or mask_coff.shape[0] != N + 1:
+        raise ValueError("contour_off must be [C+1] and mask_coff [N+1]")
+    with torch.cuda.device(boxes.device):
+        check(_L().gom_mask_fill_polygons_u32(_p(points), P, _p(contour_off), C, _p(mask_coff), _p(boxes), _p(word_off), N, nwords,
+                                              _p(sel), M, int(H), int(W), _p(words), _p(area), _stream()),
+              "gom_mask_fill_polygons_u32")
+    return words, area
+
+
+def mask_fill_rle(ends, run_off, boxes, word_off, H, W, words, area, sel=None):
+    """Expand COCO run-length masks into their bit rows (csrc/mask_pairs.hip): ends int32 [R] the cumulative run ends (runs
+    alternate 0 / 1 from 0, column-major), run_off int32 [N+1]; the other arguments and the result as `mask_fill_polygons`."""
+    N, nwords, M = _mask_fill_common(boxes, word_off, H, W, words, area, sel)
+    _chk_i(boxes.device, ("ends", ends, torch.int32, (None,)), ("run_off", run_off, torch.int32, (None,)))
+    if run_off.shape[0] != N + 1:
+        raise ValueError("run_off must be [N+1]")
+    with torch.cuda.device(boxes.device):
+        check(_L().gom_mask_fill_rle_u32(_p(ends), ends.shape[0], _p(run_off), _p(boxes), _p(word_off), N, nwords, _p(sel), M,
+                                         int(H), int(W), _p(words), _p(area), _stream()), "gom_mask_fill_rle_u32")
+    return words, area
+
+
+def mask_pairs(gt_words, gt_boxes, gt_woff, gt_area, det_words, det_boxes, det_woff, det_area, gt_off, det_off, gt_key, det_key,
+               threshold, pairs=None):
+    """The (ground truth, detection) pairs of one video whose mask IoU is above `threshold` (csrc/mask_pairs.hip; contract
+    in include/gomatching_hip.h): two filled mask sets (words, boxes, word offsets, areas as the fill calls leave them),
+    gt_off / det_off int32 [F+1], gt_key [G] / det_key [D] int32.  -> the triple of `quad_pairs`: (counts int32 [G], det
+    int32 [K], value fp64 [K]), ordered by ground truth, then detection."""
+    dev = gt_boxes.device
+    i32, i64 = torch.int32, torch.int64
+    _chk_i(dev, ("gt_words", gt_words, i32, (None,)), ("gt_boxes", gt_boxes, i32, (None, 4)), ("gt_woff", gt_woff, i64, (None,)),
+           ("gt_area", gt_area, i32, (None,)), ("det_words", det_words, i32, (None,)), ("det_boxes", det_boxes, i32, (None, 4)),
+           ("det_woff", det_woff, i64, (None,)), ("det_area", det_area, i32, (None,)), ("gt_off", gt_off, i32, (None,)),
+           ("det_off", det_off, i32, (None,)), ("gt_key", gt_key, i32, (None,)), ("det_key", det_key, i32, (None,)))
+    G, D, F = gt_boxes.shape[0], det_boxes.shape[0], gt_off.shape[0] - 1
+    if F < 0 or det_off.shape[0] != F + 1 or gt_key.shape[0] != G or det_key.shape[0] != D or gt_woff.shape[0] != G + 1 or \
+            det_woff.shape[0] != D + 1 or gt_area.shape[0] != G or det_area.shape[0] != D:
+        raise ValueError("offsets must be [F+1], word offsets [G+1] / [D+1], keys and areas [G] / [D]")
+    if gt_boxes.data_ptr() % 16 or det_boxes.data_ptr() % 16:
+        raise ValueError("gt_boxes and det_boxes must be 16-byte aligned")
+    if pairs is None:
+        pairs = 0 if F == 0 else int(((gt_off[1:] - gt_off[:-1]).to(i64) * (det_off[1:] - det_off[:-1]).to(i64)).sum())
+    counts = torch.empty((G,), dtype=i32, device=dev)
+    args = (_p(gt_words), _p(gt_boxes), _p(gt_woff), _p(gt_area), gt_words.shape[0], _p(det_words), _p(det_boxes), _p(det_woff),
+            _p(det_area), det_words.shape[0], _p(gt_off), _p(det_off), _p(gt_key), _p(det_key), G, D, F, int(pairs), float(threshold))
+    with torch.cuda.device(dev):
+        check(_L().gom_mask_pairs_count_f64(*args, _p(counts), _stream()), "gom_mask_pairs_count_f64")
+        ends = torch.cumsum(counts, 0, dtype=i64)
+        total = int(ends[-1]) if G else 0
+        scan = ends - counts
+        det = torch.empty((total,), dtype=i32, device=dev)
+        val = torch.empty((total,), dtype=torch.float64, device=dev)
+        check(_L().gom_mask_pairs_emit_f64(*args, _p(scan), total, _p(det), _p(val), _stream()), "gom_mask_pairs_emit_f64")
+    return counts, det, val
+
+
 STEM_POOL = _switch("STEM_POOL")    # f16x3 back-end: the ResNet stem (conv 7x7 / 2 + BN + ReLU + max-pool 3x3 / 2) as one launch
 
 

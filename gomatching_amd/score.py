@@ -1,6 +1,13 @@
 """Score result files: MOTA / MOTP / IDF1 of the DSText protocols.
 
     python -m gomatching_amd.score --gt GT --results RES [--e2e] [--threshold 0.5] [--host-iou] [--output scores.json]
+    python -m gomatching_amd.score --protocol {dstext,bovtext,artvideo} ...
+
+`--protocol dstext` (the default) is what this module describes; `bovtext` and `artvideo` score the `<out>/jsons` of
+`python -m gomatching_amd.eval` and live in score_json.py (the json readers, the OVERALL row, the transcription similarity
+and ArTVideo's mask IoU on the pixel grid, csrc/mask_pairs.hip), with their own list of deliberate differences and of
+UNPINNED libraries (cv2.fillPoly, pycocotools, Levenshtein, shapely).  Not built in any protocol: XSD validation, the
+per-frame event dump, the Excel summary.
 
 GT and RES are directories or .zip files.  GT holds `Video_<a>_<b>_<c>_GT.xml` (and `..._GT.txt` for --e2e); RES holds the
 `res_Video_<a>_<b>_<c>.xml` / `.txt` that `python -m gomatching_amd.eval` writes into `<out>/preds`.  The figures are those of the
@@ -559,12 +566,21 @@ def build_parser():
     p.add_argument("--threshold", type=float, default=0.5, help="a pair counts when its IoU is above this (default 0.5)")
     p.add_argument("--host-iou", action="store_true", help="polygon measure in numpy float64 instead of the HIP kernels")
     p.add_argument("--output", default="scores.json", help="where the figures are written (default scores.json)")
+    p.add_argument("--protocol", choices=("dstext", "bovtext", "artvideo"), default="dstext",
+                   help="dstext: the XML protocol (default); bovtext / artvideo: the json protocols (score_json.py), where --gt "
+                        "holds GT/<class>/<name>.json or GT/<name>.json and --results the jsons/<name>.json of the eval command")
+    p.add_argument("--curve", action="store_true", help="artvideo only: only evaluate curved text (Straight objects are ignored)")
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.protocol != "dstext":
+        from . import score_json
+        return score_json.main(args)
     try:
+        if args.curve:
+            raise ScoreError("--curve belongs to --protocol artvideo")
         if not (0.0 < args.threshold < 1.0):
             raise ScoreError("--threshold must lie strictly between 0 and 1")
         res = score_method(args.gt, args.results, args.e2e, args.threshold, args.host_iou)
@@ -583,6 +599,18 @@ def main(argv=None):
         print("Video_%s: MOTA %.4f  MOTP %.4f  IDF1 %.4f  FP %d  MS %d  SW %d" % (
             k, s["MOTA"], s["MOTP"], s["IDF1"], s["FP"], s["MS"], s["SW"]))
     return 0
+
+
+def host_mask_pairs(*args, **kwargs):
+    """The mask measure of the json protocols on the host: `score_json.host_mask_pairs`, where it lives."""
+    from . import score_json
+    return score_json.host_mask_pairs(*args, **kwargs)
+
+
+def device_mask_pairs(*args, **kwargs):
+    """The mask measure of the json protocols through the kernels: `score_json.device_mask_pairs`."""
+    from . import score_json
+    return score_json.device_mask_pairs(*args, **kwargs)
 
 
 if __name__ == "__main__":

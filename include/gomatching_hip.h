@@ -537,6 +537,68 @@ int gom_quad_pairs_emit_f64(const int32_t* gt_quads, const int32_t* det_quads, c
                             const int32_t* det_off, const int32_t* gt_key, const int32_t* det_key, int G, int D, int F,
                             long pairs, int measure, double threshold, const int64_t* scan, long total, int32_t* out_det,
                             double* out_val, void* stream);
+/* Scoring on the pixel grid (csrc/mask_pairs.hip): the mask IoU of the ArTVideo protocol.
+ *
+ * Representation.  A mask is a box plus bit rows: boxes int32 [N,4] = (y0, y1, wx0, wx1), rows [y0, y1), 32-pixel word
+ * columns [wx0, wx1) in ABSOLUTE alignment -- word wx holds the pixels 32*wx .. 32*wx+31, bit b is pixel 32*wx + b -- so two
+ * masks are ANDed without shifts.  All masks of a call live in one uint32 buffer `words` [nwords]; mask k owns the
+ * (y1-y0)*(wx1-wx0) words from word_off[k] (int64 [N+1], CSR), row-major.  Boxes and offsets are the caller's, computed
+ * from the vertex extents or from the runs and clipped to the H x W image; a box that is too small loses pixels, one that
+ * leaves the image or the buffer is cut back: only a mask's own words are ever written.
+ *
+ * Rasterisation rule (gom_mask_fill_polygons_u32): the project's statement of cv2.fillPoly(img, contours, 1) with lineType 8
+ * and shift 0 -- PARITY with OpenCV is UNPINNED -- in 64-bit signed integers with S = 16.  The set is the union over a
+ * mask's contours of Fill(contour) and Boundary(contour).
+ *   Boundary: for every edge (v[i-1], v[i]), the closing edge included, the 8-connected line between the integer end
+ *     points, both inclusive.  If x1 < x0 the end points are swapped (left to right).  M = max(|dx|, |dy|), m = min(|dx|,
+ *     |dy|), err = M - 2m; M + 1 times: emit the pixel; if err < 0 step both axes and err += 2M - 2m, else step the major
+ *     axis only and err -= 2m.  The major axis is x unless |dy| > |dx|.  Pixels outside the image are dropped.
+ *   Fill: an edge with ya != yb is active on the scanlines min(ya, yb) <= y < max(ya, yb), at X(y) = (x_top << S) +
+ *     (y - y_top) * dxq, dxq = ((x_bottom - x_top) << S) / (y_bottom - y_top) in C division (toward zero).  The active
+ *     positions of a scanline sorted, c_1 <= c_2 <= .., each pair (c_1, c_2), (c_3, c_4), .. fills the pixels
+ *     ceil(c_odd / 2^S) .. floor(c_even / 2^S) clipped to [0, W-1]; rows outside [0, H-1] are dropped; the lowest row of a
+ *     contour gets its pixels from Boundary only.  Sort-free form, the one the kernel evaluates: for pixel x, Xp = x << S,
+ *     a = the number of active positions < Xp, b = the number <= Xp: filled iff b > a or a is odd.
+ *   points int32 [P,2] (x, y; expected within +-2^20), contour_off int32 [C+1] (first point of each contour), mask_coff
+ *   int32 [N+1] (first contour of each mask).
+ * gom_mask_fill_rle_u32: COCO run lengths, runs alternating 0 / 1 starting with 0 in column-major order (pixel index
+ *   x * H + y).  ends int32 [R] = the cumulative run ends of every mask, run_off int32 [N+1] (first run of each mask): a
+ *   pixel is set when an odd number of its mask's ends are <= its index.
+ * Both: H * W <= INT32_MAX; sel = NULL fills all N masks (M must equal N), else int32 [M] names the masks to fill and the
+ * others' words and areas are left alone (a set that mixes both kinds takes one call of each); area[k] int32 = the
+ * popcount of mask k.  A thread owns a word: plain stores, bitwise reproducible.
+ *
+ * gom_mask_pairs_count_f64 / gom_mask_pairs_emit_f64: the contract of gom_quad_pairs_* over two filled sets (words, boxes,
+ * word offsets, areas, nwords of each): gt_off / det_off int32 [F+1] first mask of each frame, pairs only within a frame
+ * and between equal keys, `pairs` the sum over the frames of (ground truth) x (detections), threshold STRICT.  Per pair:
+ * inter = popcount of the AND over the intersection of the two boxes; value 0.0 when inter < 1, else
+ * (double)inter / (double)(area_g + area_d - inter), ONE division of integer counts: bitwise the host statement.
+ * counts[g] = kept detections of ground-truth mask g; the emit pass takes scan [G] int64 = exclusive prefix sum of the
+ * counts and total = their sum and writes per kept pair the detection's index within its frame (out_det int32 [total]) and
+ * the value (out_val fp64 [total]), ordered by ground truth, then detection.  One wavefront per ground-truth mask, ballot
+ * over box tests, shuffle reduction, no atomics: the output does not depend on the launch geometry.  Every index made
+ * from device-side offsets is clamped.
+ * The box arrays (boxes, gt_boxes, det_boxes) must be 16-byte aligned: a box is read as one 16-byte word.
+ * GOM_ERR_INVALID_ARG before any HIP call: null pointers, a box array that is not 16-byte aligned, negative sizes, H or W < 1, H * W above INT32_MAX, M != N
+ * without sel or M > N with it, F == 0 with masks, threshold outside (0, 1), pairs negative, above G * D or above
+ * INT32_MAX, total negative or above pairs.  M == 0, G == 0 (and for the emit pass total == 0) are GOM_OK without a launch. */
+int gom_mask_fill_polygons_u32(const int32_t* points, int P, const int32_t* contour_off, int C, const int32_t* mask_coff,
+                               const int32_t* boxes, const int64_t* word_off, int N, long nwords, const int32_t* sel, int M,
+                               int H, int W, uint32_t* words, int32_t* area, void* stream);
+int gom_mask_fill_rle_u32(const int32_t* ends, int R, const int32_t* run_off, const int32_t* boxes, const int64_t* word_off,
+                          int N, long nwords, const int32_t* sel, int M, int H, int W, uint32_t* words, int32_t* area,
+                          void* stream);
+int gom_mask_pairs_count_f64(const uint32_t* gt_words, const int32_t* gt_boxes, const int64_t* gt_woff,
+                             const int32_t* gt_area, long gt_nwords, const uint32_t* det_words, const int32_t* det_boxes,
+                             const int64_t* det_woff, const int32_t* det_area, long det_nwords, const int32_t* gt_off,
+                             const int32_t* det_off, const int32_t* gt_key, const int32_t* det_key, int G, int D, int F,
+                             long pairs, double threshold, int32_t* counts, void* stream);
+int gom_mask_pairs_emit_f64(const uint32_t* gt_words, const int32_t* gt_boxes, const int64_t* gt_woff,
+                            const int32_t* gt_area, long gt_nwords, const uint32_t* det_words, const int32_t* det_boxes,
+                            const int64_t* det_woff, const int32_t* det_area, long det_nwords, const int32_t* gt_off,
+                            const int32_t* det_off, const int32_t* gt_key, const int32_t* det_key, int G, int D, int F,
+                            long pairs, double threshold, const int64_t* scan, long total, int32_t* out_det,
+                            double* out_val, void* stream);
 int gom_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 /* out [H*W, 256] = PositionalEncoding2D(normalize=True) + level_embed, for an unpadded H x W level. */
 int gom_pos_encoding_2d_f32(const float* dim_t128, const float* level_embed256, float* out, int H, int W,
