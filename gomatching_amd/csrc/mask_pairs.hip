@@ -25,45 +25,13 @@
 // count / write position are wave-uniform scalars: no atomics, output independent of the launch geometry.  Offsets, boxes,
 // scan and areas are device data the host cannot vouch for: every index made from them is clamped.
 #include "common.h"
+#include "mask_rule.h"
 
 #define MK_FILL_THREADS 256
 #define MK_WAVES 4
 #define MK_S 16
 
 namespace {
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ long long clampl(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// bits [lo, hi] of a word (pixel offsets relative to the word's first pixel; any range)
-__device__ __forceinline__ unsigned bit_range(long long lo, long long hi) {
-    if (hi < 0 || lo > 31 || lo > hi) return 0u;
-    const int l = lo < 0 ? 0 : (int)lo, h = hi > 31 ? 31 : (int)hi;
-    return (0xffffffffu >> (31 - h)) & (0xffffffffu << l);
-}
-
-// floor(a / b), b > 0
-__device__ __forceinline__ long long floor_div(long long a, long long b) {
-    long long q = a / b;
-    if ((a % b) < 0) --q;
-    return q;
-}
-
-struct Box {
-    int y0, y1, wx0, wx1;
-};
-
-// a mask's box, made consistent with the image and with the words the caller allotted to it
-__device__ __forceinline__ Box load_box(const int* __restrict__ boxes, int k, int H, int W) {
-    const int4 b = *reinterpret_cast<const int4*>(boxes + 4 * (long long)k);
-    Box r;
-    const int NWI = (W + 31) >> 5;
-    r.y0 = clampi(b.x, 0, H);
-    r.y1 = clampi(b.y, r.y0, H);
-    r.wx0 = clampi(b.z, 0, NWI);
-    r.wx1 = clampi(b.w, r.wx0, NWI);
-    return r;
-}
 
 // sum over the block -> thread 0
 __device__ __forceinline__ int block_sum(int v, int* lds) {
@@ -118,29 +86,7 @@ __global__ __launch_bounds__(MK_FILL_THREADS) void fill_polygon_kernel(
                         if ((pos & ((1LL << MK_S) - 1)) == 0) set |= bit_range(fl - px0, fl - px0);
                     }
                 }
-                // ---- boundary: the line from the left end point to the right one
-                {
-                    const bool sw = xb < xa;
-                    const long long x0 = sw ? xb : xa, y0 = sw ? yb : ya, x1 = sw ? xa : xb, y1 = sw ? ya : yb;
-                    const long long dx = x1 - x0, dy = y1 - y0, ady = dy < 0 ? -dy : dy;
-                    const long long M = dx > ady ? dx : ady, m = dx > ady ? ady : dx;
-                    const long long j = dy < 0 ? y0 - y : y - y0;                                // the row's step along y
-                    if (ady > dx) {                                                              // y-major: one pixel per row
-                        if (j >= 0 && j <= M) {
-                            const long long x = x0 + (2 * m * j + M - 1) / (2 * M);
-                            set |= bit_range(x - px0, x - px0);
-                        }
-                    } else if (j >= 0 && j <= m) {                                               // x-major: a run of steps
-                        long long klo = 0, khi = M;
-                        if (m > 0) {
-                            klo = -floor_div(-(2 * M * j - M + 1), 2 * m);                       // ceil
-                            khi = floor_div(2 * M * j + M, 2 * m);
-                            if (klo < 0) klo = 0;
-                            if (khi > M) khi = M;
-                        }
-                        set |= bit_range(x0 + klo - px0, x0 + khi - px0);
-                    }
-                }
+                set |= boundary_bits(xa, ya, xb, yb, y, px0);
                 xa = xb;
                 ya = yb;
             }

@@ -1,9 +1,10 @@
 """`python -m gomatching_amd.eval`: run the spotter over a dataset directory and write the result files the reference's
 offline evaluation protocols consume -- the counterpart of the reference's measured entry point (eval.py:212-383)
-without drawing.
+with `--show` as the one optional drawing step.
 
-    python -m gomatching_amd.eval --config-file FILE --input DIR --output OUT --opts MODEL.WEIGHTS W
+    python -m gomatching_amd.eval --config-file FILE --input DIR --output OUT [--show] --opts MODEL.WEIGHTS W
       -> OUT/preds/res_<video>.xml, OUT/preds/res_<video>.txt, OUT/jsons/<video>.json
+      -> with --show also OUT/results/<video>/<frame file>: every frame with its tracked text drawn on it
 
 What it keeps of the reference: `setup_cfg` (with the ASSO_THRESH_TEST override of :220), the data type taken from the
 input path (DSText / ICDAR15 / BOVText / OTHER), video directories one level deeper for DSText and BOVText (:290-295),
@@ -15,7 +16,10 @@ Deliberate differences:
   * the "already written" check compares the XML stem `results.result_names` returns; the reference compares the raw
     video name, which never matches an ICDAR15 stem ('Video_35_2_3' is written as res_video_35.xml), so it never
     resumes on ICDAR15;
-  * no `--cpu` (there is no CPU path), no `--webcam`, no `--show` (nothing is drawn);
+  * no `--cpu` (there is no CPU path), no `--webcam`;
+  * `--show` draws with csrc/overlay.hip by an integer rule instead of matplotlib (`gomatching_amd.show`: colours by track
+    id, Pillow's glyphs, no antialiasing); without it the command does what it did before the flag existed, launch for launch.
+    A resumed run skips finished videos, pictures included: `python -m gomatching_amd.show` draws them from OUT/jsons;
   * frames are decoded with Pillow (`convert("RGB")`, reversed to the BGR order `read_image(format="BGR")` yields).
     OpenCV is not available here, so the parity of the decoded pixels with `cv2.imread` (JPEG decoders differ in their
     IDCT and chroma upsampling) is UNPINNED, as is the parity of `results.min_area_rect` with `cv2.minAreaRect`.
@@ -36,12 +40,17 @@ DAMAGED_VIDEOS = ("Cls1_Livestreaming_video40",)          # eval.py:316 "filter 
 DECODE_THREADS = 4                                        # a small fixed pool that decodes frames ahead (never sized by the host)
 
 
-def get_parser():
+def get_parser(drawing=False):
+    """The spotting options; drawing=True, what the command itself parses with, adds the drawing step's (--show, --font,
+    --host-draw).  A caller that builds on the default parser gets a run that draws nothing and an error for --show."""
     p = argparse.ArgumentParser(
         prog="python -m gomatching_amd.eval",
         description="Video text spotting over a dataset directory on an MI355X; writes preds/res_*.xml, preds/res_*.txt and "
-                    "jsons/*.json under --output.  There is no --cpu, --webcam or --show: the package has no CPU path and "
-                    "draws nothing.")
+                    "jsons/*.json under --output" + (
+                        ", and with --show results/<video>/<frame file> with the tracked text drawn on every frame.  There is no "
+                        "--cpu or --webcam: the package has no CPU path." if drawing else
+                        ".  There is no --cpu or --webcam (the package has no CPU path); --show belongs to the command's own "
+                        "parser, get_parser(drawing=True)."))
     p.add_argument("--config-file", default=None, metavar="FILE", help="path to config file")
     p.add_argument("--builtin", default=None, choices=sorted(_config.BUILTIN), metavar="NAME",
                    help="a packaged config instead of --config-file: " + ", ".join(sorted(_config.BUILTIN)))
@@ -53,6 +62,14 @@ def get_parser():
                    help="resize and normalise frames on the host (default: on the GPU, bit-exact with the host path)")
     p.add_argument("--host-rows", action="store_true",
                    help="build result rows per frame on the host (default: one kernel launch and one copy per clip)")
+    if drawing:
+        p.add_argument("--show", action="store_true",
+                       help="write every frame with its tracked text drawn on it to results/<video>/ (polygons in the colour "
+                            "of their track, (id)TEXT labels)")
+        p.add_argument("--font", default=None, metavar="FILE",
+                       help="with --show: a TrueType font for the labels (default: Pillow's)")
+        p.add_argument("--host-draw", action="store_true",
+                       help="with --show: draw in numpy on the host (default: on the GPU, the same bytes)")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER,
                    help="modify config options using the command-line 'KEY VALUE' pairs")
     return p
@@ -115,7 +132,7 @@ def load_weights(path):
 
 
 def main(argv=None):
-    args = get_parser().parse_args(argv)
+    args = get_parser(drawing=True).parse_args(argv)
     if (args.config_file is None) == (args.builtin is None):
         sys.stderr.write("error: give exactly one of --config-file and --builtin\n")
         return 2
@@ -149,20 +166,30 @@ def main(argv=None):
         model = GoMatching(cfg, state_dict, frames_per_step=args.frames_per_step)
         spotter = GoMBatchPredictor(cfg, model, device_ingest=not args.host_ingest)
         decoder = TextDecoder(cfg.MODEL.TRANSFORMER.VOC_SIZE, cfg.MODEL.TRANSFORMER.CUSTOM_DICT)
-    total_frame, read_seconds, rows_seconds = 0, 0.0, 0.0
+    total_frame, read_seconds, rows_seconds, draw_seconds = 0, 0.0, 0.0, 0.0
+    if args.show:
+        from . import show as _show
+        atlas = _show.Atlas(args.font)
     with ThreadPoolExecutor(max_workers=DECODE_THREADS) as pool:
         for video_name, video_dir in videos:
             print("processing {}...".format(video_name))
             t0 = time.time()
-            frames = list(pool.map(read_frame, frame_paths(video_dir)))
+            paths = frame_paths(video_dir)
+            frames = list(pool.map(read_frame, paths))
             read_seconds += time.time() - t0
             if not frames:
                 continue
             preds, per_video_time = _results.spot_video(spotter, frames, time_cost)
             total_frame += len(frames)
             t0 = time.time()
-            _results.write_video(preds, video_name, data_type, args.output, decoder, device_rows=not args.host_rows)
+            annotation = _results.write_video(preds, video_name, data_type, args.output, decoder,
+                                              device_rows=not args.host_rows)
             rows_seconds += time.time() - t0
+            if args.show:
+                t0 = time.time()
+                _show.draw_video(frames, annotation, paths, video_name, args.output, cfg.MODEL.TRANSFORMER.VOC_SIZE, pool, atlas,
+                                 host=args.host_draw)
+                draw_seconds += time.time() - t0
             print("Video: ", video_name, "per_img_time: ", per_video_time / len(frames), ", FPS: ",
                   len(frames) / per_video_time)
     t0 = time.time()
@@ -174,6 +201,8 @@ def main(argv=None):
     print(time_cost)
     print("host seconds outside the timed window: reading frames ", read_seconds, ", building rows and writing files ",
           rows_seconds, ", videos processed: ", len(videos))
+    if args.show:
+        print("host seconds drawing and encoding frames: ", draw_seconds)
     return 0
 
 

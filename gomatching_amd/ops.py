@@ -1646,7 +1646,70 @@ def mask_pairs(gt_words, gt_boxes, gt_woff, gt_area, det_words, det_boxes, det_w
     return counts, det, val
 
 
-STEM_POOL = _switch("STEM_POOL")    # f16x3 back-end: the ResNet stem (conv 7x7 / 2 + BN + ReLU + max-pool 3x3 / 2) as one launch
+def mask_outline_polygons(points, contour_off, mask_coff, boxes, word_off, H, W, words, sel=None):
+    """`mask_fill_polygons` for the outlines alone (csrc/overlay.hip): writes Boundary of the rasterisation rule, without
+    Fill and without areas, into `words` (int32 [nwords]) for every mask, or for the masks `sel` names.  -> words."""
+    dev = boxes.device
+    _chk_i(dev, ("boxes", boxes, torch.int32, (None, 4)), ("word_off", word_off, torch.int64, (None,)),
+           ("words", words, torch.int32, (None,)), ("points", points, torch.int32, (None, 2)),
+           ("contour_off", contour_off, torch.int32, (None,)), ("mask_coff", mask_coff, torch.int32, (None,)))
+    N, P, C = boxes.shape[0], points.shape[0], contour_off.shape[0] - 1
+    if word_off.shape[0] != N + 1 or C < 0 or mask_coff.shape[0] != N + 1:
+        raise ValueError("word_off and mask_coff must be [N+1] and contour_off [C+1]")
+    if sel is not None:
+        _chk_i(dev, ("sel", sel, torch.int32, (None,)))
+        if sel.shape[0] > N:
+            raise ValueError("sel names more masks than there are")
+    if boxes.data_ptr() % 16:
+        raise ValueError("boxes must be 16-byte aligned")
+    if int(H) < 1 or int(W) < 1 or int(H) * int(W) > 2 ** 31 - 1:
+        raise ValueError("H x W must lie in [1, 2^31 - 1]")
+    with torch.cuda.device(dev):
+        check(_L().gom_mask_outline_polygons_u32(_p(points), P, _p(contour_off), C, _p(mask_coff), _p(boxes), _p(word_off), N,
+                                                 words.shape[0], _p(sel), N if sel is None else sel.shape[0], int(H), int(W),
+                                                 _p(words), _stream()), "gom_mask_outline_polygons_u32")
+    return words
+
+
+def overlay_compose(frames, face_words, outline_words, boxes, word_off, inst_off, inst_rgb, label_off, label_pos, label_glyph,
+                    label_rgb, glyph_wh, glyph_woff, glyph_words, a_face, a_box, out=None):
+    """Draw instances and labels over u8 frames [F,H,W,3] (csrc/overlay.hip; the integer rule is in
+    include/gomatching_hip.h): two mask sets over one set of boxes and word offsets (what `mask_fill_polygons` and
+    `mask_outline_polygons` leave), inst_off int32 [F+1], inst_rgb u8 [N,3], the labels (label_off int32 [F+1], label_pos int32
+    [L,2], label_glyph int32 [L], label_rgb u8 [L,3]) and the atlas (glyph_wh int32 [G,2], glyph_woff int64 [G+1], glyph_words
+    int32, the uint32 bitmap rows), all CUDA.  `out` may be `frames` (in place); default a new tensor.  -> out."""
+    _chk_frames(frames)
+    dev = frames.device
+    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
+    _chk_i(dev, ("face_words", face_words, i32, (None,)), ("outline_words", outline_words, i32, (None,)),
+           ("boxes", boxes, i32, (None, 4)), ("word_off", word_off, i64, (None,)), ("inst_off", inst_off, i32, (None,)),
+           ("inst_rgb", inst_rgb, u8, (None, 3)), ("label_off", label_off, i32, (None,)), ("label_pos", label_pos, i32, (None, 2)),
+           ("label_glyph", label_glyph, i32, (None,)), ("label_rgb", label_rgb, u8, (None, 3)), ("glyph_wh", glyph_wh, i32, (None, 2)),
+           ("glyph_woff", glyph_woff, i64, (None,)), ("glyph_words", glyph_words, i32, (None,)))
+    F, H, W, _ = frames.shape
+    N, L, G = boxes.shape[0], label_pos.shape[0], glyph_wh.shape[0]
+    if inst_off.shape[0] != F + 1 or label_off.shape[0] != F + 1 or word_off.shape[0] != N + 1 or inst_rgb.shape[0] != N or \
+            outline_words.shape[0] != face_words.shape[0] or label_glyph.shape[0] != L or label_rgb.shape[0] != L or \
+            glyph_woff.shape[0] != G + 1:
+        raise ValueError("offsets must be [F+1], word_off [N+1], inst_rgb [N,3], the two word buffers of one size, "
+                         "label arrays [L] and glyph_woff [G+1]")
+    if boxes.data_ptr() % 16:
+        raise ValueError("boxes must be 16-byte aligned")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out is not frames:
+        _chk_frames(out)
+        if out.shape != frames.shape or out.device != dev:
+            raise ValueError("out must have the shape and the device of frames")
+    with torch.cuda.device(dev):
+        check(_L().gom_overlay_compose_u8(_p(frames), _p(out), F, H, W, _p(face_words), _p(outline_words), _p(boxes), _p(word_off),
+                                          N, face_words.shape[0], _p(inst_off), _p(inst_rgb), _p(label_off), _p(label_pos),
+                                          _p(label_glyph), _p(label_rgb), L, _p(glyph_wh), _p(glyph_woff), _p(glyph_words), G,
+                                          glyph_words.shape[0], int(a_face), int(a_box), _stream()), "gom_overlay_compose_u8")
+    return out
+
+
+STEM_POOL = _switch("STEM_POOL")   # f16x3 back-end: the ResNet stem (conv 7x7 / 2 + BN + ReLU + max-pool 3x3 / 2) as one launch
 
 
 def stem_conv_pool(x, w, scale=None, shift=None):

@@ -205,12 +205,13 @@ def _pack(img):
     return np.packbits(img, axis=1, bitorder="little").view("<u4").astype(np.uint32)
 
 
-def fill_polygon_rows(contours, box, W):
+def fill_polygon_rows(contours, box, W, fill=True):
     """The rasterisation rule of include/gomatching_hip.h for one mask in closed form, as fill_polygon_kernel of
     csrc/mask_pairs.hip evaluates it: -> uint32 [y1 - y0, wx1 - wx0].
     Fill: a crossing c toggles the pixels x >= (c >> S) + 1 and sets pixel c >> S when its fraction is zero (the sort-free
     form).  Boundary: step k of a line sits at the minor offset (2 m k + M - 1) // (2 M), so an x-major edge covers on row j
-    the steps ceil((2 M j - M + 1) / (2 m)) .. floor((2 M j + M) / (2 m)) and a y-major edge one pixel per row."""
+    the steps ceil((2 M j - M + 1) / (2 m)) .. floor((2 M j + M) / (2 m)) and a y-major edge one pixel per row.
+    fill=False leaves Fill out: Boundary alone, the outline `show` draws (outline_polygon_kernel of csrc/overlay.hip)."""
     y0, y1, wx0, wx1 = (int(v) for v in box)
     R, NW = y1 - y0, wx1 - wx0
     if R <= 0 or NW <= 0:
@@ -232,7 +233,7 @@ def fill_polygon_rows(contours, box, W):
         dxq = np.sign(num) * (np.abs(num) // np.maximum(dy, 1))   # C division: toward zero
         act = (dy > 0)[:, None] & (yt[:, None] <= ys) & (ys < yo[:, None])
         pos = (xt[:, None] << S) + (ys - yt[:, None]) * dxq[:, None]
-        e, r = np.nonzero(act)
+        e, r = np.nonzero(act) if fill else ((), ())
         if len(e):
             par = np.zeros((R, WB + 1), dtype=np.int64)
             np.add.at(par, (r, np.clip((pos[e, r] >> S) + 1 - X0, 0, WB)), 1)

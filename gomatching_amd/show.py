@@ -1,0 +1,464 @@
+"""`python -m gomatching_amd.show`: draw tracked text on the frames of a dataset from the result files `gomatching_amd.eval`
+wrote -- the counterpart of the reference's `eval.py --show` (eval.py:364-369, text_track_visualizer.py), without a model.
+
+    python -m gomatching_amd.show --input DIR --results OUT [--output DIR] [--font FILE] [--host-draw]
+                                  [--voc-size N | --config-file F | --builtin NAME]
+      -> DIR/results/<video name>/<basename of the source frame>   (DIR defaults to OUT)
+
+Drawing is a pure function of the frames and the result rows `[x1..y4, id, text, [polygon]]` (what `results.frame_lines` /
+`clip_lines` build and `jsons/<video>.json` stores), so `eval --show` and this command draw the same bytes.  Per instance of a
+frame, in row order: the polygon's face blended at `A_FACE` / 255 in the colour of its track and its outline in that colour,
+opaque; then, above every polygon, per instance a `(id)TEXT` label: a white box blended at `A_BOX` / 255 with the text in a
+readable variant of the track colour.  The pixels are the integer rule of include/gomatching_hip.h
+(`gom_overlay_compose_u8`): csrc/overlay.hip on the GPU, `compose_host` in numpy (`--host-draw`), byte for byte the same.
+
+What it keeps of the reference: translucent face at alpha 0.5 and an outline per polygon, label text `(id)TEXT` upper-cased for
+the 37-character vocabulary (text_track_visualizer.py:139-144), the label colour rule of `draw_text` (:231-232), the white
+label box at alpha 0.8, labels above all polygons (zorder 10), the font size `max(sqrt(H W) // 70, 10)` (:98-100), the label
+anchored with its top-left corner at the midpoint of the text's centre line (:146-148), `results/<video>/<frame file name>`
+(eval.py:269, 321, 368).
+
+Deliberate differences:
+  * `track_color` is a pure function of the track id (a fixed palette of 500 colours indexed by id % 500); the reference draws
+    random colours and hands them out by first appearance, so a redrawn or resumed video would change colours;
+  * `label_anchor` takes the centre line from the 50-point result polygon (c_i = (P[i] + P[n-1-i]) / 2); the reference walks the
+    float `ctrl_points`, which the result files do not carry;
+  * `font_px` is used as a pixel size; matplotlib's point-to-pixel scale is not reproduced, and the label box is padded by one
+    pixel (the reference's `pad: 0.7` is in points).
+UNPINNED against the reference by construction: antialiasing (there is none here), matplotlib's stroke width and fonts (label
+bitmaps come from Pillow: `ImageFont.truetype(--font)` or `ImageFont.load_default`, `getmask(text, mode="1")`; characters the
+font lacks are Pillow's business) and the encoder of `cv2.imwrite` (frames are written with Pillow, JPEG at quality 95).
+Not built: `--webcam`, video-file input, `ColorMode.IMAGE_BW`.
+"""
+import argparse
+import colorsys
+import json
+import math
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from . import score_json as _sj
+from .score import ScoreError
+
+PALETTE_SIZE = 500
+A_FACE = 128                                               # alpha 0.5 of draw_polygon, in 255ths
+A_BOX = 204                                                # alpha 0.8 of the label's bbox
+CHUNK = 100                                                # frames per fill / outline / compose call
+WRITE_THREADS = 4                                          # a small fixed pool that encodes frames (never sized by the host)
+
+
+class ShowError(Exception):
+    """Input the command cannot draw; the message names the video."""
+
+
+# ------------------------------------------------------------------------------------------ colours, text, geometry
+def _palette():
+    """Colour i: hue = frac(i * 0.618033988749895) (golden-ratio steps keep neighbouring ids apart), saturation
+    (0.55, 0.75, 0.95)[i % 3], value (1.0, 0.85)[(i // 3) % 2], `colorsys.hsv_to_rgb`, each channel int(c * 255 + 0.5)."""
+    out = np.zeros((PALETTE_SIZE, 3), dtype=np.uint8)
+    for i in range(PALETTE_SIZE):
+        rgb = colorsys.hsv_to_rgb((i * 0.618033988749895) % 1.0, (0.55, 0.75, 0.95)[i % 3], (1.0, 0.85)[(i // 3) % 2])
+        out[i] = [int(c * 255 + 0.5) for c in rgb]
+    return out
+
+
+PALETTE = _palette()
+
+
+def track_color(track_id):
+    """(r, g, b) in 0..255 of a track: PALETTE[track_id % 500]."""
+    return tuple(int(v) for v in PALETTE[int(track_id) % PALETTE_SIZE])
+
+
+def text_color(rgb):
+    """`draw_text`'s readable variant of a colour (text_track_visualizer.py:231-232): every channel at least 0.2, the largest
+    at least 0.8; channels back to 0..255 as int(c * 255 + 0.5)."""
+    c = [max(int(v) / 255.0, 0.2) for v in rgb]
+    top = max(range(3), key=lambda i: (c[i], -i))          # np.argmax: the first of equal maxima
+    c[top] = max(0.8, c[top])
+    return tuple(int(v * 255 + 0.5) for v in c)
+
+
+def label_text(track_id, text, voc_size):
+    """"(id)TEXT", upper-cased for the 37-character vocabulary (text_track_visualizer.py:139-144)."""
+    text = str(text)
+    if int(voc_size) == 37:
+        text = text.upper()
+    return "({}){}".format(int(track_id), text)
+
+
+def font_px(H, W):
+    """`_default_font_size` (text_track_visualizer.py:98-100), used as a pixel size."""
+    return max(int(math.sqrt(int(H) * int(W))) // 70, 10)
+
+
+def label_anchor(polygon):
+    """(x, y) int of a label's top-left corner: the point at half the arc length of the centre line c_i = (P[i] + P[n-1-i]) / 2,
+    i < n / 2 (what `LineString(c).interpolate(0.5, normalized=True)` returns), truncated toward zero."""
+    P = np.asarray(polygon, dtype=np.float64).reshape(-1, 2)
+    n = len(P)
+    if n == 0:
+        return 0, 0
+    half = (n + 1) // 2
+    c = (P[:half] + P[::-1][:half]) / 2.0
+    seg = np.hypot(*(c[1:] - c[:-1]).T) if half > 1 else np.zeros(0)
+    total = float(seg.sum())
+    pt = c[0]
+    if total > 0.0:
+        target, walked = total / 2.0, 0.0
+        for i, d in enumerate(seg.tolist()):
+            if d > 0.0 and walked + d >= target:
+                pt = c[i] + (target - walked) / d * (c[i + 1] - c[i])
+                break
+            walked += d
+        else:
+            pt = c[-1]
+    return int(pt[0]), int(pt[1])
+
+
+# ------------------------------------------------------------------------------------------ label bitmaps
+def pack_bitmap(bits):
+    """bool [h, w] -> uint32 [h, (w + 31) // 32], bit b of word j of a row = column 32 j + b."""
+    bits = np.asarray(bits, dtype=bool)
+    h, w = bits.shape
+    rw = (w + 31) // 32
+    padded = np.zeros((h, 32 * rw), dtype=bool)
+    padded[:, :w] = bits
+    if h == 0 or rw == 0:
+        return np.zeros((h, rw), dtype=np.uint32)
+    return np.packbits(padded, axis=1, bitorder="little").view("<u4").astype(np.uint32).reshape(h, rw)
+
+
+def unpack_bitmap(words, w):
+    """The inverse of `pack_bitmap`: uint32 [h, rw] -> bool [h, w]."""
+    words = np.ascontiguousarray(words, dtype="<u4")
+    if words.size == 0:
+        return np.zeros((words.shape[0], w), dtype=bool)
+    return np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool)[:, :w]
+
+
+class Atlas:
+    """Label bitmaps, rendered once per (string, pixel size) -- a track's label repeats over its frames -- and packed for
+    `gom_overlay_compose_u8`: glyph_wh int32 [G,2], glyph_woff int64 [G+1], glyph_words uint32."""
+
+    def __init__(self, font=None):
+        self.font_file = font
+        self._fonts, self._index = {}, {}
+        self.wh, self.rows = [], []
+
+    def _font(self, px):
+        if px not in self._fonts:
+            from PIL import ImageFont
+            self._fonts[px] = ImageFont.truetype(self.font_file, px) if self.font_file else ImageFont.load_default(px)
+        return self._fonts[px]
+
+    def render(self, text, px):
+        """bool [h + 2, w + 2]: Pillow's 1-bit mask of the string, padded by one pixel on every side."""
+        mask = self._font(px).getmask(text, mode="1")
+        w, h = mask.size
+        out = np.zeros((h + 2, w + 2), dtype=bool)
+        if w and h:
+            out[1:-1, 1:-1] = np.frombuffer(bytes(mask), dtype=np.uint8).reshape(h, w) != 0
+        return out
+
+    def add(self, bits):
+        """A bitmap of the caller's -> its index."""
+        bits = np.asarray(bits, dtype=bool)
+        self.wh.append((bits.shape[1], bits.shape[0]))
+        self.rows.append(pack_bitmap(bits))
+        return len(self.wh) - 1
+
+    def index(self, text, px):
+        key = (text, px)
+        if key not in self._index:
+            self._index[key] = self.add(self.render(text, px))
+        return self._index[key]
+
+    def arrays(self, indices=None):
+        """(glyph_wh, glyph_woff, glyph_words) of the whole atlas, or of the bitmaps `indices` names, in that order."""
+        indices = range(len(self.rows)) if indices is None else [int(i) for i in indices]
+        rows = [self.rows[i] for i in indices]
+        wh = np.asarray([self.wh[i] for i in indices], dtype=np.int32).reshape(-1, 2)
+        woff = np.zeros(len(rows) + 1, dtype=np.int64)
+        woff[1:] = np.cumsum([r.size for r in rows])
+        words = np.concatenate([r.reshape(-1) for r in rows]) if rows else np.zeros(0, dtype=np.uint32)
+        return wh, woff, words.astype(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------ a chunk, described
+class Scene:
+    """What one compose call draws over F frames of H x W, as host arrays: `mset` (`score_json.MaskSet`: contours, boxes, word
+    offsets of the N instances), inst_off int32 [F+1], inst_rgb u8 [N,3], label_off int32 [F+1], label_pos int32 [L,2],
+    label_glyph int32 [L], label_rgb u8 [L,3] and the atlas arrays."""
+
+    def __init__(self, polys, colors, labels, atlas, H, W):
+        """polys: per frame a list of int [n,2] vertex arrays; colors: per frame a list of u8 triples (the frames' channel
+        order); labels: per frame a list of (x0, y0, atlas index, u8 triple); atlas: `Atlas.arrays()`."""
+        self.H, self.W, self.F = int(H), int(W), len(polys)
+        self.mset = _sj.MaskSet([("poly", [p]) for fr in polys for p in fr], H, W)
+        self.inst_off = np.concatenate([[0], np.cumsum([len(fr) for fr in polys])]).astype(np.int32)
+        self.inst_rgb = np.asarray([c for fr in colors for c in fr], dtype=np.uint8).reshape(-1, 3)
+        self.label_off = np.concatenate([[0], np.cumsum([len(fr) for fr in labels])]).astype(np.int32)
+        flat = [l for fr in labels for l in fr]
+        self.label_pos = np.asarray([(l[0], l[1]) for l in flat], dtype=np.int32).reshape(-1, 2)
+        self.label_glyph = np.asarray([l[2] for l in flat], dtype=np.int32).reshape(-1)
+        self.label_rgb = np.asarray([l[3] for l in flat], dtype=np.uint8).reshape(-1, 3)
+        self.glyph_wh, self.glyph_woff, self.glyph_words = atlas
+        assert len(self.inst_rgb) == self.mset.N and len(colors) == self.F and len(labels) == self.F
+
+
+def _blend(p, c, a):
+    return (p * (255 - a) + c * a + 127) // 255
+
+
+def compose_host(frames, scene, a_face=A_FACE, a_box=A_BOX):
+    """The rule of `gom_overlay_compose_u8` in numpy integers: u8 [F,H,W,3] -> a new u8 [F,H,W,3]."""
+    out = np.array(frames, dtype=np.uint8, copy=True)
+    F, H, W, _ = out.shape
+    ms = scene.mset
+    assert (F, H, W) == (scene.F, scene.H, scene.W)
+    for f in range(F):
+        for k in range(int(scene.inst_off[f]), int(scene.inst_off[f + 1])):
+            y0, y1, wx0, wx1 = (int(v) for v in ms.boxes[k])
+            if y1 <= y0 or wx1 <= wx0:
+                continue
+            x0, x1 = 32 * wx0, min(32 * wx1, W)
+            face = unpack_bitmap(_sj.fill_polygon_rows(ms.contours(k), ms.boxes[k], W), x1 - x0)[..., None]
+            line = unpack_bitmap(_sj.fill_polygon_rows(ms.contours(k), ms.boxes[k], W, fill=False), x1 - x0)[..., None]
+            v = out[f, y0:y1, x0:x1].astype(np.int32)
+            c = scene.inst_rgb[k].astype(np.int32)
+            out[f, y0:y1, x0:x1] = np.where(line, c, np.where(face, _blend(v, c, a_face), v))
+        for k in range(int(scene.label_off[f]), int(scene.label_off[f + 1])):
+            g = int(scene.label_glyph[k])
+            x0, y0 = (int(v) for v in scene.label_pos[k])
+            w, h = (int(v) for v in scene.glyph_wh[g])
+            xa, xb, ya, yb = max(x0, 0), min(x0 + w, W), max(y0, 0), min(y0 + h, H)
+            if xa >= xb or ya >= yb:
+                continue
+            rw = (w + 31) // 32
+            o = int(scene.glyph_woff[g])
+            bits = unpack_bitmap(scene.glyph_words[o:o + h * rw].reshape(h, rw), w)[ya - y0:yb - y0, xa - x0:xb - x0, None]
+            v = out[f, ya:yb, xa:xb].astype(np.int32)
+            out[f, ya:yb, xa:xb] = np.where(bits, scene.label_rgb[k].astype(np.int32), _blend(v, 255, a_box))
+    return out
+
+
+def _upload(arrays, dev):
+    """Host arrays -> device tensors of the same dtypes through ONE copy: the arrays laid end to end, each 16-byte aligned."""
+    import torch
+    offs, size = [], 0
+    for a in arrays:
+        offs.append(size)
+        size += (a.nbytes + 15) // 16 * 16
+    blob = np.zeros(max(size, 16), dtype=np.uint8)
+    for a, o in zip(arrays, offs):
+        blob[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    t = torch.from_numpy(blob).to(dev)
+    dtypes = {np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8,
+              np.dtype(np.uint32): torch.int32}
+    return [t[o:o + a.nbytes].view(dtypes[a.dtype]).reshape(a.shape) for a, o in zip(arrays, offs)]
+
+
+def device_arrays(scene, dev):
+    """The scene on the device (one upload) plus its two empty word buffers, in the argument order of `launch`."""
+    import torch
+    ms = scene.mset
+    up = _upload([ms.points.astype(np.int32), ms.coff.astype(np.int32), ms.mcoff.astype(np.int32), ms.boxes.astype(np.int32),
+                  ms.woff.astype(np.int64), scene.inst_off, scene.inst_rgb, scene.label_off, scene.label_pos, scene.label_glyph,
+                  scene.label_rgb, scene.glyph_wh.astype(np.int32), scene.glyph_woff.astype(np.int64),
+                  scene.glyph_words.astype(np.uint32)], dev)
+    nwords = int(ms.woff[-1])
+    face = torch.empty((nwords,), dtype=torch.int32, device=dev)
+    line = torch.empty((nwords,), dtype=torch.int32, device=dev)
+    area = torch.empty((ms.N,), dtype=torch.int32, device=dev)
+    return up, face, line, area
+
+
+def launch(frames_dev, scene, arrays, a_face=A_FACE, a_box=A_BOX, out=None):
+    """The three launches of a chunk over resident inputs: fill, outline, compose (in place unless `out` is given)."""
+    from . import ops
+    (points, coff, mcoff, boxes, woff, inst_off, inst_rgb, label_off, label_pos, label_glyph, label_rgb, gwh, gwoff,
+     gwords), face, line, area = arrays
+    ops.mask_fill_polygons(points, coff, mcoff, boxes, woff, scene.H, scene.W, face, area)
+    ops.mask_outline_polygons(points, coff, mcoff, boxes, woff, scene.H, scene.W, line)
+    return ops.overlay_compose(frames_dev, face, line, boxes, woff, inst_off, inst_rgb, label_off, label_pos, label_glyph,
+                               label_rgb, gwh, gwoff, gwords, a_face, a_box, out=frames_dev if out is None else out)
+
+
+def compose_device(frames, scene, a_face=A_FACE, a_box=A_BOX):
+    """`compose_host` through csrc/overlay.hip: one upload of the frames and one of the description, the fill, outline and
+    compose launches, one copy back."""
+    import torch
+    if not torch.cuda.is_available():
+        raise ShowError("no GPU: drawing runs in csrc/overlay.hip (use --host-draw for the numpy path)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    fr = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).to(dev)
+    return launch(fr, scene, device_arrays(scene, dev), a_face, a_box).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ rows -> pictures
+def _scene_of_rows(rows_per_frame, voc_size, atlas, H, W, bgr):
+    px = font_px(H, W)
+    polys, colors, labels = [], [], []
+    for rows in rows_per_frame:
+        p, c, l = [], [], []
+        for row in rows:
+            if len(row) < 11 or not row[10]:
+                raise ShowError("a result row without a segmentation cannot be drawn")
+            poly = np.asarray(row[10][0], dtype=np.int64).reshape(-1, 2)
+            rgb = track_color(row[8])
+            ink = text_color(rgb)
+            x, y = label_anchor(poly)
+            p.append(poly)
+            c.append(rgb[::-1] if bgr else rgb)
+            l.append((x, y, atlas.index(label_text(row[8], row[9], voc_size), px), ink[::-1] if bgr else ink))
+        polys.append(p)
+        colors.append(c)
+        labels.append(l)
+    used = sorted(set(l[2] for fr in labels for l in fr))     # the chunk's own bitmaps, re-indexed
+    local = {g: i for i, g in enumerate(used)}
+    labels = [[(x, y, local[g], ink) for x, y, g, ink in fr] for fr in labels]
+    try:
+        return Scene(polys, colors, labels, atlas.arrays(used), H, W)
+    except ScoreError as e:
+        raise ShowError(str(e))
+
+
+def draw_clip(frames_u8, rows_per_frame, voc_size, font=None, host=False, chunk=CHUNK, bgr=True, atlas=None):
+    """Frames u8 [F,H,W,3] (an array or a list of H x W x 3 arrays) and, per frame, its result rows -> the drawn frames u8
+    [F,H,W,3].  Per chunk of at most `chunk` frames: one fill, one outline and one compose call with one upload and one copy
+    back; host=True does the same integer arithmetic in numpy and returns the same bytes.  The colours of a track are RGB;
+    bgr=True (what `eval.read_frame` yields) hands them to the rule in the frames' B, G, R order.  `atlas` carries the label
+    bitmaps from one call to the next."""
+    F = len(frames_u8)
+    if len(rows_per_frame) != F:
+        raise ValueError("%d frames but rows for %d" % (F, len(rows_per_frame)))
+    if F == 0:
+        return np.zeros((0, 0, 0, 3), dtype=np.uint8)
+    atlas = atlas or Atlas(font)
+    out = []
+    for f0 in range(0, F, int(chunk)):
+        part = np.ascontiguousarray(np.stack([np.asarray(f) for f in frames_u8[f0:f0 + chunk]]), dtype=np.uint8)
+        if part.ndim != 4 or part.shape[3] != 3:
+            raise ValueError("frames must be u8 [F,H,W,3]")
+        scene = _scene_of_rows(rows_per_frame[f0:f0 + chunk], voc_size, atlas, part.shape[1], part.shape[2], bgr)
+        out.append(compose_host(part, scene) if host else compose_device(part, scene))
+    if any(o.shape[1:] != out[0].shape[1:] for o in out):
+        raise ValueError("the frames of a clip must share one size")
+    return np.concatenate(out)
+
+
+def write_frame(bgr, path):
+    """One drawn frame in the format its extension names (JPEG at quality 95)."""
+    from PIL import Image
+    im = Image.fromarray(np.ascontiguousarray(bgr[:, :, ::-1]))
+    if os.path.splitext(path)[1].lower() in (".jpg", ".jpeg"):
+        im.save(path, quality=95)
+    else:
+        im.save(path)
+
+
+def draw_video(frames, annotation, paths, video_name, out_dir, voc_size, pool, atlas, host=False):
+    """Draw a whole video (BGR frames, `annotation` = {1-based frame id as str: rows}) chunk by chunk and write
+    out_dir/results/<video name>/<basename of the frame's source path> through `pool`."""
+    if len(annotation) != len(frames):
+        raise ShowError("video %s: %d frames but results for %d" % (video_name, len(frames), len(annotation)))
+    save_dir = os.path.join(out_dir, "results", video_name)
+    os.makedirs(save_dir, exist_ok=True)
+    try:
+        rows = [annotation[str(i + 1)] for i in range(len(frames))]
+    except KeyError as e:
+        raise ShowError("video %s: no results for frame %s" % (video_name, e))
+    for f0 in range(0, len(frames), CHUNK):
+        try:
+            drawn = draw_clip(frames[f0:f0 + CHUNK], rows[f0:f0 + CHUNK], voc_size, host=host, atlas=atlas)
+        except ShowError as e:
+            raise ShowError("video %s: %s" % (video_name, e))
+        targets = [os.path.join(save_dir, os.path.basename(p)) for p in paths[f0:f0 + CHUNK]]
+        list(pool.map(write_frame, drawn, targets))
+
+
+def rows_of_json(tracks):
+    """`jsons/<video>.json` -> the annotation `results.write_video` returns: {frame: [[x1..y4, id, text, [polygon]], ..]}."""
+    out = {}
+    for frame, objs in tracks.items():
+        rows = []
+        for o in objs:
+            row = list(o["points"]) + [o["ID"], o["transcription"]]
+            if "segmentation" in o:
+                row.append(o["segmentation"])
+            rows.append(row)
+        out[str(frame)] = rows
+    return out
+
+
+# ------------------------------------------------------------------------------------------ command line
+def get_parser():
+    p = argparse.ArgumentParser(
+        prog="python -m gomatching_amd.show",
+        description="Draw the tracked text of OUT/jsons/*.json on the frames of a dataset directory: a translucent polygon per "
+                    "instance in the colour of its track and a (id)TEXT label; writes results/<video>/<frame file>.  Needs no "
+                    "model; it is also how a resumed eval gets its pictures.")
+    p.add_argument("--input", required=True, metavar="DIR", help="dataset directory, as given to gomatching_amd.eval")
+    p.add_argument("--results", required=True, metavar="OUT", help="the --output directory of gomatching_amd.eval (reads OUT/jsons)")
+    p.add_argument("--output", default=None, metavar="DIR", help="directory for results/ (default: OUT)")
+    p.add_argument("--font", default=None, metavar="FILE", help="a TrueType font for the labels (default: Pillow's built-in font)")
+    p.add_argument("--host-draw", action="store_true", help="draw in numpy on the host (default: on the GPU, the same bytes)")
+    p.add_argument("--voc-size", type=int, default=None, metavar="N",
+                   help="vocabulary size of the model: 37 upper-cases the labels (default 37)")
+    p.add_argument("--config-file", default=None, metavar="FILE", help="take the vocabulary size from a config file")
+    p.add_argument("--builtin", default=None, metavar="NAME", help="take the vocabulary size from a packaged config")
+    return p
+
+
+def main(argv=None):
+    from . import config as _config
+    from . import eval as _eval
+    from . import results as _results
+    args = get_parser().parse_args(argv)
+    if sum(v is not None for v in (args.voc_size, args.config_file, args.builtin)) > 1:
+        sys.stderr.write("error: give at most one of --voc-size, --config-file and --builtin\n")
+        return 2
+    if args.builtin is not None and args.builtin not in _config.BUILTIN:
+        sys.stderr.write("error: unknown packaged config %r\n" % args.builtin)
+        return 2
+    if args.config_file is not None and not os.path.isfile(args.config_file):
+        sys.stderr.write("error: config file %r not found\n" % args.config_file)
+        return 2
+    if not os.path.isdir(args.input):
+        sys.stderr.write("error: input directory %r not found\n" % args.input)
+        return 2
+    voc_size = 37 if args.voc_size is None else args.voc_size
+    if args.config_file is not None or args.builtin is not None:
+        voc_size = _config.setup_cfg(config_file=args.config_file, opts=[], builtin=args.builtin).MODEL.TRANSFORMER.VOC_SIZE
+    out_dir = args.output or args.results
+    data_type, videos = _eval.list_videos(args.input)
+    atlas = Atlas(args.font)
+    try:
+        with ThreadPoolExecutor(max_workers=_eval.DECODE_THREADS) as readers, \
+                ThreadPoolExecutor(max_workers=WRITE_THREADS) as writers:
+            for video_name, video_dir in videos:
+                json_path = os.path.join(args.results, "jsons", "%s.json" % _results.result_names(video_name, data_type)[1])
+                if not os.path.isfile(json_path):
+                    raise ShowError("video %s: result file %s not found" % (video_name, json_path))
+                with open(json_path, "r", encoding="utf-8") as fp:
+                    annotation = rows_of_json(json.load(fp))
+                paths = _eval.frame_paths(video_dir)
+                if len(paths) != len(annotation):
+                    raise ShowError("video %s: %d frames but results for %d" % (video_name, len(paths), len(annotation)))
+                if any(len(row) < 11 for rows in annotation.values() for row in rows):
+                    raise ShowError("video %s: result rows without a segmentation cannot be drawn" % video_name)
+                print("drawing {}...".format(video_name))
+                frames = list(readers.map(_eval.read_frame, paths))
+                draw_video(frames, annotation, paths, video_name, out_dir, voc_size, writers, atlas, host=args.host_draw)
+    except ShowError as e:
+        sys.stderr.write("error: %s\n" % e)
+        return 2
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

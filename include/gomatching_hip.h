@@ -599,6 +599,46 @@ int gom_mask_pairs_emit_f64(const uint32_t* gt_words, const int32_t* gt_boxes, c
                             const int32_t* det_off, const int32_t* gt_key, const int32_t* det_key, int G, int D, int F,
                             long pairs, double threshold, const int64_t* scan, long total, int32_t* out_det,
                             double* out_val, void* stream);
+/* Drawing tracked text on frames (csrc/overlay.hip): an outline pass over the bit-row masks above and a compositor.
+ *
+ * gom_mask_outline_polygons_u32: the arguments and the mask representation of gom_mask_fill_polygons_u32 (boxes, CSR word
+ * offsets, sel) without `area`; writes Boundary(contour) of the rasterisation rule above ALONE, unioned over a mask's
+ * contours, clipped to the image.  A thread owns a word: plain stores.  Same argument checks as the fill.
+ *
+ * gom_overlay_compose_u8: frames u8 [F,H,W,3] -> out u8 [F,H,W,3] (out may be frames; rows and frames start at any byte
+ * alignment).  Device inputs:
+ *   face_words, outline_words uint32 [nwords] : two mask sets over the SAME boxes int32 [N,4] and word_off int64 [N+1] -- what
+ *                                               the fill call (Fill u Boundary) and the outline call leave
+ *   inst_off int32 [F+1]                      : first instance of each frame (CSR, inst_off[F] = N)
+ *   inst_rgb u8 [N,3]                         : an instance's colour, in the frames' own channel order
+ *   label_off int32 [F+1], label_pos int32 [L,2] (x0, y0 of the top-left corner; any value, may lie outside the image),
+ *   label_glyph int32 [L] (index into the atlas), label_rgb u8 [L,3]
+ *   glyph_wh int32 [G,2] (w, h), glyph_woff int64 [G+1], glyph_words uint32 [glyph_nwords] : the atlas of label bitmaps, rows
+ *                                               padded to whole words and label-local: bit b of word j of a row is column
+ *                                               32 j + b; bitmap g owns h * ((w + 31) / 32) words from glyph_woff[g]
+ *   a_face, a_box                             : 0 .. 255
+ * Rule, in integers.  For pixel (x, y) of frame f, v = frames[f,y,x,:], then
+ *   1. for the instances k = inst_off[f] .. inst_off[f+1] - 1 IN ORDER: if the outline bit of (x, y) is set v = inst_rgb[k],
+ *      else if the face bit is set v = blend(v, inst_rgb[k], a_face);
+ *   2. then for the labels k = label_off[f] .. label_off[f+1] - 1 IN ORDER, g = label_glyph[k], when x0 <= x < x0 + w and
+ *      y0 <= y < y0 + h: if bit (x - x0, y - y0) of bitmap g is set v = label_rgb[k], else v = blend(v, (255,255,255), a_box);
+ *   3. blend(p, c, a) = (p * (255 - a) + c * a + 127) / 255 per channel, exact integer division;
+ *   out[f,y,x,:] = v.  Pixels no instance and no label covers come out byte-identical.
+ * A pixel is read and written by exactly one thread, instances and labels are walked in ballot order: no atomics, the
+ * result does not depend on the launch geometry.  Offsets, boxes, positions and atlas indices are clamped or tested against
+ * their buffers (a mask word outside the words its box owns, or outside the buffer, reads as 0).
+ * GOM_ERR_INVALID_ARG before any HIP call: null pointers, negative sizes, H or W < 1, H * W above INT32_MAX, a_face or a_box
+ * outside 0 .. 255, a box array that is not 16-byte aligned, labels without an atlas (L > 0 with G == 0).  F == 0 is GOM_OK
+ * without a launch; N == 0 and L == 0 with F > 0 copy frames to out when they differ. */
+int gom_mask_outline_polygons_u32(const int32_t* points, int P, const int32_t* contour_off, int C, const int32_t* mask_coff,
+                                  const int32_t* boxes, const int64_t* word_off, int N, long nwords, const int32_t* sel,
+                                  int M, int H, int W, uint32_t* words, void* stream);
+int gom_overlay_compose_u8(const uint8_t* frames, uint8_t* out, int F, int H, int W, const uint32_t* face_words,
+                           const uint32_t* outline_words, const int32_t* boxes, const int64_t* word_off, int N, long nwords,
+                           const int32_t* inst_off, const uint8_t* inst_rgb, const int32_t* label_off,
+                           const int32_t* label_pos, const int32_t* label_glyph, const uint8_t* label_rgb, int L,
+                           const int32_t* glyph_wh, const int64_t* glyph_woff, const uint32_t* glyph_words, int G,
+                           long glyph_nwords, int a_face, int a_box, void* stream);
 int gom_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 /* out [H*W, 256] = PositionalEncoding2D(normalize=True) + level_embed, for an unpadded H x W level. */
 int gom_pos_encoding_2d_f32(const float* dim_t128, const float* level_embed256, float* out, int H, int W,
