@@ -21,8 +21,9 @@ def _L():
     return _lib_mod.load()
 
 
-# Optional launch profiler for bench.py's roofline leg: a list that receives (start_event, end_event, flops) for
-# every launch of the dominant kernel (the 128x128-tile plain GEMM).  None = no events recorded.
+# Optional launch profiler for bench.py's roofline leg: a list that receives one (start_event, end_event, flops, bytes, label,
+# scope) per launch of every instrumented kernel (`_timed`); bench.py picks kernels by label prefix and the decoder layers by
+# scope (`profile_scope`).  None = no events recorded.
 _gemm_profile = None
 
 
@@ -46,10 +47,49 @@ def set_gemm_profile(collector):
     _gemm_profile = collector
 
 
+class _Timed:
+    """HIP events around the launch(es) of a `with` block; the record is appended when the block ends without an error."""
+
+    def __init__(self, prof, figures):
+        self.prof, self.figures = prof, figures
+
+    def __enter__(self):
+        self.e0 = torch.cuda.Event(enable_timing=True)
+        self.e0.record()
+
+    def __exit__(self, etype, exc, tb):
+        if etype is None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            self.prof.append((self.e0, e1) + self.figures() + (_profile_scope,))
+
+
+_untimed = contextlib.nullcontext()
+
+
+def _timed(cond, figures):
+    """Launch bracket of the profiler: `with _timed(cond, lambda: (flops, bytes, label)): check(launch)`.  Without a collector or
+    with `cond` false it is one shared no-op: no event is created and `figures` is never called."""
+    return _Timed(_gemm_profile, figures) if (_gemm_profile is not None and cond) else _untimed
+
+
 def _p(t):
     if t is None:
         return None
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _ld(t, width=None):
+    """Leading dimension of a 2-D row-strided tensor as the kernels take it: stride(0), except that a tensor of one row (or none)
+    passes its width -- there stride(0) is whatever the view it was cut from had.  None passes 0.  `width`: the row length of a
+    tensor that has no shape[1] of its own (a 1-D vector passed as one row).  The rule looks at the tensor, not at the launch: a
+    one-row launch into a taller buffer passes that buffer's real stride, which serves a single row as well as the width does."""
+    if t is None:
+        return 0
+    shape = t.shape                                          # (one .shape and one .stride() cost what a single .stride(0) does)
+    if len(shape) > 1 and shape[0] > 1:
+        return t.stride()[0]
+    return shape[-1] if width is None else width
 
 
 def _stream():
@@ -101,7 +141,7 @@ def split_weight(w, conv_shape=None, kind=None):
     assert w.dim() == 2 and w.stride(1) == 1 and w.dtype == _f32 and w.is_cuda
     kind = kind or (GEMM_MODE if GEMM_MODE in ("bf16x6", "f16x3") else "bf16x6")
     N, K = w.shape
-    ldw = w.stride(0) if N > 1 else K
+    ldw = _ld(w)
     Kpad = (K + 31) // 32 * 32
     if kind == "f16x3":
         planes = torch.empty((2, N, Kpad), dtype=torch.float16, device=w.device)
@@ -211,33 +251,25 @@ def _gemm_split(A, W, bias, scale, A2, rows, R, relu, out, M, r_cols=None, r_per
         A = add(A.contiguous(), A2.contiguous())
     K, N = A.shape[1], W.N
     assert W.K == K
-    lda = A.stride(0) if A.shape[0] > 1 else K
     if out is None:
         out = torch.empty((M, N), dtype=_f32, device=A.device)
-    ldc = out.stride(0) if out.shape[0] > 1 else N
-    ldr = (R.stride(0) if R.shape[0] > 1 else R.shape[1]) if R is not None else 0
+    lda, ldc, ldr = _ld(A), _ld(out), _ld(R)
     pl = W.planes
-    prof = _gemm_profile if (_gemm_profile is not None and M > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     rc = (r_cols if r_cols is not None else N) if R is not None else 0
-    if W.kind == "f16x3":
-        check(_L().gom_gemm_f32_f16x3_rp(_p(A), _p(rows), lda, _p(pl), pl.stride(0), pl.stride(1), _p(W.inv_scale),
-                                         _p(scale), _p(bias), _p(R), ldr, rc, int(r_period),
-                                         2 if relu == "gelu" else (1 if relu else 0), _p(out), ldc, M, N, K,
-                                         _p(range_flag(A.device)), _stream()), "gom_gemm_f32_f16x3_rp")
-    else:
+    if W.kind != "f16x3":
         assert not r_period, "a periodic residual is served by the f16x3 kernel only"
         assert relu in (False, True, 0, 1), "only the f16x3 kernel has a GELU epilogue (use gemm_gelu)"
-        check(_L().gom_gemm_f32_bf16x6(_p(A), _p(rows), lda, _p(pl), pl.stride(0), pl.stride(1), _p(scale),
-                                       _p(bias), _p(R), ldr, rc, 1 if relu else 0, _p(out), ldc, M, N, K, _stream()),
-              "gom_gemm_f32_bf16x6")
-    if prof is not None:
-        e1.record()
-        nbytes = 4.0 * M * K + 2.0 * pl.shape[0] * N * pl.shape[2] + 4.0 * M * N \
-            + (4.0 * (r_period or M) * rc if R is not None else 0.0)
-        prof.append((e0, e1, 2.0 * M * N * K, nbytes, "%dx%dx%d" % (M, N, K), _profile_scope))
+    with _timed(M > 0, lambda: (2.0 * M * N * K, 4.0 * M * K + 2.0 * pl.shape[0] * N * pl.shape[2] + 4.0 * M * N
+                                + (4.0 * (r_period or M) * rc if R is not None else 0.0), "%dx%dx%d" % (M, N, K))):
+        if W.kind == "f16x3":
+            check(_L().gom_gemm_f32_f16x3_rp(_p(A), _p(rows), lda, _p(pl), pl.stride(0), pl.stride(1), _p(W.inv_scale),
+                                             _p(scale), _p(bias), _p(R), ldr, rc, int(r_period),
+                                             2 if relu == "gelu" else (1 if relu else 0), _p(out), ldc, M, N, K,
+                                             _p(range_flag(A.device)), _stream()), "gom_gemm_f32_f16x3_rp")
+        else:
+            check(_L().gom_gemm_f32_bf16x6(_p(A), _p(rows), lda, _p(pl), pl.stride(0), pl.stride(1), _p(scale),
+                                           _p(bias), _p(R), ldr, rc, 1 if relu else 0, _p(out), ldc, M, N, K, _stream()),
+                  "gom_gemm_f32_bf16x6")
     return out
 
 
@@ -274,17 +306,15 @@ def gemm(A, W, bias=None, scale=None, A2=None, rows=None, R=None, relu=False, ou
     N = W.shape[0]
     if M is None:
         M = A.shape[0] if rows is None else rows.numel()
-    lda, ldw = A.stride(0) if A.shape[0] > 1 else K, W.stride(0) if N > 1 else K
+    lda, ldw = _ld(A), _ld(W)
     if A2 is not None:
         assert A2.shape == A.shape and A2.stride() == A.stride()
     if out is None:
         out = torch.empty((M, N), dtype=_f32, device=A.device)
     assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] == N
-    ldc = out.stride(0) if out.shape[0] > 1 else N
-    ldr = 0
     if R is not None:
         assert R.dim() == 2 and R.stride(1) == 1 and R.shape[1] == N
-        ldr = R.stride(0) if R.shape[0] > 1 else N
+    ldc, ldr = _ld(out), _ld(R)
     if rows is not None:
         assert rows.dtype == torch.int32 and rows.is_contiguous()
     # `small` marks the tracker's latency-bound products (kernel choice must never depend on how many frames share a
@@ -306,16 +336,10 @@ def gemm(A, W, bias=None, scale=None, A2=None, rows=None, R=None, relu=False, ou
                                        1 if relu else 0, _p(out), ldc, M, N, K, _p(ws), nbytes, _stream()),
               "gom_gemm_f32_splitk")
         return out
-    prof = _gemm_profile if (_gemm_profile is not None and N > 64 and M > 0 and GEMM_MODE == "fp32") else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().gom_gemm_f32(_p(A), _p(A2), _p(rows), lda, _p(W), ldw, _p(scale), _p(bias), _p(R), ldr,
-                            1 if relu else 0, _p(out), ldc, M, N, K, _stream()), "gom_gemm_f32")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N + (M * N if R is not None else 0)),
-                     "%dx%dx%d" % (M, N, K), _profile_scope))
+    with _timed(N > 64 and M > 0 and GEMM_MODE == "fp32", lambda: (
+            2.0 * M * N * K, 4.0 * (M * K + N * K + M * N + (M * N if R is not None else 0)), "%dx%dx%d" % (M, N, K))):
+        check(_L().gom_gemm_f32(_p(A), _p(A2), _p(rows), lda, _p(W), ldw, _p(scale), _p(bias), _p(R), ldr,
+                                1 if relu else 0, _p(out), ldc, M, N, K, _stream()), "gom_gemm_f32")
     return out
 
 
@@ -373,17 +397,11 @@ def conv2d_nhwc(x, w_ohwi, scale=None, shift=None, R=None, relu=False, stride=1,
                 check(_L().gom_conv3x3_patch_image(_p(pl), pl.stride(0), pl.stride(1), Cin, Cout, _p(img), nb, _stream()),
                       "gom_conv3x3_patch_image")
                 w_ohwi.patch_image = img
-            prof = _gemm_profile
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            check(_L().gom_conv3x3_patch_f32_f16x3(_p(x), _p(img), _p(w_ohwi.inv_scale), _p(scale), _p(shift), 1 if relu else 0,
-                                                   _p(y), B, H, Wd, Cin, Cout, _p(range_flag(x.device)), _stream()),
-                  "gom_conv3x3_patch_f32_f16x3")
-            if prof is not None:
-                e1.record()
-                prof.append((e0, e1, 2.0 * M * Cout * 9 * Cin, 4.0 * M * (Cin + Cout) + 4.0 * 9 * Cin * Cout,
-                             "conv3:%dx%dx%d" % (M, Cout, 9 * Cin), _profile_scope))
+            with _timed(True, lambda: (2.0 * M * Cout * 9 * Cin, 4.0 * M * (Cin + Cout) + 4.0 * 9 * Cin * Cout,
+                                       "conv3:%dx%dx%d" % (M, Cout, 9 * Cin))):
+                check(_L().gom_conv3x3_patch_f32_f16x3(_p(x), _p(img), _p(w_ohwi.inv_scale), _p(scale), _p(shift), 1 if relu else 0,
+                                                       _p(y), B, H, Wd, Cin, Cout, _p(range_flag(x.device)), _stream()),
+                      "gom_conv3x3_patch_f32_f16x3")
             return y
         if kernel == "pw_k256":
             # conv3 of the res4 bottlenecks (256 -> 1024, + BN + shortcut + ReLU): K = 256 is the row-resident kernel's shape
@@ -399,34 +417,21 @@ def conv2d_nhwc(x, w_ohwi, scale=None, shift=None, R=None, relu=False, stride=1,
                 check(_L().gom_gemm_k256_image(_p(pl), pl.stride(0), pl.stride(1), _p(inv), _p(shift), Cout, Cin, _p(img), nb,
                                                _stream()), "gom_gemm_k256_image")
                 cache[key] = img = (img, inv, scale, shift)         # (the vectors stay referenced: ids are the cache key)
-            prof = _gemm_profile
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            check(_L().gom_gemm_k256_rp_f32(_p(x), None, Cin, _p(img[0]), _p(R), Cout if R is not None else 0,
-                                            Cout if R is not None else 0, 0, 1 if relu else 0, _p(y), Cout, M, Cout, Cin, 1,
-                                            _p(range_flag(x.device)), _stream()), "gom_gemm_k256_rp_f32")
-            if prof is not None:
-                e1.record()
-                prof.append((e0, e1, 2.0 * M * Cout * Cin, 4.0 * M * Cin + 4.0 * M * Cout * (2 if R is not None else 1) + 4.0 * Cout * Cin,
-                             "pwk256:%dx%dx%d" % (M, Cout, Cin), _profile_scope))
+            with _timed(True, lambda: (2.0 * M * Cout * Cin, 4.0 * M * Cin + 4.0 * M * Cout * (2 if R is not None else 1) + 4.0 * Cout * Cin,
+                                       "pwk256:%dx%dx%d" % (M, Cout, Cin))):
+                check(_L().gom_gemm_k256_rp_f32(_p(x), None, Cin, _p(img[0]), _p(R), Cout if R is not None else 0,
+                                                Cout if R is not None else 0, 0, 1 if relu else 0, _p(y), Cout, M, Cout, Cin, 1,
+                                                _p(range_flag(x.device)), _stream()), "gom_gemm_k256_rp_f32")
             return y
         if w_ohwi.kind == "f16x3":
             # a pointwise convolution IS a launch of the GEMM tile kernel (dispatch<0, 0> in csrc/gemm_f16x3.hip): bench.py's
             # roofline sample of that kernel covers these launches too (label "pw:")
-            prof = _gemm_profile if (_gemm_profile is not None and KH == 1 and stride == 1 and pad == 0 and splits <= 1
-                                     and Cout > 64) else None
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                _after = lambda: (e1.record(), prof.append((e0, e1, 2.0 * M * Cout * Cin, 4.0 * M * Cin + 4.0 * M * Cout * (
-                    2 if R is not None else 1) + 4.0 * Cout * Cin, "pw:%dx%dx%d" % (M, Cout, Cin), _profile_scope)))
-            check(_L().gom_conv2d_nhwc_f32_f16x3(_p(x), _p(pl), pl.stride(0), pl.stride(1), _p(w_ohwi.inv_scale),
-                                                 _p(scale), _p(shift), _p(R), 1 if relu else 0, _p(y), B, H, Wd, Cin,
-                                                 Cout, KH, KW, stride, pad, _p(ws), nbytes, splits,
-                                                 _p(range_flag(x.device)), _stream()), "gom_conv2d_nhwc_f32_f16x3")
-            if prof is not None:
-                _after()
+            with _timed(KH == 1 and stride == 1 and pad == 0 and splits <= 1 and Cout > 64, lambda: (
+                    2.0 * M * Cout * Cin, 4.0 * M * Cin + 4.0 * M * Cout * (2 if R is not None else 1) + 4.0 * Cout * Cin, "pw:%dx%dx%d" % (M, Cout, Cin))):
+                check(_L().gom_conv2d_nhwc_f32_f16x3(_p(x), _p(pl), pl.stride(0), pl.stride(1), _p(w_ohwi.inv_scale),
+                                                     _p(scale), _p(shift), _p(R), 1 if relu else 0, _p(y), B, H, Wd, Cin,
+                                                     Cout, KH, KW, stride, pad, _p(ws), nbytes, splits,
+                                                     _p(range_flag(x.device)), _stream()), "gom_conv2d_nhwc_f32_f16x3")
             return y
         check(_L().gom_conv2d_nhwc_f32_bf16x6_splitk(_p(x), _p(pl), pl.stride(0), pl.stride(1), _p(scale), _p(shift),
                                                      _p(R), 1 if relu else 0, _p(y), B, H, Wd, Cin, Cout, KH, KW, stride,
@@ -532,31 +537,23 @@ def linear(x, lin, A2=None, R=None, relu=False, r_cols=None, out=None, groups=0,
     if M == 0 or not (groups or k256_wins(M, lin.N, A2 is not None)):
         return gemm(x, lin.W, bias=lin.bias, A2=A2, R=R, relu=relu, r_cols=r_cols, out=out, r_period=r_period)
     assert x.dim() == 2 and x.stride(1) == 1 and x.shape[1] == lin.K and x.dtype == _f32
-    lda = x.stride(0) if M > 1 else lin.K
     if A2 is not None:
         assert A2.shape == x.shape and A2.stride() == x.stride() and A2.dtype == _f32
     N = lin.N
     if out is None:
         out = torch.empty((M, N), dtype=_f32, device=x.device)
     assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] == N
-    ldr, rc = 0, 0
+    rc = 0
     if R is not None:
         assert R.dim() == 2 and R.stride(1) == 1 and R.dtype == _f32
-        ldr, rc = (R.stride(0) if R.shape[0] > 1 else R.shape[1]), (r_cols if r_cols is not None else N)
+        rc = r_cols if r_cols is not None else N
     if not K256_LONG:
         _L().gom_gemm_k256_set_lines(0)                      # (A/B switch only: the round-2 mid-state of the kernel)
-    prof = _gemm_profile if _gemm_profile is not None else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().gom_gemm_k256_rp_f32(_p(x), _p(A2), lda, _p(lin.image), _p(R), ldr, rc, int(r_period), 1 if relu else 0, _p(out),
-                                    out.stride(0) if out.shape[0] > 1 else N, M, N, lin.K, groups or 1,
-                                    _p(range_flag(x.device)), _stream()), "gom_gemm_k256_rp_f32")
-    if prof is not None:
-        e1.record()
-        nbytes = 4.0 * M * lin.K * (2 if A2 is not None else 1) + lin.image.numel() + 4.0 * M * N \
-            + 4.0 * (r_period or M) * rc
-        prof.append((e0, e1, 2.0 * M * N * lin.K, nbytes, "k256:%dx%dx%d" % (M, N, lin.K), _profile_scope))
+    with _timed(True, lambda: (2.0 * M * N * lin.K, 4.0 * M * lin.K * (2 if A2 is not None else 1) + lin.image.numel() + 4.0 * M * N
+                               + 4.0 * (r_period or M) * rc, "k256:%dx%dx%d" % (M, N, lin.K))):
+        check(_L().gom_gemm_k256_rp_f32(_p(x), _p(A2), _ld(x), _p(lin.image), _p(R), _ld(R), rc, int(r_period), 1 if relu else 0,
+                                        _p(out), _ld(out), M, N, lin.K, groups or 1, _p(range_flag(x.device)), _stream()),
+              "gom_gemm_k256_rp_f32")
     return out
 
 
@@ -598,18 +595,11 @@ def proj_ln(x, blk, R, out=None):
     M = x.shape[0]
     if out is None:
         out = torch.empty((M, 256), dtype=_f32, device=x.device)
-    prof = _gemm_profile if (_gemm_profile is not None and M > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().gom_proj_ln_f32(_p(x), x.stride(0) if M > 1 else 256, _p(blk.image), _p(blk.W.inv_scale), _p(blk.bias), _p(R),
-                               (R.stride(0) if M > 1 else 256) if R is not None else 0, _p(blk.gamma), _p(blk.beta), blk.eps,
-                               _p(out), out.stride(0) if M > 1 else 256, M, _p(range_flag(x.device)), _stream()),
-          "gom_proj_ln_f32")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * 256 * 256, (12.0 if R is not None else 8.0) * M * 256 + blk.image.numel(),
-                     "projln:%dx256x256" % M, _profile_scope))
+    with _timed(M > 0, lambda: (2.0 * M * 256 * 256, (12.0 if R is not None else 8.0) * M * 256 + blk.image.numel(),
+                                "projln:%dx256x256" % M)):
+        check(_L().gom_proj_ln_f32(_p(x), _ld(x), _p(blk.image), _p(blk.W.inv_scale), _p(blk.bias), _p(R), _ld(R), _p(blk.gamma),
+                                   _p(blk.beta), blk.eps, _p(out), _ld(out), M, _p(range_flag(x.device)), _stream()),
+              "gom_proj_ln_f32")
     return out
 
 
@@ -624,16 +614,10 @@ def proj_ln_dot(x, blk, w, b):
     assert w.numel() == 256
     M = x.shape[0]
     out = torch.empty((M,), dtype=_f32, device=x.device)
-    prof = _gemm_profile if (_gemm_profile is not None and M > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().gom_proj_ln_dot_f32(_p(x), x.stride(0) if M > 1 else 256, _p(blk.image), _p(blk.W.inv_scale), _p(blk.bias),
-                                   _p(blk.gamma), _p(blk.beta), blk.eps, _p(w), float(b), _p(out), M, _p(range_flag(x.device)),
-                                   _stream()), "gom_proj_ln_dot_f32")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * 256 * 257, 4.0 * M * 257 + blk.image.numel(), "projdot:%dx256x257" % M, _profile_scope))
+    with _timed(M > 0, lambda: (2.0 * M * 256 * 257, 4.0 * M * 257 + blk.image.numel(), "projdot:%dx256x257" % M)):
+        check(_L().gom_proj_ln_dot_f32(_p(x), _ld(x), _p(blk.image), _p(blk.W.inv_scale), _p(blk.bias), _p(blk.gamma), _p(blk.beta),
+                                       blk.eps, _p(w), float(b), _p(out), M, _p(range_flag(x.device)), _stream()),
+              "gom_proj_ln_dot_f32")
     return out
 
 
@@ -723,17 +707,11 @@ def _bneck_fused_sc(a, blk, S):
     M = B * H * W
     X = torch.empty((B, H, W, blk.c4), dtype=_f32, device=a.device)
     Y1 = torch.empty((B, H, W, blk.mp), dtype=_f32, device=a.device)
-    prof = _gemm_profile if (_gemm_profile is not None and M > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().gom_bneck_sc_f32(_p(a), k1, _p(blk.image), _p(S), ks, B, Hs, Ws, st, _p(blk.sc1), _p(blk.sh1), _p(X), blk.c4, _p(Y1),
-                                blk.mp, blk.k1, blk.c4, blk.mp, blk.ks, _p(range_flag(a.device)), _stream()), "gom_bneck_sc_f32")
-    if prof is not None:
-        e1.record()
-        # A and the sampled rows of S in, X and Y1 out: no residual stream
-        prof.append((e0, e1, 2.0 * M * blk.c4 * (blk.k1 + blk.ks + blk.mp), 4.0 * M * (blk.k1 + blk.ks + blk.c4 + blk.mp) + blk.image.numel(),
-                     "bneck:%dx%dx%dx%d+sc%d/%d" % (M, blk.k1, blk.c4, blk.mp, blk.ks, st), _profile_scope))
+    # profile bytes: A and the sampled rows of S in, X and Y1 out: no residual stream
+    with _timed(M > 0, lambda: (2.0 * M * blk.c4 * (blk.k1 + blk.ks + blk.mp), 4.0 * M * (blk.k1 + blk.ks + blk.c4 + blk.mp) + blk.image.numel(),
+                                "bneck:%dx%dx%dx%d+sc%d/%d" % (M, blk.k1, blk.c4, blk.mp, blk.ks, st))):
+        check(_L().gom_bneck_sc_f32(_p(a), k1, _p(blk.image), _p(S), ks, B, Hs, Ws, st, _p(blk.sc1), _p(blk.sh1), _p(X), blk.c4, _p(Y1),
+                                    blk.mp, blk.k1, blk.c4, blk.mp, blk.ks, _p(range_flag(a.device)), _stream()), "gom_bneck_sc_f32")
     return X, Y1
 
 
@@ -748,17 +726,11 @@ def bneck_fused(a, blk, R):
     M = B * H * W
     X = torch.empty((B, H, W, blk.c4), dtype=_f32, device=a.device)
     Y1 = torch.empty((B, H, W, blk.mp), dtype=_f32, device=a.device)
-    prof = _gemm_profile if (_gemm_profile is not None and M > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     fn = _L().gom_bneck2_f32 if blk.v2 else _L().gom_bneck_f32
-    check(fn(_p(a), k1, _p(blk.image), _p(R), blk.c4, _p(blk.sc1), _p(blk.sh1), _p(X), blk.c4, _p(Y1), blk.mp, M,
-             blk.k1, blk.c4, blk.mp, _p(range_flag(a.device)), _stream()), "gom_bneck2_f32" if blk.v2 else "gom_bneck_f32")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * blk.c4 * (blk.k1 + blk.mp), 4.0 * M * (blk.k1 + 2 * blk.c4 + blk.mp) + blk.image.numel(),
-                     "bneck:%dx%dx%dx%d" % (M, blk.k1, blk.c4, blk.mp), _profile_scope))
+    with _timed(M > 0, lambda: (2.0 * M * blk.c4 * (blk.k1 + blk.mp), 4.0 * M * (blk.k1 + 2 * blk.c4 + blk.mp) + blk.image.numel(),
+                                "bneck:%dx%dx%dx%d" % (M, blk.k1, blk.c4, blk.mp))):
+        check(fn(_p(a), k1, _p(blk.image), _p(R), blk.c4, _p(blk.sc1), _p(blk.sh1), _p(X), blk.c4, _p(Y1), blk.mp, M,
+                 blk.k1, blk.c4, blk.mp, _p(range_flag(a.device)), _stream()), "gom_bneck2_f32" if blk.v2 else "gom_bneck_f32")
     return X, Y1
 
 
@@ -829,6 +801,15 @@ def dec_attn_block(in_w, in_b, out_pair, norm, inter, raw=None):
     return None
 
 
+def _dec_attn_figures(blk, groups, group_tokens, with_raw, with_pos):
+    """Profile record of a `dec_attn` launch: the block's nn.Linear products (in_proj 768 + out_proj 256 [+ raw 384] columns) +
+    QK^T and PV of every head; rows in (x [, pos | raw_pos]) and out (out [, raw 384 wide]) + the image."""
+    rows = groups * group_tokens
+    flops = 2.0 * rows * 256 * (1024 + (384 if with_raw else 0)) + 4.0 * rows * group_tokens * 256
+    nbytes = (4.0 * rows * (256 * 3 + 384) if with_raw else 4.0 * rows * 256 * (3 if with_pos else 2)) + blk.image.numel()
+    return flops, nbytes, "decattn:%s:%dx%d" % ("inter+raw" if with_raw else "inter" if blk.inter else "intra", groups, group_tokens)
+
+
 def dec_attn(x, blk, groups, group_tokens, inner=1, pos=None, out=None, raw_pos=None):
     """LayerNorm(x + out_proj(MHA(...))) of one decoder self-attention block in one launch.  x [rows, 256]; intra (blk.inter
     False): `groups` runs of `group_tokens` <= 32 consecutive rows, q = k = x + pos, v = x; inter: token t of group g is row
@@ -836,50 +817,29 @@ def dec_attn(x, blk, groups, group_tokens, inner=1, pos=None, out=None, raw_pos=
     (out, raw [rows, 384]) with raw = (out + raw_pos) Wraw^T + braw, the cross attention's sampling offsets | attention logits."""
     assert x.dim() == 2 and x.stride(1) == 1 and x.shape[1] == 256 and x.dtype == _f32
     assert (pos is None) == blk.inter
-    if raw_pos is not None:
+    rows = groups * group_tokens
+    with_raw = raw_pos is not None
+    if with_raw:
         assert blk.inter and blk.has_raw and raw_pos.shape == x.shape and raw_pos.stride(1) == 1 and raw_pos.dtype == _f32
-        rows = groups * group_tokens
         assert x.shape[0] == rows
-        if out is None:
-            out = torch.empty((rows, 256), dtype=_f32, device=x.device)
-        raw = torch.empty((rows, 384), dtype=_f32, device=x.device)
-        prof = _gemm_profile if (_gemm_profile is not None and rows > 0) else None
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        fn, img = (_L().gom_dec_attn2_raw_f32, blk.image2) if blk.form == 2 else (_L().gom_dec_attn_raw_f32, blk.image)
-        check(fn(_p(x), x.stride(0) if rows > 1 else 256, _p(img), blk.eps, _p(out),
-                 out.stride(0) if rows > 1 else 256, _p(raw_pos), raw_pos.stride(0) if rows > 1 else 256,
-                 _p(raw), 384, groups, group_tokens, inner, _p(range_flag(x.device)), _stream()),
-              "gom_dec_attn_raw_f32")
-        if prof is not None:
-            e1.record()
-            flops = 2.0 * rows * 256 * (1024 + 384) + 4.0 * rows * group_tokens * 256
-            prof.append((e0, e1, flops, 4.0 * rows * (256 * 3 + 384) + blk.image.numel(), "decattn:inter+raw:%dx%d" % (groups, group_tokens),
-                         _profile_scope))
-        return out, raw
     if pos is not None:
         assert pos.shape == x.shape and pos.stride(1) == 1 and pos.dtype == _f32
-    rows = groups * group_tokens
     assert x.shape[0] >= rows
     if out is None:
         out = torch.empty((x.shape[0], 256), dtype=_f32, device=x.device)
-    prof = _gemm_profile if (_gemm_profile is not None and rows > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    fn, img = (_L().gom_dec_attn2_f32, blk.image2) if blk.form == 2 else (_L().gom_dec_attn_f32, blk.image)
-    check(fn(_p(x), x.stride(0) if x.shape[0] > 1 else 256, _p(pos),
-             (pos.stride(0) if pos.shape[0] > 1 else 256) if pos is not None else 0, _p(img), blk.eps, _p(out),
-             out.stride(0) if out.shape[0] > 1 else 256, groups, group_tokens, inner,
-             1 if blk.inter else 0, _p(range_flag(x.device)), _stream()), "gom_dec_attn_f32")
-    if prof is not None:
-        e1.record()
-        # the block's nn.Linear products (in_proj 768 + out_proj 256 columns) + QK^T and PV of every head
-        flops = 2.0 * rows * 256 * 1024 + 4.0 * rows * group_tokens * 256
-        nbytes = 4.0 * rows * 256 * (3 if pos is not None else 2) + blk.image.numel()
-        prof.append((e0, e1, flops, nbytes, "decattn:%s:%dx%d" % ("inter" if blk.inter else "intra", groups, group_tokens), _profile_scope))
-    return out
+    raw = torch.empty((rows, 384), dtype=_f32, device=x.device) if with_raw else None
+    L, form2 = _L(), blk.form == 2
+    img = blk.image2 if form2 else blk.image
+    with _timed(rows > 0, lambda: _dec_attn_figures(blk, groups, group_tokens, with_raw, pos is not None)):
+        if with_raw:
+            check((L.gom_dec_attn2_raw_f32 if form2 else L.gom_dec_attn_raw_f32)(
+                _p(x), _ld(x), _p(img), blk.eps, _p(out), _ld(out), _p(raw_pos), _ld(raw_pos), _p(raw), 384, groups, group_tokens,
+                inner, _p(range_flag(x.device)), _stream()), "gom_dec_attn_raw_f32")
+        else:
+            check((L.gom_dec_attn2_f32 if form2 else L.gom_dec_attn_f32)(
+                _p(x), _ld(x), _p(pos), _ld(pos), _p(img), blk.eps, _p(out), _ld(out), groups, group_tokens, inner,
+                1 if blk.inter else 0, _p(range_flag(x.device)), _stream()), "gom_dec_attn_f32")
+    return (out, raw) if with_raw else out
 
 
 def dec_inter_heads(x, blk, groups, group_tokens, inner, out=None):
@@ -890,17 +850,11 @@ def dec_inter_heads(x, blk, groups, group_tokens, inner, out=None):
     assert x.shape[0] >= rows
     if out is None:
         out = torch.empty((x.shape[0], 256), dtype=_f32, device=x.device)
-    prof = _gemm_profile if (_gemm_profile is not None and rows > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().gom_dec_inter_heads_f32(_p(x), x.stride(0) if x.shape[0] > 1 else 256, _p(blk.image), _p(out),
-                                       out.stride(0) if out.shape[0] > 1 else 256, groups, group_tokens, inner,
-                                       _p(range_flag(x.device)), _stream()), "gom_dec_inter_heads_f32")
-    if prof is not None:
-        e1.record()
-        flops = 2.0 * rows * 256 * 768 + 4.0 * rows * group_tokens * 256      # in_proj + QK^T and PV of every head
-        prof.append((e0, e1, flops, 4.0 * rows * 256 * 2 + 24 * 36864, "decattn:inter-heads:%dx%d" % (groups, group_tokens), _profile_scope))
+    # profile flops: in_proj + QK^T and PV of every head
+    with _timed(rows > 0, lambda: (2.0 * rows * 256 * 768 + 4.0 * rows * group_tokens * 256, 4.0 * rows * 256 * 2 + 24 * 36864,
+                                   "decattn:inter-heads:%dx%d" % (groups, group_tokens))):
+        check(_L().gom_dec_inter_heads_f32(_p(x), _ld(x), _p(blk.image), _p(out), _ld(out), groups, group_tokens, inner,
+                                           _p(range_flag(x.device)), _stream()), "gom_dec_inter_heads_f32")
     return out
 
 
@@ -909,23 +863,36 @@ DEC_INTER_MAX_HEADS = 352
 FUSED_FFN = _switch("FUSED_FFN")     # f16x3 back-end: FFN blocks as one fused launch (False: GEMM, GEMM, LayerNorm)
 
 
+def _ffn_image(w1, b1, w2, refusal=None, acc_order=False, into=None, off=0):
+    """Fragment-linear image of a `linear1 [F, D] -> ReLU -> linear2 [D, F]` pair (csrc/ffn_fused.hip; acc_order: linear1 in
+    accumulator order, the form a block behind another block of one launch takes) -> (inv_scale1, inv_scale2, image).  The image is
+    a new buffer, or the gom_ffn_fused_image_bytes(D, F) bytes of `into` from `off`.  `refusal`: the error's text for shapes the
+    kernel does not serve (None: the caller has checked them)."""
+    F_, D_ = w1.shape
+    assert tuple(w2.shape) == (D_, F_)
+    nbytes = _L().gom_ffn_fused_image_bytes(D_, F_)
+    if nbytes < 0 and refusal is not None:
+        raise _lib_mod.GomError(refusal)
+    assert nbytes >= 0
+    s1, s2 = split_weight(w1.contiguous(), kind="f16x3"), split_weight(w2.contiguous(), kind="f16x3")
+    if into is None:
+        into = torch.empty((nbytes,), dtype=torch.uint8, device=w1.device)
+    assert off + nbytes <= into.numel()
+    p1, p2 = s1.planes, s2.planes
+    name = "gom_ffn_fused_image_acc_order" if acc_order else "gom_ffn_fused_image"
+    check(getattr(_L(), name)(_p(p1), p1.stride(0), p1.stride(1), _p(s1.inv_scale), _p(b1), _p(p2), p2.stride(0), p2.stride(1), D_, F_,
+                              ctypes.c_void_p(into.data_ptr() + off), nbytes, _stream()), name)
+    return s1.inv_scale, s2.inv_scale, into
+
+
 class FusedFFN:
     """Weights of one `linear1 -> ReLU -> linear2 -> + residual -> LayerNorm` block prepared for gom_ffn_fused_ln_f32: the
     fragment-linear image of both weight matrices + what the epilogue needs.  Built once per layer (f16x3 mode only)."""
 
     def __init__(self, w1, b1, w2, b2, gamma, beta, eps=1e-5):
-        F_, D_ = w1.shape
-        assert w2.shape == (D_, F_)
-        nbytes = _L().gom_ffn_fused_image_bytes(D_, F_)
-        if nbytes < 0:
-            raise _lib_mod.GomError("fused FFN kernel does not serve d_model %d / d_hidden %d" % (D_, F_))
-        s1, s2 = split_weight(w1.contiguous(), kind="f16x3"), split_weight(w2.contiguous(), kind="f16x3")
-        self.image = torch.empty((nbytes,), dtype=torch.uint8, device=w1.device)
-        p1, p2 = s1.planes, s2.planes
-        check(_L().gom_ffn_fused_image(_p(p1), p1.stride(0), p1.stride(1), _p(s1.inv_scale), _p(b1), _p(p2), p2.stride(0),
-                                       p2.stride(1), D_, F_, _p(self.image), nbytes, _stream()), "gom_ffn_fused_image")
-        self.inv2, self.b2, self.gamma, self.beta, self.eps = s2.inv_scale, b2, gamma, beta, eps
-        self.D, self.F = D_, F_
+        self.F, self.D = w1.shape
+        _, self.inv2, self.image = _ffn_image(w1, b1, w2, "fused FFN kernel does not serve d_model %d / d_hidden %d" % (self.D, self.F))
+        self.b2, self.gamma, self.beta, self.eps = b2, gamma, beta, eps
 
 
 FUSED_MLP2 = _switch("FUSED_MLP2")   # f16x3 back-end: the decoder's two-layer 256 -> 256 -> 256 perceptrons as one launch
@@ -936,17 +903,10 @@ class FusedMLP2:
     pipeline without residual / LayerNorm)."""
 
     def __init__(self, w1, b1, w2, b2, relu_out):
-        F_, D_ = w1.shape
-        assert tuple(w2.shape) == (D_, F_) and D_ == 256
-        nbytes = _L().gom_ffn_fused_image_bytes(D_, F_)
-        if nbytes < 0:
-            raise _lib_mod.GomError("fused two-layer perceptron does not serve %d -> %d -> %d" % (D_, F_, D_))
-        s1, s2 = split_weight(w1.contiguous(), kind="f16x3"), split_weight(w2.contiguous(), kind="f16x3")
-        self.image = torch.empty((nbytes,), dtype=torch.uint8, device=w1.device)
-        p1, p2 = s1.planes, s2.planes
-        check(_L().gom_ffn_fused_image(_p(p1), p1.stride(0), p1.stride(1), _p(s1.inv_scale), _p(b1), _p(p2), p2.stride(0),
-                                       p2.stride(1), D_, F_, _p(self.image), nbytes, _stream()), "gom_ffn_fused_image")
-        self.inv2, self.b2, self.relu_out, self.D, self.F = s2.inv_scale, b2.contiguous(), bool(relu_out), D_, F_
+        self.F, self.D = w1.shape
+        assert self.D == 256
+        _, self.inv2, self.image = _ffn_image(w1, b1, w2, "fused two-layer perceptron does not serve %d -> %d -> %d" % (self.D, self.F, self.D))
+        self.b2, self.relu_out = b2.contiguous(), bool(relu_out)
 
 
 def mlp2_block(w1, b1, w2, b2, relu_out):
@@ -960,17 +920,9 @@ def mlp2_fused(x, blk):
     assert x.dim() == 2 and x.stride(1) == 1 and x.shape[1] == 256 and x.dtype == _f32
     M = x.shape[0]
     out = torch.empty((M, 256), dtype=_f32, device=x.device)
-    prof = _gemm_profile if (_gemm_profile is not None and M > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().gom_mlp2_fused_f32(_p(x), x.stride(0) if M > 1 else 256, _p(blk.image), _p(blk.inv2), _p(blk.b2),
-                                  1 if blk.relu_out else 0, _p(out), 256, M, blk.D, blk.F, _p(range_flag(x.device)), _stream()),
-          "gom_mlp2_fused_f32")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 4.0 * M * blk.D * blk.F, 8.0 * M * blk.D + blk.image.numel(), "ffn-mlp2:%dx%dx%d" % (M, blk.D, blk.F),
-                     _profile_scope))
+    with _timed(M > 0, lambda: (4.0 * M * blk.D * blk.F, 8.0 * M * blk.D + blk.image.numel(), "ffn-mlp2:%dx%dx%d" % (M, blk.D, blk.F))):
+        check(_L().gom_mlp2_fused_f32(_p(x), _ld(x), _p(blk.image), _p(blk.inv2), _p(blk.b2), 1 if blk.relu_out else 0, _p(out), 256,
+                                      M, blk.D, blk.F, _p(range_flag(x.device)), _stream()), "gom_mlp2_fused_f32")
     return out
 
 
@@ -980,16 +932,10 @@ def ffn_fused_ln(x, ffn, out=None):
     M = x.shape[0]
     if out is None:
         out = torch.empty((M, ffn.D), dtype=_f32, device=x.device)
-    prof = _gemm_profile if (_gemm_profile is not None and M > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().gom_ffn_fused_ln_f32(_p(x), x.stride(0) if M > 1 else ffn.D, _p(ffn.image), _p(ffn.inv2), _p(ffn.b2),
-                                    _p(ffn.gamma), _p(ffn.beta), ffn.eps, _p(out), out.stride(0) if M > 1 else ffn.D, M,
-                                    ffn.D, ffn.F, _p(range_flag(x.device)), _stream()), "gom_ffn_fused_ln_f32")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 4.0 * M * ffn.D * ffn.F, 8.0 * M * ffn.D + ffn.image.numel(), "ffn%dx%dx%d" % (M, ffn.D, ffn.F), _profile_scope))
+    with _timed(M > 0, lambda: (4.0 * M * ffn.D * ffn.F, 8.0 * M * ffn.D + ffn.image.numel(), "ffn%dx%dx%d" % (M, ffn.D, ffn.F))):
+        check(_L().gom_ffn_fused_ln_f32(_p(x), _ld(x), _p(ffn.image), _p(ffn.inv2), _p(ffn.b2), _p(ffn.gamma), _p(ffn.beta), ffn.eps,
+                                        _p(out), _ld(out), M, ffn.D, ffn.F, _p(range_flag(x.device)), _stream()),
+              "gom_ffn_fused_ln_f32")
     return out
 
 
@@ -1007,95 +953,77 @@ class DecTail:
         kernel of csrc/dec_tail2.hip (80 rows per workgroup, the waves split the output columns; `waves` = 4, or 8 = two per SIMD:
         `DEC_TAIL2_WAVES`); form 1: csrc/dec_tail.hip."""
         w1, b1, w2, b2, gamma, beta = ffn_w
+        (c1, cb1), (c2, cb2), (W3, b3) = coord_w
+        (q1, qb1), (q2, qb2) = qpos_w
+        F_, D_ = w1.shape
         if form is None:
-            form = 2 if (DEC_TAIL2 and w1.shape[0] % 128 == 0) else 1
+            form = 2 if (DEC_TAIL2 and F_ % 128 == 0) else 1
         self.form = form
         self.waves = int(waves) if waves is not None else DEC_TAIL2_WAVES
-        if form == 2:
-            self._init2(ffn_w, coord_w, qpos_w, dim_t, eps, proj_w)
-            return
-        (c1, cb1), (c2, cb2), (W3, b3) = coord_w
-        (q1, qb1), (q2, qb2) = qpos_w
-        F_, D_ = w1.shape
-        assert D_ == 256 and tuple(w2.shape) == (D_, F_) and tuple(W3.shape) == (2, 256)
+        assert D_ == 256 and tuple(w2.shape) == (D_, F_) and tuple(W3.shape) == (2, 256) and (form != 2 or F_ % 128 == 0)
         for w in (c1, c2, q1, q2):
             assert tuple(w.shape) == (256, 256)
+        self.D, self.F = D_, F_
         L = _L()
-        nbytes = L.gom_dec_tail_image_bytes(D_, F_, 1)
-        if nbytes < 0:
-            raise _lib_mod.GomError("decoder tail kernel does not serve d_model %d / d_hidden %d" % (D_, F_))
-        lin_bytes = L.gom_dec_tail_lin_image_bytes() if proj_w is not None else 0
-        nbytes += lin_bytes
-        self.image = torch.empty((nbytes,), dtype=torch.uint8, device=w1.device)
-        off = 0
-        self.proj = None
+        if form == 2:
+            self.wave_bytes = {q: L.gom_dec_tail2_wave_bytes(D_, F_, 1 if proj_w is not None else 0, q, self.waves) for q in (0, 1)}
+            served = self.wave_bytes[1] >= 0
+        else:
+            served = L.gom_dec_tail_image_bytes(D_, F_, 1) >= 0
+        if not served:
+            raise _lib_mod.GomError("decoder tail kernel%s does not serve d_model %d / d_hidden %d" % (" (form 2)" if form == 2 else "", D_, F_))
+        so, self.proj = None, None
         if proj_w is not None:
             wo, bo, pg, pb = proj_w
             assert tuple(wo.shape) == (256, 256)
             so = split_weight(wo.contiguous(), kind="f16x3")
+            self.proj = (so.inv_scale, bo.contiguous(), pg.contiguous(), pb.contiguous())
+        mlps = ((w1, b1, w2), (c1, cb1, c2), (q1, qb1, q2))       # FFN | ctrl_point_coord | ref_point_head
+        invs = (self._image2 if form == 2 else self._image1)(mlps, so)
+        (self.inv1, self.inv2), (self.c_inv1, self.c_inv2), (self.q_inv1, self.q_inv2) = invs
+        self.b1, self.b2, self.gamma, self.beta = b1.contiguous(), b2.contiguous(), gamma.contiguous(), beta.contiguous()
+        self.c_b1, self.c_b2, self.q_b1, self.q_b2 = cb1.contiguous(), cb2.contiguous(), qb1.contiguous(), qb2.contiguous()
+        self.W3, self.b3, self.dim_t, self.eps = W3.contiguous(), b3.contiguous(), dim_t, eps
+
+    def _image1(self, mlps, so):
+        """csrc/dec_tail.hip: the images of [out_proj] | FFN | ctrl_point_coord | ref_point_head back to back, every block behind
+        another one with its first weight in accumulator order.  Returns the blocks' (inv_scale1, inv_scale2)."""
+        L = _L()
+        lin_bytes = L.gom_dec_tail_lin_image_bytes() if so is not None else 0
+        nbytes = L.gom_dec_tail_image_bytes(self.D, self.F, 1) + lin_bytes
+        self.image = torch.empty((nbytes,), dtype=torch.uint8, device=mlps[0][0].device)
+        if so is not None:
             check(L.gom_dec_tail_lin_image(_p(so.planes), so.planes.stride(0), so.planes.stride(1), _p(self.image), lin_bytes, _stream()),
                   "gom_dec_tail_lin_image")
-            off = lin_bytes
-            self.proj = (so.inv_scale, bo.contiguous(), pg.contiguous(), pb.contiguous())
-        keep = []
-        for (wa, ba, wb), fn, F_blk in (((w1, b1, w2), L.gom_ffn_fused_image_acc_order if proj_w is not None else L.gom_ffn_fused_image, F_),
-                                        ((c1, cb1, c2), L.gom_ffn_fused_image_acc_order, 256),
-                                        ((q1, qb1, q2), L.gom_ffn_fused_image_acc_order, 256)):
-            sa, sb = split_weight(wa.contiguous(), kind="f16x3"), split_weight(wb.contiguous(), kind="f16x3")
-            n = L.gom_ffn_fused_image_bytes(D_, F_blk)
-            pa, pb = sa.planes, sb.planes
-            check(fn(_p(pa), pa.stride(0), pa.stride(1), _p(sa.inv_scale), _p(ba), _p(pb), pb.stride(0), pb.stride(1), D_, F_blk,
-                     ctypes.c_void_p(self.image.data_ptr() + off), n, _stream()), "gom_ffn_fused_image*")
-            off += n
-            keep.append(sb.inv_scale)
+        off, invs = lin_bytes, []
+        for i, (wa, ba, wb) in enumerate(mlps):
+            invs.append(_ffn_image(wa, ba, wb, acc_order=i > 0 or so is not None, into=self.image, off=off)[:2])
+            off += L.gom_ffn_fused_image_bytes(self.D, wa.shape[0])
         assert off == nbytes
-        self.inv2, self.c_inv2, self.q_inv2 = keep
-        self.b2, self.gamma, self.beta = b2.contiguous(), gamma.contiguous(), beta.contiguous()
-        self.c_b2, self.q_b2 = cb2.contiguous(), qb2.contiguous()
-        self.W3, self.b3, self.dim_t, self.eps, self.D, self.F = W3.contiguous(), b3.contiguous(), dim_t, eps, D_, F_
+        return invs
 
-
-    def _init2(self, ffn_w, coord_w, qpos_w, dim_t, eps, proj_w):
+    def _image2(self, mlps, so):
         """One linear weight stream per wave (csrc/dec_tail2.hip): [out_proj] | FFN | ctrl_point_coord | ref_point_head; an image
-        WITHOUT ref_point_head's part serves the last layer (want_qpos=False): the streams of the two differ only in length."""
-        w1, b1, w2, b2, gamma, beta = ffn_w
-        (c1, cb1), (c2, cb2), (W3, b3) = coord_w
-        (q1, qb1), (q2, qb2) = qpos_w
-        F_, D_ = w1.shape
-        assert D_ == 256 and tuple(w2.shape) == (D_, F_) and tuple(W3.shape) == (2, 256) and F_ % 128 == 0
-        L = _L()
-        nw = self.waves
-        self.wave_bytes = {q: L.gom_dec_tail2_wave_bytes(D_, F_, 1 if proj_w is not None else 0, q, nw) for q in (0, 1)}
-        if self.wave_bytes[1] < 0:
-            raise _lib_mod.GomError("decoder tail kernel (form 2) does not serve d_model %d / d_hidden %d" % (D_, F_))
-        wb = self.wave_bytes[1]
-        self.image = torch.empty((nw * wb,), dtype=torch.uint8, device=w1.device)
-        off = 0
+        WITHOUT ref_point_head's part serves the last layer (want_qpos=False): the streams of the two differ only in length.
+        Returns the blocks' (inv_scale1, inv_scale2)."""
+        L, nw, wb = _L(), self.waves, self.wave_bytes[1]
+        self.image = torch.empty((nw * wb,), dtype=torch.uint8, device=mlps[0][0].device)
         blk_bytes = (256 // nw) * 1024                            # a wave's share of a 256 -> 256 layer or of a chunk of 128 hidden units
-        self.proj = None
-        if proj_w is not None:
-            wo, bo, pg, pb = proj_w
-            assert tuple(wo.shape) == (256, 256)
-            so = split_weight(wo.contiguous(), kind="f16x3")
+        off, invs = 0, []
+        if so is not None:
             check(L.gom_dec_tail2_image_lin(_p(so.planes), so.planes.stride(0), so.planes.stride(1), _p(self.image), wb, off, nw, _stream()),
                   "gom_dec_tail2_image_lin")
             off += blk_bytes
-            self.proj = (so.inv_scale, bo.contiguous(), pg.contiguous(), pb.contiguous())
-        keep = []
-        for (wa, wb_), F_blk in (((w1, w2), F_), ((c1, c2), 256), ((q1, q2), 256)):
+        for wa, _, wb_ in mlps:
             sa, sb = split_weight(wa.contiguous(), kind="f16x3"), split_weight(wb_.contiguous(), kind="f16x3")
             check(L.gom_dec_tail2_image_mlp(_p(sa.planes), sa.planes.stride(0), sa.planes.stride(1), _p(sb.planes), sb.planes.stride(0),
-                                            sb.planes.stride(1), F_blk, _p(self.image), wb, off, nw, _stream()), "gom_dec_tail2_image_mlp")
-            off += (F_blk // 128) * blk_bytes
-            keep.append((sa.inv_scale, sb.inv_scale))
+                                            sb.planes.stride(1), wa.shape[0], _p(self.image), wb, off, nw, _stream()), "gom_dec_tail2_image_mlp")
+            off += (wa.shape[0] // 128) * blk_bytes
+            invs.append((sa.inv_scale, sb.inv_scale))
         assert off == wb
         # the last layer's image: the same streams without ref_point_head's part, packed at the shorter stride
-        wb0 = self.wave_bytes[0]
-        self.image_last = self.image.view(nw, wb)[:, :wb0].contiguous().view(-1)
-        (self.inv1, self.inv2), (self.c_inv1, self.c_inv2), (self.q_inv1, self.q_inv2) = keep
-        self.b1, self.b2, self.gamma, self.beta = b1.contiguous(), b2.contiguous(), gamma.contiguous(), beta.contiguous()
-        self.c_b1, self.c_b2, self.q_b1, self.q_b2 = cb1.contiguous(), cb2.contiguous(), qb1.contiguous(), qb2.contiguous()
-        self.W3, self.b3, self.dim_t, self.eps, self.D, self.F = W3.contiguous(), b3.contiguous(), dim_t, eps, D_, F_
+        self.image_last = self.image.view(nw, wb)[:, :self.wave_bytes[0]].contiguous().view(-1)
+        return invs
 
 
 DEC_TAIL2 = _switch("DEC_TAIL2")            # ... as the CU-cooperative split-N kernel (csrc/dec_tail2.hip, round 6)
@@ -1129,6 +1057,13 @@ def dec_tail_block(ffn_w, coord_w, qpos_w, dim_t, proj_w=None):
     return blk
 
 
+def _dec_tail_figures(blk, M, want_qpos):
+    """Profile record of a `dec_tail` launch: FFN + ctrl_point_coord [+ ref_point_head] + the N = 2 layer [+ out_proj]."""
+    flops = 4.0 * M * 256 * blk.F + 4.0 * M * 256 * 256 * (2 if want_qpos else 1) + 4.0 * M * 256 + \
+        (2.0 * M * 256 * 256 if blk.proj is not None else 0.0)
+    return flops, 4.0 * M * 256 * (3 if want_qpos else 2) + blk.image.numel(), "dectail:%dx%d%s" % (M, blk.F, "+qpos" if want_qpos else "")
+
+
 def dec_tail(x, blk, ref, want_qpos=True, residual=None, frames=None):
     """(tgt [M,256], new_ref [M,2], qpos [M,256] | None) of one launch: LayerNorm(x + FFN(x)), the refined reference points and the
     NEXT layer's query position (deformable_transformer.py:352-369, :484-488, :470-473).  A block built with `proj_w` takes
@@ -1147,41 +1082,29 @@ def dec_tail(x, blk, ref, want_qpos=True, residual=None, frames=None):
     out = torch.empty((M, 256), dtype=_f32, device=x.device)
     new_ref = torch.empty_like(ref)
     qpos = torch.empty((M, 256), dtype=_f32, device=x.device) if want_qpos else None
-    prof = _gemm_profile if (_gemm_profile is not None and M > 0) else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if blk.form == 2:
-        r = residual
-        assert r is None or (r.dim() == 2 and r.stride(1) == 1 and r.shape == x.shape and r.dtype == _f32)
-        pi, pb, pg, pbe = blk.proj if blk.proj is not None else (None, None, None, None)
-        check(_L().gom_dec_tail2_f32(_p(x), x.stride(0) if M > 1 else 256, _p(r), (r.stride(0) if M > 1 else 256) if r is not None else 0,
-                                     _p(blk.image if want_qpos else blk.image_last), blk.wave_bytes[1 if want_qpos else 0], blk.F,
-                                     _p(pi), _p(pb), _p(pg), _p(pbe), blk.eps, _p(blk.inv1), _p(blk.b1), _p(blk.inv2), _p(blk.b2),
-                                     _p(blk.gamma), _p(blk.beta), blk.eps, _p(blk.c_inv1), _p(blk.c_b1), _p(blk.c_inv2), _p(blk.c_b2),
-                                     _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t), _p(blk.q_inv1), _p(blk.q_b1), _p(blk.q_inv2),
-                                     _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M, blk.waves, _p(range_flag(x.device)), _stream()),
-              "gom_dec_tail2_f32")
-    elif blk.proj is None:
-        check(_L().gom_dec_tail_f32(_p(x), x.stride(0) if M > 1 else 256, _p(blk.image), blk.F, _p(blk.inv2), _p(blk.b2), _p(blk.gamma),
-                                    _p(blk.beta), blk.eps, _p(blk.c_inv2), _p(blk.c_b2), _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t),
-                                    _p(blk.q_inv2), _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M,
-                                    _p(range_flag(x.device)), _stream()), "gom_dec_tail_f32")
-    else:
-        r = residual
-        assert r.dim() == 2 and r.stride(1) == 1 and r.shape == x.shape and r.dtype == _f32
-        pi, pb, pg, pbe = blk.proj
-        check(_L().gom_dec_tail_proj_f32(_p(x), x.stride(0) if M > 1 else 256, _p(r), r.stride(0) if M > 1 else 256, _p(blk.image), blk.F,
-                                         _p(pi), _p(pb), _p(pg), _p(pbe), blk.eps, _p(blk.inv2), _p(blk.b2), _p(blk.gamma), _p(blk.beta),
-                                         blk.eps, _p(blk.c_inv2), _p(blk.c_b2), _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t),
-                                         _p(blk.q_inv2), _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M,
-                                         _p(range_flag(x.device)), _stream()), "gom_dec_tail_proj_f32")
-    if prof is not None:
-        e1.record()
-        flops = 4.0 * M * 256 * blk.F + 4.0 * M * 256 * 256 * (2 if want_qpos else 1) + 4.0 * M * 256 + \
-            (2.0 * M * 256 * 256 if blk.proj is not None else 0.0)
-        prof.append((e0, e1, flops, 4.0 * M * 256 * (3 if want_qpos else 2) + blk.image.numel(), "dectail:%dx%d%s" % (M, blk.F, "+qpos" if want_qpos else ""),
-                     _profile_scope))
+    r = residual
+    assert r is None or (r.dim() == 2 and r.stride(1) == 1 and r.shape == x.shape and r.dtype == _f32)
+    pi, pb, pg, pbe = blk.proj if blk.proj is not None else (None, None, None, None)
+    with _timed(M > 0, lambda: _dec_tail_figures(blk, M, want_qpos)):
+        if blk.form == 2:
+            check(_L().gom_dec_tail2_f32(_p(x), _ld(x), _p(r), _ld(r),
+                                         _p(blk.image if want_qpos else blk.image_last), blk.wave_bytes[1 if want_qpos else 0], blk.F,
+                                         _p(pi), _p(pb), _p(pg), _p(pbe), blk.eps, _p(blk.inv1), _p(blk.b1), _p(blk.inv2), _p(blk.b2),
+                                         _p(blk.gamma), _p(blk.beta), blk.eps, _p(blk.c_inv1), _p(blk.c_b1), _p(blk.c_inv2), _p(blk.c_b2),
+                                         _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t), _p(blk.q_inv1), _p(blk.q_b1), _p(blk.q_inv2),
+                                         _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M, blk.waves, _p(range_flag(x.device)), _stream()),
+                  "gom_dec_tail2_f32")
+        elif blk.proj is None:
+            check(_L().gom_dec_tail_f32(_p(x), _ld(x), _p(blk.image), blk.F, _p(blk.inv2), _p(blk.b2), _p(blk.gamma),
+                                        _p(blk.beta), blk.eps, _p(blk.c_inv2), _p(blk.c_b2), _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t),
+                                        _p(blk.q_inv2), _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M,
+                                        _p(range_flag(x.device)), _stream()), "gom_dec_tail_f32")
+        else:
+            check(_L().gom_dec_tail_proj_f32(_p(x), _ld(x), _p(r), _ld(r), _p(blk.image), blk.F,
+                                             _p(pi), _p(pb), _p(pg), _p(pbe), blk.eps, _p(blk.inv2), _p(blk.b2), _p(blk.gamma), _p(blk.beta),
+                                             blk.eps, _p(blk.c_inv2), _p(blk.c_b2), _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t),
+                                             _p(blk.q_inv2), _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M,
+                                             _p(range_flag(x.device)), _stream()), "gom_dec_tail_proj_f32")
     return out, new_ref, qpos
 
 
@@ -1304,43 +1227,33 @@ def msda_fused(raw, ref, value2d, batch_stride, shapes, lsi, B, Lq, valid_ratios
         _L().gom_msda_set_lane_distributed(1 if MSDA_LANES else 0)
         _msda_lanes_set[0] = MSDA_LANES
     out = torch.empty((B * Lq, 256), dtype=_f32, device=raw.device)
-    prof = _gemm_profile if _gemm_profile is not None else None
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        S_rows = value2d.shape[0]
-        # the value map once + raw offsets | logits + output (fp32); 2 * Lq * 8 heads * 16 samples * 4 corners * 32
-        _after = lambda: (e1.record(), prof.append((e0, e1, 2.0 * B * Lq * 8 * 16 * 4 * 32,
-                                                    4.0 * (S_rows * 256 + B * Lq * (384 + 256)), "msda:%dx%d" % (B, Lq),
-                                                    _profile_scope)))
-    else:
-        _after = lambda: None
-    if valid_ratios is not None:
-        check(_L().gom_msda_fused_forward_vr(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride,
-                                             value2d.stride(0), _p(shapes), _p(lsi), _p(valid_ratios), _p(out), B, Lq,
-                                             _stream()), "gom_msda_fused_forward_vr")
-        _after()
-        return out
-    if encoder_hw0 is not None and MSDA_WINDOW and MSDA_LANES:
-        mask = 3 if MSDA_WINDOW_L1 else 1
-        if _msda_window_set[0] != mask:
-            _L().gom_msda_set_window(mask)
-            _msda_window_set[0] = mask
-        h1, w1 = (int(encoder_hw0[2]), int(encoder_hw0[3])) if len(encoder_hw0) >= 4 else (0, 0)
-        if fallback_counter is not None:
-            fallback_counter.zero_()
-            _L().gom_msda_window_count_fallbacks(_p(fallback_counter))
-        try:
-            check(_L().gom_msda_fused_forward_encoder(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride, value2d.stride(0),
-                                                      _p(shapes), _p(lsi), _p(out), B, Lq, int(encoder_hw0[0]), int(encoder_hw0[1]),
-                                                      h1, w1, _stream()), "gom_msda_fused_forward_encoder")
-        finally:
+    S_rows = value2d.shape[0]
+    # profile figures: 2 * Lq * 8 heads * 16 samples * 4 corners * 32; the value map once + raw offsets | logits +
+    # output (fp32)
+    with _timed(True, lambda: (2.0 * B * Lq * 8 * 16 * 4 * 32, 4.0 * (S_rows * 256 + B * Lq * (384 + 256)), "msda:%dx%d" % (B, Lq))):
+        if valid_ratios is not None:
+            check(_L().gom_msda_fused_forward_vr(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride,
+                                                 value2d.stride(0), _p(shapes), _p(lsi), _p(valid_ratios), _p(out), B, Lq,
+                                                 _stream()), "gom_msda_fused_forward_vr")
+        elif encoder_hw0 is not None and MSDA_WINDOW and MSDA_LANES:
+            mask = 3 if MSDA_WINDOW_L1 else 1
+            if _msda_window_set[0] != mask:
+                _L().gom_msda_set_window(mask)
+                _msda_window_set[0] = mask
+            h1, w1 = (int(encoder_hw0[2]), int(encoder_hw0[3])) if len(encoder_hw0) >= 4 else (0, 0)
             if fallback_counter is not None:
-                _L().gom_msda_window_count_fallbacks(None)
-    else:
-        check(_L().gom_msda_fused_forward(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride, value2d.stride(0),
-                                          _p(shapes), _p(lsi), _p(out), B, Lq, _stream()), "gom_msda_fused_forward")
-    _after()
+                fallback_counter.zero_()
+                _L().gom_msda_window_count_fallbacks(_p(fallback_counter))
+            try:
+                check(_L().gom_msda_fused_forward_encoder(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride, value2d.stride(0),
+                                                          _p(shapes), _p(lsi), _p(out), B, Lq, int(encoder_hw0[0]), int(encoder_hw0[1]),
+                                                          h1, w1, _stream()), "gom_msda_fused_forward_encoder")
+            finally:
+                if fallback_counter is not None:
+                    _L().gom_msda_window_count_fallbacks(None)
+        else:
+            check(_L().gom_msda_fused_forward(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride, value2d.stride(0),
+                                              _p(shapes), _p(lsi), _p(out), B, Lq, _stream()), "gom_msda_fused_forward")
     return out
 
 
@@ -1783,7 +1696,7 @@ def ref_update(h, last, ref, dim_t, scale=None, want_pos=True):
     new_ref = torch.empty_like(ref)
     pos = torch.empty((Q, 256), dtype=_f32, device=ref.device) if want_pos else None
     sx, sy = scale if scale is not None else (1.0, 1.0)
-    check(_L().gom_ref_update_f32(_p(h), h.stride(0) if Q > 1 else 256, _p(W3), _p(b3), _p(ref), _p(dim_t), float(sx), float(sy),
+    check(_L().gom_ref_update_f32(_p(h), _ld(h), _p(W3), _p(b3), _p(ref), _p(dim_t), float(sx), float(sy),
                                   _p(new_ref), _p(pos), Q, _stream()), "gom_ref_update_f32")
     return new_ref, pos
 
@@ -2207,10 +2120,6 @@ def gather_rows(src, rows):
     return out
 
 
-def _ld(t):
-    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
-
-
 def asso_activate(logits, offsets, T, out=None):
     """logits [n_k, N], rows `logits.stride(0)` apart (a column slice of a wider buffer is fine); out: a caller's [n_k, >= N]
     buffer (rows `out.stride(0)` apart) instead of a new one."""
@@ -2285,7 +2194,7 @@ def gemm_small_rows(A, W, bias, out):
     for t_ in (A, W, bias, out):                              # row-strided views are fine (lda / ldw / ldc below)
         assert t_ is None or (t_.dtype == _f32 and t_.is_cuda)
     step = max(8, ((1 << 22) // N) // 8 * 8)
-    lda, ldw, ldc = (A.stride(0) if M > 1 else K), (W.stride(0) if N > 1 else K), (out.stride(0) if M > 1 else N)
+    lda, ldw, ldc = _ld(A), _ld(W), _ld(out)
     for a in range(0, M, step):
         m = min(step, M - a)
         check(_L().gom_gemm_small_f32(_p(A[a:]), None, lda, _p(W), ldw, None, _p(bias), None, 0, 0, _p(out[a:]), ldc, m, N, K,

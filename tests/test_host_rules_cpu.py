@@ -104,3 +104,21 @@ def test_tail_form_rule_takes_occupancy_for_short_launches_and_throughput_for_lo
     assert ops.tail_form2_wins(8 * 100 * 25) and ops.tail_form2_wins(2500) and ops.tail_form2_wins(1)
     assert not ops.tail_form2_wins(8 * 300 * 25)
     assert ops.tail_form2_wins(16 * 100 * 25)
+
+
+def test_leading_dimension_rule():
+    """ops._ld: stride(0) of a tensor with more than one row; the width of a one-row (or empty) tensor, whose stride(0) says nothing
+    about it; 0 for None; an explicit width for a tensor without a shape[1]."""
+    import torch
+    from gomatching_amd import ops
+    buf = torch.zeros((6, 640))
+    assert ops._ld(buf) == 640 and ops._ld(buf[:, 128:384]) == 640 and ops._ld(buf[1:3, :256]) == 640
+    assert ops._ld(buf[::2, :256]) == 1280                       # rows two apart in the buffer
+    one = buf[2:3, 128:384]                                      # one row cut from a wider and taller buffer
+    assert one.stride(0) == 640 and ops._ld(one) == 256
+    assert ops._ld(buf[:1]) == 640 and ops._ld(buf[:0, :256]) == 256 and ops._ld(torch.zeros((1, 2))) == 2
+    assert ops._ld(buf.t()[:3].t()) == 640                       # [6, 3]: a column slice keeps the buffer's stride
+    assert ops._ld(None) == 0 and ops._ld(None, 256) == 0
+    vec = torch.zeros((256,))
+    assert ops._ld(vec) == 256 and ops._ld(vec, 0) == 0 and ops._ld(vec[:64], 64) == 64
+    assert ops._ld(one, 0) == 0 and ops._ld(buf, 0) == 640       # the width stands in only where the stride is meaningless
