@@ -10,7 +10,7 @@ namespace {
 
 constexpr int MAXQ = 1024;
 
-// one wave per row: index of the first maximum
+// one wave per row: index of the first maximum, always in [0, V); NaN elements never win
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, int ld, int V, long rows,
                                                           int* __restrict__ out) {
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -28,7 +28,8 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
         const int oi = __shfl_xor(bi, o, 64);
         if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
     }
-    if (lane == 0) out[r] = bi;
+    // a row with nothing above -inf (all -inf, all NaN) never sets bi: such a row is constant to `>` and gives index 0
+    if (lane == 0) out[r] = (bi == 0x7FFFFFFF) ? 0 : bi;
 }
 
 __global__ __launch_bounds__(256) void detect_post_kernel(
@@ -86,7 +87,8 @@ __global__ __launch_bounds__(256) void detect_post_kernel(
     for (int i = tid; i < n; i += 256) s_dead[i] = 0;
     __syncthreads();
 
-    // 3. greedy NMS in score order (IoU > thr suppresses)
+    // 3. greedy NMS in score order (IoU > thr suppresses; two zero-area boxes at one place give 0 / 0 = NaN, which does not:
+    //    both stay, as in torchvision)
     for (int i = 0; i < n; ++i) {
         if (!s_dead[i]) {                                   // uniform: written before the last barrier
             const int qi = s_order[i];

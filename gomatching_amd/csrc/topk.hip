@@ -3,8 +3,11 @@
 // Two LDS bitonic-sort stages: per-chunk top-k, then a merge of the chunk winners.  Keys are
 // (order-preserving float bits, ~index) packed in 64 bits, so the result is sorted by value
 // descending with ties resolved towards the LOWER token index (deterministic; the reference's tie
-// order is unspecified).  Invalid-proposal tokens get the constant logit the reference produces for
-// a zeroed memory row (see DESIGN.md "proposal masking").
+// order is unspecified).  The order is that of the bit patterns: +0.0 ranks above -0.0 (torch.topk holds
+// them equal), NaN logits are not ordered.  Invalid-proposal tokens get the constant logit the reference
+// produces for a zeroed memory row (see DESIGN.md "proposal masking").  A last chunk with fewer than k
+// tokens hands its zero padding keys to the merge as candidates; k <= S real keys, each above zero, are
+// always among the candidates, so a padding key is never among the k winners.
 #include "common.h"
 
 namespace {

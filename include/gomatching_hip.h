@@ -678,6 +678,8 @@ int gom_topk_tokens(const float* logits, int ld, const unsigned char* valid, con
                     int k, void* workspace, int* idx_out, int* rows_out, void* stream);
 
 /* ---- A11/A12: detection() + NMS + foreground filter ---------------------------------------------------*/
+/* out[r] = index of the first maximum of x[r, 0..V), always in [0, V): 0 for a constant row (all -inf too);
+ * NaN elements never win, and a row of nothing but NaN gives 0. */
 int gom_argmax_rows_f32(const float* x, int ld, int V, long rows, int* out, void* stream);
 /* Per frame b: count[b] kept instances, in NMS (descending score) order, written to the first count[b] slots of
  * the nq-padded outputs: keep_idx (row into [B*nq]), scores, boxes [.,4] px, ctrl_out [.,P,2] px,
