@@ -1436,6 +1436,20 @@ def result_rows(bd, recs, voc_size, track_ids=None):
     return out
 
 
+def quad_bezier(quads, hw):
+    """quads int32 [n,8] (x1,y1,..,x4,y4), hw int32 [n,2] (each quad's image H, W), both CUDA -> int32 [n,16]: the control points
+    of the two Bezier curves of every quad, one launch (csrc/prepare.hip; the rule is in include/gomatching_hip.h)."""
+    dev = quads.device
+    _chk_i(dev, ("quads", quads, torch.int32, (None, 8)), ("hw", hw, torch.int32, (None, 2)))
+    n = quads.shape[0]
+    if hw.shape[0] != n:
+        raise ValueError("hw must be [n,2] for quads [n,8]")
+    out = torch.empty((n, 16), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_L().gom_quad_bezier_i32(_p(quads), _p(hw), n, _p(out), _stream()), "gom_quad_bezier_i32")
+    return out
+
+
 def quad_pairs(gt_quads, det_quads, gt_off, det_off, gt_key, det_key, measure, threshold, pairs=None):
     """The (ground truth, detection) pairs of one video whose measure is above `threshold` (csrc/score.hip; contract in
     include/gomatching_hip.h).  gt_quads [G,8] / det_quads [D,8] int32, gt_off / det_off [F+1] int32 (first object of each

@@ -509,6 +509,37 @@ int gom_ingest_crop_u8_hwc3_to_nhwc4(const uint8_t* src, int B, int H, int W, co
 #define GOM_RESULT_ROWS_WORDS 234
 int gom_result_rows_i32(const float* bd, const int64_t* recs, const int64_t* track_ids, int n, int voc_size,
                         int32_t* out, int ld, void* stream);
+/* ---- Quad -> Bezier control points (csrc/prepare.hip; python -m gomatching_amd.prepare) ------------------------
+ * What datasets/vts.py:154-162 derives from a `poly` quad on every load (polygon2rbox -> LinearRing.is_ccw -> cpt_bezier_pts),
+ * computed once per dataset: quads int32 [n,8] (x1,y1,..,x4,y4), hw int32 [n,2] (the quad's image H, W), out int32 [n,16]
+ * = the two Bezier curves, 4 control points each, x then y.  One lane per quad, ONE launch for all n.
+ * The rule for one quad, in integers and fp64 (each fp64 product, sum, quotient and square root rounded once: no contraction,
+ * no fast-math), with no trigonometry, so that the kernel, the numpy path (prepare.quad_bezier_host) and the plain-Python
+ * statement (tests/prepare_statement.py) give the same 16 words:
+ *   1. Hull of the DISTINCT points: sorted by (x, y), monotone chain popping on cross <= 0 (cross products exact in int64),
+ *      order lower[:-1] + upper[:-1]; one or two distinct points are their own hull.  Sizes 1, 2 (collinear), 3 (concave or a
+ *      repeated point) and 4 all occur.
+ *   2. Minimum-area rectangle over the hull's edges in hull order (edge i = hull[i] -> hull[(i+1) % size]; two points give two
+ *      edges): norm = sqrt(ex*ex + ey*ey), ux = ex/norm, uy = ey/norm; for every hull point pu = x*ux + y*uy and
+ *      pv = y*ux - x*uy; area = (umax-umin)*(vmax-vmin); the first strict minimum wins.
+ *   3. Corners straight from the unit vector, c(u,v) = (u*ux - v*uy, u*uy + v*ux), in the order (umin,vmin), (umax,vmin),
+ *      (umax,vmax), (umin,vmax), each coordinate truncated toward zero.  A one-point hull gives four equal corners.
+ *   4. get_tight_rect (bezier_tools.py:44-77): the corners stably sorted by x into ps[0..3]; (p1, p4) = (ps[0], ps[1]) if
+ *      ps[1].y > ps[0].y, else (ps[1], ps[0]); (p2, p3) = (ps[2], ps[3]) if ps[3].y > ps[2].y, else (ps[3], ps[2]); then
+ *      x = min(max(x, 1), W-1) and y = min(max(y, 1), H-1) for p1, p2, p3, p4.
+ *   5. Orientation: S = sum_i (x_i*y_{i+1} - x_{i+1}*y_i) over (p1, p2, p3, p4) cyclically, in int64; the four points are
+ *      reversed iff S < 0.
+ *   6. cpt_bezier_pts: of the four edges (p_i, p_{(i+1)%4}) the two longest, by integer squared length, ties to the lower
+ *      index, longest first; per edge: p_i, then int((1-t)*a + t*b) per coordinate at t = 1/3 and t = 2/3 (t = k/3 in fp64, two
+ *      products and a sum, truncated toward zero), then p_{i+1}.
+ * UNPINNED against the reference: cv2.minAreaRect / cv2.boxPoints compute in float32 with their own calipers and corner
+ * order (which can move a corner across a truncation and decides ties of the stable sort), and LinearRing.is_ccw at zero
+ * area; steps 4 and 6 are pinned by the reference's own functions (tests/golden/prepare_geometry.json).
+ * Coordinates are expected within +-2^20 and H, W positive.  quads and out must be 16-byte aligned, hw 8-byte aligned (a quad
+ * is read as two 16-byte words, a row written as four).  GOM_ERR_INVALID_ARG before any HIP call: n < 0, null or misaligned
+ * pointers with n > 0.  n == 0 is GOM_OK without a launch.  The grid is sized by n alone; plain stores, no atomics: the
+ * output is bitwise reproducible. */
+int gom_quad_bezier_i32(const int32_t* quads, const int32_t* hw, int n, int32_t* out, void* stream);
 /* Scoring (csrc/score.hip): the pairwise convex-quadrilateral measure of one video's objects, as the count pass and the
  * emit pass of a stream compaction over the (ground truth, detection) pairs of every frame.
  *   gt_quads [G,8], det_quads [D,8] int32 : x1,y1,..,x4,y4 in any point order (the convex hull is taken)
