@@ -137,6 +137,7 @@ SIGNATURES = {
     "gom_quad_bezier_i32": (I, [P, P, I, P, P]),
     "gom_quad_pairs_count_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, P]),
     "gom_quad_pairs_emit_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, L, P, P, P]),
+    "gom_quad_det_match_f64": (I, [P, P, P, P, P, I, I, I, D, D, P, P, P, P]),
     "gom_mask_fill_polygons_u32": (I, [P, I, P, I, P, P, P, I, L, P, I, I, I, P, P, P]),
     "gom_mask_fill_rle_u32": (I, [P, I, P, P, P, I, L, P, I, I, I, P, P, P]),
     "gom_mask_pairs_count_f64": (I, [P, P, P, P, L, P, P, P, P, L, P, P, P, P, I, I, I, L, D, P, P]),

@@ -1482,6 +1482,37 @@ def quad_pairs(gt_quads, det_quads, gt_off, det_off, gt_key, det_key, measure, t
     return counts, det, val
 
 
+QUAD_DET_MATCH_MAX_DET = 4096        # DM_MAX_DET of csrc/score_det.hip: a frame's detections that take part in the matching
+
+
+def quad_det_match(gt_quads, det_quads, gt_off, det_off, gt_care, iou_thr=0.5, area_thr=0.5, max_det=None):
+    """The detection protocol's per-frame greedy matching of one video, one launch (csrc/score_det.hip; the rule is in
+    include/gomatching_hip.h).  gt_quads [G,8] / det_quads [D,8] int32, gt_off / det_off [F+1] int32 (first object of each
+    frame), gt_care [G] int32 (0 = don't care), all CUDA.  -> (det_care int32 [D], match int32 [G], frame_stats int32 [F,3]):
+    whether each detection stays (no don't-care object covers more than `area_thr` of it), per object the matched
+    detection's index within its frame or -1, per frame (matched, care objects, care detections).  `max_det` = the largest
+    number of detections in a frame, if the caller has it: above 4096 is refused."""
+    dev = gt_quads.device
+    _chk_i(dev, ("gt_quads", gt_quads, torch.int32, (None, 8)), ("det_quads", det_quads, torch.int32, (None, 8)),
+           ("gt_off", gt_off, torch.int32, (None,)), ("det_off", det_off, torch.int32, (None,)),
+           ("gt_care", gt_care, torch.int32, (None,)))
+    G, D, F = gt_quads.shape[0], det_quads.shape[0], gt_off.shape[0] - 1
+    if F < 0 or det_off.shape[0] != F + 1 or gt_care.shape[0] != G:
+        raise ValueError("offsets must be [F+1] and gt_care [G]")
+    if max_det is None:
+        max_det = 0 if F == 0 else int((det_off[1:] - det_off[:-1]).max())
+    if max_det > QUAD_DET_MATCH_MAX_DET:
+        raise ValueError("a frame with %d detections: at most %d are matched" % (max_det, QUAD_DET_MATCH_MAX_DET))
+    det_care = torch.empty((D,), dtype=torch.int32, device=dev)
+    match = torch.empty((G,), dtype=torch.int32, device=dev)
+    stats = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_L().gom_quad_det_match_f64(_p(gt_quads), _p(det_quads), _p(gt_off), _p(det_off), _p(gt_care), G, D, F,
+                                          float(iou_thr), float(area_thr), _p(det_care), _p(match), _p(stats), _stream()),
+              "gom_quad_det_match_f64")
+    return det_care, match, stats
+
+
 def _chk_i(dev, *named):
     for name, t, dtype, shape in named:
         if not t.is_cuda or t.device != dev or t.dtype != dtype or t.dim() != len(shape) or \

@@ -2,6 +2,13 @@
 
     python -m gomatching_amd.score --gt GT --results RES [--e2e] [--threshold 0.5] [--host-iou] [--output scores.json]
     python -m gomatching_amd.score --protocol {dstext,bovtext,artvideo} ...
+    python -m gomatching_amd.score --det --gt GT --results RES [--host-iou] [--per-frame] [--output scores.json]
+
+`--det` is DSText's third protocol, the detection task (ICDAR15-style precision / recall / hmean per frame, the reference's
+Evaluation_DSText_Det): it lives in score_det.py with its own reading rules (frames by position, no clamping, the converter's
+point order and validity drop), its greedy per-frame matching in one launch per video (`ops.quad_det_match`,
+csrc/score_det.hip) and its own list of deliberate differences; `--per-frame` adds its `per_sample` entries.  It does not
+combine with --e2e, --curve or another --protocol.
 
 `--protocol dstext` (the default) is what this module describes; `bovtext` and `artvideo` score the `<out>/jsons` of
 `python -m gomatching_amd.eval` and live in score_json.py (the json readers, the OVERALL row, the transcription similarity
@@ -570,11 +577,16 @@ def build_parser():
                    help="dstext: the XML protocol (default); bovtext / artvideo: the json protocols (score_json.py), where --gt "
                         "holds GT/<class>/<name>.json or GT/<name>.json and --results the jsons/<name>.json of the eval command")
     p.add_argument("--curve", action="store_true", help="artvideo only: only evaluate curved text (Straight objects are ignored)")
+    p.add_argument("--det", action="store_true", help="dstext only: the detection protocol, precision / recall / hmean per frame "
+                                                      "(score_det.py)")
+    p.add_argument("--per-frame", action="store_true", help="--det only: also write per_sample, one entry per frame")
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.det or args.per_frame:
+        return _main_det(args)
     if args.protocol != "dstext":
         from . import score_json
         return score_json.main(args)
@@ -598,6 +610,26 @@ def main(argv=None):
     for k, s in res["per_sample"].items():
         print("Video_%s: MOTA %.4f  MOTP %.4f  IDF1 %.4f  FP %d  MS %d  SW %d" % (
             k, s["MOTA"], s["MOTP"], s["IDF1"], s["FP"], s["MS"], s["SW"]))
+    return 0
+
+
+def _main_det(args):
+    from . import score_det
+    try:
+        if not args.det:
+            raise ScoreError("--per-frame belongs to --det")
+        if args.e2e or args.curve or args.protocol != "dstext":
+            raise ScoreError("--det is the DSText detection protocol: it does not combine with --e2e, --curve or --protocol %s"
+                             % args.protocol)
+        if not (0.0 < args.threshold < 1.0):
+            raise ScoreError("--threshold must lie strictly between 0 and 1")
+        res = score_det.score_method(args.gt, args.results, args.threshold, args.host_iou, args.per_frame)
+        with open(args.output, "w") as f:
+            json.dump(res, f, indent=2, sort_keys=True)
+    except (ScoreError, OSError) as e:
+        sys.stderr.write("error: %s\n" % e)
+        return 2
+    score_det.print_scores(res)
     return 0
 
 

@@ -568,6 +568,26 @@ int gom_quad_pairs_emit_f64(const int32_t* gt_quads, const int32_t* det_quads, c
                             const int32_t* det_off, const int32_t* gt_key, const int32_t* det_key, int G, int D, int F,
                             long pairs, int measure, double threshold, const int64_t* scan, long total, int32_t* out_det,
                             double* out_val, void* stream);
+/* Scoring, the detection protocol (csrc/score_det.hip): per frame, the ICDAR15-style greedy matching of ground truth and
+ * detections, one launch per video.  Inputs as gom_quad_pairs_* takes them: gt_quads [G,8], det_quads [D,8], gt_off /
+ * det_off [F+1] (CSR); gt_care [G] int32, 0 = a "don't care" object.
+ * THE RULE, per frame with ground truth g = 0..Gf-1 and detections d = 0..Df-1 (indices within the frame):
+ *   geometry   : exactly that of gom_quad_pairs_* (the same device functions): iou(g,d) is measure 0, over(g,d) measure 1 --
+ *                the intersection over the detection's area, 0 for a detection without area; a hull without area gives 0.
+ *   det_care[d]: 0 iff some don't-care g of the frame has over(g,d) > area_thr (STRICT), else 1.
+ *   match[g]   : for g ascending over the care objects, the SMALLEST d with det_care[d] == 1, not taken by an earlier g, and
+ *                iou(g,d) > iou_thr (STRICT); -1 when there is none; don't-care g get -1.  A matched d is taken.
+ *   frame_stats[f] = (matched = the frame's match[g] >= 0, gt_care = its care objects, det_care_count = its det_care == 1).
+ * Outputs: det_care int32 [D], match int32 [G] (the detection's index within its frame), frame_stats int32 [F,3].
+ * One wavefront per frame; ballots and popcounts, no atomics, every output word has one writer: bitwise reproducible and
+ * independent of the launch geometry.  Every index made from the device-side offsets is clamped.  A frame's detections
+ * past its first 4096 are never matched (their det_care is still written): the caller refuses such frames beforehand.
+ * GOM_ERR_INVALID_ARG before any HIP call: null pointers (of a non-empty array), negative sizes, F == 0 with objects,
+ * iou_thr or area_thr outside (0, 1).  F == 0 is GOM_OK without a launch; frames without ground truth, without detections
+ * or without both are valid. */
+int gom_quad_det_match_f64(const int32_t* gt_quads, const int32_t* det_quads, const int32_t* gt_off,
+                           const int32_t* det_off, const int32_t* gt_care, int G, int D, int F, double iou_thr,
+                           double area_thr, int32_t* det_care, int32_t* match, int32_t* frame_stats, void* stream);
 /* Scoring on the pixel grid (csrc/mask_pairs.hip): the mask IoU of the ArTVideo protocol.
  *
  * Representation.  A mask is a box plus bit rows: boxes int32 [N,4] = (y0, y1, wx0, wx1), rows [y0, y1), 32-pixel word
