@@ -8,9 +8,9 @@ namespace {
 
 constexpr int WS = 7, WT = WS * WS;
 
-// ---- LayerNorm over the last dimension, any D <= 2048 with D % 4 == 0 (96 ... 1536): the row in registers, centred
-// variance (two reductions) as nn.LayerNorm.  One wave per row; for D <= 128 (Swin stage 0: 96 channels over 900k
-// tokens) one HALF-wave per row, so that 24 of 32 lanes work instead of 24 of 64.
+// ---- LayerNorm over the last dimension, any D <= 2048 with D % 4 == 0 (96 ... 1536): the row in registers (shifted by its
+// first element), centred variance (two reductions) as nn.LayerNorm.  One wave per row; for D <= 128 (Swin stage 0: 96
+// channels over 900k tokens) one HALF-wave per row, so that 24 of 32 lanes work instead of 24 of 64.
 template <int LANES>
 __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
@@ -28,17 +28,25 @@ __global__ __launch_bounds__(256) void layernorm_any_kernel(const float* __restr
     const int lane = threadIdx.x % LANES;
     const float* xr = x + (live ? row : 0) * D;
     f32x4 v[NV];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = (lane + LANES * i) * 4;
         v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < D) v[i] = *reinterpret_cast<const f32x4*>(xr + c);
+    }
+    // The row is held relative to its first element (LayerNorm does not see a shift): on a row whose mean dwarfs its spread the
+    // fp32 sum of the raw values loses the mean to the sum's own ulp (1000 + randn over 96 columns: 1e-4 of the output).
+    const float x0 = __shfl(v[0][0], (int)(threadIdx.x & 63) & ~(LANES - 1), 64);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (lane + LANES * i) * 4;
         if (c < D) {
-            v[i] = *reinterpret_cast<const f32x4*>(xr + c);
+            v[i] = v[i] - x0;
             s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
         }
     }
-    const float mean = group_sum<LANES>(s) / (float)D;
+    const float mean = group_sum<LANES>(s) / (float)D;     // of the shifted row
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
