@@ -72,27 +72,17 @@ __device__ __forceinline__ int clip8(int v) {
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-// One thread per output pixel (3 channels).  F32OUT: write (v[perm] - mean) / std as NHWC4; else uint8 HWC.
-// The OH x OW output is the window at (y0, x0) of the resized image the tables describe (the whole of it for
-// x0 = y0 = 0): pixel (oy, ox) reads table rows oy + y0 and ox + x0, nothing outside the window is computed.
-template <bool F32OUT>
-__global__ __launch_bounds__(256) void resample_kernel(const uint8_t* __restrict__ src, int H, int W,
-                                                       const int* __restrict__ xb, const int* __restrict__ xk, int xks,
-                                                       const int* __restrict__ yb, const int* __restrict__ yk, int yks,
-                                                       void* __restrict__ dst, int OH, int OW, int y0, int x0, long total,
-                                                       int flip, float m0, float m1, float m2, float s0, float s1, float s2) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int ox = (int)(i % OW);
-    const long t = i / OW;
-    const int oy = (int)(t % OH);
-    const long b = t / OH;
-    const int rx = ox + x0, ry = oy + y0;
+// The three 8-bit channels of pixel (ry, rx) of the resized image the tables describe: Pillow's horizontal pass on the
+// (<= yks) source rows of the vertical pass, in registers.  Every resample kernel of this file calls it, so they agree bit
+// for bit.
+__device__ __forceinline__ void resample_pixel(const uint8_t* __restrict__ frame, int W, const int* __restrict__ xb,
+                                               const int* __restrict__ xk, int xks, const int* __restrict__ yb,
+                                               const int* __restrict__ yk, int yks, int ry, int rx, int& c0, int& c1,
+                                               int& c2) {
     const int xmin = xb[2 * rx], xn = xb[2 * rx + 1];
     const int ymin = yb[2 * ry], yn = yb[2 * ry + 1];
     const int* kx = xk + (long)rx * xks;
     const int* ky = yk + (long)ry * yks;
-    const uint8_t* frame = src + b * (long)H * W * 3;
     const int half = 1 << (GOM_RESAMPLE_BITS - 1);
     int v0 = half, v1 = half, v2 = half;
     for (int r = 0; r < yn; ++r) {
@@ -109,7 +99,28 @@ __global__ __launch_bounds__(256) void resample_kernel(const uint8_t* __restrict
         v1 += clip8(h1) * k;
         v2 += clip8(h2) * k;
     }
-    int c0 = clip8(v0), c1 = clip8(v1), c2 = clip8(v2);
+    c0 = clip8(v0);
+    c1 = clip8(v1);
+    c2 = clip8(v2);
+}
+
+// One thread per output pixel (3 channels).  F32OUT: write (v[perm] - mean) / std as NHWC4; else uint8 HWC.
+// The OH x OW output is the window at (y0, x0) of the resized image the tables describe (the whole of it for
+// x0 = y0 = 0): pixel (oy, ox) reads table rows oy + y0 and ox + x0, nothing outside the window is computed.
+template <bool F32OUT>
+__global__ __launch_bounds__(256) void resample_kernel(const uint8_t* __restrict__ src, int H, int W,
+                                                       const int* __restrict__ xb, const int* __restrict__ xk, int xks,
+                                                       const int* __restrict__ yb, const int* __restrict__ yk, int yks,
+                                                       void* __restrict__ dst, int OH, int OW, int y0, int x0, long total,
+                                                       int flip, float m0, float m1, float m2, float s0, float s1, float s2) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int ox = (int)(i % OW);
+    const long t = i / OW;
+    const int oy = (int)(t % OH);
+    const long b = t / OH;
+    int c0, c1, c2;
+    resample_pixel(src + b * (long)H * W * 3, W, xb, xk, xks, yb, yk, yks, oy + y0, ox + x0, c0, c1, c2);
     if (flip) {
         const int tmp = c0;
         c0 = c2;
@@ -128,6 +139,40 @@ __global__ __launch_bounds__(256) void resample_kernel(const uint8_t* __restrict
         o[1] = (uint8_t)c1;
         o[2] = (uint8_t)c2;
     }
+}
+
+// A motion clip: T windows of T resizes of ONE source image, padded to PH x PW.  The frame is blockIdx.y, so its descriptor
+// -- passed by value, read from the kernel arguments -- is wave-uniform and costs scalar loads only; table offsets are in
+// int32 words from `tab`.  One thread per pixel of the PADDED frame: inside the window the arithmetic of `resample_kernel`,
+// outside it zeros (the padding is written here: dst needs no memset).
+struct MotionFrame {
+    int y0, x0, OH, OW, xks, yks, xb, xk, yb, yk;
+};
+struct MotionFrames {
+    MotionFrame f[GOM_INGEST_MOTION_MAX_FRAMES];
+};
+
+__global__ __launch_bounds__(256) void motion_kernel(const uint8_t* __restrict__ src, int W, const int* __restrict__ tab,
+                                                     MotionFrames frames, float* __restrict__ dst, int PH, int PW, int flip,
+                                                     float m0, float m1, float m2, float s0, float s1, float s2) {
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= PH * PW) return;
+    const MotionFrame f = frames.f[blockIdx.y];
+    const int ox = i % PW, oy = i / PW;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (ox < f.OW && oy < f.OH) {
+        int c0, c1, c2;
+        resample_pixel(src, W, tab + f.xb, tab + f.xk, f.xks, tab + f.yb, tab + f.yk, f.yks, oy + f.y0, ox + f.x0, c0, c1, c2);
+        if (flip) {
+            const int tmp = c0;
+            c0 = c2;
+            c2 = tmp;
+        }
+        o[0] = ((float)c0 - m0) / s0;
+        o[1] = ((float)c1 - m1) / s1;
+        o[2] = ((float)c2 - m2) / s2;
+    }
+    *reinterpret_cast<f32x4*>(dst + ((long)blockIdx.y * PH * PW + i) * 4) = o;
 }
 
 }  // namespace
@@ -186,5 +231,30 @@ extern "C" int gom_ingest_crop_u8_hwc3_to_nhwc4(const uint8_t* src, int B, int H
     hipLaunchKernelGGL(resample_kernel<true>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src,
                        H, W, xbounds, xkk, xksize, ybounds, ykk, yksize, (void*)dst, OH, OW, y0, x0, total,
                        flip_channels, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    return gom_launch_status();
+}
+
+// One source image, T frames of a GEN_IMAGE_MOTION clip (rule in include/gomatching_hip.h).  Every descriptor is checked on
+// the host before any HIP call: the kernel indexes the tables and the source by them.
+extern "C" int gom_ingest_motion_u8_hwc3_to_nhwc4(const uint8_t* src, int H, int W, const int* tables, long table_words,
+                                                  const int* frames, int T, const float* mean3, const float* std3,
+                                                  float* dst, int PH, int PW, int flip_channels, void* stream) {
+    GOM_CHECK_ARG(src && tables && frames && mean3 && std3 && dst && H > 0 && W > 0 && table_words > 0);
+    GOM_CHECK_ARG(T >= 1 && T <= GOM_INGEST_MOTION_MAX_FRAMES && PH > 0 && PW > 0 && (long)PH * PW <= 0x7fffffffL - 256);
+    MotionFrames fr = {};
+    for (int t = 0; t < T; ++t) {
+        const int* d = frames + (long)t * GOM_INGEST_MOTION_DESC_WORDS;
+        const int SH = d[0], SW = d[1], y0 = d[2], x0 = d[3], OH = d[4], OW = d[5], xks = d[6], yks = d[7];
+        const long xb = d[8], xk = d[9], yb = d[10], yk = d[11];
+        GOM_CHECK_ARG(GOM_RESAMPLE_WINDOW_OK && OH > 0 && OW > 0 && OH <= PH && OW <= PW);
+        GOM_CHECK_ARG(xks == gom_resample_ksize_bilinear(W, SW) && yks == gom_resample_ksize_bilinear(H, SH));
+        GOM_CHECK_ARG(xb >= 0 && xk >= 0 && yb >= 0 && yk >= 0 && xb + 2L * SW <= table_words &&
+                      xk + (long)SW * xks <= table_words && yb + 2L * SH <= table_words &&
+                      yk + (long)SH * yks <= table_words);
+        fr.f[t] = MotionFrame{y0, x0, OH, OW, xks, yks, (int)xb, (int)xk, (int)yb, (int)yk};
+    }
+    hipLaunchKernelGGL(motion_kernel, dim3((unsigned)cdiv((long)PH * PW, 256), (unsigned)T), dim3(256), 0,
+                       (hipStream_t)stream, src, W, tables, fr, dst, PH, PW, flip_channels, mean3[0], mean3[1], mean3[2],
+                       std3[0], std3[1], std3[2]);
     return gom_launch_status();
 }

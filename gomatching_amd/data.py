@@ -26,9 +26,25 @@ read off vts_dataset_mapper.py but cannot be executed without Detectron2 (and dr
 numpy's global state: the reference's stream of draws is not reproduced, its distribution is); decoding with Pillow instead
 of `detection_utils.read_image` (no EXIF transposition; JPEG decoders differ in IDCT and chroma upsampling).
 
+Still images (`INPUT.VIDEO.GEN_IMAGE_MOTION`, vts_dataset_mapper.py:137-140, 162-163, 181-202, 218-220) are OPT-IN:
+`GoMDatasetMapper(..., image_motion=True)` / `train --image-motion` turn a one-image video into a clip of TRAIN_LEN copies of
+the image, frame x under numbers of its own (`motion_clip_params`).  The rule: two `EfficientDetResizeCrop(size, (0.8, 1.2))`
+transforms on the SQUARE target (size, size), size = `target_size_of(INPUT)[0]`, are drawn -- `st` for the image, `ed` for the
+image AS `st` LEFT IT (its crop, not the source: Detectron2 applies an augmentation to its `AugInput` in place) -- and offsets
+(floor division) and scale (float64) are interpolated linearly over the frames, the scaled size taken from the SOURCE size.  A
+3000x4000 source on a 1280 target therefore zooms in about threefold over the clip: the reference's behaviour, kept.  The
+frames of such a clip differ in resized size and window, so the model pads them into one batch (`ops.ingest_motion`: one
+image upload, one table upload, one launch) and runs the detector per group of equal sizes (`training.forward_losses`).
+Without the flag a one-image video is refused as before: the refusals are what existing callers and tests rely on, and making
+motion the default under GEN_IMAGE_MOTION is a later, separate change.
+PINNED: the interpolation, by executing the reference's own lines 181-202 (tools/gen_golden_clip_motion.py compiles them from
+the reference file's text at generation time; tests/golden/clip_motion.npz).  UNPINNED: that `ed` sees `st`'s crop -- the
+generator's `StandardAugInput` stand-in applies a transform in place as Detectron2's published source does, but Detectron2
+is not here to run.
+
 Deliberately not built (each raises, naming what it met): `poly` quads and 14-gons (they need `cv2.minAreaRect`, shapely and
 a Bezier fit: such an annotation loads without its point fields, and a WITH_RESR config fails on it at mapping time),
-`GEN_IMAGE_MOTION` on one-image videos (a transform per frame, hence mixed-size batches), `MultiDatasetSampler`,
+`GEN_IMAGE_MOTION` on one-image videos unless asked for with `image_motion`, `MultiDatasetSampler`,
 `RepeatFactorTrainingSampler`, the `ResizeShortestEdge` training augmentation.
 """
 import collections
@@ -139,7 +155,7 @@ def load_video_json(json_file, image_root, extra_annotation_keys=("instance_id",
     if map_inst_id:
         if "instance_id" not in extra_annotation_keys:
             raise ValueError("load_video_json: map_inst_id needs 'instance_id' among extra_annotation_keys")
-        positive = sorted({ann["instance_id"] for ann in annotations if ann["instance_id"] > 0})
+        positive = sorted({ann["instance_id"] for ann in annotations if ann.get("instance_id", 0) > 0})
         instance_index = dict(zip(positive, range(1, len(positive) + 1)))
         instance_index.update({0: 0, -1: 0})
     copied = ("iscrowd", "bbox", "category_id") + tuple(extra_annotation_keys or ())
@@ -158,7 +174,7 @@ def load_video_json(json_file, image_root, extra_annotation_keys=("instance_id",
                                    % (ann.get("id"), obj["category_id"]))
                 obj["category_id"] = category_index[obj["category_id"]]
             if instance_index is not None:
-                obj["instance_id"] = instance_index[obj["instance_id"]]
+                obj["instance_id"] = instance_index[obj.get("instance_id", 0)]     # a still's annotations may carry none
             if ann.get("bezier_pts") is not None:
                 obj.update(bezier_fields(ann["bezier_pts"]))
             elif "poly" in ann and np.size(ann["poly"]) not in (8, 28):
@@ -257,6 +273,45 @@ def apply_image(img, params, target_hw):
     return ret[y0:y0 + oh, x0:x0 + ow]
 
 
+MOTION_SCALE_RANGE = (0.8, 1.2)         # vts_dataset_mapper.py:138-140: the scale range of the motion augmentation
+
+
+class MotionPlan(list):
+    """The transform numbers of a GEN_IMAGE_MOTION clip: one `resize_crop_params` tuple PER FRAME (what `GoMDatasetMapper.plan`
+    returns in place of the one tuple of a video clip)."""
+
+
+def motion_clip_params(height, width, size, train_len, rng):
+    """The per-frame transforms of a GEN_IMAGE_MOTION clip (vts_dataset_mapper.py:181-202) for a `height` x `width` still:
+    `train_len` tuples (scaled_h, scaled_w, offset_y, offset_x, img_scale), as `resize_crop_params` returns them, in a
+    `MotionPlan`.  The window of a frame is `crop_window(params, (size, size))`.
+
+    Two transforms of `EfficientDetResizeCrop(size, MOTION_SCALE_RANGE)` on the SQUARE target (size, size) are drawn from
+    `rng`, six uniforms in the order `sample_clip` makes them (scale, y, x for `st`, then for `ed`): `st` for the source,
+    `ed` for the image as `st` left it, (OH, OW) of `st`'s window (UNPINNED: Detectron2's `AugInput` is transformed in
+    place by `apply_augmentations`, so the second `get_transform` sees the first one's crop; Detectron2 is not here to
+    run).  Frame x of n: offset = st + (ed - st) * x // (n - 1) per axis in Python ints (floor division: the difference may
+    be negative), img_scale = st + (ed - st) * x / (n - 1) in float64, scaled size = int(source * img_scale)."""
+    n = int(train_len)
+    if n < 2:
+        raise ValueError("motion_clip_params: train_len %r: the interpolation divides by train_len - 1" % (train_len,))
+    target = (size, size)
+
+    def draw(h, w):
+        u_scale, u_y, u_x = rng.uniform(*MOTION_SCALE_RANGE), rng.uniform(0, 1), rng.uniform(0, 1)
+        return resize_crop_params(h, w, target, u_scale, u_y, u_x)
+
+    st = draw(height, width)
+    ed = draw(*crop_window(st, target)[2:])
+    plan = MotionPlan()
+    for x in range(n):
+        offset_y = st[2] + (ed[2] - st[2]) * x // (n - 1)
+        offset_x = st[3] + (ed[3] - st[3]) * x // (n - 1)
+        img_scale = st[4] + (ed[4] - st[4]) * x / (n - 1)
+        plan.append((int(height * img_scale), int(width * img_scale), offset_y, offset_x, img_scale))
+    return plan
+
+
 # ------------------------------------------------------------------------------------------------ sampling
 def sample_clip(video_dict, rng, train_len, target_hw, scale_range, sample_range=2.0, dynamic_scale=True,
                 gen_image_motion=True):
@@ -320,11 +375,18 @@ class GoMDatasetMapper:
                            `flip_channels` False -- the model's input stage does resize + crop + normalise in one launch;
       device_ingest=False  the reference's `image`: u8 [3,h,w] from Pillow resize and slice on the host.
 
+    `image_motion=True` (opt-in; module doc-string) with GEN_IMAGE_MOTION and a one-image video: the clip is TRAIN_LEN copies
+    of the record, frame x under its own numbers (`motion_clip_params`; DYNAMIC_SCALE does not apply), the file decoded ONCE.
+    Every frame dict carries `motion: True`; with device ingest they all hold the SAME `frame_u8` tensor and their own
+    `resize_hw` / `crop` / `flip_channels`, with host ingest their own `image`.  Annotations are transformed per frame; the
+    instance ids are those `get_video_dataset_dicts(gen_inst_id=True)` gave, equal in all frames.  For such a clip `plan`
+    returns (TRAIN_LEN times the record, a `MotionPlan`: per-frame numbers instead of one tuple) and `map_clip` maps it.
+
     `mapper(video_dict, rng)`: every draw comes from the `numpy.random.Generator` handed in.  `plan` (the draws) and
     `map_frame` (decoding and the per-frame work, free of shared state) are separate so that a loader can decode the frames
     of a planned clip in parallel."""
 
-    def __init__(self, cfg, is_train=True, device_ingest=True):
+    def __init__(self, cfg, is_train=True, device_ingest=True, image_motion=False):
         if not is_train:
             raise NotImplementedError("GoMDatasetMapper: only the training mapper is built (inference reads frames in eval.py)")
         D = data_cfg(cfg)
@@ -349,9 +411,24 @@ class GoMDatasetMapper:
         self.dynamic_scale = bool(I.VIDEO.DYNAMIC_SCALE)
         self.gen_image_motion = bool(I.VIDEO.GEN_IMAGE_MOTION)
         self.with_resr = bool(cfg.MODEL.ROI_HEADS.WITH_RESR)
+        self.image_motion = bool(image_motion)
+        self.motion_size = self.target_size[0]                   # :139-140: `augmentations[0].target_size[0]`, a square target
+        if self.image_motion and self.gen_image_motion and self.train_len < 2:
+            raise ValueError("INPUT.VIDEO.TRAIN_LEN %d: GEN_IMAGE_MOTION interpolates over TRAIN_LEN - 1 steps and needs at "
+                             "least 2 frames" % self.train_len)
 
     def plan(self, video_dict, rng):
-        """-> (frame records of the clip, transform numbers).  No file is opened: sizes are the json's."""
+        """-> (frame records of the clip, transform numbers).  No file is opened: sizes are the json's.  For a one-image
+        video under `image_motion`: (TRAIN_LEN times the record, `MotionPlan` of per-frame numbers)."""
+        if self.image_motion and self.gen_image_motion and len(video_dict["images"]) == 1:
+            rec = video_dict["images"][0]
+            plan = motion_clip_params(rec["height"], rec["width"], self.motion_size, self.train_len, rng)
+            for x, p in enumerate(plan):
+                y0, x0, oh, ow = crop_window(p, (self.motion_size, self.motion_size))
+                if min(oh, ow) <= 0 or y0 < 0 or x0 < 0 or y0 + oh > p[0] or x0 + ow > p[1]:
+                    raise ValueError("video %r: frame %d of its motion clip has the window (y0=%d, x0=%d, %dx%d) in a %dx%d "
+                                     "resized image" % (video_dict.get("video_id"), x, y0, x0, oh, ow, p[0], p[1]))
+            return [rec] * self.train_len, plan
         inds, params = sample_clip(video_dict, rng, self.train_len, self.target_size, self.scale, self.sample_range,
                                    self.dynamic_scale, self.gen_image_motion)
         records = [video_dict["images"][x] for x in inds]
@@ -378,21 +455,38 @@ class GoMDatasetMapper:
                              % (obj.get("annotation_id"), record["image_id"], record["file_name"]))
         return out
 
-    def map_frame(self, record, params):
-        import torch
+    def _decode(self, record):
         image = read_image(record["file_name"], self.image_format)
         if (image.shape[0], image.shape[1]) != (record["height"], record["width"]):     # detection_utils.check_image_size
             raise ValueError("Mismatched image shape for image %s, got %s, expect %s. Please check the width/height in your "
                              "annotation." % (record["file_name"], (image.shape[0], image.shape[1]),
                                               (record["height"], record["width"])))
-        y0, x0, oh, ow = crop_window(params, self.target_size)
+        return image
+
+    def map_frame(self, record, params):
+        import torch
+        image = self._decode(record)
+        return self._frame(record, image, torch.from_numpy(image) if self.device_ingest else None, params, self.target_size)
+
+    def map_clip(self, records, params):
+        """The frames of a planned clip.  A `MotionPlan`: one decode, frame x under params[x] on the square motion target."""
+        if not isinstance(params, MotionPlan):
+            return [self.map_frame(r, params) for r in records]
+        import torch
+        image = self._decode(records[0])
+        shared = torch.from_numpy(image) if self.device_ingest else None
+        target = (self.motion_size, self.motion_size)
+        return [dict(self._frame(r, image, shared, p, target), motion=True) for r, p in zip(records, params)]
+
+    def _frame(self, record, image, frame_u8, params, target_size):
+        import torch
+        y0, x0, oh, ow = crop_window(params, target_size)
         image_shape = (oh, ow)
         out = {k: record[k] for k in ("file_name", "height", "width", "image_id", "video_id")}
         if self.device_ingest:
-            out.update(frame_u8=torch.from_numpy(image), resize_hw=(params[0], params[1]), crop=(y0, x0, oh, ow),
-                       flip_channels=False)
+            out.update(frame_u8=frame_u8, resize_hw=(params[0], params[1]), crop=(y0, x0, oh, ow), flip_channels=False)
         else:
-            out["image"] = torch.as_tensor(np.ascontiguousarray(apply_image(image, params, self.target_size).transpose(2, 0, 1)))
+            out["image"] = torch.as_tensor(np.ascontiguousarray(apply_image(image, params, target_size).transpose(2, 0, 1)))
         annos = [self._annotation(obj, params, image_shape, record) for obj in record.get("annotations", [])
                  if obj.get("iscrowd", 0) == 0]
         boxes = torch.as_tensor(np.array([a["bbox"] for a in annos], dtype="float64").reshape(-1, 4), dtype=torch.float32)
@@ -411,7 +505,7 @@ class GoMDatasetMapper:
 
     def __call__(self, video_dict, rng=None):
         records, params = self.plan(video_dict, np.random.default_rng() if rng is None else rng)
-        return [self.map_frame(r, params) for r in records]
+        return self.map_clip(records, params)
 
 
 # -------------------------------------------------------------------------------------------------- loader
@@ -467,7 +561,10 @@ class VTSTrainLoader:
 
     def _submit(self):
         _, records, params = self.plan(self.iteration + len(self._pending))
-        self._pending.append([self._pool.submit(self.mapper.map_frame, r, params) for r in records])
+        if isinstance(params, MotionPlan):                       # one decode serves the clip: one task, a list of frames
+            self._pending.append((True, [self._pool.submit(self.mapper.map_clip, records, params)]))
+        else:
+            self._pending.append((False, [self._pool.submit(self.mapper.map_frame, r, params) for r in records]))
 
     def __iter__(self):
         return self
@@ -477,13 +574,14 @@ class VTSTrainLoader:
             self._pool = ThreadPoolExecutor(max_workers=self.num_workers)
         while len(self._pending) < LOOKAHEAD_CLIPS:
             self._submit()
-        clip = [f.result() for f in self._pending.popleft()]
+        whole, futures = self._pending.popleft()
+        clip = futures[0].result() if whole else [f.result() for f in futures]
         self.iteration += 1
         return clip
 
     def close(self):
         if self._pool is not None:
-            for futures in self._pending:
+            for _, futures in self._pending:
                 for f in futures:
                     f.cancel()
             self._pending.clear()
@@ -506,7 +604,8 @@ def build_vts_train_loader(cfg, mapper, seed, rank=0, world_size=1, start_iter=0
     of decode threads, see the clips the first run saw, and ranks never share a position.
 
     A video the sampler would refuse (`check_videos`) is refused here, when the loader is built, not at the iteration that draws
-    it.  Frames are decoded ahead, at most LOOKAHEAD_CLIPS clips, by DATALOADER.NUM_WORKERS threads (default 4, at most 16).
+    it; a mapper built with `image_motion` takes one-image videos (module doc-string), so videos and stills mix.
+    Frames are decoded ahead, at most LOOKAHEAD_CLIPS clips, by DATALOADER.NUM_WORKERS threads (default 4, at most 16).
     `dataset_dicts`: the records of `load_video_json`; default: the one name in DATASETS.TRAIN through the split table."""
     D = data_cfg(cfg)
     if D.DATALOADER.SAMPLER_TRAIN != "TrainingSampler":
@@ -521,5 +620,5 @@ def build_vts_train_loader(cfg, mapper, seed, rank=0, world_size=1, start_iter=0
     batch_size = solver_cfg(cfg).IMS_PER_BATCH // world_size
     assert batch_size == 1, "SOLVER.IMS_PER_BATCH // world size must be 1 (one clip per rank), got %d" % batch_size
     videos = get_video_dataset_dicts([dataset_dicts], gen_inst_id=D.INPUT.VIDEO.GEN_IMAGE_MOTION)
-    check_videos(videos, mapper.gen_image_motion)
+    check_videos(videos, mapper.gen_image_motion and not getattr(mapper, "image_motion", False))
     return VTSTrainLoader(videos, mapper, seed, rank, world_size, start_iter, D.DATALOADER.NUM_WORKERS)

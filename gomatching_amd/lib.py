@@ -132,6 +132,8 @@ SIGNATURES = {
     "gom_resize_crop_bilinear_u8_hwc3": (I, [P, I, I, I, P, P, I, P, P, I, P, I, I, I, I, I, I, I, P]),
     "gom_ingest_crop_u8_hwc3_to_nhwc4": (I, [P, I, I, I, P, P, I, P, P, I, ctypes.POINTER(c_float),
                                              ctypes.POINTER(c_float), P, I, I, I, I, I, I, I, P]),
+    "gom_ingest_motion_u8_hwc3_to_nhwc4": (I, [P, I, I, P, L, P, I, ctypes.POINTER(c_float), ctypes.POINTER(c_float), P, I, I, I,
+                                               P]),
     "gom_preprocess_nchw_to_nhwc4": (I, [P, ctypes.POINTER(c_float), ctypes.POINTER(c_float), P, I, I, I, P]),
     "gom_result_rows_i32": (I, [P, P, P, I, I, P, I, P]),
     "gom_quad_bezier_i32": (I, [P, P, I, P, P]),

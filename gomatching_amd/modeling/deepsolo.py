@@ -178,6 +178,7 @@ class DeepSolo:
         self.bernstein = torch.tensor([[tt ** k * (1 - tt) ** (3 - k) * comb(3, k) for k in range(4)]
                                        for tt in ts]).to(device)
         self._geom = {}
+        self._geom_transient = False        # True: `geometry` builds without keeping (training on motion clips: new sizes every step)
         self._invalid_logit = None
 
     # --------------------------------------------------------------------------------- tables
@@ -255,7 +256,8 @@ class DeepSolo:
             "valid": ops.proposal_valid(ss_d, lsi_d, S, vs_d),
             "vshapes": vs_d, "vr": vr_d, "vr0": None if vr_d is None else (float(vr[0, 0]), float(vr[0, 1])),
         }
-        self._geom[key] = geo
+        if not self._geom_transient:        # inference's cache stays as it is: a captured graph may hold pointers into it
+            self._geom[key] = geo
         return geo
 
     def invalid_logit(self):

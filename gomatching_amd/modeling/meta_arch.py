@@ -174,8 +174,14 @@ class GoMatching:
         normalise it: ("u8", net hw, flip) for the device ingest of SURVEY §8-f2 -- `frame_u8` (u8 [H0,W0,3] as read
         from disk) + `resize_hw` (+ `flip_channels`) --, ("u8crop", crop hw, flip, resized hw, crop) when a `crop` =
         (y0, x0, OH, OW) comes with them (the training augmentation), or ("f32", hw, None) for the reference's `image`
-        (f32 [3,H,W], already resized).  gom_lstmatcher.py:164-170 for same-size frames (no padding needed)."""
+        (f32 [3,H,W], already resized).  gom_lstmatcher.py:164-170 for same-size frames (no padding needed).
+        A step whose frames ALL carry `motion` (a GEN_IMAGE_MOTION clip of `data.GoMDatasetMapper`) is the fourth kind:
+        `_raw_motion`."""
         first = batched_inputs[0]
+        if all(x.get("motion") for x in batched_inputs):
+            if out is not None:
+                raise ValueError("motion frames (GEN_IMAGE_MOTION clips) are training input: they cannot fill a static buffer")
+            return self._raw_motion(batched_inputs)
         if "frame_u8" in first and first.get("crop") is not None:
             # the training augmentation (data.GoMDatasetMapper, device_ingest): resize to `resize_hw`, keep the window
             # `crop` = (y0, x0, OH, OW).  kind[1] is the CROP's size, the reference's `image_shape` after apply_image.
@@ -214,6 +220,51 @@ class GoMatching:
             for i, f in enumerate(frames):
                 out[i].copy_(f, non_blocking=True)
         return out, kind
+
+    def _raw_motion(self, batched_inputs):
+        """The frames of a GEN_IMAGE_MOTION clip: T transforms of ONE image, padded into one batch as
+        `ImageList.from_tensors` pads them (gom_lstmatcher.py:168-169: zeros after normalising, top-left aligned, no size
+        divisibility -- UNPINNED).  Device ingest -> (the image u8 [1,H0,W0,3], uploaded ONCE, ("u8motion", padded hw, flip,
+        per frame (resize hw, crop), per frame (OH, OW))); host ingest -> (the frames' own `image`s on the device, f32
+        [1,3,OH,OW] each, ("f32motion", padded hw, None, None, per frame (OH, OW)))."""
+        first = batched_inputs[0]
+        if "frame_u8" in first:
+            src, flip = first["frame_u8"], bool(first.get("flip_channels", False))
+            descs = []
+            for x in batched_inputs:
+                f = x.get("frame_u8")
+                if f is None or x.get("crop") is None or x.get("resize_hw") is None:
+                    raise ValueError("motion frames of one step must all carry frame_u8, resize_hw and crop")
+                same = f is src or (f.device == src.device and f.data_ptr() == src.data_ptr() and tuple(f.shape) == tuple(src.shape)
+                                    and f.stride() == src.stride() and f.dtype == src.dtype)
+                if not same or bool(x.get("flip_channels", False)) != flip:
+                    raise ValueError("motion frames of one step must share ONE frame_u8 image and one channel order")
+                descs.append((tuple(int(v) for v in x["resize_hw"]), tuple(int(v) for v in x["crop"])))
+            if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3:
+                raise ValueError("frame_u8 must be a uint8 [H,W,3] tensor")
+            sizes = [d[1][2:] for d in descs]
+            if src.device == self.device:
+                raw = src.contiguous().unsqueeze(0)
+            else:
+                raw = torch.empty((1,) + tuple(src.shape), dtype=torch.uint8, device=self.device)
+                raw.copy_(self._upload([src], torch.uint8))          # the image goes up once, not once per frame
+                self._stage_release()
+            kind = ("u8motion", (max(s[0] for s in sizes), max(s[1] for s in sizes)), flip, descs, sizes)
+            return raw, kind
+        frames = []
+        for x in batched_inputs:
+            if "image" not in x or x["image"].dim() != 3 or x["image"].shape[0] != 3:
+                raise ValueError("motion frames of one step must all carry frame_u8 or all carry an `image` [3,h,w]")
+            frames.append(x["image"])
+        sizes = [tuple(int(v) for v in im.shape[-2:]) for im in frames]
+        raw = [im.to(self.device).to(_f32).unsqueeze(0).contiguous() for im in frames]
+        return raw, ("f32motion", (max(s[0] for s in sizes), max(s[1] for s in sizes)), None, None, sizes)
+
+    @staticmethod
+    def _refuse_motion(batched_inputs):
+        if any(x.get("motion") for x in batched_inputs):
+            raise ValueError("motion frames (GEN_IMAGE_MOTION clips, padded mixed-size batches) are training input: "
+                             "inference takes frames of one size")
 
     def _upload(self, frames, dtype):
         """Host frames (the reference hands `image` over as CPU tensors and moves them inside the timed window,
@@ -259,10 +310,19 @@ class GoMatching:
             return ops.ingest(raw, kind[1][0], kind[1][1], self.pixel_mean, self.pixel_std, kind[2])
         if kind[0] == "u8crop":
             return ops.ingest_crop(raw, kind[3], kind[4], self.pixel_mean, self.pixel_std, kind[2])
+        if kind[0] == "u8motion":
+            return ops.ingest_motion(raw, kind[3], self.pixel_mean, self.pixel_std, kind[2])
+        if kind[0] == "f32motion":
+            # the host path of a motion clip: every frame normalised on its own, into the top-left of a zero-filled batch
+            x = torch.zeros((len(raw),) + tuple(kind[1]) + (4,), dtype=_f32, device=self.device)
+            for t, (im, (oh, ow)) in enumerate(zip(raw, kind[4])):
+                x[t, :oh, :ow].copy_(ops.preprocess(im, self.pixel_mean, self.pixel_std)[0])
+            return x
         return ops.preprocess(raw, self.pixel_mean, self.pixel_std)
 
     def preprocess_image(self, batched_inputs):
-        """Normalised channels-last network input of a step + its (H, W)."""
+        """Normalised channels-last network input of a step + its (H, W); for a motion clip the PADDED (H, W) -- the frames'
+        own sizes are kind[4] of `_raw_input`."""
         raw, kind = self._raw_input(batched_inputs)
         return self._normalise(raw, kind), kind[1]
 
@@ -328,6 +388,7 @@ class GoMatching:
         first call runs eagerly (warms every per-resolution cache), the second captures, later ones replay.  Outputs
         are copied out of the graph's static buffers, so a replay never overwrites what an unfinished step reads.
         Returns None when this step is not (yet) graphed."""
+        self._refuse_motion(batched_inputs)
         B = len(batched_inputs)
         first = batched_inputs[0]
         src = first["frame_u8"] if "frame_u8" in first else first["image"]
@@ -381,6 +442,7 @@ class GoMatching:
         """Asynchronous half of `inference`: queues every detector kernel of the step on the current stream, ends
         with a non-blocking D2H copy of the nq-padded detection summary and an event.  No host sync, no tracker
         state touched -- a caller may queue the next step's detection before finishing this one."""
+        self._refuse_motion(batched_inputs)
         assert not self.training
         lane = getattr(self, "_det_stream", None)
         if lane is not None and torch.cuda.current_stream() != lane:     # CU-partitioned step: the detector's own lane

@@ -1412,6 +1412,69 @@ def ingest_crop(frames, scaled_hw, window, mean, std, flip):
     return out
 
 
+INGEST_MOTION_MAX_FRAMES = 16       # GOM_INGEST_MOTION_MAX_FRAMES (include/gomatching_hip.h)
+
+
+def motion_tables(H, W, frames):
+    """Host half of `ingest_motion`: the coefficient tables of every frame of a motion clip in ONE int32 buffer, and the
+    descriptors that point into it.  frames: per frame ((SH, SW), (y0, x0, OH, OW)).  -> (tables int32 [words] (CPU),
+    descriptors int32 [T, 12] (CPU; layout in include/gomatching_hip.h), (PH, PW)).  Frames that share a resized size along
+    an axis share that axis' table."""
+    if not 1 <= len(frames) <= INGEST_MOTION_MAX_FRAMES:
+        raise ValueError("a motion clip has 1..%d frames, got %d" % (INGEST_MOTION_MAX_FRAMES, len(frames)))
+    L = _L()
+    parts, where, words = [], {}, 0
+
+    def table(in_size, out_size):
+        nonlocal words
+        hit = where.get((in_size, out_size))
+        if hit is None:
+            ks = L.gom_resample_ksize_bilinear(in_size, out_size)
+            if ks <= 0:
+                raise ValueError("bad resample sizes %d -> %d" % (in_size, out_size))
+            bounds = torch.empty((out_size, 2), dtype=torch.int32)
+            kk = torch.empty((out_size, ks), dtype=torch.int32)
+            check(L.gom_resample_coeffs_bilinear(in_size, out_size, _p(bounds), _p(kk), ks), "gom_resample_coeffs")
+            hit = (ks, words, words + bounds.numel())
+            words += bounds.numel() + kk.numel()
+            parts.extend((bounds.view(-1), kk.view(-1)))
+            where[(in_size, out_size)] = hit
+        return hit
+
+    desc = []
+    for scaled_hw, window in frames:
+        SH, SW, y0, x0, OH, OW = _chk_window(scaled_hw, window)
+        xks, xb, xk = table(W, SW)
+        yks, yb, yk = table(H, SH)
+        desc.append([SH, SW, y0, x0, OH, OW, xks, yks, xb, xk, yb, yk])
+    return torch.cat(parts), torch.tensor(desc, dtype=torch.int32), (max(d[4] for d in desc), max(d[5] for d in desc))
+
+
+def ingest_motion(src, frames, mean, std, flip, out=None):
+    """ONE u8 image [H,W,3] (or [1,H,W,3]) resident on the GPU -> the normalised, zero-padded batch [T,PH,PW,4] f32 of a
+    GEN_IMAGE_MOTION clip in one launch: frame t is the window frames[t] = ((SH, SW), (y0, x0, OH, OW)) of its own Pillow
+    bilinear resize, `ingest_crop`'s bits, at the top-left; PH, PW = the largest OH, OW; everything else is written as 0.0
+    (`ImageList.from_tensors` of the normalised frames, gom_lstmatcher.py:168-169).  The tables of all frames go up in one
+    transfer.  `out`: a contiguous [T,PH,PW,4] f32 tensor to fill (it needs no clearing)."""
+    if src.dim() == 4 and src.shape[0] == 1:
+        src = src[0]
+    if src.dtype != torch.uint8 or not src.is_cuda or not src.is_contiguous() or src.dim() != 3 or src.shape[2] != 3:
+        raise ValueError("src must be a contiguous CUDA uint8 [H,W,3] tensor")
+    H, W, _ = src.shape
+    tables, desc, (PH, PW) = motion_tables(H, W, frames)
+    T = desc.shape[0]
+    if out is None:
+        out = torch.empty((T, PH, PW, 4), dtype=_f32, device=src.device)
+    elif out.dtype != _f32 or out.device != src.device or not out.is_contiguous() or tuple(out.shape) != (T, PH, PW, 4):
+        raise ValueError("out must be a contiguous float32 [%d,%d,%d,4] tensor on src's device" % (T, PH, PW))
+    tab = tables.to(src.device)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    check(_L().gom_ingest_motion_u8_hwc3_to_nhwc4(_p(src), H, W, _p(tab), tab.numel(), _p(desc), T, m, s, _p(out), PH, PW,
+                                                  int(flip), _stream()), "gom_ingest_motion_u8_hwc3_to_nhwc4")
+    return out
+
+
 RESULT_ROWS_WORDS = 234             # GOM_RESULT_ROWS_WORDS (include/gomatching_hip.h)
 
 

@@ -2,7 +2,7 @@
 the reference's train_net.py:50-211.
 
     python -m gomatching_amd.train (--config-file F | --builtin NAME) [--json FILE --image-root DIR] [--resume]
-           [--host-ingest] [--seed N] --opts MODEL.WEIGHTS W OUTPUT_DIR out ...
+           [--host-ingest] [--image-motion] [--seed N] --opts MODEL.WEIGHTS W OUTPUT_DIR out ...
       -> out/model_*.pth, out/model_final.pth, out/last_checkpoint, out/metrics.json
 
 What it keeps of the reference: `setup` (config file, then --opts; INFERENCE_TH_TEST = INFERENCE_TH_TRAIN, which `Trainer`
@@ -20,6 +20,10 @@ Deliberate differences:
     uninterrupted run would have seen (the reference's workers reseed from the clock);
   * frames are resized, cropped and normalised on the GPU, one launch per clip (`--host-ingest`: with Pillow on the host, the
     same bits);
+  * still images (records without a video id) are refused unless `--image-motion` is given: the flag builds the mapper with
+    `image_motion=True`, which turns each still into a GEN_IMAGE_MOTION clip (`data.motion_clip_params`; one image upload and
+    one ingest launch per clip, the detector per group of equally sized frames).  Opt-in because the refusal is what existing
+    callers rely on; `--host-ingest` combines with it;
   * no TensorBoard writer, no `--num-gpus` / launcher: under an initialised `torch.distributed` the rank and world size go
     to the loader and only rank 0 writes metrics, but starting the ranks is the caller's business;
   * metrics are the last iteration's values, not medians over a window; the reference's silence during the first 5
@@ -48,6 +52,9 @@ def get_parser():
     p.add_argument("--resume", action="store_true", help="continue from OUTPUT_DIR/last_checkpoint")
     p.add_argument("--host-ingest", action="store_true",
                    help="resize and crop frames with Pillow on the host (default: on the GPU, bit-exact with the host path)")
+    p.add_argument("--image-motion", action="store_true",
+                   help="train from still images too: a one-image video becomes a GEN_IMAGE_MOTION clip of TRAIN_LEN frames "
+                        "(default: such a video is refused)")
     p.add_argument("--seed", type=int, default=None, metavar="N", help="seed of the data stream (default: cfg.SEED, else drawn)")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER,
                    help="modify config options using the command-line 'KEY VALUE' pairs")
@@ -109,11 +116,11 @@ def main(argv=None):
     if not cfg.MODEL.WEIGHTS or not os.path.isfile(cfg.MODEL.WEIGHTS):
         return _error("MODEL.WEIGHTS %r is not a file (set it with --opts MODEL.WEIGHTS PATH)" % (cfg.MODEL.WEIGHTS,))
     try:
-        mapper = _data.GoMDatasetMapper(cfg, True, device_ingest=not args.host_ingest)
+        mapper = _data.GoMDatasetMapper(cfg, True, device_ingest=not args.host_ingest, image_motion=args.image_motion)
         if _data.data_cfg(cfg).DATALOADER.SAMPLER_TRAIN != "TrainingSampler":
             raise NotImplementedError("DATALOADER.SAMPLER_TRAIN %r: only TrainingSampler is built"
                                       % (_data.data_cfg(cfg).DATALOADER.SAMPLER_TRAIN,))
-    except NotImplementedError as e:
+    except (NotImplementedError, ValueError) as e:
         return _error(e.args[0])
     output_dir = cfg.get("OUTPUT_DIR", "./output")
     if args.resume and not os.path.isfile(os.path.join(output_dir, "last_checkpoint")):
@@ -121,7 +128,7 @@ def main(argv=None):
 
     dataset_dicts = _data.load_video_json(json_file, image_root)
     try:                                                         # what the sampler would refuse mid-run is refused here
-        _data.check_videos(_data.get_video_dataset_dicts([dataset_dicts]), mapper.gen_image_motion)
+        _data.check_videos(_data.get_video_dataset_dicts([dataset_dicts]), mapper.gen_image_motion and not mapper.image_motion)
     except (NotImplementedError, ValueError) as e:
         return _error(e.args[0])
 

@@ -600,14 +600,97 @@ def allreduce_gradients(parameters, group=None):
     return flat.numel()
 
 
-def forward_losses(model, batched_inputs):
-    """`GoMatching.forward` in training (gom_lstmatcher.py:213-266) for the META_ARCH wrapper (`compat/d2_register.py`): the
-    frozen detector runs on the HIP inference kernels without a tape; the losses of the trainable head carry autograd
-    history onto `model.roi_heads`' parameters.  batched_inputs: the reference's list of {"image" [3,H,W], "instances": ground
-    truth with gt_boxes / gt_instance_ids / (for loss_res) normalised ctrl points under `polyline` or `ctrl_points`}."""
+def detect_for_training(impl, params, batched_inputs, taps=None):
+    """The no-grad detector part of `forward_losses`: the frozen detector on the HIP inference kernels, the rescoring product,
+    and the training proposals (no NMS, kept by the score threshold).  -> {"frames": per frame {"image_size",
+    "proposal_boxes", "objectness_logits", "query_features", "keep_rows"}, "sizes": per frame (h, w), "padded_hw",
+    "query_features" [B,nq,P,C], "pred_ctrl_points" [B,nq,P,2], "groups": [(hw, frame indices)]}, all in FRAME order.
+
+    Frames of one size (every video clip) are one group: one backbone pass, one `detection_transformer.forward`, today's
+    launches.  The frames of a motion clip (`GoMatching._raw_motion`) are padded to one size but differ in their own: they are
+    grouped by (OH, OW) in order of first appearance, and each group runs the backbone on its (still padded) frames and the
+    transformer with `image_hw` = the group's size, the rescoring product, `argmax_rows` and `detect_post` with that size.
+    `keep_idx` of a group indexes the group's flattened query axis; results are scattered back to frame order.  Geometry
+    tables built for a motion step are not kept (`DeepSolo._geom_transient`): every clip brings new sizes.
+    `taps`: a list that receives, per group, the transformer's tap dict (`DeepSolo.forward(taps=...)`) -- a test's window."""
     torch = _torch()
     from . import ops
-    from .predictor import new_time_cost
+    cfg = impl.cfg
+    T = cfg.MODEL.TRANSFORMER
+    B, nq, P = len(batched_inputs), T.NUM_QUERIES, T.NUM_POINTS
+    tr = impl.detection_transformer
+    with torch.no_grad():
+        raw, kind = impl._raw_input(batched_inputs)
+        x = impl._normalise(raw, kind)
+        motion = kind[0] in ("u8motion", "f32motion")
+        sizes = [tuple(int(v) for v in s) for s in kind[4]] if motion else [tuple(kind[1])] * B
+        groups = {}
+        for t, hw in enumerate(sizes):
+            groups.setdefault(hw, []).append(t)
+        groups = list(groups.items())
+        parts = []
+        tr._geom_transient = motion
+        try:
+            for hw, members in groups:
+                Bg = len(members)
+                xg = x if Bg == B else x.index_select(0, torch.tensor(members, dtype=torch.int64, device=x.device))
+                feats = impl.backbone.forward(xg)
+                feats = [feats[k] for k in impl.feature_names]
+                kw = {}
+                if motion:
+                    kw["image_hw"] = hw
+                if taps is not None:
+                    taps.append({})
+                    kw["taps"] = taps[-1]
+                out = tr.forward(feats, **kw)
+                re = None
+                if impl.with_rescore:
+                    re = ops.gemm(out["query_features"], params["roi_heads.rescoring_head.weight"].detach(),
+                                  bias=params["roi_heads.rescoring_head.bias"].detach())
+                recs = ops.argmax_rows(out["pred_text_logits"])
+                # training proposals: no NMS (gom_lstmatcher.py:231-258 builds them straight from `detection`), kept by the score threshold
+                det = ops.detect_post(out["pred_logits"], re, out["pred_ctrl_points"], out["pred_bd_points"], recs, Bg, nq, P,
+                                      hw[0], hw[1], impl.test_score_threshold, 2.0, -1.0)
+                parts.append((out, det))
+        finally:
+            tr._geom_transient = False
+        torch.cuda.current_stream().synchronize()
+        if ops.GEMM_MODE == "f16x3":
+            # the range flag of the f16x3 kernels (`detect_launch` reads and clears it per inference step): an activation beyond
+            # fp16's range during a TRAINING forward must not feed the losses silently, nor stay set for the next inference step
+            ops.check_range_flag(x.device)
+        frames = [None] * B
+        for (hw, members), (out, det) in zip(groups, parts):
+            Bg = len(members)
+            qf_g = out["query_features"].view(Bg * nq, P, -1)
+            counts = det["count"].cpu().numpy()
+            keep = det["keep_idx"].cpu().numpy()
+            for j, t in enumerate(members):
+                n = int(counts[j])
+                rows = torch.from_numpy(keep[j, :n].astype(np.int64)).to(qf_g.device)   # rows of the GROUP's flattened [Bg*nq] query axis
+                frames[t] = {"image_size": hw, "proposal_boxes": det["boxes"][j, :n], "objectness_logits": det["scores"][j, :n],
+                             "query_features": qf_g.index_select(0, rows), "keep_rows": rows - j * nq}
+        if len(groups) == 1:
+            out = parts[0][0]
+            qf = out["query_features"].view(B, nq, P, -1)
+            ctrl = out["pred_ctrl_points"].view(B, nq, P, 2)
+        else:
+            order = torch.tensor([t for _, members in groups for t in members], dtype=torch.int64, device=x.device)
+            qf = torch.empty((B, nq, P, parts[0][0]["query_features"].shape[-1]), dtype=torch.float32, device=x.device)
+            ctrl = torch.empty((B, nq, P, 2), dtype=torch.float32, device=x.device)
+            qf.index_copy_(0, order, torch.cat([o["query_features"].view(-1, nq, P, qf.shape[-1]) for o, _ in parts]))
+            ctrl.index_copy_(0, order, torch.cat([o["pred_ctrl_points"].view(-1, nq, P, 2) for o, _ in parts]))
+    return {"frames": frames, "sizes": sizes, "padded_hw": tuple(kind[1]), "query_features": qf, "pred_ctrl_points": ctrl,
+            "groups": groups}
+
+
+def forward_losses(model, batched_inputs):
+    """`GoMatching.forward` in training (gom_lstmatcher.py:213-266) for the META_ARCH wrapper (`compat/d2_register.py`): the
+    frozen detector runs on the HIP inference kernels without a tape (`detect_for_training`); the losses of the trainable head
+    carry autograd history onto `model.roi_heads`' parameters.  batched_inputs: the reference's list of {"image" [3,H,W],
+    "instances": ground truth with gt_boxes / gt_instance_ids / (for loss_res) normalised ctrl points under `polyline` or
+    `ctrl_points`}; in a motion clip every frame keeps its own `image_size` (the reference's per-image `image_sizes`)."""
+    torch = _torch()
     if hasattr(model, "impl"):                                   # the META_ARCH wrapper: live nn.Parameters
         impl = model.impl(for_training=True)
         params = {k: p for k, p in model.named_parameters() if k.startswith("roi_heads.")}
@@ -615,50 +698,26 @@ def forward_losses(model, batched_inputs):
         impl = model
         params = model.trainable_parameters()
     cfg = model.cfg
-    T = cfg.MODEL.TRANSFORMER
-    B, nq, P = len(batched_inputs), T.NUM_QUERIES, T.NUM_POINTS
-    with torch.no_grad():
-        tc = new_time_cost()
-        raw, kind = impl._raw_input(batched_inputs)
-        x = impl._normalise(raw, kind)
-        feats = impl.backbone.forward(x)
-        out = impl.detection_transformer.forward([feats[k] for k in impl.feature_names])
-        qf = out["query_features"].view(B, nq, P, -1)
-        re = None
-        if impl.with_rescore:
-            re = ops.gemm(out["query_features"], params["roi_heads.rescoring_head.weight"].detach(),
-                          bias=params["roi_heads.rescoring_head.bias"].detach())
-        recs = ops.argmax_rows(out["pred_text_logits"])
-        # training proposals: no NMS (gom_lstmatcher.py:231-258 builds them straight from `detection`), kept by the score threshold
-        det = ops.detect_post(out["pred_logits"], re, out["pred_ctrl_points"], out["pred_bd_points"], recs, B, nq, P,
-                              kind[1][0], kind[1][1], impl.test_score_threshold, 2.0, -1.0)
-        torch.cuda.current_stream().synchronize()
-        if ops.GEMM_MODE == "f16x3":
-            # the range flag of the f16x3 kernels (`detect_launch` reads and clears it per inference step): an activation beyond
-            # fp16's range during a TRAINING forward must not feed the losses silently, nor stay set for the next inference step
-            ops.check_range_flag(qf.device)
-    counts = det["count"].cpu().numpy()
-    keep = det["keep_idx"].cpu().numpy()
+    P = cfg.MODEL.TRANSFORMER.NUM_POINTS
+    det = detect_for_training(impl, params, batched_inputs)
     frames, targets, res_targets = [], [], []
     for b, inp in enumerate(batched_inputs):
-        n = int(counts[b])
-        rows = torch.from_numpy(keep[b, :n].astype(np.int64)).to(qf.device)      # rows of the flattened [B*nq] query axis
-        frames.append({"image_size": kind[1], "proposal_boxes": det["boxes"][b, :n], "objectness_logits": det["scores"][b, :n],
-                       "query_features": qf.view(B * nq, P, -1).index_select(0, rows)})
+        hw = det["sizes"][b]
+        frames.append({k: v for k, v in det["frames"][b].items() if k != "keep_rows"})
         gt = inp["instances"]
         get = (lambda k: gt.get(k)) if hasattr(gt, "get") else (lambda k: gt[k])
         boxes = get("gt_boxes")
         boxes = boxes.tensor if hasattr(boxes, "tensor") else boxes
-        targets.append({"image_size": kind[1], "gt_boxes": boxes, "gt_instance_ids": get("gt_instance_ids")})
+        targets.append({"image_size": hw, "gt_boxes": boxes, "gt_instance_ids": get("gt_instance_ids")})
         if impl.with_rescore:
             pts = get("ctrl_points") if (hasattr(gt, "has") and gt.has("ctrl_points")) or (isinstance(gt, dict) and "ctrl_points" in gt) \
                 else get("polyline")
-            pts = torch.as_tensor(pts).float().reshape(-1, P, 2) / torch.tensor([kind[1][1], kind[1][0]], dtype=torch.float32)
+            pts = torch.as_tensor(pts).float().reshape(-1, P, 2) / torch.tensor([hw[1], hw[0]], dtype=torch.float32)
             res_targets.append({"labels": np.zeros((pts.shape[0],), np.int64), "ctrl_points": pts})
     dropout = _active(getattr(model, "dropout_state", None))    # Trainer / the META_ARCH wrapper attach it when DROPOUT > 0
     if dropout is not None:
         dropout.begin_forward(dropout.iteration)                # sites count from 0 in every forward
     losses = asso_losses(params, cfg, frames, targets, dropout=dropout)
     if impl.with_rescore:
-        losses.update(loss_res(params, cfg, qf, out["pred_ctrl_points"].view(B, nq, P, 2), res_targets))
+        losses.update(loss_res(params, cfg, det["query_features"], det["pred_ctrl_points"], res_targets))
     return losses

@@ -477,6 +477,21 @@ int gom_ingest_crop_u8_hwc3_to_nhwc4(const uint8_t* src, int B, int H, int W, co
                                      int xksize, const int* ybounds, const int* ykk, int yksize, const float* mean3,
                                      const float* std3, float* dst, int SH, int SW, int y0, int x0, int OH, int OW,
                                      int flip_channels, void* stream);
+/* A GEN_IMAGE_MOTION clip (vts_dataset_mapper.py:181-202 + `ImageList.from_tensors`, gom_lstmatcher.py:168-169): ONE source
+ * image, T frames, one launch.  Frame t is the OH_t x OW_t window at (y0_t, x0_t) of its own SH_t x SW_t resize, normalised as
+ * gom_ingest_crop_u8_hwc3_to_nhwc4 does (the same bits), at the top-left of a PH x PW frame; every other element of the frame,
+ * the 4th channel included, is written as 0.0f by the kernel: dst needs no memset and may hold anything before the call.
+ * frames [host] int32 [T][GOM_INGEST_MOTION_DESC_WORDS] = (SH, SW, y0, x0, OH, OW, xksize, yksize, xbounds, xkk, ybounds, ykk),
+ * the last four being offsets in int32 words into `tables` [device, table_words words], which holds the tables of
+ * gom_resample_coeffs_bilinear for W -> SW_t and H -> SH_t (frames may share a table).  GOM_ERR_INVALID_ARG, before any
+ * HIP call: a null pointer, T outside 1..GOM_INGEST_MOTION_MAX_FRAMES, a window that leaves its resized image or PH x PW, a
+ * tap count that is not gom_resample_ksize_bilinear's, a table that does not lie inside `tables`.
+ * src [H,W,3] u8 -> dst [T,PH,PW,4] f32. */
+#define GOM_INGEST_MOTION_MAX_FRAMES 16
+#define GOM_INGEST_MOTION_DESC_WORDS 12
+int gom_ingest_motion_u8_hwc3_to_nhwc4(const uint8_t* src, int H, int W, const int* tables, long table_words,
+                                       const int* frames, int T, const float* mean3, const float* std3, float* dst, int PH,
+                                       int PW, int flip_channels, void* stream);
 /* ---- f1: result rows (eval.py:346-363, the per-instance conversion in front of the XML / JSON writers) --------
  * The per-instance work of the host's `frame_lines` for all n instances of a clip in ONE launch (one wave64 per instance):
  *   bd [n,25,4] fp32 (top x, top y, bottom x, bottom y per point, frame pixels), recs [n,25] int64 class ids,
