@@ -89,6 +89,7 @@ class GoMatchingMI355X(nn.Module):
         self._impl_version = None
         self._device = torch.device(self.cfg.MODEL.DEVICE if self.cfg.MODEL.DEVICE != "cpu" else "cpu")
         self._dropout = None                                     # made by the first training forward
+        self.motion_whole_batch = False                          # training.forward_losses: motion clips as one padded batch
         self._forwards = 0
 
     @property

@@ -35,8 +35,8 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
 __global__ __launch_bounds__(256) void detect_post_kernel(
     const float* __restrict__ cls, int ld_cls, const float* __restrict__ recls, int ld_recls,
     const float* __restrict__ ctrl, const float* __restrict__ bd, const int* __restrict__ recs_in, int nq, int P,
-    float img_h, float img_w, float det_thr, float nms_thr, float asso_thr, int* __restrict__ count,
-    int* __restrict__ keep_idx, float* __restrict__ scores_out, float* __restrict__ boxes_out,
+    float img_h, float img_w, const float* __restrict__ sizes, float det_thr, float nms_thr, float asso_thr,
+    int* __restrict__ count, int* __restrict__ keep_idx, float* __restrict__ scores_out, float* __restrict__ boxes_out,
     float* __restrict__ ctrl_out, float* __restrict__ bd_out, long long* __restrict__ recs_out) {
     __shared__ float s_score[MAXQ];
     __shared__ float s_box[MAXQ][4];
@@ -45,6 +45,10 @@ __global__ __launch_bounds__(256) void detect_post_kernel(
     __shared__ int s_kept[MAXQ];
     __shared__ int s_n, s_nkeep;
     const int b = blockIdx.x, tid = threadIdx.x;
+    if (sizes) {                                             // a size per frame: sizes [B][2] = (img_h, img_w)
+        img_h = sizes[2 * b];
+        img_w = sizes[2 * b + 1];
+    }
 
     // 1. scores + selection + pixel-space boxes
     for (int q = tid; q < nq; q += 256) {
@@ -161,7 +165,23 @@ extern "C" int gom_detect_post(const float* cls_logits, int ld_cls, const float*
     GOM_CHECK_ARG(B > 0 && num_queries > 0 && num_queries <= MAXQ && num_points > 0 && ld_cls >= 1);
     hipLaunchKernelGGL(detect_post_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, cls_logits, ld_cls,
                        rescoring_logits, ld_rescoring, ctrl_points, bd_points, recs, num_queries, num_points, img_h,
-                       img_w, det_thresh, nms_thresh, asso_thresh, count, keep_idx, scores, boxes, ctrl_out, bd_out,
+                       img_w, (const float*)nullptr, det_thresh, nms_thresh, asso_thresh, count, keep_idx, scores, boxes,
+                       ctrl_out, bd_out, recs_out);
+    return gom_launch_status();
+}
+
+/* ... with a size per frame: sizes [B][2] = (img_h, img_w) fp32 on the device (a padded batch of frames of different sizes) */
+extern "C" int gom_detect_post_sizes(const float* cls_logits, int ld_cls, const float* rescoring_logits, int ld_rescoring,
+                                     const float* ctrl_points, const float* bd_points, const int* recs, int B,
+                                     int num_queries, int num_points, const float* sizes, float det_thresh,
+                                     float nms_thresh, float asso_thresh, int* count, int* keep_idx, float* scores,
+                                     float* boxes, float* ctrl_out, float* bd_out, long long* recs_out, void* stream) {
+    GOM_CHECK_ARG(cls_logits && ctrl_points && bd_points && recs && sizes && count && keep_idx && scores && boxes && ctrl_out &&
+                  bd_out && recs_out);
+    GOM_CHECK_ARG(B > 0 && num_queries > 0 && num_queries <= MAXQ && num_points > 0 && ld_cls >= 1);
+    hipLaunchKernelGGL(detect_post_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, cls_logits, ld_cls,
+                       rescoring_logits, ld_rescoring, ctrl_points, bd_points, recs, num_queries, num_points, 0.f, 0.f,
+                       sizes, det_thresh, nms_thresh, asso_thresh, count, keep_idx, scores, boxes, ctrl_out, bd_out,
                        recs_out);
     return gom_launch_status();
 }

@@ -100,9 +100,12 @@ __global__ __launch_bounds__(256) void ref_sigmoid_kernel(const float* __restric
 //   ref'  = sigmoid(delta + inverse_sigmoid(ref))
 //   pos   = sine embedding of ref' * (sx, sy)                    (skipped when pos == nullptr: the last layer)
 // instead of an N = 2 GEMM launch, ref_sigmoid_kernel and point_pos_kernel (three dispatches for 10 KB of arithmetic).
+// FRAMES: (sx, sy) = scales[q / ppf] -- a padded batch whose frames have their own valid extents (scales [B][2], ppf points each).
+template <bool FRAMES>
 __global__ __launch_bounds__(256) void ref_update_kernel(const float* __restrict__ h, int ld_h, const float* __restrict__ W3,
                                                          const float* __restrict__ b3, const float* __restrict__ ref,
                                                          const float* __restrict__ dim_t, float sx, float sy,
+                                                         const float* __restrict__ scales, long ppf,
                                                          float* __restrict__ new_ref, float* __restrict__ pos, long Q) {
     const int lane = threadIdx.x & 63;
     const f32x4 w0 = *(const f32x4*)(W3 + lane * 4), w1 = *(const f32x4*)(W3 + 256 + lane * 4);
@@ -124,6 +127,10 @@ __global__ __launch_bounds__(256) void ref_update_kernel(const float* __restrict
             new_ref[q * 2 + 1] = ry;
         }
         if (pos) {
+            if (FRAMES) {
+                sx = scales[2 * (q / ppf)];
+                sy = scales[2 * (q / ppf) + 1];
+            }
             const float e = (lane < 32 ? rx * sx : ry * sy) * 6.283185307179586f;       // channels [0,128) <- x, [128,256) <- y
             f32x4 o;
 #pragma unroll
@@ -163,12 +170,13 @@ __global__ __launch_bounds__(256) void bezier_refs_kernel(const float* __restric
                                                           const int64_t* __restrict__ lsi, int L,
                                                           const float* __restrict__ bern, float* __restrict__ refs,
                                                           int B, long S, int nq, int P, int compact,
-                                                          const int64_t* __restrict__ vshapes) {
+                                                          const int64_t* __restrict__ vshapes, int vs_bs) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;     // over B*nq*P
     if (i >= (long)B * nq * P) return;
     const int p = (int)(i % P);
     const long bq = i / P;
     const int b = (int)(bq / nq);
+    if (vshapes) vshapes += (long)b * vs_bs;                 // vs_bs = 2 L: every frame its own valid extents (0: one for the batch)
     const long s = topk[bq];
     int l = 0;
     for (int k = 1; k < L; ++k) if (s >= lsi[k]) l = k;
@@ -217,12 +225,14 @@ __global__ __launch_bounds__(256) void enc_ref_kernel(const int64_t* __restrict_
 __global__ __launch_bounds__(256) void zero_padded_kernel(float* __restrict__ buf, int ld, int col0, int ncols4,
                                                           const int64_t* __restrict__ shapes,
                                                           const int64_t* __restrict__ lsi,
-                                                          const int64_t* __restrict__ vshapes, int L, long S, long total) {
+                                                          const int64_t* __restrict__ vshapes, int vs_bs, int L, long S,
+                                                          long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;     // over B*S*ncols4
     if (i >= total) return;
     const int c = (int)(i % ncols4);
     const long tok = i / ncols4;
     const long s = tok % S;
+    vshapes += (tok / S) * vs_bs;                            // vs_bs = 2 L: frame tok / S's valid extents (0: one for the batch)
     int l = 0;
     for (int k = 1; k < L; ++k) if (s >= lsi[k]) l = k;
     const int W = (int)shapes[2 * l + 1];
@@ -259,6 +269,59 @@ __global__ __launch_bounds__(256) void scale_xy_kernel(float* __restrict__ x, lo
     if (i >= n_pairs) return;
     x[2 * i] *= sx;
     x[2 * i + 1] *= sy;
+}
+
+// ... with a scale pair per frame: scales [B][2], ppf pairs per frame
+__global__ __launch_bounds__(256) void scale_xy_frames_kernel(float* __restrict__ x, long n_pairs,
+                                                              const float* __restrict__ scales, long ppf) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_pairs) return;
+    const float* sc = scales + 2 * (i / ppf);
+    x[2 * i] *= sc[0];
+    x[2 * i + 1] *= sc[1];
+}
+
+// Padded batch whose frames have their OWN valid extents (vshapes [B][L][2]): the three geometry tables of every frame and
+// level in one launch -- pos2d_kernel's position rows, enc_ref_kernel's masked grid and proposal_valid_kernel's flags, each
+// with frame b's extents, operand for operand.  One thread per (frame, token, channel); channels 0 / 1 / 2 of a token also
+// write its reference x / y / validity: every word has one writer.
+__global__ __launch_bounds__(256) void padded_geometry_kernel(const float* __restrict__ dim_t,
+                                                              const float* __restrict__ level_embed,
+                                                              const int64_t* __restrict__ shapes,
+                                                              const int64_t* __restrict__ lsi,
+                                                              const int64_t* __restrict__ vshapes, int L, long S, long total,
+                                                              float scale, float* __restrict__ lvl_pos,
+                                                              float* __restrict__ ref, unsigned char* __restrict__ valid) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;     // over B*S*256
+    if (i >= total) return;
+    const int ch = (int)(i & 255);
+    const long tok = i >> 8;
+    const long s = tok % S;
+    int l = 0;
+    for (int k = 1; k < L; ++k) if (s >= lsi[k]) l = k;
+    const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
+    const int64_t* vs = vshapes + (tok / S) * 2 * L + 2 * l;
+    const int Hv = (int)vs[0], Wv = (int)vs[1];
+    const long t = s - lsi[l];
+    const int r = (int)(t / W), c = (int)(t % W);
+    const bool is_y = ch < 128;
+    const int j = is_y ? ch : ch - 128;
+    const float e = is_y ? (float)(r + 1) : (float)(c + 1);
+    const float last = is_y ? (float)Hv : (float)Wv;
+    const float emb = (e - 0.5f) / (last + 1e-6f) * scale;
+    const float a = emb / dim_t[j];
+    lvl_pos[i] = ((j & 1) ? cosf(a) : sinf(a)) + level_embed[l * 256 + ch];
+    if (ch == 0) {
+        const float vx = (float)vs[1] / (float)W;
+        ref[tok * 2] = ((float)(t % W) + 0.5f) / (vx * (float)W);
+    } else if (ch == 1) {
+        const float vy = (float)vs[0] / (float)H;
+        ref[tok * 2 + 1] = ((float)(t / W) + 0.5f) / (vy * (float)H);
+    } else if (ch == 2) {
+        const float Hn = (float)vs[0], Wn = (float)vs[1];
+        const float x = ((float)(t % W) + 0.5f) / Wn, y = ((float)(t / W) + 0.5f) / Hn;
+        valid[tok] = (x > 0.01f && x < 0.99f && y > 0.01f && y < 0.99f) ? 1 : 0;
+    }
 }
 
 }  // namespace
@@ -324,8 +387,22 @@ extern "C" int gom_ref_update_f32(const float* h, int ld_h, const float* W3, con
                   (pos == nullptr || ((uintptr_t)pos % 16) == 0));
     if (num_points == 0) return GOM_OK;
     const long blocks = (num_points + 3) / 4;
-    hipLaunchKernelGGL(ref_update_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, h,
-                       ld_h, W3, b3, ref, dim_t128, sx, sy, new_ref, pos, num_points);
+    hipLaunchKernelGGL(ref_update_kernel<false>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       h, ld_h, W3, b3, ref, dim_t128, sx, sy, (const float*)nullptr, 1L, new_ref, pos, num_points);
+    return gom_launch_status();
+}
+
+extern "C" int gom_ref_update_frames_f32(const float* h, int ld_h, const float* W3, const float* b3, const float* ref,
+                                         const float* dim_t128, const float* scales, long points_per_frame, float* new_ref,
+                                         float* pos, long num_points, void* stream) {
+    GOM_CHECK_ARG(h && W3 && b3 && ref && dim_t128 && scales && new_ref && num_points >= 0 && ld_h >= 256 && (ld_h % 4) == 0);
+    GOM_CHECK_ARG(points_per_frame > 0 && (num_points % points_per_frame) == 0);
+    GOM_CHECK_ARG(((uintptr_t)h % 16) == 0 && ((uintptr_t)W3 % 16) == 0 && ((uintptr_t)dim_t128 % 16) == 0 &&
+                  (pos == nullptr || ((uintptr_t)pos % 16) == 0));
+    if (num_points == 0) return GOM_OK;
+    const long blocks = (num_points + 3) / 4;
+    hipLaunchKernelGGL(ref_update_kernel<true>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       h, ld_h, W3, b3, ref, dim_t128, 1.f, 1.f, scales, points_per_frame, new_ref, pos, num_points);
     return gom_launch_status();
 }
 
@@ -353,7 +430,7 @@ extern "C" int gom_bezier_reference_points(const float* coord_raw, const int* to
     GOM_CHECK_ARG(B > 0 && S > 0 && num_queries > 0 && num_points > 0);
     hipLaunchKernelGGL(bezier_refs_kernel, GOM_GRID((long)B * num_queries * num_points), coord_raw, topk_idx,
                        spatial_shapes, level_start_index, num_levels, bernstein, refs, B, S, num_queries, num_points,
-                       compact, (const int64_t*)nullptr);
+                       compact, (const int64_t*)nullptr, 0);
     return gom_launch_status();
 }
 
@@ -365,7 +442,7 @@ extern "C" int gom_bezier_reference_points_masked(const float* coord_raw, const 
     GOM_CHECK_ARG(B > 0 && S > 0 && num_queries > 0 && num_points > 0);
     hipLaunchKernelGGL(bezier_refs_kernel, GOM_GRID((long)B * num_queries * num_points), coord_raw, topk_idx,
                        spatial_shapes, level_start_index, num_levels, bernstein, refs, B, S, num_queries, num_points,
-                       compact, valid_shapes);
+                       compact, valid_shapes, 0);
     return gom_launch_status();
 }
 
@@ -392,7 +469,50 @@ extern "C" int gom_zero_padded_tokens_f32(float* buf, int ld, int col0, int ncol
     GOM_CHECK_ARG(ncols > 0 && (ncols % 4) == 0 && (col0 % 4) == 0 && (ld % 4) == 0 && col0 + ncols <= ld);
     const long total = (long)B * S * (ncols / 4);
     hipLaunchKernelGGL(zero_padded_kernel, GOM_GRID(total), buf, ld, col0, ncols / 4, spatial_shapes, level_start_index,
-                       valid_shapes, num_levels, S, total);
+                       valid_shapes, 0, num_levels, S, total);
+    return gom_launch_status();
+}
+
+// ---- per-frame forms: a padded batch whose frames each have their own valid extents, valid_shapes [B][L][2] on the device ----
+extern "C" int gom_padded_geometry_f32(const float* dim_t128, const float* level_embed, const int64_t* spatial_shapes,
+                                       const int64_t* level_start_index, const int64_t* valid_shapes, int num_levels, int B,
+                                       long S, float* lvl_pos, float* ref, unsigned char* valid, void* stream) {
+    GOM_CHECK_ARG(dim_t128 && level_embed && spatial_shapes && level_start_index && valid_shapes && lvl_pos && ref && valid);
+    GOM_CHECK_ARG(num_levels > 0 && B > 0 && S > 0);
+    const long total = (long)B * S * 256;
+    GOM_CHECK_ARG(cdiv(total, 256) < (1L << 31));
+    hipLaunchKernelGGL(padded_geometry_kernel, GOM_GRID(total), dim_t128, level_embed, spatial_shapes, level_start_index,
+                       valid_shapes, num_levels, S, total, 6.283185307179586f, lvl_pos, ref, valid);
+    return gom_launch_status();
+}
+
+extern "C" int gom_zero_padded_tokens_frames_f32(float* buf, int ld, int col0, int ncols, const int64_t* spatial_shapes,
+                                                 const int64_t* level_start_index, const int64_t* valid_shapes, int num_levels,
+                                                 int B, long S, void* stream) {
+    GOM_CHECK_ARG(buf && spatial_shapes && level_start_index && valid_shapes && num_levels > 0 && B > 0 && S > 0);
+    GOM_CHECK_ARG(ncols > 0 && (ncols % 4) == 0 && (col0 % 4) == 0 && (ld % 4) == 0 && col0 + ncols <= ld);
+    const long total = (long)B * S * (ncols / 4);
+    hipLaunchKernelGGL(zero_padded_kernel, GOM_GRID(total), buf, ld, col0, ncols / 4, spatial_shapes, level_start_index,
+                       valid_shapes, 2 * num_levels, num_levels, S, total);
+    return gom_launch_status();
+}
+
+extern "C" int gom_bezier_reference_points_frames(const float* coord_raw, const int* topk_idx, const int64_t* spatial_shapes,
+                                                  const int64_t* level_start_index, const int64_t* valid_shapes,
+                                                  int num_levels, const float* bernstein, float* refs, int B, long S,
+                                                  int num_queries, int num_points, int compact, void* stream) {
+    GOM_CHECK_ARG(coord_raw && topk_idx && spatial_shapes && level_start_index && valid_shapes && bernstein && refs);
+    GOM_CHECK_ARG(B > 0 && S > 0 && num_queries > 0 && num_points > 0 && num_levels > 0);
+    hipLaunchKernelGGL(bezier_refs_kernel, GOM_GRID((long)B * num_queries * num_points), coord_raw, topk_idx,
+                       spatial_shapes, level_start_index, num_levels, bernstein, refs, B, S, num_queries, num_points,
+                       compact, valid_shapes, 2 * num_levels);
+    return gom_launch_status();
+}
+
+extern "C" int gom_scale_xy_frames_f32(float* x, long n_pairs, const float* scales, long pairs_per_frame, void* stream) {
+    GOM_CHECK_ARG(n_pairs >= 0 && (x || n_pairs == 0) && scales && pairs_per_frame > 0 && (n_pairs % pairs_per_frame) == 0);
+    if (n_pairs == 0) return GOM_OK;
+    hipLaunchKernelGGL(scale_xy_frames_kernel, GOM_GRID(n_pairs), x, n_pairs, scales, pairs_per_frame);
     return gom_launch_status();
 }
 

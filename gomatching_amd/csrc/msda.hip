@@ -131,7 +131,9 @@ __device__ __forceinline__ void msda_fma4(f32x4& acc, const float w, const f32x4
     for (int c = 0; c < 4; ++c) acc[c] = fmaf(w, v[c], acc[c]);
 }
 
-template <int POINTS, bool HAS_VR>
+// VR: 0 = unpadded (valid ratios 1, `vr` unused); 1 = one valid-ratio table [L][2] for the batch; 2 = a table per frame,
+// vr [B][L][2] (a padded batch whose frames have their own valid extents).  Compile-time: see the note in the loop.
+template <int POINTS, int VR>
 __global__ __launch_bounds__(256) void msda_fused_kernel(const float* __restrict__ value,
                                                          const int64_t* __restrict__ shapes,
                                                          const int64_t* __restrict__ lsi,
@@ -147,6 +149,8 @@ __global__ __launch_bounds__(256) void msda_fused_kernel(const float* __restrict
     const int c4 = (lane & 7) * 4;
     const int b = (int)(q_global / Lq);
 
+    constexpr bool HAS_VR = VR != 0;
+    if (VR == 2) vr += (size_t)__builtin_amdgcn_readfirstlane(b) * (2 * LEVELS);   // (b is the wave's: a scalar base)
     const float* vb = value + (size_t)b * v_bs + m * CH + c4;
     const float* op = raw + (size_t)q_global * ld_raw + m * (LP * 2);
     const float* lp = raw + (size_t)q_global * ld_raw + HEADS * LP * 2 + m * LP;
@@ -247,7 +251,7 @@ __device__ __forceinline__ float group8_read(float v, int owner) {      // value
 }
 
 
-template <bool HAS_VR>
+template <int VR>                                            // 0 / 1 / 2 as in msda_fused_kernel
 __global__ __launch_bounds__(256) void msda_fused_lanes_kernel(const float* __restrict__ value,
                                                                const int64_t* __restrict__ shapes,
                                                                const int64_t* __restrict__ lsi,
@@ -264,6 +268,8 @@ __global__ __launch_bounds__(256) void msda_fused_lanes_kernel(const float* __re
     const int b = (int)(q_local / q_count);
     const long q_global = (long)b * Lq + q_begin + (q_local - (long)b * q_count);
     const int l = k >> 1;                                    // level of this lane's two samples (2k, 2k + 1)
+    constexpr bool HAS_VR = VR != 0;
+    if (VR == 2) vr += (size_t)__builtin_amdgcn_readfirstlane(b) * (2 * LEVELS);   // (b is the wave's: a scalar base)
 
     // ---- owner part: two samples per lane ----
     const float* op = raw + (size_t)q_global * ld_raw + m * (LP * 2) + 4 * k;      // (ox, oy) of samples 2k, 2k + 1
@@ -771,11 +777,11 @@ extern "C" int gom_msda_fused_forward(const float* raw, int ld_raw, const float*
     GOM_CHECK_ARG(((uintptr_t)raw % 16) == 0 && ((uintptr_t)value % 16) == 0);
     const long nq = (long)batch * num_query;
     if (g_msda_lanes && value_batch_stride > 0 && value_batch_stride < (1L << 29))     // 32-bit byte offsets inside a batch image
-        hipLaunchKernelGGL((msda_fused_lanes_kernel<false>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((msda_fused_lanes_kernel<0>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream,
                            value, spatial_shapes, level_start_index, raw, ld_raw, ref, output, batch, num_query,
                            value_batch_stride, value_row_stride, (const float*)nullptr, 0, num_query);
     else
-        hipLaunchKernelGGL((msda_fused_kernel<4, false>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, value,
+        hipLaunchKernelGGL((msda_fused_kernel<4, 0>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, value,
                            spatial_shapes, level_start_index, raw, ld_raw, ref, output, batch, num_query,
                            value_batch_stride, value_row_stride, (const float*)nullptr);
     return gom_launch_status();
@@ -838,7 +844,7 @@ extern "C" int gom_msda_fused_forward_encoder(const float* raw, int ld_raw, cons
     }
     const long rest = num_query - done;
     if (rest > 0)                                            // the coarser levels' queries: the lane-distributed kernel (disjoint rows)
-        hipLaunchKernelGGL((msda_fused_lanes_kernel<false>), dim3((unsigned)cdiv((long)batch * rest, 4)), dim3(256), 0, s, value,
+        hipLaunchKernelGGL((msda_fused_lanes_kernel<0>), dim3((unsigned)cdiv((long)batch * rest, 4)), dim3(256), 0, s, value,
                            spatial_shapes, level_start_index, raw, ld_raw, ref, output, batch, num_query, value_batch_stride,
                            value_row_stride, (const float*)nullptr, (int)done, (int)rest);
     return gom_launch_status();
@@ -854,11 +860,32 @@ extern "C" int gom_msda_fused_forward_vr(const float* raw, int ld_raw, const flo
     GOM_CHECK_ARG(((uintptr_t)raw % 16) == 0 && ((uintptr_t)value % 16) == 0);
     const long nq = (long)batch * num_query;
     if (g_msda_lanes && value_batch_stride > 0 && value_batch_stride < (1L << 29))
-        hipLaunchKernelGGL((msda_fused_lanes_kernel<true>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((msda_fused_lanes_kernel<1>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream,
                            value, spatial_shapes, level_start_index, raw, ld_raw, ref, output, batch, num_query,
                            value_batch_stride, value_row_stride, valid_ratios, 0, num_query);
     else
-        hipLaunchKernelGGL((msda_fused_kernel<4, true>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, value,
+        hipLaunchKernelGGL((msda_fused_kernel<4, 1>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, value,
+                           spatial_shapes, level_start_index, raw, ld_raw, ref, output, batch, num_query,
+                           value_batch_stride, value_row_stride, valid_ratios);
+    return gom_launch_status();
+}
+
+/* ... with a valid-ratio table per frame: valid_ratios [B][L][2] */
+extern "C" int gom_msda_fused_forward_vr_frames(const float* raw, int ld_raw, const float* ref, const float* value,
+                                                long value_batch_stride, int value_row_stride, const int64_t* spatial_shapes,
+                                                const int64_t* level_start_index, const float* valid_ratios, float* output,
+                                                int batch, int num_query, void* stream) {
+    GOM_CHECK_ARG(raw && ref && value && spatial_shapes && level_start_index && valid_ratios && output);
+    GOM_CHECK_ARG(batch > 0 && num_query > 0 && ld_raw >= HEADS * LEVELS * 4 * 3 && (ld_raw % 4) == 0);
+    GOM_CHECK_ARG(value_row_stride >= HEADS * CH && (value_row_stride % 4) == 0 && (value_batch_stride % 4) == 0);
+    GOM_CHECK_ARG(((uintptr_t)raw % 16) == 0 && ((uintptr_t)value % 16) == 0);
+    const long nq = (long)batch * num_query;
+    if (g_msda_lanes && value_batch_stride > 0 && value_batch_stride < (1L << 29))
+        hipLaunchKernelGGL((msda_fused_lanes_kernel<2>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream,
+                           value, spatial_shapes, level_start_index, raw, ld_raw, ref, output, batch, num_query,
+                           value_batch_stride, value_row_stride, valid_ratios, 0, num_query);
+    else
+        hipLaunchKernelGGL((msda_fused_kernel<4, 2>), dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, value,
                            spatial_shapes, level_start_index, raw, ld_raw, ref, output, batch, num_query,
                            value_batch_stride, value_row_stride, valid_ratios);
     return gom_launch_status();

@@ -39,7 +39,7 @@ __device__ void bitonic_sort_desc(unsigned long long* keys) {   // N power of tw
 }
 
 __global__ __launch_bounds__(1024) void topk_chunk_kernel(const float* __restrict__ logits, int ld,
-                                                          const unsigned char* __restrict__ valid,
+                                                          const unsigned char* __restrict__ valid, long valid_bs,
                                                           const float* __restrict__ invalid_logit, long S, int k,
                                                           unsigned long long* __restrict__ cand, int chunks) {
     __shared__ unsigned long long keys[CHUNK];
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(1024) void topk_chunk_kernel(const float* __restric
         unsigned long long key = 0ull;                       // below every real key
         if (s < S) {
             float v = logits[((size_t)b * S + s) * ld];
-            if (valid && !valid[s]) v = c0;
+            if (valid && !valid[b * valid_bs + s]) v = c0;          // valid_bs = S: a flag row per frame (0: one for the batch)
             key = make_key(v, (unsigned)s);
         }
         keys[t] = key;
@@ -81,15 +81,15 @@ extern "C" long gom_topk_workspace_bytes(int B, long S, int k) {
     return (long)sizeof(unsigned long long) * B * cdiv(S, CHUNK) * k;
 }
 
-extern "C" int gom_topk_tokens(const float* logits, int ld, const unsigned char* valid, const float* invalid_logit,
-                               int B, long S, int k, void* workspace, int* idx_out, int* rows_out, void* stream) {
+static int topk_launch(const float* logits, int ld, const unsigned char* valid, long valid_bs, const float* invalid_logit,
+                       int B, long S, int k, void* workspace, int* idx_out, int* rows_out, void* stream) {
     GOM_CHECK_ARG(logits && workspace && idx_out && B > 0 && S > 0 && k > 0 && ld >= 1);
     const int chunks = cdiv(S, CHUNK);
     GOM_CHECK_ARG(k <= CHUNK && k <= S && (long)chunks * k <= MERGE_MAX && (long)B * S < (1L << 31));
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* cand = (unsigned long long*)workspace;
     hipLaunchKernelGGL(topk_chunk_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(1024), 0, s, logits, ld, valid,
-                       invalid_logit, S, k, cand, chunks);
+                       valid_bs, invalid_logit, S, k, cand, chunks);
     auto kern = topk_merge_kernel;
     const int lds = MERGE_MAX * sizeof(unsigned long long);
     // (the attribute is per DEVICE: set on every launch -- a process-wide flag would miss a second GPU; it costs ~1 us)
@@ -97,4 +97,16 @@ extern "C" int gom_topk_tokens(const float* logits, int ld, const unsigned char*
     if (e != hipSuccess) return GOM_ERR_HIP_BASE + (int)e;
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(1024), lds, s, cand, chunks * k, k, S, idx_out, rows_out);
     return gom_launch_status();
+}
+
+extern "C" int gom_topk_tokens(const float* logits, int ld, const unsigned char* valid, const float* invalid_logit,
+                               int B, long S, int k, void* workspace, int* idx_out, int* rows_out, void* stream) {
+    return topk_launch(logits, ld, valid, 0, invalid_logit, B, S, k, workspace, idx_out, rows_out, stream);
+}
+
+/* ... with a validity row per frame: valid [B][S] (a padded batch whose frames have their own valid extents) */
+extern "C" int gom_topk_tokens_frames(const float* logits, int ld, const unsigned char* valid, const float* invalid_logit,
+                                      int B, long S, int k, void* workspace, int* idx_out, int* rows_out, void* stream) {
+    GOM_CHECK_ARG(valid);
+    return topk_launch(logits, ld, valid, S, invalid_logit, B, S, k, workspace, idx_out, rows_out, stream);
 }

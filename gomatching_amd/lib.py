@@ -175,6 +175,14 @@ SIGNATURES = {
     "gom_bezier_reference_points_masked": (I, [P, P, P, P, P, I, P, P, I, L, I, I, I, P]),
     "gom_msda_fused_forward_vr": (I, [P, I, P, P, L, I, P, P, P, P, I, I, P]),
     "gom_zero_padded_tokens_f32": (I, [P, I, I, I, P, P, P, I, I, L, P]),
+    "gom_padded_geometry_f32": (I, [P, P, P, P, P, I, I, L, P, P, P, P]),
+    "gom_zero_padded_tokens_frames_f32": (I, [P, I, I, I, P, P, P, I, I, L, P]),
+    "gom_topk_tokens_frames": (I, [P, I, P, P, I, L, I, P, P, P, P]),
+    "gom_bezier_reference_points_frames": (I, [P, P, P, P, P, I, P, P, I, L, I, I, I, P]),
+    "gom_msda_fused_forward_vr_frames": (I, [P, I, P, P, L, I, P, P, P, P, I, I, P]),
+    "gom_scale_xy_frames_f32": (I, [P, L, P, L, P]),
+    "gom_ref_update_frames_f32": (I, [P, I, P, P, P, P, P, L, P, P, L, P]),
+    "gom_detect_post_sizes": (I, [P, I, P, I, P, P, P, I, I, I, P, F, F, F, P, P, P, P, P, P, P, P]),
     "gom_layernorm_any_f32": (I, [P, P, P, P, L, I, F, P]),
     "gom_gelu_f32": (I, [P, L, P]),
     "gom_swin_patchify_f32": (I, [P, P, I, I, I, P]),

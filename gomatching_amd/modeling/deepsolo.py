@@ -211,6 +211,41 @@ class DeepSolo:
         v.append((resample(shapes[0][0], shapes[3][0], v[0][0]), resample(shapes[0][1], shapes[3][1], v[0][1])))
         return v
 
+    @staticmethod
+    def valid_shapes_frames(shapes, image_sizes, strides=(8, 16, 32)):
+        """`valid_shapes` of every frame of a padded batch: image_sizes = B x (h, w) -> [B][L][2]."""
+        return [DeepSolo.valid_shapes(shapes, tuple(hw), strides) for hw in image_sizes]
+
+    def geometry_frames(self, shapes, image_sizes):
+        """The tables of a padded batch whose frames have their OWN valid extents (a motion clip made from a still): per-frame
+        `lvl_pos`, `enc_ref`, `valid` (one launch, `ops.padded_geometry`), `vshapes` [B,L,2], `vr` [B,L,2] and `vr0` [B,2] on the
+        device; `pos_w` is the non-periodic form, a [B*S,384] residual per encoder layer.  A frame that fills the padded size
+        takes ratio 1.0 and its full extents through the same kernels.  Never cached: every clip brings new sizes, and
+        inference's cache (whose entries captured graphs may point into) is not touched."""
+        import numpy as np
+        dev, B = self.device, len(image_sizes)
+        fv = self.valid_shapes_frames(shapes, image_sizes)
+        for vshapes in fv:
+            if any(v[0] <= 0 or v[1] <= 0 for v in vshapes):
+                raise ValueError("a level has no valid token: image %s too small for the padded batch" % (vshapes,))
+        ss = torch.as_tensor(shapes, dtype=torch.long)
+        lsi = torch.cat((ss.new_zeros((1,)), ss.prod(1).cumsum(0)[:-1]))
+        S = int(ss.prod(1).sum())
+        ss_d, lsi_d = ss.to(dev), lsi.to(dev)
+        vs_d = torch.as_tensor(fv, dtype=torch.long).to(dev)                              # [B, L, 2] (Hv, Wv)
+        vr = np.array([[[np.float32(v[1]) / np.float32(s_[1]), np.float32(v[0]) / np.float32(s_[0])]
+                        for v, s_ in zip(vshapes, shapes)] for vshapes in fv], np.float32)   # (Wv/W, Hv/H), get_valid_ratio
+        vr_d = torch.from_numpy(vr).to(dev)
+        lvl_pos, enc_ref, valid = ops.padded_geometry(self.dim_t, self.level_embed, ss_d, lsi_d, vs_d, B, S)
+        lvl_pos = lvl_pos.view(B * S, 256)
+        return {
+            "S": S, "shapes": ss_d, "lsi": lsi_d, "lsi_host": [int(v) for v in lsi],
+            "pos_w": [ops.gemm(lvl_pos, L["attn"]["raw"][0]) for L in self.enc], "pos_periodic": False,
+            "hw0": tuple(int(v) for hw in shapes[:2] for v in hw),
+            "lvl_pos": lvl_pos, "enc_ref": enc_ref.view(B * S, 1, 2), "valid": valid,
+            "vshapes": vs_d, "vr": vr_d, "vr0": vr_d[:, 0].contiguous(), "frames": True,
+        }
+
     def geometry(self, shapes, B, vshapes=None):
         """Per-resolution tables.  `vshapes`: valid extents per level for a padded batch (None: nothing is padded)."""
         if vshapes is not None and all(tuple(v) == tuple(s) for v, s in zip(vshapes, shapes)):
@@ -272,7 +307,7 @@ class DeepSolo:
         return self._invalid_logit
 
     # --------------------------------------------------------------------------------- pieces
-    def input_tokens(self, feats, B, image_hw=None):
+    def input_tokens(self, feats, B, image_hw=None, image_sizes=None):
         """A4 + A5: input_proj (conv + GroupNorm) of the 3 backbone levels + the stride-2 extra level,
         written level by level into the flattened token buffer."""
         shapes = [(f.shape[1], f.shape[2]) for f in feats]
@@ -283,7 +318,10 @@ class DeepSolo:
             top = padded
         x3 = ops.conv2d_nhwc(top, self.proj3[0], shift=self.proj3[1], stride=2, pad=1)
         shapes.append((x3.shape[1], x3.shape[2]))
-        geo = self.geometry(shapes, B, None if image_hw is None else self.valid_shapes(shapes, image_hw))
+        if image_sizes is not None:
+            geo = self.geometry_frames(shapes, image_sizes)
+        else:
+            geo = self.geometry(shapes, B, None if image_hw is None else self.valid_shapes(shapes, image_hw))
         S = geo["S"]
         src = torch.empty((B, S, 256), dtype=_f32, device=self.device)
         for l, f in enumerate(feats):
@@ -299,7 +337,10 @@ class DeepSolo:
         for li, L in enumerate(self.enc):
             rv = ops.linear(src, L["attn"]["raw_value"], R=geo["pos_w"][li], r_cols=384,
                             r_period=S if geo["pos_periodic"] else 0)   # [B*S, 384 | 256]
-            if geo["vr"] is not None:                      # padded batch: value.masked_fill(padding_mask, 0)
+            frames = geo.get("frames", False)              # a valid extent per frame (`geometry_frames`)
+            if frames:
+                ops.zero_padded_tokens_frames_(rv, 384, 256, geo["shapes"], geo["lsi"], geo["vshapes"], B, S)
+            elif geo["vr"] is not None:                    # padded batch: value.masked_fill(padding_mask, 0)
                 ops.zero_padded_tokens_(rv, 384, 256, geo["shapes"], geo["lsi"], geo["vshapes"], B, S)
             # LDS windows for this layer's queries?  Decided once per layer, on its first eager call, from the measured share of octet
             # groups whose samples leave the windows (ops.MSDA_WINDOW_POLICY); undecided calls (a capture in progress) use the windows
@@ -308,8 +349,10 @@ class DeepSolo:
                 not torch.cuda.is_current_stream_capturing()
             if decide and self._msda_counter is None:
                 self._msda_counter = torch.zeros((1,), dtype=torch.int32, device=src.device)
-            samp = ops.msda_fused(rv, geo["enc_ref"], rv[:, 384:], S * 640, geo["shapes"], geo["lsi"], B, S, geo["vr"],
-                                  encoder_hw0=geo["hw0"] if use_win else None, fallback_counter=self._msda_counter if decide else None)
+            samp = ops.msda_fused(rv, geo["enc_ref"], rv[:, 384:], S * 640, geo["shapes"], geo["lsi"], B, S,
+                                  None if frames else geo["vr"], encoder_hw0=geo["hw0"] if use_win else None,
+                                  fallback_counter=self._msda_counter if decide else None,
+                                  frame_valid_ratios=geo["vr"] if frames else None)
             if decide:
                 frac = float(self._msda_counter.item()) / max(1, ops.msda_window_groups(geo["hw0"], B))
                 L["msda_window"] = frac <= ops.MSDA_WINDOW_MAX_FALLBACK
@@ -335,8 +378,9 @@ class DeepSolo:
         else:
             om = ops.layernorm(ops.gemm(memory, self.enc_output[0], bias=self.enc_output[1]), *self.enc_output_norm)
             enc_class = ops.gemm(om, self.bezier_class[0], bias=self.bezier_class[1])          # [B*S, 1]
-        topk, rows = ops.topk_tokens(enc_class, B, S, self.nq, valid=geo["valid"],
-                                     invalid_logit=self.invalid_logit(), with_rows=True)
+        frames = geo.get("frames", False)
+        topk, rows = ops.topk_tokens(enc_class, B, S, self.nq, invalid_logit=self.invalid_logit(), with_rows=True,
+                                     **({"frame_valid": geo["valid"]} if frames else {"valid": geo["valid"]}))
         rows = rows.view(-1)                       # coordinate MLP on the nq winning rows per frame only
         if self.enc_output_ln is not None:
             om_sel = ops.proj_ln(ops.gather_rows(memory, rows), self.enc_output_ln, None)
@@ -346,7 +390,7 @@ class DeepSolo:
         h = ops.gemm(h, self.bezier_coord[1][0], bias=self.bezier_coord[1][1], relu=True)
         coord_sel = ops.gemm(h, self.bezier_coord[2][0], bias=self.bezier_coord[2][1])          # [B*nq, 8]
         refs = ops.bezier_reference_points(coord_sel, topk, geo["shapes"], geo["lsi"], self.bernstein, B, S, self.nq,
-                                           self.P, compact=True, vshapes=geo["vshapes"])
+                                           self.P, compact=True, **({"frame_vshapes" if frames else "vshapes": geo["vshapes"]}))
         return refs, topk, enc_class
 
     def decoder(self, memory, refs, geo, B):
@@ -357,7 +401,8 @@ class DeepSolo:
         values = ops.linear(memory, self.dec_value)                                           # [B*S, 1536]
         vr = geo["vr"]
         if vr is not None:
-            ops.zero_padded_tokens_(values, 0, values.shape[1], geo["shapes"], geo["lsi"], geo["vshapes"], B, S)
+            zero = ops.zero_padded_tokens_frames_ if geo.get("frames", False) else ops.zero_padded_tokens_
+            zero(values, 0, values.shape[1], geo["shapes"], geo["lsi"], geo["vshapes"], B, S)
         refs = refs.view(Q, 2)
         inter_refs = []
         E = 256
@@ -375,7 +420,12 @@ class DeepSolo:
             # reference_points_input = reference_points * valid_ratios; the query position comes from level 0's (:470-473)
             if qpos is None:
                 if emb is None:
-                    qref = refs if vr is None else ops.scale_xy_(refs.clone(), *geo["vr0"])
+                    if vr is None:
+                        qref = refs
+                    elif geo.get("frames", False):
+                        qref = ops.scale_xy_frames_(refs.clone(), geo["vr0"])
+                    else:
+                        qref = ops.scale_xy_(refs.clone(), *geo["vr0"])
                     emb = ops.point_pos_embed(qref, self.dim_t)
                 qpos = emb
                 if self.ref_point_mlp2 is not None:
@@ -436,8 +486,9 @@ class DeepSolo:
             # reference refinement (:484-488); with the MLP's hidden layers fused, its N = 2 layer, the sigmoid update and the NEXT
             # layer's point embedding (:470-473) are one launch
             if ops.REF_UPDATE and self.ctrl_coord_mlp2 is not None:
+                scale = {} if vr is None else {"frame_scales" if geo.get("frames", False) else "scale": geo["vr0"]}
                 refs, emb = ops.ref_update(ops.mlp2_fused(tgt, self.ctrl_coord_mlp2), self.ctrl_coord[2], refs, self.dim_t,
-                                           None if vr is None else geo["vr0"], want_pos=more)
+                                           want_pos=more, **scale)
             else:
                 d = self._mlp3(tgt, self.ctrl_coord)
                 refs, emb = ops.ref_sigmoid(d, refs, 2), None
@@ -457,6 +508,8 @@ class DeepSolo:
         logits when the inter block's launch already made them."""
         if raw is None:
             raw = ops.linear(query, W["raw"], A2=query_pos)
+        if geo.get("frames", False):
+            return ops.msda_fused(raw, ref, value_view, geo["S"] * ld_value, geo["shapes"], geo["lsi"], B, Lq, frame_valid_ratios=vr)
         return ops.msda_fused(raw, ref, value_view, geo["S"] * ld_value, geo["shapes"], geo["lsi"], B, Lq, vr)
 
     def _mlp3(self, x, layers):
@@ -482,12 +535,19 @@ class DeepSolo:
                 "query_features": hs}
 
     # --------------------------------------------------------------------------------- whole forward
-    def forward(self, feats, taps=None, image_hw=None):
+    def forward(self, feats, taps=None, image_hw=None, image_sizes=None):
         """feats: [res3, res4, res5] NHWC tensors of one batch of same-size frames.  Returns the reference's
         output dict with tensors flattened over (B, nq, P): pred_logits [B*nq*P,1], pred_text_logits [.,voc+1],
-        pred_ctrl_points [.,2], pred_bd_points [.,4], query_features [.,256]."""
+        pred_ctrl_points [.,2], pred_bd_points [.,4], query_features [.,256].
+        image_hw: the (h, w) all frames of a padded batch share; image_sizes: B x (h, w), every frame its own (exclusive)."""
         B = feats[0].shape[0]
-        src, geo = self.input_tokens(feats, B, image_hw)
+        if image_sizes is not None:
+            if image_hw is not None:
+                raise ValueError("image_hw and image_sizes are exclusive")
+            image_sizes = [tuple(int(v) for v in hw) for hw in image_sizes]
+            if len(image_sizes) != B:
+                raise ValueError("image_sizes has %d entries for a batch of %d frames" % (len(image_sizes), B))
+        src, geo = self.input_tokens(feats, B, image_hw, image_sizes)
         memory = self.encoder(src, geo, B)
         refs, topk, enc_class = self.proposals(memory, geo, B)
         hs, inter_refs = self.decoder(memory, refs, geo, B)

@@ -111,6 +111,14 @@ def _chk_f32(*ts):
                 t.dtype, t.device, t.is_contiguous()))
 
 
+def _chk_frame_desc(t, B, tail, dtype, name):
+    """A per-frame descriptor of a padded batch (`padded_geometry` and the `frame_*` keywords): [B, *tail], contiguous, on the GPU."""
+    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.dim() != 1 + len(tail) or t.shape[0] != B or \
+            tuple(t.shape[1:]) != tuple(tail):
+        raise _lib_mod.GomError("%s: expected a contiguous %s CUDA tensor of shape %s (one entry per frame of the batch), got %s %s" % (
+            name, dtype, (B,) + tuple(tail), t.dtype, tuple(t.shape)))
+
+
 # ------------------------------------------------------------------------------------------ GEMM
 # "bf16x6": weights of the big contractions are pre-split into three bf16 planes and multiplied on the bf16
 # matrix cores with fp32-level accuracy (csrc/gemm_bf16x6.hip); "fp32": exact-fp32 MFMA everywhere.
@@ -1215,14 +1223,18 @@ def msda_window_groups(encoder_hw0, B):
     return B * 8 * n
 
 
-def msda_fused(raw, ref, value2d, batch_stride, shapes, lsi, B, Lq, valid_ratios=None, encoder_hw0=None, fallback_counter=None):
+def msda_fused(raw, ref, value2d, batch_stride, shapes, lsi, B, Lq, valid_ratios=None, encoder_hw0=None, fallback_counter=None,
+               frame_valid_ratios=None):
     """raw [B*Lq, >=384] (offsets | logits, stride(1)==1), ref [B*Lq, 2], value2d [B*S, 256] column slice;
     valid_ratios [4,2] fp32 (Wv/W, Hv/H) for padded batches.  encoder_hw0 = (H0, W0[, H1, W1]): an ENCODER call (query q = token
     q, reference points = the tokens' own positions) -- the level-0 (and level-1) queries then run on the LDS-window kernel
     (csrc/msda.hip).  fallback_counter: a one-word int32 device tensor the window launches of THIS call add their fallback octet
-    groups to (zeroed here)."""
+    groups to (zeroed here).  frame_valid_ratios [B,4,2]: a table per frame (exclusive with valid_ratios)."""
     assert raw.stride(1) == 1 and value2d.stride(1) == 1
     _chk_f32(ref, valid_ratios)
+    if frame_valid_ratios is not None:
+        assert valid_ratios is None, "valid_ratios and frame_valid_ratios are exclusive"
+        _chk_frame_desc(frame_valid_ratios, B, (shapes.shape[0], 2), _f32, "frame_valid_ratios")
     if _msda_lanes_set[0] != MSDA_LANES:                     # library-side switch follows ops.MSDA_LANES
         _L().gom_msda_set_lane_distributed(1 if MSDA_LANES else 0)
         _msda_lanes_set[0] = MSDA_LANES
@@ -1231,7 +1243,11 @@ def msda_fused(raw, ref, value2d, batch_stride, shapes, lsi, B, Lq, valid_ratios
     # profile figures: 2 * Lq * 8 heads * 16 samples * 4 corners * 32; the value map once + raw offsets | logits +
     # output (fp32)
     with _timed(True, lambda: (2.0 * B * Lq * 8 * 16 * 4 * 32, 4.0 * (S_rows * 256 + B * Lq * (384 + 256)), "msda:%dx%d" % (B, Lq))):
-        if valid_ratios is not None:
+        if frame_valid_ratios is not None:
+            check(_L().gom_msda_fused_forward_vr_frames(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride,
+                                                        value2d.stride(0), _p(shapes), _p(lsi), _p(frame_valid_ratios), _p(out),
+                                                        B, Lq, _stream()), "gom_msda_fused_forward_vr_frames")
+        elif valid_ratios is not None:
             check(_L().gom_msda_fused_forward_vr(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride,
                                                  value2d.stride(0), _p(shapes), _p(lsi), _p(valid_ratios), _p(out), B, Lq,
                                                  _stream()), "gom_msda_fused_forward_vr")
@@ -1793,9 +1809,10 @@ def ref_sigmoid(delta, ref, C):
 REF_UPDATE = _switch("REF_UPDATE")   # decoder: last MLP layer (N = 2) + reference refinement + next layer's point embedding, one launch
 
 
-def ref_update(h, last, ref, dim_t, scale=None, want_pos=True):
+def ref_update(h, last, ref, dim_t, scale=None, want_pos=True, frame_scales=None):
     """(new_ref [Q,2], pos [Q,256] | None): sigmoid(h @ W3^T + b3 + inverse_sigmoid(ref)) and the sine embedding of the new
-    reference points (times `scale` = the level-0 valid ratios of a padded batch); `last` = the (weight [2,256], bias) pair."""
+    reference points (times `scale` = the level-0 valid ratios of a padded batch); `last` = the (weight [2,256], bias) pair.
+    frame_scales [B,2]: a scale pair per frame of Q / B points each (exclusive with `scale`)."""
     W3, b3 = last
     _chk_f32(ref, W3, b3, dim_t)
     assert h.dim() == 2 and h.stride(1) == 1 and h.shape[1] == 256 and h.dtype == _f32 and tuple(W3.shape) == (2, 256)
@@ -1803,6 +1820,15 @@ def ref_update(h, last, ref, dim_t, scale=None, want_pos=True):
     assert h.shape[0] == Q
     new_ref = torch.empty_like(ref)
     pos = torch.empty((Q, 256), dtype=_f32, device=ref.device) if want_pos else None
+    if frame_scales is not None:
+        assert scale is None, "scale and frame_scales are exclusive"
+        B = frame_scales.shape[0] if frame_scales.dim() else 0
+        if B <= 0 or Q % B:
+            raise _lib_mod.GomError("frame_scales: %d points do not divide into %s frames" % (Q, B))
+        _chk_frame_desc(frame_scales, B, (2,), _f32, "frame_scales")
+        check(_L().gom_ref_update_frames_f32(_p(h), _ld(h), _p(W3), _p(b3), _p(ref), _p(dim_t), _p(frame_scales), Q // B,
+                                             _p(new_ref), _p(pos), Q, _stream()), "gom_ref_update_frames_f32")
+        return new_ref, pos
     sx, sy = scale if scale is not None else (1.0, 1.0)
     check(_L().gom_ref_update_f32(_p(h), _ld(h), _p(W3), _p(b3), _p(ref), _p(dim_t), float(sx), float(sy),
                                   _p(new_ref), _p(pos), Q, _stream()), "gom_ref_update_f32")
@@ -1827,6 +1853,32 @@ def zero_padded_tokens_(buf, col0, ncols, shapes, lsi, vshapes, B, S):
     return buf
 
 
+def zero_padded_tokens_frames_(buf, col0, ncols, shapes, lsi, frame_vshapes, B, S):
+    """`zero_padded_tokens_` with frame tok // S's valid extents: frame_vshapes [B,L,2] int64."""
+    _chk_f32(buf)
+    _chk_frame_desc(frame_vshapes, B, (shapes.shape[0], 2), torch.int64, "frame_vshapes")
+    check(_L().gom_zero_padded_tokens_frames_f32(_p(buf), buf.stride(0), col0, ncols, _p(shapes), _p(lsi), _p(frame_vshapes),
+                                                 shapes.shape[0], B, S, _stream()), "gom_zero_padded_tokens_frames_f32")
+    return buf
+
+
+def padded_geometry(dim_t, level_embed, shapes, lsi, frame_vshapes, B, S):
+    """The geometry tables of a padded batch whose frames have their own valid extents (frame_vshapes [B,L,2] int64), ONE launch:
+    (lvl_pos [B,S,256], enc_ref [B,S,2], valid [B,S] uint8) -- per frame what `pos_encoding_into(..., valid_hw)` + level embed,
+    `encoder_reference_points(..., vshapes)` and `proposal_valid(..., vshapes)` give for that frame's extents."""
+    L = shapes.shape[0]
+    _chk_f32(dim_t, level_embed)
+    assert tuple(level_embed.shape) == (L, 256) and dim_t.numel() == 128
+    _chk_frame_desc(frame_vshapes, B, (L, 2), torch.int64, "frame_vshapes")
+    dev = shapes.device
+    lvl_pos = torch.empty((B, S, 256), dtype=_f32, device=dev)
+    ref = torch.empty((B, S, 2), dtype=_f32, device=dev)
+    valid = torch.empty((B, S), dtype=torch.uint8, device=dev)
+    check(_L().gom_padded_geometry_f32(_p(dim_t), _p(level_embed), _p(shapes), _p(lsi), _p(frame_vshapes), L, B, S, _p(lvl_pos),
+                                       _p(ref), _p(valid), _stream()), "gom_padded_geometry_f32")
+    return lvl_pos, ref, valid
+
+
 def encoder_reference_points(shapes, lsi, S, vshapes=None):
     out = torch.empty((S, 2), dtype=_f32, device=shapes.device)
     if vshapes is not None:
@@ -1838,10 +1890,18 @@ def encoder_reference_points(shapes, lsi, S, vshapes=None):
     return out
 
 
-def bezier_reference_points(coord_raw, topk_idx, shapes, lsi, bern, B, S, nq, P, compact=False, vshapes=None):
-    """coord_raw: [B,S,8] (compact=False) or the selected tokens' rows [B*nq,8] (compact=True)."""
+def bezier_reference_points(coord_raw, topk_idx, shapes, lsi, bern, B, S, nq, P, compact=False, vshapes=None, frame_vshapes=None):
+    """coord_raw: [B,S,8] (compact=False) or the selected tokens' rows [B*nq,8] (compact=True).  vshapes [L,2]: the batch's valid
+    extents; frame_vshapes [B,L,2]: every frame's own (exclusive)."""
     _chk_f32(coord_raw, bern)
     out = torch.empty((B, nq, P, 2), dtype=_f32, device=coord_raw.device)
+    if frame_vshapes is not None:
+        assert vshapes is None, "vshapes and frame_vshapes are exclusive"
+        _chk_frame_desc(frame_vshapes, B, (shapes.shape[0], 2), torch.int64, "frame_vshapes")
+        check(_L().gom_bezier_reference_points_frames(_p(coord_raw), _p(topk_idx), _p(shapes), _p(lsi), _p(frame_vshapes),
+                                                      shapes.shape[0], _p(bern), _p(out), B, S, nq, P,
+                                                      1 if compact else 0, _stream()), "gom_bezier_reference_points_frames")
+        return out
     if vshapes is not None:
         check(_L().gom_bezier_reference_points_masked(_p(coord_raw), _p(topk_idx), _p(shapes), _p(lsi), _p(vshapes),
                                                       shapes.shape[0], _p(bern), _p(out), B, S, nq, P,
@@ -1857,6 +1917,18 @@ def scale_xy_(x, sx, sy):
     """In-place scaling of interleaved (x, y) pairs of a contiguous tensor."""
     _chk_f32(x)
     check(_L().gom_scale_xy_f32(_p(x), x.numel() // 2, float(sx), float(sy), _stream()), "gom_scale_xy_f32")
+    return x
+
+
+def scale_xy_frames_(x, frame_scales):
+    """`scale_xy_` with a scale pair per frame: frame_scales [B,2], x = B equal runs of (x, y) pairs."""
+    _chk_f32(x)
+    B = frame_scales.shape[0] if frame_scales.dim() else 0
+    n = x.numel() // 2
+    if B <= 0 or n % B:
+        raise _lib_mod.GomError("frame_scales: %d pairs do not divide into %s frames" % (n, B))
+    _chk_frame_desc(frame_scales, B, (2,), _f32, "frame_scales")
+    check(_L().gom_scale_xy_frames_f32(_p(x), n, _p(frame_scales), n // B, _stream()), "gom_scale_xy_frames_f32")
     return x
 
 
@@ -1882,12 +1954,19 @@ def broadcast_rows(src, B):
     return out
 
 
-def topk_tokens(logits, B, S, k, valid=None, invalid_logit=None, with_rows=False):
-    """logits: [B*S, ld] (column 0 used) -> int32 [B,k] sorted by value desc."""
+def topk_tokens(logits, B, S, k, valid=None, invalid_logit=None, with_rows=False, frame_valid=None):
+    """logits: [B*S, ld] (column 0 used) -> int32 [B,k] sorted by value desc.  valid [S]: one validity row for the batch;
+    frame_valid [B,S]: a row per frame (exclusive)."""
     nbytes = _L().gom_topk_workspace_bytes(B, S, k)
     ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=logits.device)
     idx = torch.empty((B, k), dtype=torch.int32, device=logits.device)
     rows = torch.empty((B, k), dtype=torch.int32, device=logits.device) if with_rows else None
+    if frame_valid is not None:
+        assert valid is None, "valid and frame_valid are exclusive"
+        _chk_frame_desc(frame_valid, B, (S,), torch.uint8, "frame_valid")
+        check(_L().gom_topk_tokens_frames(_p(logits), logits.stride(0), _p(frame_valid), _p(invalid_logit), B, S, k, _p(ws),
+                                          _p(idx), _p(rows), _stream()), "gom_topk_tokens_frames")
+        return (idx, rows) if with_rows else idx
     check(_L().gom_topk_tokens(_p(logits), logits.stride(0), _p(valid), _p(invalid_logit), B, S, k, _p(ws), _p(idx),
                                _p(rows), _stream()), "gom_topk_tokens")
     return (idx, rows) if with_rows else idx
@@ -1900,7 +1979,8 @@ def argmax_rows(x):
     return out
 
 
-def detect_post(cls, recls, ctrl, bd, recs, B, nq, P, img_h, img_w, det_thr, nms_thr, asso_thr):
+def detect_post(cls, recls, ctrl, bd, recs, B, nq, P, img_h, img_w, det_thr, nms_thr, asso_thr, frame_sizes=None):
+    """frame_sizes [B,2] fp32 (img_h, img_w): a size per frame instead of the two scalars (pass img_h = img_w = None)."""
     dev = cls.device
     # count | keep_idx | scores | boxes share one buffer so the host needs a single D2H copy per step
     small = torch.zeros((B * (1 + 6 * nq),), dtype=torch.int32, device=dev)
@@ -1915,6 +1995,15 @@ def detect_post(cls, recls, ctrl, bd, recs, B, nq, P, img_h, img_w, det_thr, nms
         "bd": torch.zeros((B, nq, P, 4), dtype=_f32, device=dev),
         "recs": torch.zeros((B, nq, P), dtype=torch.int64, device=dev),
     }
+    if frame_sizes is not None:
+        assert img_h is None and img_w is None, "img_h / img_w and frame_sizes are exclusive"
+        _chk_frame_desc(frame_sizes, B, (2,), _f32, "frame_sizes")
+        check(_L().gom_detect_post_sizes(_p(cls), cls.stride(0), _p(recls), recls.stride(0) if recls is not None else 0,
+                                         _p(ctrl), _p(bd), _p(recs), B, nq, P, _p(frame_sizes), float(det_thr),
+                                         float(nms_thr), float(asso_thr), _p(out["count"]), _p(out["keep_idx"]),
+                                         _p(out["scores"]), _p(out["boxes"]), _p(out["ctrl"]), _p(out["bd"]), _p(out["recs"]),
+                                         _stream()), "gom_detect_post_sizes")
+        return out
     check(_L().gom_detect_post(_p(cls), cls.stride(0), _p(recls), recls.stride(0) if recls is not None else 0,
                                _p(ctrl), _p(bd), _p(recs), B, nq, P, float(img_h), float(img_w), float(det_thr),
                                float(nms_thr), float(asso_thr), _p(out["count"]), _p(out["keep_idx"]),

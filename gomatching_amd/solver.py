@@ -235,8 +235,11 @@ class Trainer:
     the config has one >= 0, else drawn once from the operating system and printed.  It is written into every checkpoint and
     restored by `resume()`, so that iteration i of a resumed run draws the masks iteration i of the uninterrupted run drew."""
 
-    def __init__(self, cfg, model, output_dir, inference_th_train=0.3, seed=None):
+    def __init__(self, cfg, model, output_dir, inference_th_train=0.3, seed=None, motion_whole_batch=False):
         self.cfg, self.model, self.output_dir = cfg, model, output_dir
+        # motion clips (still images) as ONE padded batch with per-frame extents instead of one pass per frame size
+        # (training.detect_for_training(whole_batch=...)); video clips are one batch either way
+        self.motion_whole_batch = model.motion_whole_batch = bool(motion_whole_batch)
         self.solver = S = solver_cfg(cfg)
         self.max_iter = S.MAX_ITER if S.TRAIN_ITER < 0 else S.TRAIN_ITER
         T = cfg.MODEL.TRANSFORMER
@@ -287,7 +290,7 @@ class Trainer:
         from . import training
         if self.dropout is not None:
             self.dropout.begin_forward(self.iteration)
-        losses = training.forward_losses(self.model, batched_inputs)
+        losses = training.forward_losses(self.model, batched_inputs, motion_whole_batch=self.motion_whole_batch)
         total = sum(v for k, v in losses.items() if "loss" in k)
         if not bool(torch.isfinite(total).all()):
             raise FloatingPointError("non-finite loss at iteration %d: %r" % (self.iteration, {k: float(v) for k, v in losses.items()}))

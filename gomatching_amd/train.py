@@ -2,7 +2,7 @@
 the reference's train_net.py:50-211.
 
     python -m gomatching_amd.train (--config-file F | --builtin NAME) [--json FILE --image-root DIR] [--resume]
-           [--host-ingest] [--image-motion] [--seed N] --opts MODEL.WEIGHTS W OUTPUT_DIR out ...
+           [--host-ingest] [--image-motion [--motion-batch {grouped,whole}]] [--seed N] --opts MODEL.WEIGHTS W OUTPUT_DIR out ...
       -> out/model_*.pth, out/model_final.pth, out/last_checkpoint, out/metrics.json
 
 What it keeps of the reference: `setup` (config file, then --opts; INFERENCE_TH_TEST = INFERENCE_TH_TRAIN, which `Trainer`
@@ -23,7 +23,9 @@ Deliberate differences:
   * still images (records without a video id) are refused unless `--image-motion` is given: the flag builds the mapper with
     `image_motion=True`, which turns each still into a GEN_IMAGE_MOTION clip (`data.motion_clip_params`; one image upload and
     one ingest launch per clip, the detector per group of equally sized frames).  Opt-in because the refusal is what existing
-    callers rely on; `--host-ingest` combines with it;
+    callers rely on; `--host-ingest` combines with it.  `--motion-batch whole` runs such a clip through the detector as ONE
+    padded batch with per-frame valid extents inside the kernels instead (`training.detect_for_training(whole_batch=True)`);
+    `grouped` stays the default;
   * no TensorBoard writer, no `--num-gpus` / launcher: under an initialised `torch.distributed` the rank and world size go
     to the loader and only rank 0 writes metrics, but starting the ranks is the caller's business;
   * metrics are the last iteration's values, not medians over a window; the reference's silence during the first 5
@@ -55,6 +57,9 @@ def get_parser():
     p.add_argument("--image-motion", action="store_true",
                    help="train from still images too: a one-image video becomes a GEN_IMAGE_MOTION clip of TRAIN_LEN frames "
                         "(default: such a video is refused)")
+    p.add_argument("--motion-batch", default="grouped", choices=("grouped", "whole"),
+                   help="with --image-motion: the detector per group of equally sized frames (grouped, the default) or once on the "
+                        "whole padded clip with per-frame valid extents (whole)")
     p.add_argument("--seed", type=int, default=None, metavar="N", help="seed of the data stream (default: cfg.SEED, else drawn)")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER,
                    help="modify config options using the command-line 'KEY VALUE' pairs")
@@ -92,6 +97,8 @@ def metric_line(m, max_iter):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    if args.motion_batch == "whole" and not args.image_motion:
+        return _error("--motion-batch whole needs --image-motion (video clips are one batch already)")
     if (args.config_file is None) == (args.builtin is None):
         return _error("give exactly one of --config-file and --builtin")
     if args.config_file is not None and not os.path.isfile(args.config_file):
@@ -138,7 +145,7 @@ def main(argv=None):
     from .solver import Trainer
     rank, world_size = _distributed()
     model = GoMatching(cfg, load_weights(cfg.MODEL.WEIGHTS))
-    trainer = Trainer(cfg, model, output_dir)
+    trainer = Trainer(cfg, model, output_dir, motion_whole_batch=args.motion_batch == "whole")
     start_iter = trainer.resume() if args.resume else 0
     seed = args.seed
     if args.resume and trainer.data_seed is not None:

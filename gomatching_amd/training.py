@@ -600,7 +600,7 @@ def allreduce_gradients(parameters, group=None):
     return flat.numel()
 
 
-def detect_for_training(impl, params, batched_inputs, taps=None):
+def detect_for_training(impl, params, batched_inputs, taps=None, whole_batch=False):
     """The no-grad detector part of `forward_losses`: the frozen detector on the HIP inference kernels, the rescoring product,
     and the training proposals (no NMS, kept by the score threshold).  -> {"frames": per frame {"image_size",
     "proposal_boxes", "objectness_logits", "query_features", "keep_rows"}, "sizes": per frame (h, w), "padded_hw",
@@ -612,7 +612,12 @@ def detect_for_training(impl, params, batched_inputs, taps=None):
     transformer with `image_hw` = the group's size, the rescoring product, `argmax_rows` and `detect_post` with that size.
     `keep_idx` of a group indexes the group's flattened query axis; results are scattered back to frame order.  Geometry
     tables built for a motion step are not kept (`DeepSolo._geom_transient`): every clip brings new sizes.
-    `taps`: a list that receives, per group, the transformer's tap dict (`DeepSolo.forward(taps=...)`) -- a test's window."""
+    `taps`: a list that receives, per group, the transformer's tap dict (`DeepSolo.forward(taps=...)`) -- a test's window.
+
+    `whole_batch`: a motion clip runs as ONE padded batch with per-frame valid extents inside the kernels (the reference's own
+    form: one batch, per-image masks) -- one backbone pass, one `forward(image_sizes=sizes)`, one rescoring product, one
+    `argmax_rows`, one `detect_post` with a size per frame.  `groups` is then the single entry (padded_hw, [0..B-1]); every frame
+    keeps its own `image_size`.  A step that is not a motion step issues the launches it issues without the flag."""
     torch = _torch()
     from . import ops
     cfg = impl.cfg
@@ -624,10 +629,11 @@ def detect_for_training(impl, params, batched_inputs, taps=None):
         x = impl._normalise(raw, kind)
         motion = kind[0] in ("u8motion", "f32motion")
         sizes = [tuple(int(v) for v in s) for s in kind[4]] if motion else [tuple(kind[1])] * B
+        whole = bool(whole_batch) and motion
         groups = {}
         for t, hw in enumerate(sizes):
             groups.setdefault(hw, []).append(t)
-        groups = list(groups.items())
+        groups = [(tuple(int(v) for v in kind[1]), list(range(B)))] if whole else list(groups.items())
         parts = []
         tr._geom_transient = motion
         try:
@@ -637,7 +643,9 @@ def detect_for_training(impl, params, batched_inputs, taps=None):
                 feats = impl.backbone.forward(xg)
                 feats = [feats[k] for k in impl.feature_names]
                 kw = {}
-                if motion:
+                if whole:
+                    kw["image_sizes"] = sizes
+                elif motion:
                     kw["image_hw"] = hw
                 if taps is not None:
                     taps.append({})
@@ -649,8 +657,13 @@ def detect_for_training(impl, params, batched_inputs, taps=None):
                                   bias=params["roi_heads.rescoring_head.bias"].detach())
                 recs = ops.argmax_rows(out["pred_text_logits"])
                 # training proposals: no NMS (gom_lstmatcher.py:231-258 builds them straight from `detection`), kept by the score threshold
-                det = ops.detect_post(out["pred_logits"], re, out["pred_ctrl_points"], out["pred_bd_points"], recs, Bg, nq, P,
-                                      hw[0], hw[1], impl.test_score_threshold, 2.0, -1.0)
+                if whole:
+                    det = ops.detect_post(out["pred_logits"], re, out["pred_ctrl_points"], out["pred_bd_points"], recs, Bg, nq, P,
+                                          None, None, impl.test_score_threshold, 2.0, -1.0,
+                                          frame_sizes=torch.tensor(sizes, dtype=torch.float32).to(x.device))
+                else:
+                    det = ops.detect_post(out["pred_logits"], re, out["pred_ctrl_points"], out["pred_bd_points"], recs, Bg, nq, P,
+                                          hw[0], hw[1], impl.test_score_threshold, 2.0, -1.0)
                 parts.append((out, det))
         finally:
             tr._geom_transient = False
@@ -668,7 +681,7 @@ def detect_for_training(impl, params, batched_inputs, taps=None):
             for j, t in enumerate(members):
                 n = int(counts[j])
                 rows = torch.from_numpy(keep[j, :n].astype(np.int64)).to(qf_g.device)   # rows of the GROUP's flattened [Bg*nq] query axis
-                frames[t] = {"image_size": hw, "proposal_boxes": det["boxes"][j, :n], "objectness_logits": det["scores"][j, :n],
+                frames[t] = {"image_size": sizes[t], "proposal_boxes": det["boxes"][j, :n], "objectness_logits": det["scores"][j, :n],
                              "query_features": qf_g.index_select(0, rows), "keep_rows": rows - j * nq}
         if len(groups) == 1:
             out = parts[0][0]
@@ -684,12 +697,13 @@ def detect_for_training(impl, params, batched_inputs, taps=None):
             "groups": groups}
 
 
-def forward_losses(model, batched_inputs):
+def forward_losses(model, batched_inputs, motion_whole_batch=None):
     """`GoMatching.forward` in training (gom_lstmatcher.py:213-266) for the META_ARCH wrapper (`compat/d2_register.py`): the
     frozen detector runs on the HIP inference kernels without a tape (`detect_for_training`); the losses of the trainable head
     carry autograd history onto `model.roi_heads`' parameters.  batched_inputs: the reference's list of {"image" [3,H,W],
     "instances": ground truth with gt_boxes / gt_instance_ids / (for loss_res) normalised ctrl points under `polyline` or
-    `ctrl_points`}; in a motion clip every frame keeps its own `image_size` (the reference's per-image `image_sizes`)."""
+    `ctrl_points`}; in a motion clip every frame keeps its own `image_size` (the reference's per-image `image_sizes`).
+    `motion_whole_batch`: `detect_for_training(whole_batch=...)`; None reads `model.motion_whole_batch` (False when absent)."""
     torch = _torch()
     if hasattr(model, "impl"):                                   # the META_ARCH wrapper: live nn.Parameters
         impl = model.impl(for_training=True)
@@ -699,7 +713,9 @@ def forward_losses(model, batched_inputs):
         params = model.trainable_parameters()
     cfg = model.cfg
     P = cfg.MODEL.TRANSFORMER.NUM_POINTS
-    det = detect_for_training(impl, params, batched_inputs)
+    if motion_whole_batch is None:
+        motion_whole_batch = getattr(model, "motion_whole_batch", False)
+    det = detect_for_training(impl, params, batched_inputs, whole_batch=motion_whole_batch)
     frames, targets, res_targets = [], [], []
     for b, inp in enumerate(batched_inputs):
         hw = det["sizes"][b]

@@ -778,6 +778,40 @@ int gom_zero_padded_tokens_f32(float* buf, int ld, int col0, int ncols, const in
                                const int64_t* level_start_index, const int64_t* valid_shapes, int num_levels, int B, long S,
                                void* stream);
 
+/* ---- padded batches whose frames have their OWN valid extents (a motion clip made from a still: one padded size, a valid
+ * rectangle per frame).  Descriptors live on the device: valid_shapes [B][L][2] int64 (Hv, Wv), valid_ratios [B][L][2] fp32
+ * (Wv/W, Hv/H), scales [B][2] fp32 (sx, sy), sizes [B][2] fp32 (img_h, img_w).  Each form computes, for frame b, what the
+ * single-extent entry above computes for a batch of that frame alone -- the same arithmetic, operand for operand. */
+/* ONE launch for the three geometry tables of all B frames and L levels: lvl_pos [B,S,256] (gom_pos_encoding_2d_valid_f32 +
+ * level_embed [L][256]), ref [B,S,2] (gom_encoder_reference_points_masked), valid [B,S] (gom_proposal_valid_masked). */
+int gom_padded_geometry_f32(const float* dim_t128, const float* level_embed, const int64_t* spatial_shapes,
+                            const int64_t* level_start_index, const int64_t* valid_shapes, int num_levels, int B, long S,
+                            float* lvl_pos, float* ref, unsigned char* valid, void* stream);
+int gom_zero_padded_tokens_frames_f32(float* buf, int ld, int col0, int ncols, const int64_t* spatial_shapes,
+                                      const int64_t* level_start_index, const int64_t* valid_shapes, int num_levels, int B,
+                                      long S, void* stream);
+/* gom_topk_tokens with a validity row per frame: valid [B][S] (required). */
+int gom_topk_tokens_frames(const float* logits, int ld, const unsigned char* valid, const float* invalid_logit, int B, long S,
+                           int k, void* workspace, int* idx_out, int* rows_out, void* stream);
+int gom_bezier_reference_points_frames(const float* coord_raw, const int* topk_idx, const int64_t* spatial_shapes,
+                                       const int64_t* level_start_index, const int64_t* valid_shapes, int num_levels,
+                                       const float* bernstein, float* refs, int B, long S, int num_queries, int num_points,
+                                       int compact, void* stream);
+int gom_msda_fused_forward_vr_frames(const float* raw, int ld_raw, const float* ref, const float* value,
+                                     long value_batch_stride, int value_row_stride, const int64_t* spatial_shapes,
+                                     const int64_t* level_start_index, const float* valid_ratios, float* output, int batch,
+                                     int num_query, void* stream);
+/* pair i takes scales[i / pairs_per_frame]; point q takes scales[q / points_per_frame]. */
+int gom_scale_xy_frames_f32(float* x, long n_pairs, const float* scales, long pairs_per_frame, void* stream);
+int gom_ref_update_frames_f32(const float* h, int ld_h, const float* W3, const float* b3, const float* ref,
+                              const float* dim_t128, const float* scales, long points_per_frame, float* new_ref, float* pos,
+                              long num_points, void* stream);
+int gom_detect_post_sizes(const float* cls_logits, int ld_cls, const float* rescoring_logits, int ld_rescoring,
+                          const float* ctrl_points, const float* bd_points, const int* recs, int B, int num_queries,
+                          int num_points, const float* sizes, float det_thresh, float nms_thresh, float asso_thresh,
+                          int* count, int* keep_idx, float* scores, float* boxes, float* ctrl_out, float* bd_out,
+                          long long* recs_out, void* stream);
+
 /* ---- f3: Swin-T backbone glue (third_party/adet/modeling/swin/swin_transformer.py) ---------------------------------
  * The linear layers use the GEMM entry points above.  Tokens are [B,H,W,C] channels-last.  Window rows are ordered
  * (image, window row, window column, token 0..48), windows of 7x7 over the map zero-padded to multiples of 7. */

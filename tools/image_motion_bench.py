@@ -8,12 +8,22 @@ TRAIN_SIZE 1280, TRAIN_LEN 6, fixed seeds, one process, the paths alternating, m
   launch alone  `ops.ingest_motion` on the resident image with device events (the host-side table build and the table upload
                 are in front of the first event's kernel: the figure holds them), the kernel alone into a preallocated batch with
                 resident tables, and a device-to-device copy of as many bytes.
-  Trainer.step  on a motion clip, beside the same step on a 6-frame same-size video clip from the same source at scale 1.0.
+  Trainer.step  on a motion clip with the detector per group of equally sized frames (`--motion-batch grouped`, the default) and
+                once on the whole padded clip with per-frame valid extents (`--motion-batch whole`), beside the same step on a
+                6-frame same-size video clip from the same source at scale 1.0 (the floor); the three alternate.
   groups        detector groups (distinct frame sizes) per clip over 100 planned clips.
   memory        `torch.cuda.memory_allocated` after steps 50, 100, 150 and 200 of a motion run (a new clip every step), and after
                 the clip of step 50 run once more at the end.
 
     python tools/image_motion_bench.py [--repeats 7] > profiles/image_motion_bench.log
+
+Launches per step, in a run of its own (tracing slows the host: no time of that run is reported):
+
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o launches -- python tools/image_motion_bench.py --launches
+    python tools/image_motion_bench.py --count-trace DIR/*/launches_kernel_trace.csv >> profiles/image_motion_bench.log
+
+`--launches` runs two warm-up rounds and then one step of each kind between marker launches (`gom_copy_words` of MARKER_WORDS
+words: a grid no other launch of the run has); `--count-trace` counts the dispatches between the markers.
 """
 import argparse
 import ctypes
@@ -141,26 +151,85 @@ def input_stage(model, cfg, record, repeats):
     return dev_clip
 
 
-def steps(model, cfg, record, dev_clip):
-    tr = solver.Trainer(cfg, model, None)
+KINDS = ("video", "grouped", "whole")                       # the order inside a round
+MARKER_WORDS = 777777                                       # `gom_copy_words` of this many words: cdiv(., 256) * 256 = 777984 threads
+
+
+def step_of(tr, kind, video_clip, dev_clip):
+    tr.motion_whole_batch = kind == "whole"                  # what Trainer(..., motion_whole_batch=) sets; a video step ignores it
+    tr.step(video_clip if kind == "video" else dev_clip)
+
+
+def video_clip_of(cfg, record):
     mapper = data.GoMDatasetMapper(cfg, True, device_ingest=True)
     params = data.resize_crop_params(H, W, mapper.target_size, 1.0, 0.5, 0.5)
-    video_clip = [mapper.map_frame(record, params) for _ in range(FRAMES)]
-    print("Trainer.step (full icdar15 config, %d queries, synthetic weights; alternating, median of 5 after 2 warm-up steps, "
-          "host-synchronised):" % cfg.MODEL.TRANSFORMER.NUM_QUERIES)
-    ts = {"motion": [], "video": []}
-    for i in range(7):
-        for name, clip in (("video", video_clip), ("motion", dev_clip)):
+    return [mapper.map_frame(record, params) for _ in range(FRAMES)]
+
+
+def steps(model, cfg, record, dev_clip, repeats):
+    tr = solver.Trainer(cfg, model, None)
+    video_clip = video_clip_of(cfg, record)
+    print("Trainer.step (full icdar15 config, %d queries, synthetic weights; video / grouped / whole alternating, %d repeats after 2 "
+          "warm-up rounds, host-synchronised):" % (cfg.MODEL.TRANSFORMER.NUM_QUERIES, repeats))
+    ts = {k: [] for k in KINDS}
+    for i in range(repeats + 2):
+        for name in KINDS:
             torch.cuda.synchronize(); t0 = time.perf_counter()
-            tr.step(clip)
+            step_of(tr, name, video_clip, dev_clip)
             torch.cuda.synchronize()
             if i >= 2:
                 ts[name].append(time.perf_counter() - t0)
+    tr.motion_whole_batch = False
     sizes = [fr["crop"][2:] for fr in dev_clip]
     print("   video clip, %d frames of %dx%d (one group)             %s" % (FRAMES, video_clip[0]["crop"][3], video_clip[0]["crop"][2], fmt(ts["video"])))
-    print("   motion clip, %d frames in %d groups %s  %s" % (FRAMES, len(set(sizes)), sorted(set(sizes)), fmt(ts["motion"])))
-    print("   motion / video = %.2f" % (statistics.median(ts["motion"]) / statistics.median(ts["video"])))
+    print("   motion clip, grouped: %d frames in %d groups %s  %s" % (FRAMES, len(set(sizes)), sorted(set(sizes)), fmt(ts["grouped"])))
+    print("   motion clip, whole: one padded batch of %d frames, per-frame valid extents  %s" % (FRAMES, fmt(ts["whole"])))
+    med = {k: statistics.median(v) for k, v in ts.items()}
+    print("   grouped / video = %.2f, whole / video = %.2f, whole / grouped = %.3f" % (med["grouped"] / med["video"], med["whole"] / med["video"],
+                                                                                     med["whole"] / med["grouped"]))
+    if max(ts["whole"]) < min(ts["grouped"]):
+        print("   whole is faster than grouped beyond the spread of the %d repeats" % repeats)
+    elif min(ts["whole"]) > max(ts["grouped"]):
+        print("   whole is SLOWER than grouped beyond the spread of the %d repeats" % repeats)
+    else:
+        print("   whole and grouped are within each other's spread")
     return tr
+
+
+def launches(model, cfg, record):
+    """One step of each kind between marker launches, for a kernel trace (see the module docstring)."""
+    mapper = data.GoMDatasetMapper(cfg, True, device_ingest=True, image_motion=True)
+    dev_clip, _ = clip_of(mapper, record, 3)
+    video_clip = video_clip_of(cfg, record)
+    tr = solver.Trainer(cfg, model, None)
+    a = torch.zeros((MARKER_WORDS,), dtype=torch.int32, device=DEV)
+    b = torch.empty_like(a)
+    for _ in range(2):
+        for name in KINDS:
+            step_of(tr, name, video_clip, dev_clip)
+    torch.cuda.synchronize()
+    for name in KINDS:
+        ops.copy_words(a, b)
+        step_of(tr, name, video_clip, dev_clip)
+        torch.cuda.synchronize()
+    ops.copy_words(a, b)
+    torch.cuda.synchronize()
+
+
+def count_trace(path):
+    import csv
+    with open(path) as f:
+        rows = sorted(csv.DictReader(f), key=lambda r: int(r["Start_Timestamp"]))
+    grid = -(-MARKER_WORDS // 256) * 256
+    marks = [i for i, r in enumerate(rows) if "copy_words_kernel" in r["Kernel_Name"] and
+             int(r.get("Grid_Size") or r.get("Grid_Size_X")) == grid]
+    assert len(marks) == len(KINDS) + 1, "expected %d marker launches in the trace, found %d" % (len(KINDS) + 1, len(marks))
+    print("launches per Trainer.step (kernel dispatches between marker launches of a rocprofv3 --kernel-trace run, every kind of "
+          "dispatch counted: the library's kernels and torch's):")
+    for name, lo, hi in zip(KINDS, marks, marks[1:]):
+        seg = rows[lo + 1:hi]
+        ours = sum(1 for r in seg if "anonymous namespace" in r["Kernel_Name"])
+        print("   %-8s %5d dispatches, %d of them the library's kernels" % (name, len(seg), ours))
 
 
 def groups(cfg, record):
@@ -204,7 +273,11 @@ def memory(model, cfg, record, tr):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--launches", action="store_true", help="one step of each kind between marker launches, for a kernel trace")
+    ap.add_argument("--count-trace", default=None, metavar="CSV", help="count the dispatches per step in the kernel trace of a --launches run")
     args = ap.parse_args()
+    if args.count_trace is not None:
+        return count_trace(args.count_trace)
     cfg = setup_cfg(builtin="icdar15")
     cfg.MODEL.DEVICE = "cuda"
     cfg.MODEL.ASSO_HEAD.DROPOUT = 0.0
@@ -215,8 +288,12 @@ def main():
         record = record_of(root)
         from gomatching_amd.modeling import GoMatching
         model = GoMatching(cfg, synth_state_dict(cfg, seed=7, cls_bias=TRAINING_CLS_BIAS), device=DEV)
+        if args.launches:
+            launches(model, cfg, record)
+            model.close()
+            return
         dev_clip = input_stage(model, cfg, record, args.repeats)
-        tr = steps(model, cfg, record, dev_clip)
+        tr = steps(model, cfg, record, dev_clip, args.repeats)
         groups(cfg, record)
         memory(model, cfg, record, tr)
         model.close()
