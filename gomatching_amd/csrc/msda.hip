@@ -353,6 +353,48 @@ __global__ __launch_bounds__(256) void msda_fused_lanes_kernel(const float* __re
     *reinterpret_cast<f32x4*>(out + (size_t)q_global * (HEADS * CH) + m * CH + k * 4) = acc;
 }
 
+// Where every level's window of a tile lies: its rectangle on the level map (clamped to the map and to its region's capacity) and
+// the first LINE of its region in the workgroup's CAP-line LDS buffer.  One function for both kernel forms and both fill schedules,
+// and for the host replay (gom_msda_window_plan):
+//   * schedule 0 (one level in the buffer at a time): every window starts at line 0 and may take all CAP lines;
+//   * schedule 1 (fills overlapped, see the kernel): windows that are in the buffer TOGETHER get disjoint regions --
+//       level-0 tiles (glv 0):  L0 [0, CAP) alone; then L1 [0, s) with L2 [s, CAP), s = L1's lines rounded up to 8; L3 goes into
+//                               [0, s) while L2 is still being read;
+//       level-1 tiles (glv 1):  L1 [0, CAP) alone; then L2 [0, s) with L3 [s, CAP), s = L2's lines rounded up to 8.
+//     Region starts are multiples of 8 lines (a fill writes whole groups of 8 lines; the tail group re-reads the last line), and
+//     the first window of a pair leaves 8 lines, so no window is ever empty: a sample outside the map (weight 0) reads its
+//     window's first line, which must hold finite values.
+// A window that does not fit is shrunk row-wise; samples outside it take the global path, same bits.  On the shipped pyramids the
+// pairs always fit (largest L1 + L2 = L2 + L3 = 544 lines of 576), so both schedules give the same windows there.
+template <int R, int CAP>
+__host__ __device__ __forceinline__ void msda_window_plan(const int (&Hs)[LEVELS], const int (&Ws)[LEVELS], float rxa, float rya,
+                                                          float rxz, float ryz, int glv, int schedule, int (&wx0)[LEVELS],
+                                                          int (&wy0)[LEVELS], int (&wx1)[LEVELS], int (&wy1)[LEVELS],
+                                                          int (&wwd)[LEVELS], int (&wst)[LEVELS]) {
+    static_assert(CAP % 8 == 0 && CAP >= 16, "regions are whole groups of 8 lines");
+    const int first = glv == 0 ? 1 : 2;                      // schedule 1: the level that shares the buffer with level `first + 1`
+    int split = 0;                                           // first line of the pair's second region
+#pragma unroll
+    for (int i = 0; i < LEVELS; ++i) {
+        int ax = (int)floorf(fminf(rxa, rxz) * Ws[i] - 0.5f) - R, zx = (int)floorf(fmaxf(rxa, rxz) * Ws[i] - 0.5f) + R + 1;
+        int ay = (int)floorf(fminf(rya, ryz) * Hs[i] - 0.5f) - R, zy = (int)floorf(fmaxf(rya, ryz) * Hs[i] - 0.5f) + R + 1;
+        ax = ax > 0 ? ax : 0; ay = ay > 0 ? ay : 0; zx = zx < Ws[i] - 1 ? zx : Ws[i] - 1; zy = zy < Hs[i] - 1 ? zy : Hs[i] - 1;
+        if (zx < ax) zx = ax;
+        if (zy < ay) zy = ay;
+        int start = 0, cap = CAP;
+        if (schedule == 1) {
+            if (i == first) cap = CAP - 8;
+            if (i == first + 1) { start = split; cap = CAP - split; }
+            if (glv == 0 && i == 3) cap = split;             // under level 2's samples, into what level 1 left
+        }
+        int w_ = zx - ax + 1, h_ = zy - ay + 1;
+        if (w_ > cap) { w_ = cap; zx = ax + w_ - 1; }
+        if (w_ * h_ > cap) { h_ = cap / w_; zy = ay + h_ - 1; }   // whatever does not fit is served by the global path
+        if (i == first) split = (w_ * h_ + 7) & ~7;
+        wx0[i] = ax; wy0[i] = ay; wx1[i] = zx; wy1[i] = zy; wwd[i] = w_; wst[i] = start;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // The fused op for the ENCODER's level-0 queries with the value map served from LDS (round 4).
 //
@@ -369,8 +411,19 @@ __global__ __launch_bounds__(256) void msda_fused_lanes_kernel(const float* __re
 //     groups per wave = 128 queries per tile;
 //   * the per-sample arithmetic is the lane-distributed kernel's, instruction for instruction (softmax, location, the four
 //     corner weights x the attention weight, four fused multiply-adds per sample in sample order), so results are BIT-IDENTICAL;
-//   * levels are processed one after the other through one LDS buffer (fill level l, barrier, its four samples of every query);
-//     the accumulation order l = 0..3, p = 0..3 is the kernels' above;
+//   * levels are SAMPLED one after the other, l = 0..3, p = 0..3 (the accumulation order of the kernels above), from one LDS buffer of
+//     CAP lines.  How the windows get there is the fill schedule, OVL:
+//       OVL = 0: one level at a time -- barrier, fill level l, vmcnt(0), barrier, its samples: every line of every window arrives
+//                while the four waves wait for it (eight barriers; only the partner workgroup on the CU hides any of it);
+//       OVL = 1 (default): the owner loads are waited for first, then level 0's window is requested and lands under the owner part
+//                (pure VALU and swizzles, 13.6k of a wave's 44k cycles); levels 1 and 2 are requested together into two regions
+//                of the buffer (msda_window_plan: their line counts never sum to more than 544 of the 576 on the shipped
+//                pyramids); level 3 is requested into level 1's region once level 1 is sampled and lands under level 2's
+//                samples.  Five barriers.  Level-1 tiles (GLV = 1): level 1 in front of the owner part, levels 2 and 3 together,
+//                three barriers instead of five.  Same windows, same bits; the window launches of an encoder call 485 + 168 ->
+//                463 + 161 us alone, 527 + 167 -> 479 + 159 us inside the bench step (profiles/msda_fill_schedule_*).
+//     The rule both follow: a first read of a region comes behind the issuing waves' vmcnt(0) AND a barrier (an LDS-DMA request stays
+//     in flight across s_barrier), a fill into a region behind a barrier that follows the last read of what was there;
 //   * a sample whose clamped corners are not all inside the window makes its wave's octet group (8 queries) take the global-
 //     memory path for that group -- the lane-distributed kernel's arithmetic again, same bits; never taken on the bench workload;
 //   * workgroup id = tile * 8 + head: workgroups go round-robin to the 8 XCDs, so XCD m sees exactly head m's lines (1/8 of the
@@ -380,7 +433,7 @@ __global__ __launch_bounds__(256) void msda_fused_lanes_kernel(const float* __re
 // arithmetic, its accumulation order) instead of served from a window -- for tiles of level-1 queries, whose projection on level 0
 // (twice the pixels per query) is the window that does not fit: an 8 x 16 level-1 tile needs 27 x 43 = 1 161 level-0 lines, its
 // level-1 .. 3 windows 513 + 285 + 195.
-template <int TY, int TX, int R, int CAP, int NB, int GLV = 0>
+template <int TY, int TX, int R, int CAP, int NB, int GLV = 0, int OVL = 0>
 __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __restrict__ value,
                                                              const int64_t* __restrict__ shapes,
                                                              const int64_t* __restrict__ lsi,
@@ -419,19 +472,8 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
     // windows: the projection of the tile's first and last query on every level, R pixels of halo + the second bilinear corner
     const long qa = q0 + (long)y0t * Wq + x0t, qz = q0 + (long)y1t * Wq + x1t;
     const float rxa = ref[qa * 2], rya = ref[qa * 2 + 1], rxz = ref[qz * 2], ryz = ref[qz * 2 + 1];
-    int wx0[LEVELS], wy0[LEVELS], wx1[LEVELS], wy1[LEVELS], wwd[LEVELS];
-#pragma unroll
-    for (int i = 0; i < LEVELS; ++i) {
-        int ax = (int)floorf(fminf(rxa, rxz) * Ws[i] - 0.5f) - R, zx = (int)floorf(fmaxf(rxa, rxz) * Ws[i] - 0.5f) + R + 1;
-        int ay = (int)floorf(fminf(rya, ryz) * Hs[i] - 0.5f) - R, zy = (int)floorf(fmaxf(rya, ryz) * Hs[i] - 0.5f) + R + 1;
-        ax = max(ax, 0); ay = max(ay, 0); zx = min(zx, Ws[i] - 1); zy = min(zy, Hs[i] - 1);
-        if (zx < ax) zx = ax;
-        if (zy < ay) zy = ay;
-        int w_ = zx - ax + 1, h_ = zy - ay + 1;
-        if (w_ > CAP) { w_ = CAP; zx = ax + w_ - 1; }
-        if (w_ * h_ > CAP) { h_ = CAP / w_; zy = ay + h_ - 1; }   // whatever does not fit is served by the global path
-        wx0[i] = ax; wy0[i] = ay; wx1[i] = zx; wy1[i] = zy; wwd[i] = w_;
-    }
+    int wx0[LEVELS], wy0[LEVELS], wx1[LEVELS], wy1[LEVELS], wwd[LEVELS], wst[LEVELS];
+    msda_window_plan<R, CAP>(Hs, Ws, rxa, rya, rxz, ryz, GLV, OVL, wx0, wy0, wx1, wy1, wwd, wst);
     // this lane's level (runtime index l): select with compares, not an indexed array (registers)
     const int H = l == 0 ? Hs[0] : l == 1 ? Hs[1] : l == 2 ? Hs[2] : Hs[3];
     const int W = l == 0 ? Ws[0] : l == 1 ? Ws[1] : l == 2 ? Ws[2] : Ws[3];
@@ -440,6 +482,7 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
     const int mx1 = l == 0 ? wx1[0] : l == 1 ? wx1[1] : l == 2 ? wx1[2] : wx1[3];
     const int my1 = l == 0 ? wy1[0] : l == 1 ? wy1[1] : l == 2 ? wy1[2] : wy1[3];
     const int mww = l == 0 ? wwd[0] : l == 1 ? wwd[1] : l == 2 ? wwd[2] : wwd[3];
+    const int mst = l == 0 ? wst[0] : l == 1 ? wst[1] : l == 2 ? wst[2] : wst[3];   // (0 on every level without OVL)
     const unsigned lvl = l == 0 ? lv[0] : l == 1 ? lv[1] : l == 2 ? lv[2] : lv[3];
     const float Hf = (float)H, Wf = (float)W;
     const float rW = 1.f / Wf, rH = 1.f / Hf;
@@ -452,7 +495,7 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
     // (straight-line code over the ITERS groups: no branch in here or in the level loops, so that the scheduler can overlap the
     // groups' loads, swizzles and LDS reads -- a wave has at most one partner on its SIMD to hide latency behind)
     float sw1[ITERS][2], sw2[ITERS][2], sw3[ITERS][2], sw4[ITERS][2];   // corner weights x the sample's attention weight
-    unsigned pk[ITERS][2];                                   // LDS byte address of corner (yc0, xc0) | dx << 20 | dy << 21
+    unsigned pk[ITERS][2];                                   // LDS byte address of corner (yc0, xc0) in `win` | dx << 20 | dy << 21
     unsigned go1[GLV ? ITERS : 1][2], go2[GLV ? ITERS : 1][2], go3[GLV ? ITERS : 1][2], go4[GLV ? ITERS : 1][2];   // GLV: global corner offsets
     f32x4 acc[ITERS];
     long qrow[ITERS];
@@ -474,6 +517,34 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
         lgb[it] = lp[1];
         rxs[it] = ref[q_global * 2];
         rys[it] = ref[q_global * 2 + 1];
+    }
+    // Fill = LDS-DMA (buffer_load_dwordx4 ... lds): a wave-instruction moves 8 lines (1 KB) into 8 consecutive window lines,
+    // every lane from its own source address; all requests of a level are in flight together.  (Rounds 4-5 also carried a double-
+    // buffered form -- the next level's fill under this level's samples, one workgroup per CU -- and forms with two / four corner
+    // addresses computed at the owner, a DPP broadcast: none faster, tools/exp + docs/LAB_NOTES.md; removed in round 6.)
+    auto fill = [&](auto LEVC) {
+        constexpr int lev = decltype(LEVC)::value;
+        unsigned char* buf = win + (size_t)wst[lev] * 128;      // the level's region (line 0 without OVL)
+        const int ww_ = wwd[lev], n_lines = ww_ * (wy1[lev] - wy0[lev] + 1);
+        const float inv_w = 1.f / (float)ww_;
+        for (int base = wave * 8; base < n_lines; base += 32) {
+            int line = base + g;
+            if (line > n_lines - 1) line = n_lines - 1;      // the tail of the last group re-reads the last line
+            int yy = (int)(((float)line + 0.5f) * inv_w);
+            int xx = line - yy * ww_;
+            if (xx < 0) { --yy; xx += ww_; }
+            if (xx >= ww_) { ++yy; xx -= ww_; }
+            const unsigned src = (lv[lev] + (unsigned)((wy0[lev] + yy) * Ws[lev] + wx0[lev] + xx)) * (unsigned)v_rs * 4u + head + mine;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(buf + (size_t)base * 128), 16,
+                                                     (int)src, 0, 0, 0);
+        }
+    };
+    if constexpr (OVL != 0) {
+        // the owner loads are CONSUMED here (the compiler waits for a load in front of the first instruction that names its
+        // register): behind the fill loop, whose trip count is not known, its wait for them would be vmcnt(0) and drain the fill
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) asm volatile("" : "+v"(offs[it]), "+v"(lga[it]), "+v"(lgb[it]), "+v"(rxs[it]), "+v"(rys[it]));
+        fill(std::integral_constant<int, GLV>{});            // the first window lands under the owner part (no vector memory in there)
     }
     // geometry of sample (IT, T) of this lane (a macro, not a lambda: the arrays must be indexed by literals to stay in registers)
 #define MSDA_GEOMETRY(IT, T, OFF4, RX, RY, E, INV_SUM, OK, SO)                                                    \
@@ -508,7 +579,7 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
         OK = !inside || l < GLV || (yc0 >= my0 && yc1 <= my1 && xc0 >= mx0 && xc1 <= mx1);                        \
         const bool use = inside && OK; /* (an address inside the buffer in every case) */                         \
         const int ly0 = use ? yc0 - my0 : 0, lx0 = use ? xc0 - mx0 : 0;                                           \
-        const unsigned la_ = (unsigned)((ly0 * mww + lx0) * 128);                                                 \
+        const unsigned la_ = (unsigned)((mst + ly0 * mww + lx0) * 128);                                           \
         pk[IT][T] = la_ | ((use && xc1 != xc0) ? (1u << 20) : 0u) | ((use && yc1 != yc0) ? (1u << 21) : 0u);      \
     }
     unsigned any_slow = 0;
@@ -542,31 +613,16 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
     }
 
     // ---- level by level: fill the window, then the level's four samples of every octet group ----
-    // Fill = LDS-DMA (buffer_load_dwordx4 ... lds): a wave-instruction moves 8 lines (1 KB) into 8 consecutive window lines,
-    // every lane from its own source address; all requests of a level are in flight together.  (Rounds 4-5 also carried a double-
-    // buffered form -- the next level's fill under this level's samples, one workgroup per CU -- and forms with two / four corner
-    // addresses computed at the owner, a DPP broadcast: none faster, tools/exp + docs/LAB_NOTES.md; removed in round 6.)
     // (the level is a compile-time constant of every call: as a run-time loop the compiler keeps `lev` in a register, indexes the
     // windows' arrays in scratch and turns every literal owner of a broadcast into an eight-way branch)
-    auto fill = [&](auto LEVC, unsigned char* buf) {
-        constexpr int lev = decltype(LEVC)::value;
-        const int ww_ = wwd[lev], n_lines = ww_ * (wy1[lev] - wy0[lev] + 1);
-        const float inv_w = 1.f / (float)ww_;
-        for (int base = wave * 8; base < n_lines; base += 32) {
-            int line = base + g;
-            if (line > n_lines - 1) line = n_lines - 1;      // the tail of the last group re-reads the last line
-            int yy = (int)(((float)line + 0.5f) * inv_w);
-            int xx = line - yy * ww_;
-            if (xx < 0) { --yy; xx += ww_; }
-            if (xx >= ww_) { ++yy; xx -= ww_; }
-            const unsigned src = (lv[lev] + (unsigned)((wy0[lev] + yy) * Ws[lev] + wx0[lev] + xx)) * (unsigned)v_rs * 4u + head + mine;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(buf + (size_t)base * 128), 16,
-                                                     (int)src, 0, 0, 0);
-        }
-    };
     auto bcast = [](float v, int owner) { return group8_read(v, owner); };
-    auto level_samples = [&](auto LEVC, const unsigned char* buf) {
+    // UNDERC (OVL): the level is read while ANOTHER region's fill is in flight.  The compiler puts `s_waitcnt vmcnt(0)` in front of
+    // the first LDS load that follows an LDS-DMA request (it cannot tell the regions apart), which would drain that fill; so the
+    // sixteen reads of a batch are issued as bare instructions, which it does not track, and are waited for here: LDS operations
+    // return in order, so lgkmcnt(4 (NB - 1 - u)) means group u's four lines have arrived.  Same addresses, same values.
+    auto level_samples = [&](auto LEVC, const unsigned char* buf, auto UNDERC) {
         constexpr int lev = decltype(LEVC)::value;
+        constexpr bool under = decltype(UNDERC)::value;
         typedef __attribute__((address_space(3))) f32x4 LdsF4;
         const unsigned mine_lds = mine + (unsigned)(size_t)buf;   // (a flat LDS address: its low word is the LDS offset)
         const unsigned row_bytes = (unsigned)wwd[lev] * 128u;
@@ -606,10 +662,23 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
                     asm volatile("" : "+v"(a2), "+v"(a3), "+v"(a4));
                     // (absolute LDS addresses -- the window's offset rides in `mine_lds`: as `buf + a` behind the opaque asm the
                     // compiler spends one v_add_u32 per read on a base it cannot fold, 4 of ~30 vector instructions per sample)
-                    v1[u] = *reinterpret_cast<const LdsF4*>((size_t)a1);
-                    v2[u] = *reinterpret_cast<const LdsF4*>((size_t)a2);
-                    v3[u] = *reinterpret_cast<const LdsF4*>((size_t)a3);
-                    v4[u] = *reinterpret_cast<const LdsF4*>((size_t)a4);
+                    if constexpr (under) {
+                        asm volatile("ds_read_b128 %0, %1" : "=&v"(v1[u]) : "v"(a1));
+                        asm volatile("ds_read_b128 %0, %1" : "=&v"(v2[u]) : "v"(a2));
+                        asm volatile("ds_read_b128 %0, %1" : "=&v"(v3[u]) : "v"(a3));
+                        asm volatile("ds_read_b128 %0, %1" : "=&v"(v4[u]) : "v"(a4));
+                    } else {
+                        v1[u] = *reinterpret_cast<const LdsF4*>((size_t)a1);
+                        v2[u] = *reinterpret_cast<const LdsF4*>((size_t)a2);
+                        v3[u] = *reinterpret_cast<const LdsF4*>((size_t)a3);
+                        v4[u] = *reinterpret_cast<const LdsF4*>((size_t)a4);
+                    }
+                }
+                if constexpr (under) {
+                    static_assert(4 * (NB - 1) < 16, "lgkmcnt counts to 15");
+#pragma unroll
+                    for (int u = 0; u < NB; ++u)
+                        asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(v1[u]), "+v"(v2[u]), "+v"(v3[u]), "+v"(v4[u]) : "n"(4 * (NB - 1 - u)));
                 }
 #pragma unroll
                 for (int u = 0; u < NB; ++u) {
@@ -625,10 +694,10 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
 #define MSDA_LEVEL_SINGLE(L)                                                                                      \
     {                                                                                                             \
         __syncthreads(); /* the previous level's reads are done */                                                \
-        fill(std::integral_constant<int, L>{}, win);                                                              \
+        fill(std::integral_constant<int, L>{});                                                                   \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                          \
         __syncthreads();                                                                                          \
-        level_samples(std::integral_constant<int, L>{}, win);                                                     \
+        level_samples(std::integral_constant<int, L>{}, win, std::false_type{});                                  \
     }
     // GLV: the four samples of a GATHERED level -- the lane-distributed kernel's inner loop (corner offsets broadcast from the owner
     // lane, four 16-byte loads of the head's 128-byte slices, the same products in the same order)
@@ -679,21 +748,58 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
         }
     };
     static_assert(GLV == 0 || GLV == 1, "only the finest level is ever gathered");
-    if constexpr (GLV == 0) {
-        MSDA_LEVEL_SINGLE(0)
-    } else {
+    static_assert(OVL == 0 || OVL == 1, "two fill schedules");
+    // Every first read of a region has the issuing waves' vmcnt(0) and a barrier in front of it (an LDS-DMA request stays in flight
+    // across s_barrier); every fill into a region has a barrier behind the last read of what was there.
+#define MSDA_LANDED()                                                                                             \
+    {                                                                                                             \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                          \
+        __syncthreads();                                                                                          \
+    }
+    if constexpr (OVL == 0 && GLV == 0) {
+        MSDA_LEVEL_SINGLE(0) MSDA_LEVEL_SINGLE(1) MSDA_LEVEL_SINGLE(2) MSDA_LEVEL_SINGLE(3)
+    } else if constexpr (OVL == 0) {
         // level 1's window is requested first and lands under level 0's gathers (accumulation order l = 0, 1, 2, 3 as everywhere)
-        fill(std::integral_constant<int, 1>{}, win);
+        fill(std::integral_constant<int, 1>{});
         level_gather(std::integral_constant<int, 0>{});
-    }
-    if constexpr (GLV == 0) {
-        MSDA_LEVEL_SINGLE(1)
+        MSDA_LANDED()
+        level_samples(std::integral_constant<int, 1>{}, win, std::false_type{});
+        MSDA_LEVEL_SINGLE(2) MSDA_LEVEL_SINGLE(3)
+    } else if constexpr (GLV == 0) {
+        // OVL, level-0 tiles: L0 was requested in front of the owner part; L1 and L2 arrive together; L3 lands under L2's samples
+        // in the region L1 has left.  Five barriers (eight without OVL).
+        // (the owner part's results are named here: otherwise the compiler sinks a quarter of it behind the wait)
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it)
+            asm volatile("" ::"v"(pk[it][0]), "v"(pk[it][1]), "v"(sw1[it][0]), "v"(sw2[it][0]), "v"(sw3[it][0]), "v"(sw4[it][0]),
+                         "v"(sw1[it][1]), "v"(sw2[it][1]), "v"(sw3[it][1]), "v"(sw4[it][1]));
+        __builtin_amdgcn_sched_barrier(0);
+        MSDA_LANDED()
+        level_samples(std::integral_constant<int, 0>{}, win, std::false_type{});
+        __syncthreads();                                      // L0's reads are done
+        fill(std::integral_constant<int, 1>{});
+        fill(std::integral_constant<int, 2>{});
+        MSDA_LANDED()
+        level_samples(std::integral_constant<int, 1>{}, win, std::false_type{});
+        __syncthreads();                                      // L1's reads are done: its region takes L3
+        fill(std::integral_constant<int, 3>{});
+        level_samples(std::integral_constant<int, 2>{}, win, std::true_type{});
+        MSDA_LANDED()
+        level_samples(std::integral_constant<int, 3>{}, win, std::false_type{});
     } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        level_samples(std::integral_constant<int, 1>{}, win);
+        // OVL, level-1 tiles: L1 was requested in front of the owner part and lands under it and the level-0 gathers; L2 and L3
+        // arrive together and are sampled back to back.  Three barriers (five without OVL).
+        level_gather(std::integral_constant<int, 0>{});
+        MSDA_LANDED()
+        level_samples(std::integral_constant<int, 1>{}, win, std::false_type{});
+        __syncthreads();                                      // L1's reads are done
+        fill(std::integral_constant<int, 2>{});
+        fill(std::integral_constant<int, 3>{});
+        MSDA_LANDED()
+        level_samples(std::integral_constant<int, 2>{}, win, std::false_type{});
+        level_samples(std::integral_constant<int, 3>{}, win, std::false_type{});
     }
-    MSDA_LEVEL_SINGLE(2) MSDA_LEVEL_SINGLE(3)
+#undef MSDA_LANDED
 #undef MSDA_LEVEL_SINGLE
     if (any_slow) {
         if (slow_groups && lane == 0) {                       // diagnostic count (gom_msda_window_count_fallbacks): octet groups on the global path
@@ -787,13 +893,14 @@ extern "C" int gom_msda_fused_forward(const float* raw, int ld_raw, const float*
     return gom_launch_status();
 }
 
-static int g_msda_window = 3;
+static int g_msda_window = 7;
 static unsigned* g_msda_slow = nullptr;
 /* [host] which encoder queries the entry below serves from LDS windows: bit 0 = the level-0 pixels (8 x 16 tiles, round 4), bit 1 =
- * the level-1 pixels (4 x 8 tiles, round 6); default 3 = both, 0 = everything on the lane-distributed kernel (A/B runs, tests).
- * Same bits either way. */
+ * the level-1 pixels (8 x 16 tiles, level 0 gathered, round 6); bit 2 = the overlapped fill schedule of the window kernel (the
+ * first window requested in front of the owner part, the others in pairs) instead of one fill at a time; default 7 = all three,
+ * 0 = everything on the lane-distributed kernel (A/B runs, tests).  Same bits either way. */
 extern "C" int gom_msda_set_window(int mask) {
-    g_msda_window = mask < 0 ? 0 : (mask & 3);
+    g_msda_window = mask < 0 ? 0 : (mask & 7);
     return GOM_OK;
 }
 /* [host] diagnostic: a device word that every window workgroup adds its FALLBACK octet groups to (groups of 8 (query, head) pairs
@@ -826,8 +933,9 @@ extern "C" int gom_msda_fused_forward_encoder(const float* raw, int ld_raw, cons
         return gom_msda_fused_forward(raw, ld_raw, ref, value, value_batch_stride, value_row_stride, spatial_shapes,
                                       level_start_index, output, batch, num_query, stream);
     hipStream_t s = (hipStream_t)stream;
+    const bool ovl = (g_msda_window & 4) != 0;
     {
-        auto kern = msda_window_kernel<TY0, TX0, R, CAP, 4>;
+        auto kern = ovl ? msda_window_kernel<TY0, TX0, R, CAP, 4, 0, 1> : msda_window_kernel<TY0, TX0, R, CAP, 4, 0, 0>;
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * 128);
         if (e != hipSuccess) return GOM_ERR_HIP_BASE + (int)e;
         hipLaunchKernelGGL(kern, dim3((unsigned)wgs0), dim3(256), CAP * 128, s, value, spatial_shapes, level_start_index, raw, ld_raw,
@@ -835,7 +943,7 @@ extern "C" int gom_msda_fused_forward_encoder(const float* raw, int ld_raw, cons
     }
     long done = n0;
     if ((g_msda_window & 2) && n1 > 0) {
-        auto kern = msda_window_kernel<TY1, TX1, R, CAP, 4, 1>;
+        auto kern = ovl ? msda_window_kernel<TY1, TX1, R, CAP, 4, 1, 1> : msda_window_kernel<TY1, TX1, R, CAP, 4, 1, 0>;
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * 128);
         if (e != hipSuccess) return GOM_ERR_HIP_BASE + (int)e;
         hipLaunchKernelGGL(kern, dim3((unsigned)wgs1), dim3(256), CAP * 128, s, value, spatial_shapes, level_start_index, raw, ld_raw,
@@ -848,6 +956,34 @@ extern "C" int gom_msda_fused_forward_encoder(const float* raw, int ld_raw, cons
                            spatial_shapes, level_start_index, raw, ld_raw, ref, output, batch, num_query, value_batch_stride,
                            value_row_stride, (const float*)nullptr, (int)done, (int)rest);
     return gom_launch_status();
+}
+
+/* [host] launches nothing: the windows of ONE tile of the encoder entry above, as the kernel computes them (the same function).
+ * spatial_shapes: 4 x (H, W) in HOST memory; tile_level 0 / 1: a tile of level-0 / level-1 queries; ref_first / ref_last: the
+ * reference points (x, y) of the tile's first and last query; schedule 0 / 1 as bit 2 of gom_msda_set_window.
+ * plan[level] = (first line in the workgroup's buffer, width, rows) -- a level the tile gathers from global memory (level 0 of a
+ * level-1 tile) gets (0, 0, 0).  Returns the buffer's capacity in lines through *cap_lines. */
+extern "C" int gom_msda_window_plan(const int64_t* spatial_shapes, int tile_level, const float* ref_first, const float* ref_last,
+                                    int schedule, int* plan, int* cap_lines) {
+    GOM_CHECK_ARG(spatial_shapes && ref_first && ref_last && plan && cap_lines);
+    GOM_CHECK_ARG((tile_level == 0 || tile_level == 1) && (schedule == 0 || schedule == 1));
+    constexpr int R = 5, CAP = 576;                          // gom_msda_fused_forward_encoder's
+    int Hs[LEVELS], Ws[LEVELS], wx0[LEVELS], wy0[LEVELS], wx1[LEVELS], wy1[LEVELS], wwd[LEVELS], wst[LEVELS];
+    for (int i = 0; i < LEVELS; ++i) {
+        GOM_CHECK_ARG(spatial_shapes[2 * i] > 0 && spatial_shapes[2 * i + 1] > 0);
+        Hs[i] = (int)spatial_shapes[2 * i];
+        Ws[i] = (int)spatial_shapes[2 * i + 1];
+    }
+    msda_window_plan<R, CAP>(Hs, Ws, ref_first[0], ref_first[1], ref_last[0], ref_last[1], tile_level, schedule, wx0, wy0, wx1, wy1,
+                             wwd, wst);
+    for (int i = 0; i < LEVELS; ++i) {
+        const bool gathered = i < tile_level;
+        plan[3 * i] = gathered ? 0 : wst[i];
+        plan[3 * i + 1] = gathered ? 0 : wwd[i];
+        plan[3 * i + 2] = gathered ? 0 : wy1[i] - wy0[i] + 1;
+    }
+    *cap_lines = CAP;
+    return GOM_OK;
 }
 
 extern "C" int gom_msda_fused_forward_vr(const float* raw, int ld_raw, const float* ref, const float* value,

@@ -41,6 +41,7 @@ SIGNATURES = {
     "gom_msda_fused_forward_encoder": (I, [P, I, P, P, L, I, P, P, P, I, I, I, I, I, I, P]),
     "gom_msda_set_window": (I, [I]),
     "gom_msda_window_count_fallbacks": (I, [P]),
+    "gom_msda_window_plan": (I, [P, I, P, P, I, P, P]),
     "gom_msda_prepare": (I, [P, I, P, I, P, P, P, L, P]),
     "gom_gemm_f32": (I, [P, P, P, I, P, I, P, P, P, I, I, P, I, I, I, I, P]),
     "gom_gemm_splitk_workspace_bytes": (L, [I, I, I]),

@@ -1201,6 +1201,9 @@ MSDA_WINDOW = _switch("MSDA_WINDOW")   # encoder calls: level-0 queries served f
 # would be 1 161 lines) and whose level-1 .. 3 samples come from windows: bit-identical, encoder call 830 -> 808 us.  (4 x 8 tiles with
 # all four levels from windows were slower: 958 vs 865 us; profiles/r06_msda_level1_windows_and_offset_scale.log)
 MSDA_WINDOW_L1 = _switch("MSDA_WINDOW_L1")
+# ... with the window kernel's overlapped fill schedule: the first window is requested in front of the owner part, the others in
+# pairs that share the buffer (same windows on the shipped pyramids, same bits; off = one fill at a time, barriers on both sides)
+MSDA_WINDOW_OVERLAP = _switch("MSDA_WINDOW_OVERLAP")
 _msda_window_set = [None]
 
 
@@ -1252,7 +1255,7 @@ def msda_fused(raw, ref, value2d, batch_stride, shapes, lsi, B, Lq, valid_ratios
                                                  value2d.stride(0), _p(shapes), _p(lsi), _p(valid_ratios), _p(out), B, Lq,
                                                  _stream()), "gom_msda_fused_forward_vr")
         elif encoder_hw0 is not None and MSDA_WINDOW and MSDA_LANES:
-            mask = 3 if MSDA_WINDOW_L1 else 1
+            mask = (3 if MSDA_WINDOW_L1 else 1) | (4 if MSDA_WINDOW_OVERLAP else 0)
             if _msda_window_set[0] != mask:
                 _L().gom_msda_set_window(mask)
                 _msda_window_set[0] = mask

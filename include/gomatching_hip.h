@@ -96,10 +96,18 @@ int gom_msda_fused_forward(const float* raw, int ld_raw, const float* ref, const
  * + 5 pixels of halo; level-1 tiles (round 6) gather their level-0 samples from global memory instead (that window does not fit);
  * an octet group with a sample outside its window falls back to global memory -- the coarser levels' queries run on the kernel of
  * gom_msda_fused_forward.  Bit-identical to gom_msda_fused_forward.
- * [host] gom_msda_set_window(mask): bit 0 = level-0 windows, bit 1 = level-1 windows (default 3), 0 = always the gather kernel.
- * [host] gom_msda_window_count_fallbacks(ptr): diagnostic device word the window launches add their fallback octet groups to. */
+ * [host] gom_msda_set_window(mask): bit 0 = level-0 windows, bit 1 = level-1 windows, bit 2 = the window kernel's overlapped fill
+ *        schedule (the first window requested in front of the owner part, the others in pairs that share the buffer) instead of
+ *        one fill at a time (default 7); 0 = always the gather kernel.
+ * [host] gom_msda_window_count_fallbacks(ptr): diagnostic device word the window launches add their fallback octet groups to.
+ * [host] gom_msda_window_plan: launches nothing; the windows of ONE tile as the kernel lays them out.  spatial_shapes: 4 x (H, W) in
+ *        HOST memory; tile_level 0 / 1 (a tile of level-0 / level-1 queries); ref_first / ref_last: the reference points (x, y) of the
+ *        tile's first and last query; schedule 0 / 1 as bit 2 above.  plan[3 * level + 0 .. 2] = first line in the workgroup's buffer,
+ *        width, rows ((0, 0, 0) for a level the tile gathers from global memory); *cap_lines = the buffer's lines. */
 int gom_msda_set_window(int mask);
 int gom_msda_window_count_fallbacks(unsigned int* device_counter);
+int gom_msda_window_plan(const int64_t* spatial_shapes, int tile_level, const float* ref_first, const float* ref_last, int schedule,
+                         int* plan, int* cap_lines);
 int gom_msda_fused_forward_encoder(const float* raw, int ld_raw, const float* ref, const float* value, long value_batch_stride,
                                    int value_row_stride, const int64_t* spatial_shapes, const int64_t* level_start_index,
                                    float* output, int batch, int num_query, int h0, int w0, int h1, int w1, void* stream);

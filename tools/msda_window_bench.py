@@ -33,9 +33,11 @@ import hashlib                                                    # noqa: E402
 
 
 def run(mask, rv_=None):
-    """mask 0: everything on the lane-distributed (gather) kernel; 1: level-0 queries from LDS windows; 3: level-0 and level-1."""
+    """mask as gom_msda_set_window's: 0: everything on the lane-distributed (gather) kernel; bit 0: level-0 queries from LDS windows;
+    bit 1: level-1 queries too; bit 2: the overlapped fill schedule (1 / 3 = one fill at a time, 5 / 7 = overlapped)."""
     ops.MSDA_WINDOW = mask != 0
-    ops.MSDA_WINDOW_L1 = mask == 3
+    ops.MSDA_WINDOW_L1 = bool(mask & 2)
+    ops.MSDA_WINDOW_OVERLAP = bool(mask & 4)
     r = rv if rv_ is None else rv_
     return ops.msda_fused(r, geo["enc_ref"], r[:, 384:], S * 640, geo["shapes"], geo["lsi"], B, S, None, encoder_hw0=geo["hw0"])
 
@@ -51,12 +53,34 @@ def burst(mask, n=10, rv_=None):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
-a, b, c = run(0), run(1), run(3)
-print("sha1 gather %s windows %s" % (hashlib.sha1(a.cpu().numpy().tobytes()).hexdigest()[:16], hashlib.sha1(c.cpu().numpy().tobytes()).hexdigest()[:16]))
-print("bit-identical:", bool(torch.equal(a, b)), bool(torch.equal(a, c)), "max |d| %.3e" % float((a - c).abs().max()))
-for rnd in range(4):
+a, b, c, d, e = run(0), run(1), run(3), run(5), run(7)
+print("sha1 gather %s windows %s" % (hashlib.sha1(a.cpu().numpy().tobytes()).hexdigest()[:16], hashlib.sha1(e.cpu().numpy().tobytes()).hexdigest()[:16]))
+print("bit-identical:", bool(torch.equal(a, b)), bool(torch.equal(a, c)), bool(torch.equal(a, d)), bool(torch.equal(a, e)),
+      "max |d| %.3e" % float((a - e).abs().max()))
+for rnd in range(2):
     print("round %d: gather kernel %.1f us | level-0 windows + gather for the rest %.1f us | level-0 + level-1 windows + gather for levels 2-3 %.1f us"
           % (rnd, burst(0), burst(1), burst(3)), flush=True)
+
+
+def schedule_ab(rv_, what, pairs=6):
+    """The two fill schedules alternating in this process, one burst each per pair.  Mask 1 against 5 moves only the level-0 form
+    (the level-1 queries ride on the gather kernel in both); the level-1 form is the difference between 3 - 1 and 7 - 5."""
+    wins = {"level-0 form": 0, "both forms": 0, "level-1 form": 0}
+    for rnd in range(pairs):
+        t1, t5, t3, t7 = burst(1, 10, rv_), burst(5, 10, rv_), burst(3, 10, rv_), burst(7, 10, rv_)
+        wins["level-0 form"] += t5 < t1
+        wins["both forms"] += t7 < t3
+        wins["level-1 form"] += (t7 - t5) < (t3 - t1)
+        print("%s pair %d: level-0 windows, one fill at a time %.1f us -> overlapped %.1f us (%+.1f) | level-0 + level-1 windows %.1f -> %.1f us "
+              "(%+.1f) | level-1 launch alone (by difference) %.1f -> %.1f us" % (what, rnd, t1, t5, t5 - t1, t3, t7, t7 - t3, t3 - t1, t7 - t5),
+              flush=True)
+    print("%s: overlapped faster in %s of %d pairs" % (what, wins, pairs), flush=True)
+
+
+schedule_ab(None, "bench offsets")
+r2x = rv.clone()
+r2x[:, :256] *= 2.0
+schedule_ab(r2x, "offsets x 2", pairs=5)
 
 # ---- what the window assumption is worth when the offsets are larger than the synthetic weights make them (VERDICT r5 3b): the
 #      sampling offsets (raw columns [0, 256), in pixels of the sampled level) scaled x1 / x2 / x4; halo R = 5 pixels ----
@@ -72,10 +96,10 @@ for scale in (1.0, 2.0, 4.0):
     r2[:, :256] *= scale
     counter.zero_()
     ref_out = run(0, r2)
-    got = run(3, r2)
+    got = run(7, r2)
     torch.cuda.synchronize()
     slow = int(counter.item())
     print("offsets x %.0f: %6.2f %% of the octet groups fall back to the gather path (%d of %d), bit-identical %s | gather %.1f us, "
           "level-0 windows %.1f us, level-0 + level-1 windows %.1f us"
-          % (scale, 100.0 * slow / groups, slow, groups, bool(torch.equal(ref_out, got)), burst(0, 10, r2), burst(1, 10, r2), burst(3, 10, r2)), flush=True)
+          % (scale, 100.0 * slow / groups, slow, groups, bool(torch.equal(ref_out, got)), burst(0, 10, r2), burst(5, 10, r2), burst(7, 10, r2)), flush=True)
 Lh.gom_msda_window_count_fallbacks(None)

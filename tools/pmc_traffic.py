@@ -21,8 +21,15 @@ def per_kernel(path, counter, api_grids):
             agg[name].append(float(r["Counter_Value"]))
             if name.startswith("msda_fused_lanes_kernel<"):  # encoder tail / decoder launches of the lane kernel apart, by grid size
                 agg[name + " [grid %d]" % int(r["Grid_Size"])].append(float(r["Counter_Value"]))
+            if name == "msda_fused_lanes_kernel<0>":         # bench.py's keys: the unpadded form was <false> while VR was a bool
+                agg["msda_fused_lanes_kernel<false>"].append(float(r["Counter_Value"]))
+                agg["msda_fused_lanes_kernel<false> [grid %d]" % int(r["Grid_Size"])].append(float(r["Counter_Value"]))
             if name.startswith("msda_window_kernel<"):
                 agg["msda_window_kernel"].append(float(r["Counter_Value"]))
+                # bench.py asks for a form by its first six parameters; the seventh is the fill schedule (1 = overlapped, the default)
+                head, _, sched = name.rpartition(",")
+                if head.count(",") == 5:
+                    agg[head + ">"].append(float(r["Counter_Value"]))
             if name.startswith("bneck_kernel<") or name.startswith("bneck2_kernel<"):   # every fused bottleneck launch together as well
                 agg["bneck_kernel"].append(float(r["Counter_Value"]))
             if name.startswith("proj_ln_kernel<") or name.startswith("proj_ln2_kernel<"):   # both forms, all three FORMs
