@@ -37,15 +37,50 @@ __device__ __forceinline__ double cross3(const RowsLds& L, int o, int a, int b) 
     return (L.sx[a] - L.sx[o]) * (L.sy[b] - L.sy[o]) - (L.sy[a] - L.sy[o]) * (L.sx[b] - L.sx[o]);
 }
 
-__global__ __launch_bounds__(64 * RR_WAVES) void result_rows_kernel(const float* __restrict__ bd,
-                                                                    const int64_t* __restrict__ recs,
-                                                                    const int64_t* __restrict__ track_ids, int n,
-                                                                    int voc_size, int* __restrict__ out, int ld) {
+// Where instance k's operands come from.  `Packed`: instance k is row k of bd / recs / track_ids, as a clip's concatenated
+// fields are (gom_result_rows_i32).  `Gathered`: a descriptor names a row of a ring of cap rows, the track id and the frame's
+// scale pair, and the point is scaled here as scale_xy_kernel (elementwise.hip) scales it: one fp32 product per coordinate,
+// rounded once (gom_result_rows_gather_i32).
+struct Packed {
+    const float* __restrict__ bd;
+    const int64_t* __restrict__ recs;
+    const int64_t* __restrict__ track_ids;
+    __device__ __forceinline__ long row(long k) const { return k; }
+    __device__ __forceinline__ void point(long k, const float* p, float& fx, float& fy) const {
+        fx = p[0];
+        fy = p[1];
+    }
+    __device__ __forceinline__ long long track_id(long k) const { return track_ids ? track_ids[k] : 0; }
+};
+
+struct Gathered {
+    const float* __restrict__ bd;
+    const int64_t* __restrict__ recs;
+    const int* __restrict__ desc;                    // [n][GOM_RR_DESC_WORDS]
+    long cap;
+    __device__ __forceinline__ long row(long k) const {          // never outside the ring, whatever the descriptor holds
+        const long r = desc[k * GOM_RR_DESC_WORDS];
+        return r < 0 ? 0 : (r >= cap ? cap - 1 : r);
+    }
+    __device__ __forceinline__ void point(long k, const float* p, float& fx, float& fy) const {
+        fx = p[0] * __int_as_float(desc[k * GOM_RR_DESC_WORDS + 3]);
+        fy = p[1] * __int_as_float(desc[k * GOM_RR_DESC_WORDS + 4]);
+    }
+    __device__ __forceinline__ long long track_id(long k) const {
+        const unsigned long long lo = (unsigned)desc[k * GOM_RR_DESC_WORDS + 1], hi = (unsigned)desc[k * GOM_RR_DESC_WORDS + 2];
+        return (long long)(lo | (hi << 32));
+    }
+};
+
+template <class Src>
+__global__ __launch_bounds__(64 * RR_WAVES) void result_rows_kernel(const Src src, int n, int voc_size, int* __restrict__ out,
+                                                                    int ld) {
     __shared__ RowsLds lds[RR_WAVES];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long k = (long)blockIdx.x * RR_WAVES + w;
     const bool active = k < n;                       // a tail wave recomputes the last instance and stores nothing,
     const long kk = active ? k : (long)n - 1;        // so that every wave reaches every barrier
+    const long src_row = src.row(kk);
     RowsLds& L = lds[w];
     int* row = out + kk * (long)ld;
 
@@ -53,9 +88,7 @@ __global__ __launch_bounds__(64 * RR_WAVES) void result_rows_kernel(const float*
     float fx = 0.f, fy = 0.f;
     if (lane < RR_PTS) {
         const int r = lane < RR_P ? lane : RR_PTS - 1 - lane;
-        const float* p = bd + kk * (RR_P * 4) + r * 4 + (lane < RR_P ? 0 : 2);
-        fx = p[0];
-        fy = p[1];
+        src.point(kk, src.bd + src_row * (RR_P * 4) + r * 4 + (lane < RR_P ? 0 : 2), fx, fy);
         if (active) {
             row[GOM_RR_POLY_I32 + 2 * lane] = (int)fx;                     // astype(int): truncation toward zero
             row[GOM_RR_POLY_I32 + 2 * lane + 1] = (int)fy;
@@ -69,7 +102,7 @@ __global__ __launch_bounds__(64 * RR_WAVES) void result_rows_kernel(const float*
 
     // ---- CTC emit mask (TextDecoder.decode): a character that follows a blank or differs from its predecessor
     long long id = 0;
-    if (lane < RR_P) id = recs[kk * RR_P + lane];
+    if (lane < RR_P) id = src.recs[src_row * RR_P + lane];
     const long long prev = __shfl_up(id, 1);
     const bool is_char = lane < RR_P && id < (long long)voc_size - 1;
     const bool prev_char = lane > 0 && prev < (long long)voc_size - 1;
@@ -179,7 +212,7 @@ __global__ __launch_bounds__(64 * RR_WAVES) void result_rows_kernel(const float*
         row[GOM_RR_EDGE] = bi >= 0 ? L.hp[bi] : -1;
         row[GOM_RR_EDGE + 1] = bi >= 0 ? L.hp[bi + 1 == nh ? 0 : bi + 1] : -1;
         row[GOM_RR_EDGE + 2] = 0;
-        const long long t = track_ids ? track_ids[kk] : 0;
+        const long long t = src.track_id(kk);
         row[GOM_RR_TRACK_ID] = (int)(unsigned)((unsigned long long)t & 0xffffffffull);
         row[GOM_RR_TRACK_ID + 1] = (int)(unsigned)((unsigned long long)t >> 32);
     }
@@ -192,7 +225,17 @@ extern "C" int gom_result_rows_i32(const float* bd, const int64_t* recs, const i
     GOM_CHECK_ARG(n >= 0 && voc_size >= 2 && ld >= GOM_RESULT_ROWS_WORDS);
     if (n == 0) return GOM_OK;
     GOM_CHECK_ARG(bd && recs && out);
-    hipLaunchKernelGGL(result_rows_kernel, dim3((unsigned)cdiv((long)n, (long)RR_WAVES)), dim3(64 * RR_WAVES), 0,
-                       (hipStream_t)stream, bd, recs, track_ids, n, voc_size, (int*)out, ld);
+    hipLaunchKernelGGL(result_rows_kernel<Packed>, dim3((unsigned)cdiv((long)n, (long)RR_WAVES)), dim3(64 * RR_WAVES), 0,
+                       (hipStream_t)stream, Packed{bd, recs, track_ids}, n, voc_size, (int*)out, ld);
+    return gom_launch_status();
+}
+
+extern "C" int gom_result_rows_gather_i32(const float* bd, const int64_t* recs, long cap, const int32_t* desc, int n,
+                                          int voc_size, int32_t* out, int ld, void* stream) {
+    GOM_CHECK_ARG(n >= 0 && voc_size >= 2 && ld >= GOM_RESULT_ROWS_WORDS);
+    if (n == 0) return GOM_OK;
+    GOM_CHECK_ARG(cap >= 1 && bd && recs && desc && out);
+    hipLaunchKernelGGL(result_rows_kernel<Gathered>, dim3((unsigned)cdiv((long)n, (long)RR_WAVES)), dim3(64 * RR_WAVES), 0,
+                       (hipStream_t)stream, Gathered{bd, recs, (const int*)desc, cap}, n, voc_size, (int*)out, ld);
     return gom_launch_status();
 }

@@ -16,7 +16,14 @@ Deliberate differences:
   * the "already written" check compares the XML stem `results.result_names` returns; the reference compares the raw
     video name, which never matches an ICDAR15 stem ('Video_35_2_3' is written as res_video_35.xml), so it never
     resumes on ICDAR15;
-  * no `--cpu` (there is no CPU path), no `--webcam`;
+  * no `--cpu` (there is no CPU path), no `--webcam` (no capture library is installed).  What a camera needs is there, though:
+    `--online [--push N]` runs every video as a stream through `gomatching_amd.online.OnlineSpotter` -- frames are decoded one
+    push (N frames, default 4 detector steps, rounded up to whole steps) ahead instead of the whole video at once, rows leave
+    the model as soon as their tracks have settled (at most 20 frames after the frame was tracked with the shipped configs) and
+    go straight to `results.VideoResultWriter`, and host and device memory do not grow with the length of the video.  The
+    three files per video are byte-identical to a run without the flag, which issues the launches it always issued.
+    `--online` draws nothing and builds rows on the GPU only: with `--show` or `--host-rows` the command exits with status 2
+    (`python -m gomatching_amd.show` draws from OUT/jsons afterwards, as it does for resumed runs);
   * `--show` draws with csrc/overlay.hip by an integer rule instead of matplotlib (`gomatching_amd.show`: colours by track
     id, Pillow's glyphs, no antialiasing); without it the command does what it did before the flag existed, launch for launch.
     A resumed run skips finished videos, pictures included: `python -m gomatching_amd.show` draws them from OUT/jsons;
@@ -62,6 +69,11 @@ def get_parser(drawing=False):
                    help="resize and normalise frames on the host (default: on the GPU, bit-exact with the host path)")
     p.add_argument("--host-rows", action="store_true",
                    help="build result rows per frame on the host (default: one kernel launch and one copy per clip)")
+    p.add_argument("--online", action="store_true",
+                   help="run every video as a stream: frames are decoded one push ahead, rows are written as their tracks "
+                        "settle, memory does not grow with the video; the files are the same (not with --show / --host-rows)")
+    p.add_argument("--push", type=int, default=None, metavar="N",
+                   help="with --online: frames per push, rounded up to whole detector steps (default 4 steps)")
     if drawing:
         p.add_argument("--show", action="store_true",
                        help="write every frame with its tracked text drawn on it to results/<video>/ (polygons in the colour "
@@ -131,8 +143,54 @@ def load_weights(path):
     return normalize_state_dict(torch.load(path, map_location="cpu"))
 
 
+def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost):
+    """One video through `online.OnlineSpotter`: the pool decodes one push ahead, rows go to the incremental writer as they
+    settle.  -> seconds reading / inside the timed window / building rows and writing, and the session's wait figures."""
+    from .online import OnlineSpotter
+    step = model.frames_per_step
+    push = args.push if args.push is not None else 4 * step
+    push = (push + step - 1) // step * step
+    session = OnlineSpotter(cfg, model, decoder, device_ingest=not args.host_ingest, time_cost=time_cost)
+    writer = _results.VideoResultWriter(video_name, data_type, args.output)
+    read, write = 0.0, 0.0
+    chunks = [paths[i:i + push] for i in range(0, len(paths), push)]
+    try:
+        ahead = [pool.submit(read_frame, p) for p in chunks[0]]
+        for c in range(len(chunks)):
+            t0 = time.time()
+            frames = [f.result() for f in ahead]
+            ahead = [pool.submit(read_frame, p) for p in chunks[c + 1]] if c + 1 < len(chunks) else []
+            read += time.time() - t0
+            settled = session.push(frames)
+            del frames
+            t0 = time.time()
+            for index, rows in settled:
+                writer.add(index, rows)
+            write += time.time() - t0
+        settled = session.close()
+        t0 = time.time()
+        for index, rows in settled:
+            writer.add(index, rows)
+        assert writer.frames == len(paths), (writer.frames, len(paths))
+        writer.close()
+        write += time.time() - t0
+    except BaseException:
+        writer.abort()
+        raise
+    time_cost["total_time"] += session.seconds
+    return {"read": read, "window": session.seconds, "rows": session.rows_seconds + write, "max_wait": session.max_wait,
+            "bound": session.latency_bound, "launches": session.gather_launches}
+
+
 def main(argv=None):
     args = get_parser(drawing=True).parse_args(argv)
+    if args.online and (getattr(args, "show", False) or args.host_rows):
+        sys.stderr.write("error: --online builds rows on the GPU and draws nothing: it takes neither --show nor --host-rows "
+                         "(python -m gomatching_amd.show draws from OUT/jsons afterwards)\n")
+        return 2
+    if args.push is not None and (not args.online or args.push < 1):
+        sys.stderr.write("error: --push N (N >= 1) goes with --online\n")
+        return 2
     if (args.config_file is None) == (args.builtin is None):
         sys.stderr.write("error: give exactly one of --config-file and --builtin\n")
         return 2
@@ -175,6 +233,18 @@ def main(argv=None):
             print("processing {}...".format(video_name))
             t0 = time.time()
             paths = frame_paths(video_dir)
+            if args.online:
+                if not paths:
+                    continue
+                stats = spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost)
+                read_seconds += stats["read"]
+                rows_seconds += stats["rows"]
+                total_frame += len(paths)
+                print("Video: ", video_name, "per_img_time: ", stats["window"] / len(paths), ", FPS: ",
+                      len(paths) / stats["window"])
+                print("online: largest wait ", stats["max_wait"], " frames (bound ", stats["bound"], "), gather launches ",
+                      stats["launches"])
+                continue
             frames = list(pool.map(read_frame, paths))
             read_seconds += time.time() - t0
             if not frames:

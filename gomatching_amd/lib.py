@@ -137,6 +137,7 @@ SIGNATURES = {
                                                P]),
     "gom_preprocess_nchw_to_nhwc4": (I, [P, ctypes.POINTER(c_float), ctypes.POINTER(c_float), P, I, I, I, P]),
     "gom_result_rows_i32": (I, [P, P, P, I, I, P, I, P]),
+    "gom_result_rows_gather_i32": (I, [P, P, L, P, I, I, P, I, P]),
     "gom_quad_bezier_i32": (I, [P, P, I, P, P]),
     "gom_quad_pairs_count_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, P]),
     "gom_quad_pairs_emit_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, L, P, P, P]),

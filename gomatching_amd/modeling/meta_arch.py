@@ -947,6 +947,39 @@ class GoMatching:
         main.wait_stream(trk)
         return instances, id_count
 
+    def stream_inference(self, batched_inputs, frame0, id_count, instances, time_cost, on_step=None):
+        """`batch_inference` for a stream without 100-frame batches: `frame0` is the absolute index of the first new frame
+        (= len(instances)), passed to `track_frames` directly.  `batch_id` enters `track_frames` only as
+        batch_id * 100 + frame_offset, so batch_id = 0 with frame_offset = frame0 + offset is the same recurrence.  The detector
+        of step j + 1 is queued before the tracker of step j runs on the tracker stream, as in `batch_inference`, across the steps
+        of ONE call.  `instances` stays a list indexed by absolute frame; entries older than the tracker window
+        (index < last tracked frame - test_len) may be None, nothing here reads them.  `on_step(dets, first)`, when given, runs
+        on the tracker stream after each step's frames (absolute indices first, first + 1, ...) have their ids: the online
+        session takes its copies and releases old entries there, so the list never holds a whole push."""
+        if frame0 != len(instances):
+            raise ValueError("frame0 (%d) must be the number of frames already in `instances` (%d)" % (frame0, len(instances)))
+        self.begin_batch(instances, len(batched_inputs))
+        steps = self._steps(batched_inputs)
+        if not steps:
+            return instances, id_count
+        main, trk = torch.cuda.current_stream(), self._tracker_stream()
+        h = self.detect_launch(batched_inputs[steps[0][0]:steps[0][1]], time_cost)
+        offset = 0
+        for j in range(len(steps)):
+            h_next = None
+            if j + 1 < len(steps):
+                h_next = self.detect_launch(batched_inputs[steps[j + 1][0]:steps[j + 1][1]], time_cost)
+            with torch.cuda.stream(trk):
+                dets = self.detect_finish(h, time_cost)
+                instances, id_count = self.track_frames(dets, 0, id_count, instances, time_cost,
+                                                        frame_offset=frame0 + offset)
+                if on_step is not None:
+                    on_step(dets, frame0 + offset)
+            offset += len(dets)
+            h = h_next
+        main.wait_stream(trk)
+        return instances, id_count
+
     def _tracker_stream(self):
         if getattr(self, "_trk_stream", None) is None:
             self._trk_stream = torch.cuda.Stream(device=self.device, priority=-1)
@@ -1254,6 +1287,24 @@ class GoMatching:
             instances[k] = new
         return instances
 
+    def output_scale(self, net_size, image_size):
+        """(sx, sy) that take a frame's points from network-input pixels (`net_size`, the Instances' image_size) to the source
+        frame (`image_size`), detector_postprocess :78-111, both branches.  `batch_postprocess` and the online session
+        (online.py) scale by this one expression."""
+        sx, sy = image_size[1] / net_size[1], image_size[0] / net_size[0]
+        if self.min_size_test and self.max_size_test:
+            # ViTAE branch (:82-96): the network input was padded, so the scale comes from the resize rule
+            # (ResizeShortestEdge re-derived from the output size), not from the padded tensor's shape
+            oh, ow = image_size
+            size = self.min_size_test * 1.0
+            k = self.min_size_test / min(ow, oh)
+            newh, neww = (size, k * ow) if oh < ow else (k * oh, size)
+            if max(newh, neww) > self.max_size_test:
+                k = self.max_size_test * 1.0 / max(newh, neww)
+                newh, neww = newh * k, neww * k
+            sx, sy = ow / int(neww + 0.5), oh / int(newh + 0.5)
+        return sx, sy
+
     def batch_postprocess(self, instances, image_sizes):
         """gom_lstmatcher.py:353-364 + detector_postprocess :78-111 (both branches): scale ctrl_points and
         bd to the original frame size; pred_boxes stay in network-input pixels.  Frames that share the scale factors
@@ -1264,18 +1315,7 @@ class GoMatching:
                 r._fields["reid_features"] = r.reid_features.clone()
                 self._host(r)["row0"] = None
         for i, (r, image_size) in enumerate(zip(instances, image_sizes)):
-            sx, sy = image_size[1] / r.image_size[1], image_size[0] / r.image_size[0]
-            if self.min_size_test and self.max_size_test:
-                # ViTAE branch (:82-96): the network input was padded, so the scale comes from the resize rule
-                # (ResizeShortestEdge re-derived from the output size), not from the padded tensor's shape
-                oh, ow = image_size
-                size = self.min_size_test * 1.0
-                k = self.min_size_test / min(ow, oh)
-                newh, neww = (size, k * ow) if oh < ow else (k * oh, size)
-                if max(newh, neww) > self.max_size_test:
-                    k = self.max_size_test * 1.0 / max(newh, neww)
-                    newh, neww = newh * k, neww * k
-                sx, sy = ow / int(neww + 0.5), oh / int(newh + 0.5)
+            sx, sy = self.output_scale(r.image_size, image_size)
             key = (sx, sy, r.has("ctrl_points"), r.has("pred_boxes") and not isinstance(r.bd, list))
             groups.setdefault(key, []).append(i)
         for (sx, sy, has_ctrl, has_bd), idxs in groups.items():

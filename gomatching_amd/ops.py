@@ -1518,6 +1518,51 @@ def result_rows(bd, recs, voc_size, track_ids=None):
     return out
 
 
+RESULT_ROWS_DESC_WORDS = 6          # GOM_RR_DESC_WORDS
+
+
+def result_rows_desc(rows, track_ids, sx, sy):
+    """The descriptor `result_rows_gather` takes, int32 [n, 6]: ring row, track id low / high word, the fp32 bit patterns of the
+    row's scale pair (rounded to fp32 as `scale_xy_` rounds its arguments), 0.  All arguments are arrays of n (or scalars)."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+    n = rows.shape[0]
+    if n and (rows.min() < -2 ** 31 or rows.max() >= 2 ** 31):
+        raise ValueError("ring rows must fit 32 bits")
+    desc = np.zeros((n, RESULT_ROWS_DESC_WORDS), dtype=np.int32)
+    desc[:, 0] = rows
+    desc[:, 1:3] = np.ascontiguousarray(np.broadcast_to(np.asarray(track_ids, dtype=np.int64), (n,))).view(np.int32).reshape(n, 2)
+    desc[:, 3] = np.ascontiguousarray(np.broadcast_to(np.asarray(sx, dtype=np.float32), (n,))).view(np.int32)
+    desc[:, 4] = np.ascontiguousarray(np.broadcast_to(np.asarray(sy, dtype=np.float32), (n,))).view(np.int32)
+    return desc
+
+
+def result_rows_gather(bd, recs, desc, voc_size, upload=None):
+    """`result_rows` of the instances a host descriptor picks out of a ring: bd [cap,25,4] f32 and recs [cap,25] int64 (CUDA, the
+    unscaled fields of every pending frame), desc int32 numpy [n, 6] (`result_rows_desc`) -> int32 [n, RESULT_ROWS_WORDS], row k
+    being the row `result_rows` gives for ring row desc[k, 0] after `scale_xy_` with that row's scale pair, carrying that row's
+    track id.  One upload (through `upload`, a model's pinned staging `_h2d`, when given), one launch.  A ring row outside
+    [0, cap) is refused here, before anything is uploaded."""
+    if not bd.is_cuda or bd.dtype != _f32 or bd.dim() != 3 or tuple(bd.shape[1:]) != (25, 4) or not bd.is_contiguous():
+        raise ValueError("bd must be a contiguous CUDA float32 [cap,25,4] tensor")
+    cap = bd.shape[0]
+    if recs.dtype != torch.int64 or tuple(recs.shape) != (cap, 25) or recs.device != bd.device or not recs.is_contiguous():
+        raise ValueError("recs must be a contiguous int64 [cap,25] tensor on bd's device")
+    if not isinstance(desc, np.ndarray) or desc.dtype != np.int32 or desc.ndim != 2 or desc.shape[1] != RESULT_ROWS_DESC_WORDS:
+        raise ValueError("desc must be an int32 numpy array of shape [n, %d]" % RESULT_ROWS_DESC_WORDS)
+    n = desc.shape[0]
+    if n and (int(desc[:, 0].min()) < 0 or int(desc[:, 0].max()) >= cap):
+        raise ValueError("desc names a ring row outside [0, %d)" % cap)
+    out = torch.empty((n, RESULT_ROWS_WORDS), dtype=torch.int32, device=bd.device)
+    if n == 0:
+        return out
+    with torch.cuda.device(bd.device):
+        desc = np.ascontiguousarray(desc)
+        desc_d = upload(desc) if upload is not None else torch.from_numpy(desc).to(bd.device)
+        check(_L().gom_result_rows_gather_i32(_p(bd), _p(recs), cap, _p(desc_d), n, int(voc_size), _p(out), RESULT_ROWS_WORDS,
+                                              _stream()), "gom_result_rows_gather_i32")
+    return out
+
+
 def quad_bezier(quads, hw):
     """quads int32 [n,8] (x1,y1,..,x4,y4), hw int32 [n,2] (each quad's image H, W), both CUDA -> int32 [n,16]: the control points
     of the two Bezier curves of every quad, one launch (csrc/prepare.hip; the rule is in include/gomatching_hip.h)."""

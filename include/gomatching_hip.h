@@ -532,6 +532,31 @@ int gom_ingest_motion_u8_hwc3_to_nhwc4(const uint8_t* src, int H, int W, const i
 #define GOM_RESULT_ROWS_WORDS 234
 int gom_result_rows_i32(const float* bd, const int64_t* recs, const int64_t* track_ids, int n, int voc_size,
                         int32_t* out, int ld, void* stream);
+/* ---- Result rows of an online session (gomatching_amd/online.py): gathered from a ring, scaled per row ------------
+ * The settling rule that decides WHEN a frame's rows may leave the model.  L = test_len, M = min_track_len,
+ * R = max(L - 1, 1) = how many frames back a match can reach (meta_arch.py `track_frames`: the long-term window starts at
+ * win_st = real + 1 - test_len and the short-term match sees frame real - 1; the native path carries
+ * instances[-max(test_len - 1, 1):]).  After frame t (0-based) is tracked, with c(id) the detections of a track so far and
+ * s(id) the last frame it was seen in, a track is
+ *   confirmed  c >= M                : its rows are kept, past ones included;
+ *   dead       c <  M and t >= s + R : frame t + 1 can no longer reach frame s, no later frame can take the id; rows dropped;
+ *   open       otherwise.
+ * A frame is settled when none of its ids is open; frames leave in frame order (the longest settled prefix of the pending
+ * ones); M <= 0 settles every frame at once; closing the stream makes every open track dead.  A frame therefore leaves at
+ * most D = max(M - 1, 0) * R frames after it was tracked, with exactly the rows `_remove_short_track` keeps offline.
+ *
+ * gom_result_rows_gather_i32: the rows of the n instances a descriptor names, one launch whatever frames they belong to.
+ *   bd [cap,25,4] fp32 and recs [cap,25] int64: the session's ring, in NETWORK-input pixels (unscaled);
+ *   desc [n][GOM_RR_DESC_WORDS] int32: ring row, track id low word, track id high word, sx bits, sy bits, 0.
+ * Row k of out is word for word the row gom_result_rows_i32 writes for ONE instance whose boundary is bd[desc[k].row] with
+ * every x multiplied by sx and every y by sy in fp32, each product rounded once (what gom_scale_xy_f32 leaves in place),
+ * whose class ids are recs[desc[k].row] and whose track id is the descriptor's.  The scale pair is per row, so frames of
+ * different sizes share a launch.  A ring row outside [0, cap) is clamped into the ring by the kernel (it never reads past
+ * it); the Python wrapper refuses such a descriptor.  n == 0 is GOM_OK without a launch; otherwise cap >= 1 and no pointer
+ * is NULL. */
+#define GOM_RR_DESC_WORDS 6
+int gom_result_rows_gather_i32(const float* bd, const int64_t* recs, long cap, const int32_t* desc, int n, int voc_size,
+                               int32_t* out, int ld, void* stream);
 /* ---- Quad -> Bezier control points (csrc/prepare.hip; python -m gomatching_amd.prepare) ------------------------
  * What datasets/vts.py:154-162 derives from a `poly` quad on every load (polygon2rbox -> LinearRing.is_ccw -> cpt_bezier_pts),
  * computed once per dataset: quads int32 [n,8] (x1,y1,..,x4,y4), hw int32 [n,2] (the quad's image H, W), out int32 [n,16]
