@@ -26,6 +26,8 @@
 //     registers and every lane stores its token's 16-byte pieces.
 // Plane products in the tile kernel's order (x-lo w-hi, x-hi w-lo, x-hi w-hi per 16-wide k-step); activations must stay within
 // fp16's range (|x| <= 65504: q, k, v and the inputs are checked, *flag is raised otherwise -- gemm_f16x3.hip's contract).
+// Tests: tests/test_dec_attn_gpu.py (flat tolerance, the launches it replaces) and tests/test_dec_forms_gpu.py (every form against the fp64
+// statements of tests/dec_statement.py, elementwise within their derived bounds, strided NaN-padded views).
 #include "common.h"
 
 namespace {

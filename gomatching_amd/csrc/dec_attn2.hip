@@ -26,6 +26,8 @@
 //   * residual + LayerNorm in registers (lane = token: in-lane sums + two half-row exchanges), 64-byte pieces per token and store;
 //   * RAW (inter): the cross attention's offsets | logits product on (output + query_pos) behind the block, twelve more stages.
 // Plane products: w-lo x-hi, w-hi x-lo, w-hi x-hi per 32-wide k-step.  Range contract and *flag as gom_dec_attn_f32.
+// Tests: tests/test_dec_attn_gpu.py (flat tolerance, the launches it replaces) and tests/test_dec_forms_gpu.py (every form against the fp64
+// statements of tests/dec_statement.py, elementwise within their derived bounds, strided NaN-padded views).
 #include "common.h"
 
 namespace {

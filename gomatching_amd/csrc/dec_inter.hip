@@ -18,6 +18,8 @@
 // The rows of a group are read twice per head (16 times per layer, L2-resident: 300 KB per group) instead of the q | k | v
 // round trip through HBM ([rows, 768] written and read) and a VALU attention core.  f16x3 products (x-lo w-hi, x-hi w-lo,
 // x-hi w-hi), fp32 accumulation and softmax; operands must stay within fp16's range (*flag otherwise, gemm_f16x3.hip's contract).
+// Tests: tests/test_dec_attn_gpu.py (flat tolerance, the launches it replaces) and tests/test_dec_forms_gpu.py (every form against the fp64
+// statements of tests/dec_statement.py, elementwise within their derived bounds, strided NaN-padded views).
 #include "common.h"
 
 namespace {

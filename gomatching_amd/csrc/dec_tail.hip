@@ -27,6 +27,8 @@
 //     sincosf per lane and row group, the pair (2 k, 2 k + 1) sharing its angle).
 // Per row the arithmetic does not depend on what shares the launch (batch invariance); against the four-launch path the
 // LayerNorm sums and the second / third block's k order differ in the last bits (tests hold both to the same fp64 tolerance).
+// Tests: tests/test_dec_tail_gpu.py (flat tolerance, the launches it replaces) and tests/test_dec_forms_gpu.py (every form against the fp64
+// statements of tests/dec_statement.py, elementwise within their derived bounds, strided NaN-padded views).
 #include "common.h"
 
 namespace {

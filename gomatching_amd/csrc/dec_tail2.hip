@@ -32,7 +32,7 @@
 //     embedding is evaluated directly in operand order by the wave that owns the feature.
 // Per row the arithmetic does not depend on what shares the launch (batch invariance); against dec_tail.hip the LayerNorm
 // statistics (Chan's combination instead of two passes over the row) and nothing else differ: both are held to the same fp64
-// tolerance by tests/test_dec_tail_gpu.py.
+// tolerance by tests/test_dec_tail_gpu.py, and to the fp64 statements of tests/dec_statement.py by tests/test_dec_forms_gpu.py.
 #include "common.h"
 
 namespace {

@@ -31,6 +31,8 @@
 //   * epilogue: Y^T goes through the (now free) LDS ring to row-major, then 16 lanes per row apply the weight scale, bias,
 //     residual and the LayerNorm of norm.hip (same two-pass arithmetic) and store whole 1 KB rows.
 // MFMA work per 128 rows: 4 waves x 6144 v_mfma_f32_16x16x32_f16; LDS reads 1/3 KB per MFMA; L2 -> LDS 2 MB.
+// Tests: tests/test_ffn_gpu.py (flat tolerance, the launches it replaces) and tests/test_dec_forms_gpu.py (every form against the fp64
+// statements of tests/dec_statement.py, elementwise within their derived bounds, strided NaN-padded views).
 #include "common.h"
 
 namespace {

@@ -10,6 +10,8 @@
 // Structure (round 5; the round-2 form -- 128-row tiles at one workgroup per CU, 32x32x16, the tile kernel's bits -- was one
 // workgroup's 27 us latency chain whatever the launch's length and left in round 6: docs/LAB_NOTES.md): a workgroup owns 64 rows,
 // a wave 16 of them as v_mfma_f32_16x16x32_f16 operand fragments, TWO workgroups per CU; see proj_ln2_kernel below.
+// Tests: tests/test_proj_ln_gpu.py (flat tolerance, the launches it replaces) and tests/test_dec_forms_gpu.py (every form against the fp64
+// statements of tests/dec_statement.py, elementwise within their derived bounds, strided NaN-padded views).
 #include "common.h"
 
 namespace {
