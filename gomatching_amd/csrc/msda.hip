@@ -433,7 +433,15 @@ __host__ __device__ __forceinline__ void msda_window_plan(const int (&Hs)[LEVELS
 // arithmetic, its accumulation order) instead of served from a window -- for tiles of level-1 queries, whose projection on level 0
 // (twice the pixels per query) is the window that does not fit: an 8 x 16 level-1 tile needs 27 x 43 = 1 161 level-0 lines, its
 // level-1 .. 3 windows 513 + 285 + 195.
-template <int TY, int TX, int R, int CAP, int NB, int GLV = 0, int OVL = 0>
+// LPQ (lanes per (query, head) pair): 8 = the layout described above; 4 = msda_window_lanes4 below, a DPP quad per pair with 8 channels
+// per lane.  CHA: the 4-lane layout's channel assignment (see there).
+template <int TY, int TX, int R, int CAP, int NB, int GLV, int OVL, int CHA>
+__device__ __forceinline__ void msda_window_lanes4(const float* __restrict__ value, const int64_t* __restrict__ shapes,
+                                                   const int64_t* __restrict__ lsi, const float* __restrict__ raw, int ld_raw,
+                                                   const float* __restrict__ ref, float* __restrict__ out, int Lq, long v_bs, int v_rs,
+                                                   int tiles_y, int tiles_x, int ql, unsigned* __restrict__ slow_groups);
+
+template <int TY, int TX, int R, int CAP, int NB, int GLV = 0, int OVL = 0, int LPQ = 8, int CHA = 0>
 __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __restrict__ value,
                                                              const int64_t* __restrict__ shapes,
                                                              const int64_t* __restrict__ lsi,
@@ -441,6 +449,12 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
                                                              const float* __restrict__ ref, float* __restrict__ out,
                                                              int Lq, long v_bs, int v_rs, int tiles_y, int tiles_x, int ql,
                                                              unsigned* __restrict__ slow_groups) {
+    static_assert(LPQ == 8 || LPQ == 4, "two lane layouts");
+    if constexpr (LPQ == 4) {                                // (compile-time: nothing below is emitted for this form)
+        msda_window_lanes4<TY, TX, R, CAP, NB, GLV, OVL, CHA>(value, shapes, lsi, raw, ld_raw, ref, out, Lq, v_bs, v_rs, tiles_y, tiles_x,
+                                                              ql, slow_groups);
+        return;
+    }
     constexpr int POINTS = 4, LP = LEVELS * POINTS, ITERS = (TY * TX) / 32;
     extern __shared__ __attribute__((aligned(16))) unsigned char win[];          // CAP lines of 128 bytes
     const int tid = threadIdx.x, lane = tid & 63;
@@ -862,6 +876,429 @@ __global__ __launch_bounds__(256, 2) void msda_window_kernel(const float* __rest
         if (live[it]) *reinterpret_cast<f32x4*>(out + (size_t)qrow[it] * (HEADS * CH) + m * CH + k * 4) = acc[it];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The window kernel with FOUR lanes per (query, head) pair, 8 channels each (LPQ = 4).  In the 8-lane layout every lane of a pair
+// issues, per sample, the five broadcasts of the owner's packed address word and corner weights and the ~10 address instructions
+// behind them -- all identical in the eight lanes.  With four lanes they are issued half as often per channel, and a group of
+// four lanes is a DPP quad: a broadcast is ONE v_mov_b32 with quad_perm:[o,o,o,o] and leaves the LDS pipe, which then carries
+// only the corner reads.
+//   * lane j = lane & 3 of a quad owns the four samples of level j (4j .. 4j + 3): two 16-byte loads of their offsets, one of
+//     their logits; the level constants are selected by j;
+//   * a wave handles 16 pairs per iteration (ITERS = TY * TX / 64), the tile's queries in the same raster order: lanes 0-31 are
+//     one octet of 8 consecutive tile queries, lanes 32-63 the next;
+//   * softmax: the maximum over the quad by two DPP exchanges (order-free), numerators by the same expf, the sum over samples
+//     0 .. 15 in ascending order from 0.f on every lane, 1.f / sum, e * inv_sum; geometry = MSDA_GEOMETRY; per channel the same
+//     four FMAs per sample in corner order, samples l = 0..3, p = 0..3: BIT-IDENTICAL to the 8-lane layout;
+//   * two ds_read_b128 per corner and lane.  CHA picks the lane's 8 channels:
+//       0: contiguous 8j .. 8j + 7 (second read = offset:16 of the first);
+//       1: split 4j .. 4j + 3 and 16 + 4j .. 16 + 4j + 3 (second read = offset:64);
+//       2: split, and the odd PAIRS of quads (bit 3 of the lane) read their upper half first: a ds_read_b128 is served in 16-lane
+//          groups of four quads each ({0,3,5,6}, {1,2,4,7} of a half-wave), a 128-byte line is half a bank row, and neighbouring
+//          queries read neighbouring lines, so this puts the four quads of a group on the four 64-byte quarters of the two bank
+//          rows halves -- at the price of one v_add per corner for the second address (no immediate offset can be negative);
+//     all sixteen reads of a batch are bare instructions waited for with lgkmcnt (LDS operations return in order), so the compiler
+//     never sees an LDS load behind an LDS-DMA request (see UNDERC above) and one form serves both fill schedules;
+//   * fills, barriers, windows and both schedules are the 8-lane kernel's (the fill keeps its 8 lanes per line);
+//   * the fallback stays per OCTET: one ballot per iteration, one mask per half-wave; a slow octet's half of the wave takes the
+//     gather path (two 16-byte loads per corner and lane), and slow_groups counts octets as before.
+__device__ __forceinline__ float quad_read(float v, int owner) {         // value of lane (lane & ~3) | owner, owner a constant
+    const int x = __builtin_bit_cast(int, v);
+    switch (owner) {
+        case 0: return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(x, 0x00, 0xF, 0xF, true));
+        case 1: return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(x, 0x55, 0xF, 0xF, true));
+        case 2: return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(x, 0xAA, 0xF, 0xF, true));
+        default: return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(x, 0xFF, 0xF, 0xF, true));
+    }
+}
+__device__ __forceinline__ unsigned quad_read(unsigned v, int owner) {
+    return __builtin_bit_cast(unsigned, quad_read(__builtin_bit_cast(float, v), owner));
+}
+
+template <int TY, int TX, int R, int CAP, int NB, int GLV, int OVL, int CHA>
+__device__ __forceinline__ void msda_window_lanes4(const float* __restrict__ value, const int64_t* __restrict__ shapes,
+                                                   const int64_t* __restrict__ lsi, const float* __restrict__ raw, int ld_raw,
+                                                   const float* __restrict__ ref, float* __restrict__ out, int Lq, long v_bs, int v_rs,
+                                                   int tiles_y, int tiles_x, int ql, unsigned* __restrict__ slow_groups) {
+    constexpr int POINTS = 4, LP = LEVELS * POINTS, ITERS = (TY * TX) / 64;
+    static_assert((TY * TX) % 64 == 0 && ITERS % NB == 0, "whole iterations of 16 queries per wave, whole batches");
+    static_assert(8 * NB <= 16, "lgkmcnt counts to 15");
+    static_assert(CHA >= 0 && CHA <= 2, "three channel assignments");
+    static_assert(GLV == 0 || GLV == 1, "only the finest level is ever gathered");
+    static_assert(OVL == 0 || OVL == 1, "two fill schedules");
+    extern __shared__ __attribute__((aligned(16))) unsigned char win[];          // CAP lines of 128 bytes
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 3, k = lane & 7;                   // the fill's: 8 lanes per line
+    const int p16 = lane >> 2, l = lane & 3;                 // pair of the iteration; level of this lane's four samples
+    const int m = (int)(blockIdx.x & 7u);                    // head
+    unsigned tile = blockIdx.x >> 3;
+    const int tx = (int)(tile % (unsigned)tiles_x);
+    tile /= (unsigned)tiles_x;
+    const int ty = (int)(tile % (unsigned)tiles_y);
+    const int b = (int)(tile / (unsigned)tiles_y);
+
+    int Hs[LEVELS], Ws[LEVELS];
+    unsigned lv[LEVELS];
+#pragma unroll
+    for (int i = 0; i < LEVELS; ++i) {
+        Hs[i] = (int)shapes[2 * i];
+        Ws[i] = (int)shapes[2 * i + 1];
+        lv[i] = (unsigned)lsi[i];
+    }
+    const int Hq = ql == 0 ? Hs[0] : ql == 1 ? Hs[1] : ql == 2 ? Hs[2] : Hs[3];
+    const int Wq = ql == 0 ? Ws[0] : ql == 1 ? Ws[1] : ql == 2 ? Ws[2] : Ws[3];
+    const long q0 = (long)b * Lq + (long)(ql == 0 ? lv[0] : ql == 1 ? lv[1] : ql == 2 ? lv[2] : lv[3]);
+    const int y0t = ty * TY, x0t = tx * TX;
+    const int y1t = min(y0t + TY, Hq) - 1, x1t = min(x0t + TX, Wq) - 1;
+    const long qa = q0 + (long)y0t * Wq + x0t, qz = q0 + (long)y1t * Wq + x1t;
+    const float rxa = ref[qa * 2], rya = ref[qa * 2 + 1], rxz = ref[qz * 2], ryz = ref[qz * 2 + 1];
+    int wx0[LEVELS], wy0[LEVELS], wx1[LEVELS], wy1[LEVELS], wwd[LEVELS], wst[LEVELS];
+    msda_window_plan<R, CAP>(Hs, Ws, rxa, rya, rxz, ryz, GLV, OVL, wx0, wy0, wx1, wy1, wwd, wst);
+    const int H = l == 0 ? Hs[0] : l == 1 ? Hs[1] : l == 2 ? Hs[2] : Hs[3];
+    const int W = l == 0 ? Ws[0] : l == 1 ? Ws[1] : l == 2 ? Ws[2] : Ws[3];
+    const int mx0 = l == 0 ? wx0[0] : l == 1 ? wx0[1] : l == 2 ? wx0[2] : wx0[3];
+    const int my0 = l == 0 ? wy0[0] : l == 1 ? wy0[1] : l == 2 ? wy0[2] : wy0[3];
+    const int mx1 = l == 0 ? wx1[0] : l == 1 ? wx1[1] : l == 2 ? wx1[2] : wx1[3];
+    const int my1 = l == 0 ? wy1[0] : l == 1 ? wy1[1] : l == 2 ? wy1[2] : wy1[3];
+    const int mww = l == 0 ? wwd[0] : l == 1 ? wwd[1] : l == 2 ? wwd[2] : wwd[3];
+    const int mst = l == 0 ? wst[0] : l == 1 ? wst[1] : l == 2 ? wst[2] : wst[3];
+    const unsigned lvl = l == 0 ? lv[0] : l == 1 ? lv[1] : l == 2 ? lv[2] : lv[3];
+    const float Hf = (float)H, Wf = (float)W;
+    const float rW = 1.f / Wf, rH = 1.f / Hf;
+
+    const __amdgpu_buffer_rsrc_t rs = gom_buffer_rsrc(value + (size_t)b * v_bs, 0x7FFFFFFF);
+    const unsigned head = (unsigned)(m * CH) * 4u;
+    // this lane's two groups of 4 channels inside a 128-byte line: byte offsets of its first and second read
+    constexpr unsigned SECOND = CHA == 0 ? 16u : 64u;
+    const unsigned flip = CHA == 2 ? (unsigned)((lane >> 3) & 1) : 0u;
+    const unsigned mine = CHA == 0 ? (unsigned)l * 32u : (unsigned)l * 16u + flip * 64u;
+    const unsigned mine2 = CHA == 2 ? (unsigned)l * 16u + (1u - flip) * 64u : mine + SECOND;
+
+    // ---- owner part of every iteration: four samples per lane ----
+    float sw1[ITERS][4], sw2[ITERS][4], sw3[ITERS][4], sw4[ITERS][4];   // corner weights x the sample's attention weight
+    unsigned pk[ITERS][4];                                   // LDS byte address of corner (yc0, xc0) in `win` | dx << 20 | dy << 21
+    unsigned go1[GLV ? ITERS : 1][4], go2[GLV ? ITERS : 1][4], go3[GLV ? ITERS : 1][4], go4[GLV ? ITERS : 1][4];   // GLV: global corner offsets
+    f32x4 acc[ITERS][2];
+    long qrow[ITERS];
+    bool fast[ITERS][2], live[ITERS];                        // fast: per octet (half-wave), wave-uniform
+    f32x4 offa[ITERS], offb[ITERS], lgs[ITERS];
+    float rxs[ITERS], rys[ITERS];
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+        const int j = (wave * ITERS + it) * 16 + p16;        // query of the tile
+        const int jy = j / TX, jx = j - jy * TX;
+        const int qy = y0t + jy, qx = x0t + jx;
+        live[it] = qy <= y1t && qx <= x1t;
+        const long q_global = q0 + (long)(live[it] ? qy : y0t) * Wq + (live[it] ? qx : x0t);
+        qrow[it] = q_global;
+        const float* op = raw + (size_t)q_global * ld_raw + m * (LP * 2) + 8 * l;      // (ox, oy) of samples 4l .. 4l + 3
+        const float* lp = raw + (size_t)q_global * ld_raw + HEADS * LP * 2 + m * LP + 4 * l;
+        offa[it] = *reinterpret_cast<const f32x4*>(op);
+        offb[it] = *reinterpret_cast<const f32x4*>(op + 4);
+        lgs[it] = *reinterpret_cast<const f32x4*>(lp);
+        rxs[it] = ref[q_global * 2];
+        rys[it] = ref[q_global * 2 + 1];
+    }
+    auto fill = [&](auto LEVC) {                             // the 8-lane kernel's fill: 8 lanes per line, 8 lines per wave-instruction
+        constexpr int lev = decltype(LEVC)::value;
+        unsigned char* buf = win + (size_t)wst[lev] * 128;
+        const int ww_ = wwd[lev], n_lines = ww_ * (wy1[lev] - wy0[lev] + 1);
+        const float inv_w = 1.f / (float)ww_;
+        for (int base = wave * 8; base < n_lines; base += 32) {
+            int line = base + g;
+            if (line > n_lines - 1) line = n_lines - 1;      // the tail of the last group re-reads the last line
+            int yy = (int)(((float)line + 0.5f) * inv_w);
+            int xx = line - yy * ww_;
+            if (xx < 0) { --yy; xx += ww_; }
+            if (xx >= ww_) { ++yy; xx -= ww_; }
+            const unsigned src = (lv[lev] + (unsigned)((wy0[lev] + yy) * Ws[lev] + wx0[lev] + xx)) * (unsigned)v_rs * 4u + head + (unsigned)k * 16u;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(buf + (size_t)base * 128), 16,
+                                                     (int)src, 0, 0, 0);
+        }
+    };
+    if constexpr (OVL != 0) {
+        // the owner loads are consumed in front of the fill loop (as in the 8-lane kernel: else their wait is vmcnt(0) behind it)
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) asm volatile("" : "+v"(offa[it]), "+v"(offb[it]), "+v"(lgs[it]), "+v"(rxs[it]), "+v"(rys[it]));
+        fill(std::integral_constant<int, GLV>{});
+    }
+    unsigned any_slow = 0;
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+        const f32x4 lg = lgs[it];
+        float mx = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
+        mx = fmaxf(mx, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, mx), 0xB1, 0xF, 0xF, true)));   // quad_perm:[1,0,3,2]
+        mx = fmaxf(mx, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, mx), 0x4E, 0xF, 0xF, true)));   // quad_perm:[2,3,0,1]
+        float e[POINTS];
+#pragma unroll
+        for (int t = 0; t < POINTS; ++t) e[t] = expf(lg[t] - mx);
+        float sum = 0.f;
+#pragma unroll
+        for (int o = 0; o < LEVELS; ++o)
+#pragma unroll
+            for (int t = 0; t < POINTS; ++t) sum += quad_read(e[t], o);
+        const float inv_sum = 1.f / sum;
+        const float off8[8] = {offa[it][0], offa[it][1], offa[it][2], offa[it][3], offb[it][0], offb[it][1], offb[it][2], offb[it][3]};
+        bool ok0, ok1, ok2, ok3;
+        unsigned sa1, sa2, sa3, sa4, sb1, sb2, sb3, sb4, sc1, sc2, sc3, sc4, sd1, sd2, sd3, sd4;
+        MSDA_GEOMETRY(it, 0, off8, rxs[it], rys[it], e[0], inv_sum, ok0, sa)
+        MSDA_GEOMETRY(it, 1, off8, rxs[it], rys[it], e[1], inv_sum, ok1, sb)
+        MSDA_GEOMETRY(it, 2, off8, rxs[it], rys[it], e[2], inv_sum, ok2, sc)
+        MSDA_GEOMETRY(it, 3, off8, rxs[it], rys[it], e[3], inv_sum, ok3, sd)
+        if constexpr (GLV > 0) {
+            go1[it][0] = sa1; go2[it][0] = sa2; go3[it][0] = sa3; go4[it][0] = sa4;
+            go1[it][1] = sb1; go2[it][1] = sb2; go3[it][1] = sb3; go4[it][1] = sb4;
+            go1[it][2] = sc1; go2[it][2] = sc2; go3[it][2] = sc3; go4[it][2] = sc4;
+            go1[it][3] = sd1; go2[it][3] = sd2; go3[it][3] = sd3; go4[it][3] = sd4;
+        }
+        (void)sa1; (void)sa2; (void)sa3; (void)sa4; (void)sb1; (void)sb2; (void)sb3; (void)sb4;
+        (void)sc1; (void)sc2; (void)sc3; (void)sc4; (void)sd1; (void)sd2; (void)sd3; (void)sd4;
+        // one ballot, two masks: an octet is a half-wave
+        const unsigned long long bad = __builtin_amdgcn_ballot_w64(!(ok0 && ok1 && ok2 && ok3));
+        fast[it][0] = (unsigned)bad == 0u;
+        fast[it][1] = (unsigned)(bad >> 32) == 0u;
+        any_slow |= (fast[it][0] && fast[it][1]) ? 0u : 1u;
+        acc[it][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc[it][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+
+    // ---- level by level: the level's four samples of every iteration, owner = lane `lev` of the quad ----
+    auto level_samples = [&](auto LEVC) {
+        constexpr int lev = decltype(LEVC)::value;
+        const unsigned mine_lds = mine + (unsigned)(size_t)win;   // (a flat LDS address: its low word is the LDS offset)
+        const unsigned row_bytes = (unsigned)wwd[lev] * 128u;
+#pragma unroll
+        for (int t = 0; t < POINTS; ++t) {
+#pragma unroll
+            for (int half = 0; half < ITERS; half += NB) {
+                // (wave-uniform, almost never taken; keeps every batch a basic block of its own, as in the 8-lane kernel)
+                bool any_fast = false;
+#pragma unroll
+                for (int u = 0; u < NB; ++u) any_fast = any_fast || fast[half + u][0] || fast[half + u][1];
+                if (!any_fast) continue;
+                unsigned word[NB];
+                float w1[NB], w2[NB], w3[NB], w4[NB];
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const int it = half + u;
+                    // (opaque: else the broadcasts of ALL levels are computed in front of the first barrier and spill)
+                    asm volatile("" : "+v"(pk[it][t]), "+v"(sw1[it][t]), "+v"(sw2[it][t]), "+v"(sw3[it][t]), "+v"(sw4[it][t]));
+                    word[u] = quad_read(pk[it][t], lev);
+                    w1[u] = quad_read(sw1[it][t], lev);
+                    w2[u] = quad_read(sw2[it][t], lev);
+                    w3[u] = quad_read(sw3[it][t], lev);
+                    w4[u] = quad_read(sw4[it][t], lev);
+                }
+                f32x4 va[NB][4], vb[NB][4];                  // [corner]: the lane's first and second 4 channels
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const unsigned a1 = (word[u] & 0xFFFFFu) + mine_lds;
+                    const unsigned dx = (word[u] >> 20) & 1u, dy = (word[u] >> 21) & 1u;
+                    unsigned a[4] = {a1, a1 + dx * 128u, a1 + dy * row_bytes, 0u};
+                    a[3] = a[2] + dx * 128u;
+                    // opaque: otherwise the compiler branches around the reads whose address may equal another one's
+                    asm volatile("" : "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        asm volatile("ds_read_b128 %0, %1" : "=&v"(va[u][c]) : "v"(a[c]));
+                        if constexpr (CHA == 2) {
+                            const unsigned a_ = a[c] + (mine2 - mine);
+                            asm volatile("ds_read_b128 %0, %1" : "=&v"(vb[u][c]) : "v"(a_));
+                        } else {
+                            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(vb[u][c]) : "v"(a[c]), "n"(SECOND));
+                        }
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const float w[4] = {w1[u], w2[u], w3[u], w4[u]};
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {             // LDS operations return in order: this corner's two reads have arrived
+                        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(va[u][c]), "+v"(vb[u][c]) : "n"(8 * NB - 2 - (8 * u + 2 * c)));
+                        msda_fma4(acc[half + u][0], w[c], va[u][c]);
+                        msda_fma4(acc[half + u][1], w[c], vb[u][c]);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);           // (keeps the scheduler from hoisting later batches' reads: spills)
+            }
+        }
+    };
+    // GLV: the four samples of a GATHERED level: corner offsets broadcast from the owner lane, two 16-byte loads per corner and lane
+    auto level_gather = [&](auto LEVC) {
+        constexpr int lev = decltype(LEVC)::value;
+#pragma unroll
+        for (int t = 0; t < POINTS; ++t) {
+#pragma unroll
+            for (int half = 0; half < ITERS; half += NB) {
+                bool any_fast = false;
+#pragma unroll
+                for (int u = 0; u < NB; ++u) any_fast = any_fast || fast[half + u][0] || fast[half + u][1];
+                if (!any_fast) continue;
+                unsigned a[NB][4];
+                float w[NB][4];
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const int it = half + u;
+                    asm volatile("" : "+v"(go1[it][t]), "+v"(go2[it][t]), "+v"(go3[it][t]), "+v"(go4[it][t]));
+                    asm volatile("" : "+v"(sw1[it][t]), "+v"(sw2[it][t]), "+v"(sw3[it][t]), "+v"(sw4[it][t]));
+                    a[u][0] = quad_read(go1[it][t], lev);
+                    a[u][1] = quad_read(go2[it][t], lev);
+                    a[u][2] = quad_read(go3[it][t], lev);
+                    a[u][3] = quad_read(go4[it][t], lev);
+                    w[u][0] = quad_read(sw1[it][t], lev);
+                    w[u][1] = quad_read(sw2[it][t], lev);
+                    w[u][2] = quad_read(sw3[it][t], lev);
+                    w[u][3] = quad_read(sw4[it][t], lev);
+                }
+                f32x4 va[NB][4], vb[NB][4];
+#pragma unroll
+                for (int u = 0; u < NB; ++u)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        va[u][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(a[u][c] + mine), 0, 0));
+                        vb[u][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(a[u][c] + mine2), 0, 0));
+                    }
+#pragma unroll
+                for (int u = 0; u < NB; ++u)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        msda_fma4(acc[half + u][0], w[u][c], va[u][c]);
+                        msda_fma4(acc[half + u][1], w[u][c], vb[u][c]);
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    // Every first read of a region has the issuing waves' vmcnt(0) and a barrier in front of it; every fill into a region has a
+    // barrier behind the last read of what was there (the 8-lane kernel's sequences, level for level).
+    auto landed = [] {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    };
+    auto level_single = [&](auto LEVC) {
+        __syncthreads();                                      // the previous level's reads are done
+        fill(LEVC);
+        landed();
+        level_samples(LEVC);
+    };
+    typedef std::integral_constant<int, 0> L0;
+    typedef std::integral_constant<int, 1> L1;
+    typedef std::integral_constant<int, 2> L2;
+    typedef std::integral_constant<int, 3> L3;
+    if constexpr (OVL == 0 && GLV == 0) {
+        level_single(L0{});
+        level_single(L1{});
+        level_single(L2{});
+        level_single(L3{});
+    } else if constexpr (OVL == 0) {
+        fill(L1{});                                           // lands under level 0's gathers
+        level_gather(L0{});
+        landed();
+        level_samples(L1{});
+        level_single(L2{});
+        level_single(L3{});
+    } else if constexpr (GLV == 0) {
+        // (the owner part's results are named here: otherwise the compiler sinks part of it behind the wait)
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it)
+#pragma unroll
+            for (int t = 0; t < POINTS; ++t)
+                asm volatile("" ::"v"(pk[it][t]), "v"(sw1[it][t]), "v"(sw2[it][t]), "v"(sw3[it][t]), "v"(sw4[it][t]));
+        __builtin_amdgcn_sched_barrier(0);
+        landed();                                             // L0 was requested in front of the owner part
+        level_samples(L0{});
+        __syncthreads();                                      // L0's reads are done
+        fill(L1{});
+        fill(L2{});
+        landed();
+        level_samples(L1{});
+        __syncthreads();                                      // L1's reads are done: its region takes L3
+        fill(L3{});
+        level_samples(L2{});                                  // (under L3's fill: bare reads, no vmcnt in front of them)
+        landed();
+        level_samples(L3{});
+    } else {
+        level_gather(L0{});                                   // L1 was requested in front of the owner part
+        landed();
+        level_samples(L1{});
+        __syncthreads();                                      // L1's reads are done
+        fill(L2{});
+        fill(L3{});
+        landed();
+        level_samples(L2{});
+        level_samples(L3{});
+    }
+    if (any_slow) {
+        if (slow_groups && lane == 0) {                       // diagnostic count: OCTETS on the global path, as in the 8-lane kernel
+            unsigned n_slow = 0;
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) n_slow += (fast[it][0] ? 0u : 1u) + (fast[it][1] ? 0u : 1u);
+            atomicAdd(slow_groups, n_slow);
+        }
+        // an octet with a sample outside its window: its half of the wave gathers all 16 samples from global memory (same arithmetic,
+        // same order); the window result of that half is discarded.  Quads lie inside a half-wave, so the broadcasts stay whole.
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const bool slow_here = lane < 32 ? !fast[it][0] : !fast[it][1];
+            if (!slow_here) continue;
+            const long q_global = qrow[it];
+            const float* op = raw + (size_t)q_global * ld_raw + m * (LP * 2) + 8 * l;
+            const f32x4 oa = *reinterpret_cast<const f32x4*>(op), ob = *reinterpret_cast<const f32x4*>(op + 4);
+            const f32x4 lg = *reinterpret_cast<const f32x4*>(raw + (size_t)q_global * ld_raw + HEADS * LP * 2 + m * LP + 4 * l);
+            float mx = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
+            mx = fmaxf(mx, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, mx), 0xB1, 0xF, 0xF, true)));
+            mx = fmaxf(mx, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, mx), 0x4E, 0xF, 0xF, true)));
+            float e[POINTS];
+#pragma unroll
+            for (int t = 0; t < POINTS; ++t) e[t] = expf(lg[t] - mx);
+            float sum = 0.f;
+#pragma unroll
+            for (int o = 0; o < LEVELS; ++o)
+#pragma unroll
+                for (int t = 0; t < POINTS; ++t) sum += quad_read(e[t], o);
+            const float inv_sum = 1.f / sum;
+            const float off8[8] = {oa[0], oa[1], oa[2], oa[3], ob[0], ob[1], ob[2], ob[3]};
+            bool ok_;
+            unsigned sa1, sa2, sa3, sa4, sb1, sb2, sb3, sb4, sc1, sc2, sc3, sc4, sd1, sd2, sd3, sd4;
+            const float rx_ = ref[q_global * 2], ry_ = ref[q_global * 2 + 1];
+            MSDA_GEOMETRY(it, 0, off8, rx_, ry_, e[0], inv_sum, ok_, sa)
+            MSDA_GEOMETRY(it, 1, off8, rx_, ry_, e[1], inv_sum, ok_, sb)
+            MSDA_GEOMETRY(it, 2, off8, rx_, ry_, e[2], inv_sum, ok_, sc)
+            MSDA_GEOMETRY(it, 3, off8, rx_, ry_, e[3], inv_sum, ok_, sd)
+            (void)ok_;
+            const unsigned s1[4] = {sa1, sb1, sc1, sd1}, s2[4] = {sa2, sb2, sc2, sd2}, s3[4] = {sa3, sb3, sc3, sd3},
+                           s4[4] = {sa4, sb4, sc4, sd4};
+            f32x4 ra = {0.f, 0.f, 0.f, 0.f}, rb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < LP; ++i) {
+                const int o = i >> 2, t = i & 3;
+                const unsigned a[4] = {quad_read(s1[t], o), quad_read(s2[t], o), quad_read(s3[t], o), quad_read(s4[t], o)};
+                const float w[4] = {quad_read(sw1[it][t], o), quad_read(sw2[it][t], o), quad_read(sw3[it][t], o), quad_read(sw4[it][t], o)};
+                f32x4 va[4], vb[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    va[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(a[c] + mine), 0, 0));
+                    vb[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(a[c] + mine2), 0, 0));
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    msda_fma4(ra, w[c], va[c]);
+                    msda_fma4(rb, w[c], vb[c]);
+                }
+            }
+            acc[it][0] = ra;
+            acc[it][1] = rb;
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it)
+        if (live[it]) {
+            float* o_ = out + (size_t)qrow[it] * (HEADS * CH) + m * CH;
+            *reinterpret_cast<f32x4*>(o_ + (mine >> 2)) = acc[it][0];
+            *reinterpret_cast<f32x4*>(o_ + (mine2 >> 2)) = acc[it][1];
+        }
+}
+
 #undef MSDA_GEOMETRY
 
 }  // namespace
@@ -893,14 +1330,41 @@ extern "C" int gom_msda_fused_forward(const float* raw, int ld_raw, const float*
     return gom_launch_status();
 }
 
-static int g_msda_window = 7;
+// Which window-kernel forms KEPT the four-lane layout (bit 3 of gom_msda_set_window selects it for these; the others run the 8-lane
+// layout whatever the bit says), and the channel assignment it runs with: decided by measurement (docs/LAB_NOTES.md, "The window
+// kernel's four-lane layout").  Level-0 tiles: 469 -> 403 us per launch at the bench shape, 740 -> 696 us at offsets x 2, every
+// pair.  Level-1 tiles: 164 -> 156 us at the bench shape but 244 -> 262 us at offsets x 2, where their gather path pays two
+// instructions per corner line: not every pair, so that form stays on eight lanes (-DMSDA_LANES4_L1=1 builds it for a re-run).
+#ifndef MSDA_LANES4_L0
+#define MSDA_LANES4_L0 1
+#endif
+#ifndef MSDA_LANES4_L1
+#define MSDA_LANES4_L1 0
+#endif
+#ifndef MSDA_LANES4_CHA
+#define MSDA_LANES4_CHA 2
+#endif
+typedef void (*msda_window_fn)(const float*, const int64_t*, const int64_t*, const float*, int, const float*, float*, int, long, int, int,
+                               int, int, unsigned*);
+template <int TY, int TX, int R, int CAP, int GLV, int KEPT4>
+static msda_window_fn msda_window_pick(bool ovl, bool lanes4) {
+    if constexpr (KEPT4 != 0) {
+        if (lanes4)
+            return ovl ? msda_window_kernel<TY, TX, R, CAP, 2, GLV, 1, 4, MSDA_LANES4_CHA>
+                       : msda_window_kernel<TY, TX, R, CAP, 2, GLV, 0, 4, MSDA_LANES4_CHA>;
+    }
+    return ovl ? msda_window_kernel<TY, TX, R, CAP, 4, GLV, 1> : msda_window_kernel<TY, TX, R, CAP, 4, GLV, 0>;
+}
+
+static int g_msda_window = 15;
 static unsigned* g_msda_slow = nullptr;
 /* [host] which encoder queries the entry below serves from LDS windows: bit 0 = the level-0 pixels (8 x 16 tiles, round 4), bit 1 =
  * the level-1 pixels (8 x 16 tiles, level 0 gathered, round 6); bit 2 = the overlapped fill schedule of the window kernel (the
- * first window requested in front of the owner part, the others in pairs) instead of one fill at a time; default 7 = all three,
+ * first window requested in front of the owner part, the others in pairs) instead of one fill at a time; bit 3 = the window kernel's
+ * four-lane layout (4 lanes per (query, head) pair, 8 channels each) for the forms that kept it; default 15 = all four,
  * 0 = everything on the lane-distributed kernel (A/B runs, tests).  Same bits either way. */
 extern "C" int gom_msda_set_window(int mask) {
-    g_msda_window = mask < 0 ? 0 : (mask & 7);
+    g_msda_window = mask < 0 ? 0 : (mask & 15);
     return GOM_OK;
 }
 /* [host] diagnostic: a device word that every window workgroup adds its FALLBACK octet groups to (groups of 8 (query, head) pairs
@@ -933,9 +1397,9 @@ extern "C" int gom_msda_fused_forward_encoder(const float* raw, int ld_raw, cons
         return gom_msda_fused_forward(raw, ld_raw, ref, value, value_batch_stride, value_row_stride, spatial_shapes,
                                       level_start_index, output, batch, num_query, stream);
     hipStream_t s = (hipStream_t)stream;
-    const bool ovl = (g_msda_window & 4) != 0;
+    const bool ovl = (g_msda_window & 4) != 0, l4 = (g_msda_window & 8) != 0;
     {
-        auto kern = ovl ? msda_window_kernel<TY0, TX0, R, CAP, 4, 0, 1> : msda_window_kernel<TY0, TX0, R, CAP, 4, 0, 0>;
+        auto kern = msda_window_pick<TY0, TX0, R, CAP, 0, MSDA_LANES4_L0>(ovl, l4);
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * 128);
         if (e != hipSuccess) return GOM_ERR_HIP_BASE + (int)e;
         hipLaunchKernelGGL(kern, dim3((unsigned)wgs0), dim3(256), CAP * 128, s, value, spatial_shapes, level_start_index, raw, ld_raw,
@@ -943,7 +1407,7 @@ extern "C" int gom_msda_fused_forward_encoder(const float* raw, int ld_raw, cons
     }
     long done = n0;
     if ((g_msda_window & 2) && n1 > 0) {
-        auto kern = ovl ? msda_window_kernel<TY1, TX1, R, CAP, 4, 1, 1> : msda_window_kernel<TY1, TX1, R, CAP, 4, 1, 0>;
+        auto kern = msda_window_pick<TY1, TX1, R, CAP, 1, MSDA_LANES4_L1>(ovl, l4);
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * 128);
         if (e != hipSuccess) return GOM_ERR_HIP_BASE + (int)e;
         hipLaunchKernelGGL(kern, dim3((unsigned)wgs1), dim3(256), CAP * 128, s, value, spatial_shapes, level_start_index, raw, ld_raw,

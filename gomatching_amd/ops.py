@@ -1204,6 +1204,9 @@ MSDA_WINDOW_L1 = _switch("MSDA_WINDOW_L1")
 # ... with the window kernel's overlapped fill schedule: the first window is requested in front of the owner part, the others in
 # pairs that share the buffer (same windows on the shipped pyramids, same bits; off = one fill at a time, barriers on both sides)
 MSDA_WINDOW_OVERLAP = _switch("MSDA_WINDOW_OVERLAP")
+# ... and the window kernel's four-lane layout: 4 lanes per (query, head) pair with 8 channels each, the owner's values broadcast by
+# DPP inside the quad (same bits, same fallback octets; off = 8 lanes of 4 channels, broadcasts through the LDS crossbar)
+MSDA_WINDOW_LANES4 = _switch("MSDA_WINDOW_LANES4")
 _msda_window_set = [None]
 
 
@@ -1255,7 +1258,7 @@ def msda_fused(raw, ref, value2d, batch_stride, shapes, lsi, B, Lq, valid_ratios
                                                  value2d.stride(0), _p(shapes), _p(lsi), _p(valid_ratios), _p(out), B, Lq,
                                                  _stream()), "gom_msda_fused_forward_vr")
         elif encoder_hw0 is not None and MSDA_WINDOW and MSDA_LANES:
-            mask = (3 if MSDA_WINDOW_L1 else 1) | (4 if MSDA_WINDOW_OVERLAP else 0)
+            mask = (3 if MSDA_WINDOW_L1 else 1) | (4 if MSDA_WINDOW_OVERLAP else 0) | (8 if MSDA_WINDOW_LANES4 else 0)
             if _msda_window_set[0] != mask:
                 _L().gom_msda_set_window(mask)
                 _msda_window_set[0] = mask

@@ -98,7 +98,9 @@ int gom_msda_fused_forward(const float* raw, int ld_raw, const float* ref, const
  * gom_msda_fused_forward.  Bit-identical to gom_msda_fused_forward.
  * [host] gom_msda_set_window(mask): bit 0 = level-0 windows, bit 1 = level-1 windows, bit 2 = the window kernel's overlapped fill
  *        schedule (the first window requested in front of the owner part, the others in pairs that share the buffer) instead of
- *        one fill at a time (default 7); 0 = always the gather kernel.
+ *        one fill at a time, bit 3 = the window kernel's four-lane layout (4 lanes per (query, head) pair, 8 channels each, DPP
+ *        broadcasts inside the quad) for the forms that kept it instead of 8 lanes of 4 channels (default 15); 0 = always the
+ *        gather kernel.  Same bits for every mask.
  * [host] gom_msda_window_count_fallbacks(ptr): diagnostic device word the window launches add their fallback octet groups to.
  * [host] gom_msda_window_plan: launches nothing; the windows of ONE tile as the kernel lays them out.  spatial_shapes: 4 x (H, W) in
  *        HOST memory; tile_level 0 / 1 (a tile of level-0 / level-1 queries); ref_first / ref_last: the reference points (x, y) of the

@@ -26,10 +26,12 @@ def per_kernel(path, counter, api_grids):
                 agg["msda_fused_lanes_kernel<false> [grid %d]" % int(r["Grid_Size"])].append(float(r["Counter_Value"]))
             if name.startswith("msda_window_kernel<"):
                 agg["msda_window_kernel"].append(float(r["Counter_Value"]))
-                # bench.py asks for a form by its first six parameters; the seventh is the fill schedule (1 = overlapped, the default)
-                head, _, sched = name.rpartition(",")
-                if head.count(",") == 5:
-                    agg[head + ">"].append(float(r["Counter_Value"]))
+                # bench.py asks for a form by the 8-lane kernel's first six parameters <TY,TX,R,CAP,4,GLV>; behind them come the fill
+                # schedule (1 = overlapped, the default) and, from the four-lane layout on, the lanes per pair and the channel
+                # assignment -- the four-lane kernel has NB = 2 in the fifth place: filed under the form it stands in for
+                par = name[name.index("<") + 1:name.rindex(">")].split(",")
+                if len(par) >= 7:
+                    agg["msda_window_kernel<%s,4,%s>" % (",".join(par[:4]), par[5])].append(float(r["Counter_Value"]))
             if name.startswith("bneck_kernel<") or name.startswith("bneck2_kernel<"):   # every fused bottleneck launch together as well
                 agg["bneck_kernel"].append(float(r["Counter_Value"]))
             if name.startswith("proj_ln_kernel<") or name.startswith("proj_ln2_kernel<"):   # both forms, all three FORMs
