@@ -27,6 +27,9 @@ Deliberate differences:
   * `--show` draws with csrc/overlay.hip by an integer rule instead of matplotlib (`gomatching_amd.show`: colours by track
     id, Pillow's glyphs, no antialiasing); without it the command does what it did before the flag existed, launch for launch.
     A resumed run skips finished videos, pictures included: `python -m gomatching_amd.show` draws them from OUT/jsons;
+  * `--lexicon FILE|DIR [--lexicon-pairs FILE] [--lexicon-max-dist N] [--lexicon-unmatched keep|drop]` runs
+    `gomatching_amd.lexicon.correct_results` over OUT after the videos are written (those of earlier, resumed runs included)
+    and writes OUT/lexicon/{jsons,preds}; without it the command issues the launches and writes the bytes it always did;
   * frames are decoded with Pillow (`convert("RGB")`, reversed to the BGR order `read_image(format="BGR")` yields).
     OpenCV is not available here, so the parity of the decoded pixels with `cv2.imread` (JPEG decoders differ in their
     IDCT and chroma upsampling) is UNPINNED, as is the parity of `results.min_area_rect` with `cv2.minAreaRect`.
@@ -82,6 +85,14 @@ def get_parser(drawing=False):
                        help="with --show: a TrueType font for the labels (default: Pillow's)")
         p.add_argument("--host-draw", action="store_true",
                        help="with --show: draw in numpy on the host (default: on the GPU, the same bytes)")
+    p.add_argument("--lexicon", default=None, metavar="FILE|DIR",
+                   help="after the videos are written, also write OUT/lexicon/ with every transcription snapped to the nearest "
+                        "word of this vocabulary (gomatching_amd.lexicon; a directory holds per-video <video>.txt files)")
+    p.add_argument("--lexicon-pairs", default=None, metavar="FILE", help="with --lexicon FILE: its pair list")
+    p.add_argument("--lexicon-max-dist", type=int, default=1, metavar="N",
+                   help="with --lexicon: accept a word at an edit distance of at most N (default 1)")
+    p.add_argument("--lexicon-unmatched", choices=("keep", "drop"), default="keep",
+                   help="with --lexicon: keep a transcription without an accepted word (default) or remove its row")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER,
                    help="modify config options using the command-line 'KEY VALUE' pairs")
     return p
@@ -203,6 +214,14 @@ def main(argv=None):
     if not os.path.isdir(args.input):
         sys.stderr.write("error: input directory %r not found\n" % args.input)
         return 2
+    if args.lexicon is None and (args.lexicon_pairs is not None or args.lexicon_max_dist != 1 or args.lexicon_unmatched != "keep"):
+        sys.stderr.write("error: --lexicon-pairs, --lexicon-max-dist and --lexicon-unmatched go with --lexicon\n")
+        return 2
+    if args.lexicon is not None and (not os.path.exists(args.lexicon) or args.lexicon_max_dist < 0 or (
+            args.lexicon_pairs is not None and not os.path.isfile(args.lexicon_pairs))):
+        sys.stderr.write("error: --lexicon %r / --lexicon-pairs %r not found, or a negative --lexicon-max-dist\n"
+                         % (args.lexicon, args.lexicon_pairs))
+        return 2
     cfg = _config.setup_cfg(config_file=args.config_file, opts=args.opts, builtin=args.builtin)
     state_dict = load_weights(cfg.MODEL.WEIGHTS)
     if state_dict is None:
@@ -273,6 +292,17 @@ def main(argv=None):
           rows_seconds, ", videos processed: ", len(videos))
     if args.show:
         print("host seconds drawing and encoding frames: ", draw_seconds)
+    if args.lexicon is not None:                            # every video under OUT, those of earlier (resumed) runs included
+        from . import lexicon as _lexicon
+        t0 = time.time()
+        try:
+            figures = _lexicon.correct_results(args.output, None, args.lexicon, args.lexicon_pairs, args.lexicon_max_dist,
+                                               args.lexicon_unmatched)
+        except _lexicon.LexiconError as e:
+            sys.stderr.write("error: lexicon: %s\n" % e)
+            return 2
+        print("lexicon: ", figures["rows"], " rows, ", figures["distinct"], " distinct strings matched, ", figures["changed"],
+              " changed, ", figures["dropped"], " dropped -> ", figures["output"], ", seconds: ", time.time() - t0)
     return 0
 
 

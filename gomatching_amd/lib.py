@@ -148,6 +148,7 @@ SIGNATURES = {
     "gom_mask_pairs_emit_f64": (I, [P, P, P, P, L, P, P, P, P, L, P, P, P, P, I, I, I, L, D, P, L, P, P, P]),
     "gom_mask_outline_polygons_u32": (I, [P, I, P, I, P, P, P, I, L, P, I, I, I, P, P]),
     "gom_overlay_compose_u8": (I, [P, P, I, I, I, P, P, P, P, I, L, P, P, P, P, P, P, I, P, P, P, I, L, I, I, P]),
+    "gom_lexicon_match_u32": (I, [P, L, P, P, I, P, L, P, I, P, I, I, P, P, P]),
     "gom_maxpool3x3s2_nhwc_f32": (I, [P, P, I, I, I, I, P]),
     "gom_pos_encoding_2d_f32": (I, [P, P, P, I, I, P]),
     "gom_point_pos_embed_f32": (I, [P, P, P, L, P]),

@@ -1734,6 +1734,40 @@ def mask_pairs(gt_words, gt_boxes, gt_woff, gt_area, det_words, det_boxes, det_w
     return counts, det, val
 
 
+LEXICON_MAX_LEN = 64                 # GOM_LEXICON_MAX_LEN of include/gomatching_hip.h
+
+
+def lexicon_match(q_chars, q_off, q_seg, w_chars, w_off, seg_off, max_len=None, out=None):
+    """The nearest word of its lexicon segment for every query, by Levenshtein distance, lowest index on ties, one launch
+    (csrc/lexicon.hip; the rule is in include/gomatching_hip.h).  q_chars int32 [q_nchars] / w_chars int32 [w_nchars] (the
+    uint32 code points), q_off [S+1], q_seg [S], w_off [W+1], seg_off [n_seg+1] int32, all CUDA.  -> (index int32 [S], the
+    word's index within the query's segment, or -1 for an empty segment; dist int32 [S], 100 beside a -1).  `max_len` = the largest length of a query or a word, if
+    the caller has it: above 64 is refused.  `out` = an int32 [2, S] buffer to hold both results (the two returned tensors
+    are its rows, so one copy brings both back)."""
+    dev = q_off.device
+    i32 = torch.int32
+    _chk_i(dev, ("q_chars", q_chars, i32, (None,)), ("q_off", q_off, i32, (None,)), ("q_seg", q_seg, i32, (None,)),
+           ("w_chars", w_chars, i32, (None,)), ("w_off", w_off, i32, (None,)), ("seg_off", seg_off, i32, (None,)))
+    S, W, n_seg = q_seg.shape[0], w_off.shape[0] - 1, seg_off.shape[0] - 1
+    if q_off.shape[0] != S + 1 or W < 0 or n_seg < 0:
+        raise ValueError("q_off must be [S+1] for q_seg [S], w_off [W+1] and seg_off [n_seg+1]")
+    if S > 0 and n_seg == 0:
+        raise ValueError("queries without a lexicon segment")
+    if max_len is None:
+        max_len = max(int((q_off[1:] - q_off[:-1]).max()) if S else 0, int((w_off[1:] - w_off[:-1]).max()) if W else 0)
+    if max_len > LEXICON_MAX_LEN:
+        raise ValueError("a query or a word of %d code points: at most %d are matched" % (max_len, LEXICON_MAX_LEN))
+    if out is None:
+        out = torch.empty((2, S), dtype=i32, device=dev)
+    else:
+        _chk_i(dev, ("out", out, i32, (2, S)))
+    with torch.cuda.device(dev):
+        check(_L().gom_lexicon_match_u32(_p(q_chars), q_chars.shape[0], _p(q_off), _p(q_seg), S, _p(w_chars), w_chars.shape[0],
+                                         _p(w_off), W, _p(seg_off), n_seg, int(max_len), _p(out[0]), _p(out[1]), _stream()),
+              "gom_lexicon_match_u32")
+    return out[0], out[1]
+
+
 def mask_outline_polygons(points, contour_off, mask_coff, boxes, word_off, H, W, words, sel=None):
     """`mask_fill_polygons` for the outlines alone (csrc/overlay.hip): writes Boundary of the rasterisation rule, without
     Fill and without areas, into `words` (int32 [nwords]) for every mask, or for the masks `sel` names.  -> words."""

@@ -740,6 +740,50 @@ int gom_overlay_compose_u8(const uint8_t* frames, uint8_t* out, int F, int H, in
                            const int32_t* label_pos, const int32_t* label_glyph, const uint8_t* label_rgb, int L,
                            const int32_t* glyph_wh, const int64_t* glyph_woff, const uint32_t* glyph_words, int G,
                            long glyph_nwords, int a_face, int a_box, void* stream);
+/* ---- Lexicon correction of transcriptions (csrc/lexicon.hip; python -m gomatching_amd.lexicon) ------------------
+ * The reference's `find_match_word` (third_party/adet/evaluation/text_evaluation_all.py:249-264, accepted at :332): a
+ * recognised word is snapped to the first lexicon word at the smallest edit distance.  THE RULE, integer-exact, so that the
+ * kernel, the numpy path (lexicon.host_match) and the plain-Python statement (tests/lexicon_statement.py) agree word for word:
+ *   Normalisation : norm(s) = s.upper(), Python's str.upper (it can lengthen a string: 'ß' -> 'SS'), taken as a sequence of
+ *                   Unicode code points.  Both sides are normalised on the host; the device sees code points only.
+ *   Length limit  : at most GOM_LEXICON_MAX_LEN = 64 code points after normalisation, for queries and for words (a longer
+ *                   lexicon line is an error naming the file and line, a longer transcription one naming the video and frame).
+ *   Lexicon       : the lines of a text file, stripped, blank lines skipped, in file order, duplicates kept.
+ *   Display map   : `pairs`.  With a pair-list file, for each stripped line key = line.split(' ')[0].upper(),
+ *                   value = line[len(key)+1:], later lines win (:206-210).  Without one pairs[norm(line)] = line over the
+ *                   lexicon's lines, later lines win (:198).  A lexicon word whose normal form has no entry is an error (the
+ *                   reference raises KeyError).
+ *   Match         : of a query q against a segment of words w_0 .. w_{n-1}: d_i = the Levenshtein distance of q and w_i (unit
+ *                   insert, delete and substitute, NO transposition: "AB" against "BA" is 2); the result is (i*, d*) with
+ *                   d* = min d_i and i* the LOWEST index that attains it (the reference's strict `<` in file order); an
+ *                   empty segment gives (-1, 100), the reference's initial values.
+ *   Acceptance    : d* <= max_dist, by default 1 (the reference's `< 1.5`); an accepted transcription becomes
+ *                   pairs[norm(w_i*)], one that is not accepted is kept (`keep`) or its row removed (`drop`).  On the host.
+ * gom_lexicon_match_u32: ONE launch for all queries of all segments (per-video lexicons and one shared lexicon are the same call).
+ *   q_chars uint32 [q_nchars], q_off int32 [S+1] : the queries' code points (CSR)
+ *   q_seg int32 [S]                              : each query's segment
+ *   w_chars uint32 [w_nchars], w_off int32 [W+1] : the words' code points (CSR), all segments one after the other
+ *   seg_off int32 [n_seg+1]                      : first word of each segment (CSR, seg_off[n_seg] = W)
+ *   max_len                                      : the largest length of a query or a word, as the caller counts it
+ *   best_index, best_dist int32 [S]              : i* WITHIN the query's segment (or -1) and d*
+ * Code points are 32-bit words, not packed 16-bit ones: an astral code point needs 21 bits, surrogate pairs would change the
+ * distance, and the whole 90 000-word vocabulary is 3 MB that stays in L2 -- the launch is bound by integer ALU, not by bytes.
+ * One 256-thread workgroup per query; lanes stride over the segment's words in ascending index; per pair the Hyyro bit-vector
+ * form of the Levenshtein recurrence on one 32- or 64-bit word (the query is the pattern; the equality masks of the code
+ * points below 256 are a per-query LDS table, any other code point is compared against the query's); a lane skips a word when
+ * |len(w) - len(q)| >= its own running best, which is exact because a lane's indices ascend and a distance is never below the
+ * length difference -- nothing depends on max_dist; (dist << 32 | index) is minimised by shuffles within a wave and through
+ * LDS across the four waves, one lane writes.  No atomics, no scratch, every output word has one writer: bitwise
+ * reproducible.  Offsets, segments and lengths are device data the host cannot vouch for: every index made from them is
+ * clamped (a length above the limit is cut to it).
+ * GOM_ERR_INVALID_ARG before any HIP call: null pointers of non-empty arrays, negative sizes, q_nchars or w_nchars above
+ * INT32_MAX, max_len above GOM_LEXICON_MAX_LEN, queries without a segment (S > 0 with n_seg == 0).  S == 0 is GOM_OK without
+ * a launch. */
+#define GOM_LEXICON_MAX_LEN 64
+#define GOM_LEXICON_NO_MATCH_DIST 100
+int gom_lexicon_match_u32(const uint32_t* q_chars, long q_nchars, const int32_t* q_off, const int32_t* q_seg, int S,
+                          const uint32_t* w_chars, long w_nchars, const int32_t* w_off, int W, const int32_t* seg_off,
+                          int n_seg, int max_len, int32_t* best_index, int32_t* best_dist, void* stream);
 int gom_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 /* out [H*W, 256] = PositionalEncoding2D(normalize=True) + level_embed, for an unpadded H x W level. */
 int gom_pos_encoding_2d_f32(const float* dim_t128, const float* level_embed256, float* out, int H, int W,
