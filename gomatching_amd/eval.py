@@ -26,7 +26,9 @@ Deliberate differences:
     (`python -m gomatching_amd.show` draws from OUT/jsons afterwards, as it does for resumed runs);
   * `--show` draws with csrc/overlay.hip by an integer rule instead of matplotlib (`gomatching_amd.show`: colours by track
     id, Pillow's glyphs, no antialiasing); without it the command does what it did before the flag existed, launch for launch.
-    A resumed run skips finished videos, pictures included: `python -m gomatching_amd.show` draws them from OUT/jsons;
+    A resumed run skips finished videos, pictures included: `python -m gomatching_amd.show` draws them from OUT/jsons.
+    With `--show`, `--device-encode` / `--host-encode` [`--jpeg-quality N`] write the JPEG frames with the project's own
+    baseline encoder (csrc/jpeg.hip on the GPU / the same rule in numpy) instead of Pillow, as the show command does;
   * `--lexicon FILE|DIR [--lexicon-pairs FILE] [--lexicon-max-dist N] [--lexicon-unmatched keep|drop]` runs
     `gomatching_amd.lexicon.correct_results` over OUT after the videos are written (those of earlier, resumed runs included)
     and writes OUT/lexicon/{jsons,preds}; without it the command issues the launches and writes the bytes it always did;
@@ -85,6 +87,8 @@ def get_parser(drawing=False):
                        help="with --show: a TrueType font for the labels (default: Pillow's)")
         p.add_argument("--host-draw", action="store_true",
                        help="with --show: draw in numpy on the host (default: on the GPU, the same bytes)")
+        from . import show as _show
+        _show.add_encode_arguments(p)                      # with --show: --device-encode, --host-encode, --jpeg-quality
     p.add_argument("--lexicon", default=None, metavar="FILE|DIR",
                    help="after the videos are written, also write OUT/lexicon/ with every transcription snapped to the nearest "
                         "word of this vocabulary (gomatching_amd.lexicon; a directory holds per-video <video>.txt files)")
@@ -199,6 +203,16 @@ def main(argv=None):
         sys.stderr.write("error: --online builds rows on the GPU and draws nothing: it takes neither --show nor --host-rows "
                          "(python -m gomatching_amd.show draws from OUT/jsons afterwards)\n")
         return 2
+    encode, quality = None, 95
+    if getattr(args, "device_encode", False) or getattr(args, "host_encode", False) or getattr(args, "jpeg_quality", None) is not None:
+        if not args.show:
+            sys.stderr.write("error: --device-encode, --host-encode and --jpeg-quality go with --show\n")
+            return 2
+        from . import show as _show
+        encode, quality, status, message = _show.encode_choice(args)
+        if status:
+            sys.stderr.write("error: %s\n" % message)
+            return status
     if args.push is not None and (not args.online or args.push < 1):
         sys.stderr.write("error: --push N (N >= 1) goes with --online\n")
         return 2
@@ -277,7 +291,7 @@ def main(argv=None):
             if args.show:
                 t0 = time.time()
                 _show.draw_video(frames, annotation, paths, video_name, args.output, cfg.MODEL.TRANSFORMER.VOC_SIZE, pool, atlas,
-                                 host=args.host_draw)
+                                 host=args.host_draw, encode=encode, quality=quality)
                 draw_seconds += time.time() - t0
             print("Video: ", video_name, "per_img_time: ", per_video_time / len(frames), ", FPS: ",
                   len(frames) / per_video_time)

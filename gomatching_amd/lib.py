@@ -149,6 +149,9 @@ SIGNATURES = {
     "gom_mask_outline_polygons_u32": (I, [P, I, P, I, P, P, P, I, L, P, I, I, I, P, P]),
     "gom_overlay_compose_u8": (I, [P, P, I, I, I, P, P, P, P, I, L, P, P, P, P, P, P, I, P, P, P, I, L, I, I, P]),
     "gom_lexicon_match_u32": (I, [P, L, P, P, I, P, L, P, I, P, I, I, P, P, P]),
+    "gom_jpeg_workspace_bytes": (L, [I, I, I]),
+    "gom_jpeg_encode_scan_u8": (I, [P, I, I, I, I, I, P, L, P, P]),
+    "gom_jpeg_encode_pack_u8": (I, [P, L, I, I, I, L, P, L, P]),
     "gom_maxpool3x3s2_nhwc_f32": (I, [P, P, I, I, I, I, P]),
     "gom_pos_encoding_2d_f32": (I, [P, P, P, I, I, P]),
     "gom_point_pos_embed_f32": (I, [P, P, P, L, P]),

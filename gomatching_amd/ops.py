@@ -1768,6 +1768,40 @@ def lexicon_match(q_chars, q_off, q_seg, w_chars, w_off, seg_off, max_len=None, 
     return out[0], out[1]
 
 
+JPEG_MAX_WIDTH, JPEG_MAX_HEIGHT = 4096, 65535   # GOM_JPEG_MAX_WIDTH / GOM_JPEG_MAX_HEIGHT of include/gomatching_hip.h
+
+
+def jpeg_encode(frames, quality=95, bgr=True):
+    """Baseline JPEG entropy-coded data of u8 frames [F,H,W,3] (CUDA), four launches (csrc/jpeg.hip; the integer rule is in
+    include/gomatching_hip.h; `jpeg.header` makes the rest of a file).  -> (payload u8 [offsets[F]] on the device, offsets
+    int64 [F+1] on the host): frame f's data is payload[offsets[f]:offsets[f+1]].  One small copy brings the offsets back
+    (the payload's size is a result); the caller copies the payload.  Wider than 4096 or higher than 65535 is refused here,
+    before any launch."""
+    _chk_frames(frames)
+    dev = frames.device
+    F, H, W, _ = frames.shape
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError("quality must lie in 1 .. 100, not %d" % quality)
+    if F == 0:
+        return torch.empty((0,), dtype=torch.uint8, device=dev), torch.zeros((1,), dtype=torch.int64)
+    nbytes = _L().gom_jpeg_workspace_bytes(F, H, W)
+    if W > JPEG_MAX_WIDTH or H > JPEG_MAX_HEIGHT or nbytes < 0:
+        raise _lib_mod.GomError("gom_jpeg_encode_scan_u8 refused: GOM_ERR_UNSUPPORTED (%d x %d frames; at most %d wide and "
+                                "%d high are encoded)" % (W, H, JPEG_MAX_WIDTH, JPEG_MAX_HEIGHT))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    off_dev = torch.empty((F + 1,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(_L().gom_jpeg_encode_scan_u8(_p(frames), F, H, W, 1 if bgr else 0, quality, _p(ws), nbytes, _p(off_dev),
+                                           _stream()), "gom_jpeg_encode_scan_u8")
+        offsets = off_dev.cpu()
+        total = int(offsets[F])
+        payload = torch.empty(((total + 3) // 4 * 4,), dtype=torch.uint8, device=dev)
+        check(_L().gom_jpeg_encode_pack_u8(_p(ws), nbytes, F, H, W, total, _p(payload), payload.shape[0], _stream()),
+              "gom_jpeg_encode_pack_u8")
+    return payload[:total], offsets
+
+
 def mask_outline_polygons(points, contour_off, mask_coff, boxes, word_off, H, W, words, sel=None):
     """`mask_fill_polygons` for the outlines alone (csrc/overlay.hip): writes Boundary of the rasterisation rule, without
     Fill and without areas, into `words` (int32 [nwords]) for every mask, or for the masks `sel` names.  -> words."""

@@ -2,6 +2,7 @@
 wrote -- the counterpart of the reference's `eval.py --show` (eval.py:364-369, text_track_visualizer.py), without a model.
 
     python -m gomatching_amd.show --input DIR --results OUT [--output DIR] [--font FILE] [--host-draw]
+                                  [--device-encode | --host-encode] [--jpeg-quality N]
                                   [--voc-size N | --config-file F | --builtin NAME]
       -> DIR/results/<video name>/<basename of the source frame>   (DIR defaults to OUT)
 
@@ -29,6 +30,17 @@ UNPINNED against the reference by construction: antialiasing (there is none here
 bitmaps come from Pillow: `ImageFont.truetype(--font)` or `ImageFont.load_default`, `getmask(text, mode="1")`; characters the
 font lacks are Pillow's business) and the encoder of `cv2.imwrite` (frames are written with Pillow, JPEG at quality 95).
 Not built: `--webcam`, video-file input, `ColorMode.IMAGE_BW`.
+
+Writing.  By default Pillow encodes every drawn frame on a pool of four threads.  Two opt-in flags write the JPEG frames (source
+extension .jpg / .jpeg) with the project's own baseline encoder instead -- the integer rule of include/gomatching_hip.h
+(`gom_jpeg_encode_*`): the same sampling and quantisation tables as Pillow's files, a restart interval per MCU row, not
+libjpeg's bytes:
+  --device-encode   csrc/jpeg.hip: the drawn frames stay on the GPU, `ops.jpeg_encode` codes the chunk, the F + 1 offsets and
+                    one copy of exactly the compressed bytes come back and the pool only writes them.  Not with --host-draw
+                    (status 2); without a GPU status 1.  A choice, not a fall-back.
+  --host-encode     `jpeg.encode_host`, the same rule in numpy: the same files.  With --host-draw the command needs no GPU.
+  --jpeg-quality N  1 .. 100, default 95; only with one of the two.
+Frames of any other extension go through Pillow as before, and with neither flag nothing changes.
 """
 import argparse
 import colorsys
@@ -288,15 +300,20 @@ def launch(frames_dev, scene, arrays, a_face=A_FACE, a_box=A_BOX, out=None):
                                label_rgb, gwh, gwoff, gwords, a_face, a_box, out=frames_dev if out is None else out)
 
 
-def compose_device(frames, scene, a_face=A_FACE, a_box=A_BOX):
-    """`compose_host` through csrc/overlay.hip: one upload of the frames and one of the description, the fill, outline and
-    compose launches, one copy back."""
+def compose_resident(frames, scene, a_face=A_FACE, a_box=A_BOX):
+    """`compose_host` through csrc/overlay.hip, the drawn frames LEFT on the device: one upload of the frames and one of the
+    description, the fill, outline and compose launches.  -> a CUDA u8 tensor [F,H,W,3]."""
     import torch
     if not torch.cuda.is_available():
         raise ShowError("no GPU: drawing runs in csrc/overlay.hip (use --host-draw for the numpy path)")
     dev = torch.device("cuda", torch.cuda.current_device())
     fr = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).to(dev)
-    return launch(fr, scene, device_arrays(scene, dev), a_face, a_box).cpu().numpy()
+    return launch(fr, scene, device_arrays(scene, dev), a_face, a_box)
+
+
+def compose_device(frames, scene, a_face=A_FACE, a_box=A_BOX):
+    """`compose_resident` and one copy back."""
+    return compose_resident(frames, scene, a_face, a_box).cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------ rows -> pictures
@@ -327,6 +344,20 @@ def _scene_of_rows(rows_per_frame, voc_size, atlas, H, W, bgr):
         raise ShowError(str(e))
 
 
+def _chunk_scene(frames_u8, rows_per_frame, voc_size, atlas, bgr):
+    part = np.ascontiguousarray(np.stack([np.asarray(f) for f in frames_u8]), dtype=np.uint8)
+    if part.ndim != 4 or part.shape[3] != 3:
+        raise ValueError("frames must be u8 [F,H,W,3]")
+    return part, _scene_of_rows(rows_per_frame, voc_size, atlas, part.shape[1], part.shape[2], bgr)
+
+
+def draw_chunk_resident(frames_u8, rows_per_frame, voc_size, atlas, bgr=True):
+    """One chunk of `draw_clip` on the GPU, the drawn frames left there for the encoder: -> a CUDA u8 tensor [F,H,W,3]."""
+    if len(rows_per_frame) != len(frames_u8) or not len(frames_u8):
+        raise ValueError("%d frames but rows for %d" % (len(frames_u8), len(rows_per_frame)))
+    return compose_resident(*_chunk_scene(frames_u8, rows_per_frame, voc_size, atlas, bgr))
+
+
 def draw_clip(frames_u8, rows_per_frame, voc_size, font=None, host=False, chunk=CHUNK, bgr=True, atlas=None):
     """Frames u8 [F,H,W,3] (an array or a list of H x W x 3 arrays) and, per frame, its result rows -> the drawn frames u8
     [F,H,W,3].  Per chunk of at most `chunk` frames: one fill, one outline and one compose call with one upload and one copy
@@ -341,10 +372,7 @@ def draw_clip(frames_u8, rows_per_frame, voc_size, font=None, host=False, chunk=
     atlas = atlas or Atlas(font)
     out = []
     for f0 in range(0, F, int(chunk)):
-        part = np.ascontiguousarray(np.stack([np.asarray(f) for f in frames_u8[f0:f0 + chunk]]), dtype=np.uint8)
-        if part.ndim != 4 or part.shape[3] != 3:
-            raise ValueError("frames must be u8 [F,H,W,3]")
-        scene = _scene_of_rows(rows_per_frame[f0:f0 + chunk], voc_size, atlas, part.shape[1], part.shape[2], bgr)
+        part, scene = _chunk_scene(frames_u8[f0:f0 + chunk], rows_per_frame[f0:f0 + chunk], voc_size, atlas, bgr)
         out.append(compose_host(part, scene) if host else compose_device(part, scene))
     if any(o.shape[1:] != out[0].shape[1:] for o in out):
         raise ValueError("the frames of a clip must share one size")
@@ -361,9 +389,52 @@ def write_frame(bgr, path):
         im.save(path)
 
 
-def draw_video(frames, annotation, paths, video_name, out_dir, voc_size, pool, atlas, host=False):
+def is_jpeg(path):
+    return os.path.splitext(path)[1].lower() in (".jpg", ".jpeg")
+
+
+def write_bytes(data, path):
+    with open(path, "wb") as fp:
+        fp.write(data)
+
+
+def _write_encoded(drawn, targets, pool, encode, quality):
+    """The writing step of a chunk under --device-encode (`drawn` = the resident CUDA tensor) or --host-encode (a host
+    array): the JPEG targets through the project's encoder -- the pool only writes bytes --, every other target through Pillow."""
+    from . import jpeg as _jpeg
+    jpg = [i for i, t in enumerate(targets) if is_jpeg(t)]
+    rest = [i for i, t in enumerate(targets) if not is_jpeg(t)]
+    H, W = int(drawn.shape[1]), int(drawn.shape[2])
+    if encode == "device":
+        import torch
+        from . import lib as _lib
+        from . import ops
+        if jpg:
+            sel = drawn if not rest else drawn[torch.as_tensor(jpg, device=drawn.device)]
+            try:
+                payload, offsets = ops.jpeg_encode(sel, quality, True)
+            except _lib.GomError as e:
+                raise ShowError(str(e))
+            data = _jpeg.files(payload.cpu().numpy(), offsets.numpy(), H, W, quality)
+        others = drawn[torch.as_tensor(rest, device=drawn.device)].cpu().numpy() if rest else []
+    else:
+        if jpg:
+            try:
+                data = _jpeg.files(*_jpeg.encode_host(drawn[jpg], quality, True), H, W, quality)
+            except ValueError as e:
+                raise ShowError(str(e))
+        others = drawn[rest] if rest else []
+    if jpg:
+        list(pool.map(write_bytes, data, [targets[i] for i in jpg]))
+    if rest:
+        list(pool.map(write_frame, others, [targets[i] for i in rest]))
+
+
+def draw_video(frames, annotation, paths, video_name, out_dir, voc_size, pool, atlas, host=False, encode=None, quality=95):
     """Draw a whole video (BGR frames, `annotation` = {1-based frame id as str: rows}) chunk by chunk and write
-    out_dir/results/<video name>/<basename of the frame's source path> through `pool`."""
+    out_dir/results/<video name>/<basename of the frame's source path> through `pool`.  encode = None: Pillow writes every
+    file; "device" / "host": the JPEG frames go through csrc/jpeg.hip (the drawn chunk never leaves the GPU) / through
+    `jpeg.encode_host`, at `quality`."""
     if len(annotation) != len(frames):
         raise ShowError("video %s: %d frames but results for %d" % (video_name, len(frames), len(annotation)))
     save_dir = os.path.join(out_dir, "results", video_name)
@@ -373,12 +444,18 @@ def draw_video(frames, annotation, paths, video_name, out_dir, voc_size, pool, a
     except KeyError as e:
         raise ShowError("video %s: no results for frame %s" % (video_name, e))
     for f0 in range(0, len(frames), CHUNK):
+        targets = [os.path.join(save_dir, os.path.basename(p)) for p in paths[f0:f0 + CHUNK]]
         try:
-            drawn = draw_clip(frames[f0:f0 + CHUNK], rows[f0:f0 + CHUNK], voc_size, host=host, atlas=atlas)
+            if encode == "device":
+                drawn = draw_chunk_resident(frames[f0:f0 + CHUNK], rows[f0:f0 + CHUNK], voc_size, atlas)
+            else:
+                drawn = draw_clip(frames[f0:f0 + CHUNK], rows[f0:f0 + CHUNK], voc_size, host=host, atlas=atlas)
+            if encode is not None:
+                _write_encoded(drawn, targets, pool, encode, quality)
         except ShowError as e:
             raise ShowError("video %s: %s" % (video_name, e))
-        targets = [os.path.join(save_dir, os.path.basename(p)) for p in paths[f0:f0 + CHUNK]]
-        list(pool.map(write_frame, drawn, targets))
+        if encode is None:
+            list(pool.map(write_frame, drawn, targets))
 
 
 def rows_of_json(tracks):
@@ -396,6 +473,38 @@ def rows_of_json(tracks):
 
 
 # ------------------------------------------------------------------------------------------ command line
+def add_encode_arguments(p):
+    """--device-encode, --host-encode and --jpeg-quality, for this command and for `eval --show`."""
+    p.add_argument("--device-encode", action="store_true",
+                   help="encode the drawn JPEG frames on the GPU (csrc/jpeg.hip): only compressed bytes come back (default: "
+                        "Pillow on the host; not with --host-draw)")
+    p.add_argument("--host-encode", action="store_true",
+                   help="encode the drawn JPEG frames with the same integer rule in numpy: the files of --device-encode")
+    p.add_argument("--jpeg-quality", type=int, default=None, metavar="N",
+                   help="with --device-encode or --host-encode: JPEG quality 1 .. 100 (default 95)")
+
+
+def encode_choice(args):
+    """The parsed encode flags -> (None | "device" | "host", quality, exit status, message): status 2 for flags that do not go
+    together, 1 for --device-encode on a machine without a GPU, 0 otherwise."""
+    quality = 95 if args.jpeg_quality is None else args.jpeg_quality
+    if args.device_encode and args.host_encode:
+        return None, quality, 2, "give at most one of --device-encode and --host-encode"
+    if args.device_encode and args.host_draw:
+        return None, quality, 2, "--device-encode encodes frames drawn on the GPU: it does not go with --host-draw " \
+                                 "(--host-encode writes the same files)"
+    if args.jpeg_quality is not None and not (args.device_encode or args.host_encode):
+        return None, quality, 2, "--jpeg-quality goes with --device-encode or --host-encode"
+    if not 1 <= quality <= 100:
+        return None, quality, 2, "--jpeg-quality must lie in 1 .. 100"
+    if args.device_encode:
+        import torch
+        if not torch.cuda.is_available():
+            return None, quality, 1, "--device-encode needs a GPU (--host-encode writes the same files without one)"
+        return "device", quality, 0, ""
+    return ("host" if args.host_encode else None), quality, 0, ""
+
+
 def get_parser():
     p = argparse.ArgumentParser(
         prog="python -m gomatching_amd.show",
@@ -407,6 +516,7 @@ def get_parser():
     p.add_argument("--output", default=None, metavar="DIR", help="directory for results/ (default: OUT)")
     p.add_argument("--font", default=None, metavar="FILE", help="a TrueType font for the labels (default: Pillow's built-in font)")
     p.add_argument("--host-draw", action="store_true", help="draw in numpy on the host (default: on the GPU, the same bytes)")
+    add_encode_arguments(p)
     p.add_argument("--voc-size", type=int, default=None, metavar="N",
                    help="vocabulary size of the model: 37 upper-cases the labels (default 37)")
     p.add_argument("--config-file", default=None, metavar="FILE", help="take the vocabulary size from a config file")
@@ -431,6 +541,10 @@ def main(argv=None):
     if not os.path.isdir(args.input):
         sys.stderr.write("error: input directory %r not found\n" % args.input)
         return 2
+    encode, quality, status, message = encode_choice(args)
+    if status:
+        sys.stderr.write("error: %s\n" % message)
+        return status
     voc_size = 37 if args.voc_size is None else args.voc_size
     if args.config_file is not None or args.builtin is not None:
         voc_size = _config.setup_cfg(config_file=args.config_file, opts=[], builtin=args.builtin).MODEL.TRANSFORMER.VOC_SIZE
@@ -453,7 +567,8 @@ def main(argv=None):
                     raise ShowError("video %s: result rows without a segmentation cannot be drawn" % video_name)
                 print("drawing {}...".format(video_name))
                 frames = list(readers.map(_eval.read_frame, paths))
-                draw_video(frames, annotation, paths, video_name, out_dir, voc_size, writers, atlas, host=args.host_draw)
+                draw_video(frames, annotation, paths, video_name, out_dir, voc_size, writers, atlas, host=args.host_draw,
+                           encode=encode, quality=quality)
     except ShowError as e:
         sys.stderr.write("error: %s\n" % e)
         return 2

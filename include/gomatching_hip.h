@@ -784,6 +784,70 @@ int gom_overlay_compose_u8(const uint8_t* frames, uint8_t* out, int F, int H, in
 int gom_lexicon_match_u32(const uint32_t* q_chars, long q_nchars, const int32_t* q_off, const int32_t* q_seg, int S,
                           const uint32_t* w_chars, long w_nchars, const int32_t* w_off, int W, const int32_t* seg_off,
                           int n_seg, int max_len, int32_t* best_index, int32_t* best_dist, void* stream);
+/* ---- JPEG encoding of drawn frames (csrc/jpeg.hip; gomatching_amd/jpeg.py; show --device-encode) -------------------
+ * Baseline sequential DCT, 8 bits, three components at 4:2:0 (sampling (2,2), (1,1), (1,1)) in a JFIF 1.01 container: the
+ * layout of Pillow's `save(quality=q)`, with a restart interval per MCU row so that every MCU row is coded independently.
+ * THE RULE, in integers only (no floating point anywhere), so that the kernels, the numpy path (jpeg.encode_host) and the
+ * plain-Python statement (tests/jpeg_statement.py) agree byte for byte.  `>>` is the arithmetic shift (floor), `/` of
+ * non-negative integers is floor division.
+ *   Input     : frames u8 [F,H,W,3]; bgr = 1: the channels are B, G, R (what `show` holds), 0: R, G, B.
+ *   Padding   : MH = (H + 15) / 16 MCU rows of MW = (W + 15) / 16 MCUs of 16 x 16 pixels; pixel (y, x) of the padded image is
+ *               pixel (min(y, H - 1), min(x, W - 1)): the last row and column replicated.  SOF0 carries the true H and W.
+ *   Colour    : JFIF's full-range matrix in 16-bit fixed point, per pixel
+ *                 Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *                 Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *                 Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16          (each lies in 0 .. 255)
+ *   Chroma    : a chrominance sample = the mean of its 2 x 2 block of Cb (Cr) values, (a + b + c + d + 2) >> 2.
+ *   Blocks    : an MCU is Y00 Y01 Y10 Y11 Cb Cr (luminance blocks left to right, top to bottom); every sample s = value - 128.
+ *   Transform : F = T s T^t on the integer table T[u][x] = round(8192 a(u) cos((2 x + 1) u pi / 16)), a(0) = sqrt(1/8),
+ *               a(u) = 1/2, rows first:
+ *                 T = { 2896,  2896,  2896,  2896,  2896,  2896,  2896,  2896,
+ *                       4017,  3406,  2276,   799,  -799, -2276, -3406, -4017,
+ *                       3784,  1567, -1567, -3784, -3784, -1567,  1567,  3784,
+ *                       3406,  -799, -4017, -2276,  2276,  4017,   799, -3406,
+ *                       2896, -2896, -2896,  2896,  2896, -2896, -2896,  2896,
+ *                       2276, -4017,   799,  3406, -3406,  -799,  4017, -2276,
+ *                       1567, -3784,  3784, -1567, -1567,  3784, -3784,  1567,
+ *                        799, -2276,  3406, -4017,  4017, -3406,  2276,  -799 }
+ *                 t[y][u] = (sum_x T[u][x] s[y][x] + 128) >> 8            (five fractional bits kept; |sum| < 2^23)
+ *                 f[v][u] = (sum_y T[v][y] t[y][u] + (1 << 17)) >> 18     (|sum| < 2^30: 32-bit accumulators throughout)
+ *   Quantise  : tables = Annex K.1 (luminance) and K.2 (chrominance), each entry (base * scale + 50) / 100 clamped to 1 .. 255
+ *               with scale = 5000 / quality below 50 and 200 - 2 quality from 50 (quality 1 .. 100) -- Pillow's
+ *               `Image.quantization` for the same quality.  k = sign(f) ((|f| + (q >> 1)) / q): half away from zero.  AC
+ *               coefficients are clamped to -1023 .. 1023 (category 10, the largest a baseline AC code names).
+ *   Entropy   : the four Annex K Huffman tables (K.3 - K.6), coefficients in zigzag order, DC as the difference from the
+ *               previous block of the same component, categories and amplitude bits of F.1.2 (a negative value v is written
+ *               as the low bits of v - 1), ZRL for every 16 zeros in front of a non-zero coefficient, EOB unless coefficient
+ *               63 is non-zero.  Bits fill bytes from the most significant bit.
+ *   Intervals : a restart interval = one MCU row (DRI = MW): the predictors start at 0, the last byte is filled with 1-bits,
+ *               every byte 0xFF of the interval is followed by 0x00; between interval r and r + 1 of a frame stands RSTn,
+ *               0xFF 0xD0 + (r mod 8).  A frame's DATA = its MH intervals and the MH - 1 markers between them.
+ *   Container : SOI, APP0 (JFIF 1.01, density 1:1, no thumbnail), DQT 0 and DQT 1 (zigzag order), SOF0 (8 bits, H, W, components
+ *               1: 0x22 table 0, 2 and 3: 0x11 table 1), DHT DC 0, AC 0, DC 1, AC 1, DRI, SOS (Ss 0, Se 63, Ah Al 0), DATA, EOI.
+ *               Everything but DATA depends on H, W and quality alone and is made on the host (jpeg.header).
+ * The device produces DATA of every frame, packed: payload[frame_off[f] .. frame_off[f+1]) for frame f.  Two calls, because the
+ * payload's size is a result: the caller reads frame_off (F + 1 values), allocates, and packs.
+ *   gom_jpeg_workspace_bytes : bytes of the workspace for F frames of H x W, or -1 (sizes the encoder refuses).  Per block 128
+ *                              bytes of coefficients and 208 of staged code, per interval 416 bytes per block (+ 16) of stuffed
+ *                              data -- the worst case of the format, of which a launch touches what the data needs.
+ *   gom_jpeg_encode_scan_u8  : transform, entropy coding and the scan of the interval lengths (three launches): leaves every
+ *                              interval's bytes in the workspace and writes frame_off int64 [F+1] (device).
+ *   gom_jpeg_encode_pack_u8  : with total = frame_off[F] as the caller read it: one launch that writes payload[0 .. total)
+ *                              (payload 4-byte aligned with payload_bytes >= total rounded up to 4; the bytes behind total in
+ *                              the last word are written as 0).  The workspace must be the one the scan call left.
+ * No atomics, no scratch; a thread owns every word it writes (a word of the bit stream, a word of the payload); the result
+ * depends on nothing but the input: bitwise reproducible.  Widths up to GOM_JPEG_MAX_WIDTH = 4096 (the block starts of an
+ * interval, 6 per MCU, live in LDS) and heights up to 65535 (SOF0): beyond them GOM_ERR_UNSUPPORTED before any HIP call.
+ * GOM_ERR_INVALID_ARG before any HIP call: null pointers, F < 0, H or W < 1, quality outside 1 .. 100, bgr outside {0, 1}, a
+ * workspace that is too small or not 256-byte aligned, a payload that is too small or not 4-byte aligned, total < 0 or above
+ * what the workspace can hold.  F == 0 is GOM_OK without a launch (frame_off is not written). */
+#define GOM_JPEG_MAX_WIDTH 4096
+#define GOM_JPEG_MAX_HEIGHT 65535
+long gom_jpeg_workspace_bytes(int F, int H, int W);
+int gom_jpeg_encode_scan_u8(const uint8_t* frames, int F, int H, int W, int bgr, int quality, void* workspace,
+                            long workspace_bytes, int64_t* frame_off, void* stream);
+int gom_jpeg_encode_pack_u8(const void* workspace, long workspace_bytes, int F, int H, int W, long total, uint8_t* payload,
+                            long payload_bytes, void* stream);
 int gom_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 /* out [H*W, 256] = PositionalEncoding2D(normalize=True) + level_embed, for an unpadded H x W level. */
 int gom_pos_encoding_2d_f32(const float* dim_t128, const float* level_embed256, float* out, int H, int W,
