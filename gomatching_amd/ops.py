@@ -325,6 +325,8 @@ def gemm(A, W, bias=None, scale=None, A2=None, rows=None, R=None, relu=False, ou
     ldc, ldr = _ld(out), _ld(R)
     if rows is not None:
         assert rows.dtype == torch.int32 and rows.is_contiguous()
+    if M == 0:
+        return out                                           # no row, no launch: an empty tensor has no address for the entry's null checks
     # `small` marks the tracker's latency-bound products (kernel choice must never depend on how many frames share a
     # step, so this is an explicit request): up to SMALL_GEMM_OUTPUTS outputs one wave owns a column for 8 rows on the
     # VALU (7-20 us); larger ones take the deterministic split-K (20-50 us) instead of looping the whole K in few
@@ -2362,8 +2364,14 @@ def asso_ce(logits, frame_offsets, gt, want_loss=True, grad_scale=None):
     assert gt.dtype == torch.int32 and gt.is_contiguous() and frame_offsets.dtype == torch.int32
     loss = torch.empty((R, T), dtype=_f32, device=logits.device) if want_loss else None
     dl = torch.zeros_like(logits) if grad_scale is not None else None
-    check(_L().gom_asso_ce_f32(_p(logits), logits.shape[1] if logits.dim() == 2 else 0, _p(frame_offsets), T, _p(gt), R,
-                               _p(loss), _p(grad_scale), _p(dl), _stream()), "gom_asso_ce_f32")
+    lp, dp = _p(logits), _p(dl)
+    if R > 0 and logits.numel() == 0:
+        # rows without a single proposal column (every frame empty): the kernel reads and writes no logit, but an empty tensor has
+        # no address and the entry refuses a null pointer -- one float stands in for both
+        anchor = torch.zeros((1,), dtype=_f32, device=logits.device)
+        lp, dp = _p(anchor), (None if dl is None else _p(anchor))
+    check(_L().gom_asso_ce_f32(lp, logits.shape[1] if logits.dim() == 2 else 0, _p(frame_offsets), T, _p(gt), R,
+                               _p(loss), _p(grad_scale), dp, _stream()), "gom_asso_ce_f32")
     return loss, dl
 
 
