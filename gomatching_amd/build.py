@@ -1,5 +1,6 @@
 """Build libgomatching_hip.so in-tree with hipcc for gfx950 (no torch extension machinery: the library
 has a plain C ABI and links only the HIP runtime)."""
+import glob
 import hashlib
 import os
 import shutil
@@ -26,7 +27,7 @@ def _hipcc():
 
 def _stamp(path):
     h = hashlib.sha1()
-    for dep in [path, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "tracker_tasks.h"), os.path.join(CSRC, "mask_rule.h"), os.path.join(CSRC, "quad_geom.h"), os.path.join(HERE, "..", "include", "gomatching_hip.h")]:
+    for dep in [path] + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "gomatching_hip.h")]:
         with open(dep, "rb") as f:
             h.update(f.read())
     h.update(" ".join(FLAGS + _extra(os.path.basename(path))).encode())

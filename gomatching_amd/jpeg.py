@@ -15,7 +15,9 @@ is claimed: its DCT rounds differently (tests/test_jpeg_cpu.py measures the diff
 """
 import numpy as np
 
-MAX_WIDTH = 4096                                           # GOM_JPEG_MAX_WIDTH of include/gomatching_hip.h
+from .lib import CONSTANTS as _ABI
+
+MAX_WIDTH = _ABI["GOM_JPEG_MAX_WIDTH"]
 MAX_HEIGHT = 65535                                         # SOF0 holds 16 bits
 
 # natural index of the k-th coefficient in zigzag order

@@ -38,9 +38,10 @@ import sys
 import numpy as np
 
 from . import results as _results
+from .lib import CONSTANTS as _ABI
 
-MAX_LEN = 64                         # GOM_LEXICON_MAX_LEN of include/gomatching_hip.h
-NO_MATCH_DIST = 100                  # GOM_LEXICON_NO_MATCH_DIST
+MAX_LEN = _ABI["GOM_LEXICON_MAX_LEN"]
+NO_MATCH_DIST = _ABI["GOM_LEXICON_NO_MATCH_DIST"]
 
 
 class LexiconError(Exception):

@@ -1,230 +1,105 @@
-"""ctypes binding of libgomatching_hip.so (the C ABI in include/gomatching_hip.h).
+"""ctypes binding of libgomatching_hip.so, derived from the C ABI's one statement: include/gomatching_hip.h.
+
+The header is parsed when this module is imported: its declarations become `SIGNATURES`, its `#define GOM_* <integer>` lines
+`CONSTANTS`, its struct typedefs the ctypes `Structure` classes in `STRUCTS`.  Nothing of the ABI is restated here.
 
 The product path has NO fallback: if the shared library is missing or cannot be loaded, importing
 the ops raises.  torch is used for device memory and streams only.
 """
 import ctypes
 import os
-from ctypes import c_int, c_long, c_float, c_void_p
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GOM_LIB_PATH") or os.path.join(HERE, "libgomatching_hip.so")   # (override: same-box A/B of two builds)
-
-GOM_OK = 0
-_ERR = {1: "GOM_ERR_INVALID_ARG (violated precondition)", 2: "GOM_ERR_UNSUPPORTED"}
-
-P = c_void_p
-I = c_int
-L = c_long
-F = c_float
-D = ctypes.c_double
-U = ctypes.c_uint
-U64 = ctypes.c_ulonglong
-
-
-class OptimTensor(ctypes.Structure):
-    """`gom_optim_tensor` of include/gomatching_hip.h: one row of the clipped-AdamW table."""
-    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
-                ("n", c_long), ("step", c_long), ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double)]
-
-
-# name -> (restype, argtypes); must list every symbol declared in include/gomatching_hip.h
-SIGNATURES = {
-    "gom_abi_version": (I, []),
-    "gom_built_for_arch": (ctypes.c_char_p, []),
-    "gom_ms_deform_attn_forward": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
-    "gom_ms_deform_attn_forward_any": (I, [I, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
-    "gom_ms_deform_attn_backward": (I, [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
-    "gom_ms_deform_attn_forward_strided": (I, [P, L, I, P, P, P, P, P, I, I, P]),
-    "gom_msda_set_lane_distributed": (I, [I]),
-    "gom_msda_fused_forward": (I, [P, I, P, P, L, I, P, P, P, I, I, P]),
-    "gom_msda_fused_forward_encoder": (I, [P, I, P, P, L, I, P, P, P, I, I, I, I, I, I, P]),
-    "gom_msda_set_window": (I, [I]),
-    "gom_msda_window_count_fallbacks": (I, [P]),
-    "gom_msda_window_plan": (I, [P, I, P, P, I, P, P]),
-    "gom_msda_prepare": (I, [P, I, P, I, P, P, P, L, P]),
-    "gom_gemm_f32": (I, [P, P, P, I, P, I, P, P, P, I, I, P, I, I, I, I, P]),
-    "gom_gemm_splitk_workspace_bytes": (L, [I, I, I]),
-    "gom_gemm_f32_splitk": (I, [P, P, I, P, I, P, P, P, I, I, P, I, I, I, I, P, L, P]),
-    "gom_conv2d_nhwc_f32": (I, [P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, P]),
-    "gom_split_bf16x3": (I, [P, I, I, I, P, I, P]),
-    "gom_gemm_f32_bf16x6": (I, [P, P, I, P, L, I, P, P, P, I, I, I, P, I, I, I, I, P]),
-    "gom_conv2d_nhwc_f32_bf16x6": (I, [P, P, L, I, P, P, P, I, P, I, I, I, I, I, I, I, I, I, P]),
-    "gom_gemm_small_f32": (I, [P, P, I, P, I, P, P, P, I, I, P, I, I, I, I, P]),
-    "gom_conv_bf16x6_splits": (I, [I, I, I]),
-    "gom_conv2d_nhwc_f32_bf16x6_splitk": (I, [P, P, L, I, P, P, P, I, P, I, I, I, I, I, I, I, I, I, P, L, I, P]),
-    "gom_split_f16x2": (I, [P, I, I, I, P, I, P, P]),
-    "gom_gemm_f32_f16x3": (I, [P, P, I, P, L, I, P, P, P, P, I, I, I, P, I, I, I, I, P, P]),
-    "gom_gemm_f32_f16x3_rp": (I, [P, P, I, P, L, I, P, P, P, P, I, I, I, I, P, I, I, I, I, P, P]),
-    "gom_conv2d_nhwc_f32_f16x3": (I, [P, P, L, I, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, P, L, I, P, P]),
-    "gom_conv3x3_patch_supported": (I, [I, I]),
-    "gom_conv3x3_patch_image_bytes": (L, [I, I]),
-    "gom_conv3x3_patch_image": (I, [P, L, I, I, I, P, L, P]),
-    "gom_conv3x3_patch_f32_f16x3": (I, [P, P, P, P, P, I, P, I, I, I, I, I, P, P]),
-    "gom_bneck_image_bytes": (L, [I, I, I]),
-    "gom_bneck_image": (I, [P, L, I, P, P, P, P, L, I, I, I, I, P, L, P]),
-    "gom_bneck_f32": (I, [P, I, P, P, I, P, P, P, I, P, I, I, I, I, I, P, P]),
-    "gom_bneck_sc_image_bytes": (L, [I, I, I, I, I]),
-    "gom_bneck_sc_image": (I, [P, L, I, P, P, P, P, L, I, P, L, I, P, P, P, I, I, I, I, I, P, L, P]),
-    "gom_bneck_sc_f32": (I, [P, I, P, P, I, I, I, I, I, P, P, P, I, P, I, I, I, I, I, P, P]),
-    "gom_bneck2_image_bytes": (L, [I, I, I]),
-    "gom_bneck2_image": (I, [P, L, I, P, P, P, P, L, I, I, I, I, P, L, P]),
-    "gom_bneck2_f32": (I, [P, I, P, P, I, P, P, P, I, P, I, I, I, I, I, P, P]),
-    "gom_dec_attn_image_bytes": (L, [I, I]),
-    "gom_dec_attn_image": (I, [P, L, I, P, P, P, L, I, P, P, P, P, I, P, L, P]),
-    "gom_dec_attn_f32": (I, [P, I, P, I, P, F, P, I, I, I, I, I, P, P]),
-    "gom_dec_attn_raw_image_bytes": (L, []),
-    "gom_dec_attn_raw_image": (I, [P, L, I, P, P, P, L, P]),
-    "gom_dec_attn_raw_f32": (I, [P, I, P, F, P, I, P, I, P, I, I, I, I, P, P]),
-    "gom_dec_attn2_image_bytes": (L, [I, I]),
-    "gom_dec_attn2_image": (I, [P, L, I, P, P, P, L, I, P, P, P, P, I, P, L, P]),
-    "gom_dec_attn2_f32": (I, [P, I, P, I, P, F, P, I, I, I, I, I, P, P]),
-    "gom_dec_attn2_raw_image_bytes": (L, []),
-    "gom_dec_attn2_raw_image": (I, [P, L, I, P, P, P, L, P]),
-    "gom_dec_attn2_raw_f32": (I, [P, I, P, F, P, I, P, I, P, I, I, I, I, P, P]),
-    "gom_dec_inter_heads_f32": (I, [P, I, P, P, I, I, I, I, P, P]),
-    "gom_proj_ln_image_bytes": (L, [I, I]),
-    "gom_proj_ln_image": (I, [P, L, I, I, I, P, L, P]),
-    "gom_proj_ln_f32": (I, [P, I, P, P, P, P, I, P, P, F, P, I, I, P, P]),
-    "gom_proj_ln_dot_f32": (I, [P, I, P, P, P, P, P, F, P, F, P, I, P, P]),
-    "gom_gemm_k256_image_bytes": (L, [I, I]),
-    "gom_gemm_k256_image": (I, [P, L, I, P, P, I, I, P, L, P]),
-    "gom_gemm_k256_f32": (I, [P, P, I, P, P, I, I, I, P, I, I, I, I, I, P, P]),
-    "gom_gemm_k256_rp_f32": (I, [P, P, I, P, P, I, I, I, I, P, I, I, I, I, I, P, P]),
-    "gom_gemm_k256_set_lines": (None, [I]),
-    "gom_gemm_k256_set_interleave": (None, [I]),
-    "gom_stem_conv_pool_f32": (I, [P, P, L, I, P, P, P, P, I, I, I, P, P]),
-    "gom_ffn_fused_image_bytes": (L, [I, I]),
-    "gom_ffn_fused_image": (I, [P, L, I, P, P, P, L, I, I, I, P, L, P]),
-    "gom_ffn_set_half_tail": (I, [I]),
-    "gom_ffn_set_stream_cus": (I, [I]),
-    "gom_ffn_fused_ln_f32": (I, [P, I, P, P, P, P, P, F, P, I, I, I, I, P, P]),
-    "gom_ffn_fused_image_acc_order": (I, [P, L, I, P, P, P, L, I, I, I, P, L, P]),
-    "gom_dec_tail_image_bytes": (L, [I, I, I]),
-    "gom_dec_tail_f32": (I, [P, I, P, I, P, P, P, P, F, P, P, P, P, P, P, P, P, P, I, P, P, I, I, P, P]),
-    "gom_dec_tail2_wave_bytes": (L, [I, I, I, I, I]),
-    "gom_dec_tail2_image_lin": (I, [P, L, I, P, L, L, I, P]),
-    "gom_dec_tail2_image_mlp": (I, [P, L, I, P, L, I, I, P, L, L, I, P]),
-    "gom_dec_tail2_f32": (I, [P, I, P, I, P, L, I, P, P, P, P, F, P, P, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, I, I,
-                              I, P, P]),
-    "gom_dec_tail_lin_image_bytes": (L, []),
-    "gom_dec_tail_lin_image": (I, [P, L, I, P, L, P]),
-    "gom_dec_tail_proj_f32": (I, [P, I, P, I, P, I, P, P, P, P, F, P, P, P, P, F, P, P, P, P, P, P, P, P, P, I, P, P, I, I, P, P]),
-    "gom_mlp2_fused_f32": (I, [P, I, P, P, P, I, P, I, I, I, I, P, P]),
-    "gom_pack_records_f32": (I, [P, I, I, P, P, P, P, P, P, I, I, I, I, F, F, P, P]),
-    "gom_relu_backward_f32": (I, [P, P, P, L, P]),
-    "gom_softmax_rows_backward_f32": (I, [P, P, P, L, I, L, F, P]),
-    "gom_asso_ce_f32": (I, [P, I, P, I, P, L, P, P, P, P]),
-    "gom_sigmoid_focal_f32": (I, [P, P, F, F, L, P, P, P]),
-    "gom_dropout_f32": (I, [P, L, P, L, P, L, L, L, U64, U, U, U, L, F, P]),
-    "gom_relu_backward_scaled_f32": (I, [P, P, P, L, F, P]),
-    "gom_softmax_dropout_rows_f32": (I, [P, P, L, I, L, F, L, U64, U, U, U, L, F, P]),
-    "gom_softmax_dropout_rows_backward_f32": (I, [P, P, P, L, I, L, F, L, U64, U, U, U, L, F, P]),
-    "gom_clipped_adamw_partials": (L, [P, I]),
-    "gom_clipped_adamw_step": (I, [P, I, D, D, D, D, P, L, P, P]),
-    "gom_layernorm_f32": (I, [P, P, P, P, P, L, I, F, P]),
-    "gom_groupnorm32_nhwc_f32": (I, [P, P, P, P, P, L, I, I, I, F, P]),
-    "gom_mha_core_f32": (I, [P, P, P, P, I, I, I, I, I, I, ctypes.POINTER(c_long), P]),
-    "gom_resample_ksize_bilinear": (I, [I, I]),
-    "gom_resample_coeffs_bilinear": (I, [I, I, P, P, I]),
-    "gom_resize_bilinear_u8_hwc3": (I, [P, I, I, I, P, P, I, P, P, I, P, I, I, I, P]),
-    "gom_ingest_u8_hwc3_to_nhwc4": (I, [P, I, I, I, P, P, I, P, P, I, ctypes.POINTER(c_float),
-                                        ctypes.POINTER(c_float), P, I, I, I, P]),
-    "gom_resize_crop_bilinear_u8_hwc3": (I, [P, I, I, I, P, P, I, P, P, I, P, I, I, I, I, I, I, I, P]),
-    "gom_ingest_crop_u8_hwc3_to_nhwc4": (I, [P, I, I, I, P, P, I, P, P, I, ctypes.POINTER(c_float),
-                                             ctypes.POINTER(c_float), P, I, I, I, I, I, I, I, P]),
-    "gom_ingest_motion_u8_hwc3_to_nhwc4": (I, [P, I, I, P, L, P, I, ctypes.POINTER(c_float), ctypes.POINTER(c_float), P, I, I, I,
-                                               P]),
-    "gom_preprocess_nchw_to_nhwc4": (I, [P, ctypes.POINTER(c_float), ctypes.POINTER(c_float), P, I, I, I, P]),
-    "gom_result_rows_i32": (I, [P, P, P, I, I, P, I, P]),
-    "gom_result_rows_gather_i32": (I, [P, P, L, P, I, I, P, I, P]),
-    "gom_quad_bezier_i32": (I, [P, P, I, P, P]),
-    "gom_quad_pairs_count_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, P]),
-    "gom_quad_pairs_emit_f64": (I, [P, P, P, P, P, P, I, I, I, L, I, D, P, L, P, P, P]),
-    "gom_quad_det_match_f64": (I, [P, P, P, P, P, I, I, I, D, D, P, P, P, P]),
-    "gom_mask_fill_polygons_u32": (I, [P, I, P, I, P, P, P, I, L, P, I, I, I, P, P, P]),
-    "gom_mask_fill_rle_u32": (I, [P, I, P, P, P, I, L, P, I, I, I, P, P, P]),
-    "gom_mask_pairs_count_f64": (I, [P, P, P, P, L, P, P, P, P, L, P, P, P, P, I, I, I, L, D, P, P]),
-    "gom_mask_pairs_emit_f64": (I, [P, P, P, P, L, P, P, P, P, L, P, P, P, P, I, I, I, L, D, P, L, P, P, P]),
-    "gom_mask_outline_polygons_u32": (I, [P, I, P, I, P, P, P, I, L, P, I, I, I, P, P]),
-    "gom_overlay_compose_u8": (I, [P, P, I, I, I, P, P, P, P, I, L, P, P, P, P, P, P, I, P, P, P, I, L, I, I, P]),
-    "gom_lexicon_match_u32": (I, [P, L, P, P, I, P, L, P, I, P, I, I, P, P, P]),
-    "gom_jpeg_workspace_bytes": (L, [I, I, I]),
-    "gom_jpeg_encode_scan_u8": (I, [P, I, I, I, I, I, P, L, P, P]),
-    "gom_jpeg_encode_pack_u8": (I, [P, L, I, I, I, L, P, L, P]),
-    "gom_maxpool3x3s2_nhwc_f32": (I, [P, P, I, I, I, I, P]),
-    "gom_pos_encoding_2d_f32": (I, [P, P, P, I, I, P]),
-    "gom_point_pos_embed_f32": (I, [P, P, P, L, P]),
-    "gom_ref_sigmoid_f32": (I, [P, I, P, P, L, I, P]),
-    "gom_ref_update_f32": (I, [P, I, P, P, P, P, F, F, P, P, L, P]),
-    "gom_proposal_valid": (I, [P, P, I, P, L, P]),
-    "gom_encoder_reference_points": (I, [P, P, I, P, L, P]),
-    "gom_bezier_reference_points": (I, [P, P, P, P, I, P, P, I, L, I, I, I, P]),
-    "gom_scale_xy_f32": (I, [P, L, F, F, P]),
-    "gom_flag_nonfinite_f32": (I, [P, L, P, P]),
-    "gom_add_f32": (I, [P, P, P, L, P]),
-    "gom_copy_words": (I, [P, P, L, P]),
-    "gom_broadcast_rows_f32": (I, [P, P, L, I, P]),
-    "gom_topk_workspace_bytes": (L, [I, L, I]),
-    "gom_topk_tokens": (I, [P, I, P, P, I, L, I, P, P, P, P]),
-    "gom_argmax_rows_f32": (I, [P, I, I, L, P, P]),
-    "gom_detect_post": (I, [P, I, P, I, P, P, P, I, I, I, F, F, F, F, F, P, P, P, P, P, P, P, P]),
-    "gom_gather_rows_f32": (I, [P, P, P, I, I, P]),
-    "gom_asso_activate_f32": (I, [P, I, P, I, I, P, I, P]),
-    "gom_track_score_f32": (I, [P, I, P, P, P, F, F, I, I, I, I, F, P, P]),
-    "gom_asso_score_f32": (I, [P, I, P, I, P, P, P, F, F, I, I, I, I, F, P, P]),
-    "gom_short_term_pairs_f32": (I, [P, P, I, P, P, P, F, F, I, I, I, P, P]),
-    "gom_mha_core_segments_f32": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
-    "gom_pos_encoding_2d_valid_f32": (I, [P, P, P, I, I, I, I, P]),
-    "gom_proposal_valid_masked": (I, [P, P, I, P, P, L, P]),
-    "gom_encoder_reference_points_masked": (I, [P, P, P, I, P, L, P]),
-    "gom_bezier_reference_points_masked": (I, [P, P, P, P, P, I, P, P, I, L, I, I, I, P]),
-    "gom_msda_fused_forward_vr": (I, [P, I, P, P, L, I, P, P, P, P, I, I, P]),
-    "gom_zero_padded_tokens_f32": (I, [P, I, I, I, P, P, P, I, I, L, P]),
-    "gom_padded_geometry_f32": (I, [P, P, P, P, P, I, I, L, P, P, P, P]),
-    "gom_zero_padded_tokens_frames_f32": (I, [P, I, I, I, P, P, P, I, I, L, P]),
-    "gom_topk_tokens_frames": (I, [P, I, P, P, I, L, I, P, P, P, P]),
-    "gom_bezier_reference_points_frames": (I, [P, P, P, P, P, I, P, P, I, L, I, I, I, P]),
-    "gom_msda_fused_forward_vr_frames": (I, [P, I, P, P, L, I, P, P, P, P, I, I, P]),
-    "gom_scale_xy_frames_f32": (I, [P, L, P, L, P]),
-    "gom_ref_update_frames_f32": (I, [P, I, P, P, P, P, P, L, P, P, L, P]),
-    "gom_detect_post_sizes": (I, [P, I, P, I, P, P, P, I, I, I, P, F, F, F, P, P, P, P, P, P, P, P]),
-    "gom_layernorm_any_f32": (I, [P, P, P, P, L, I, F, P]),
-    "gom_gelu_f32": (I, [P, L, P]),
-    "gom_swin_patchify_f32": (I, [P, P, I, I, I, P]),
-    "gom_swin_window_gather_f32": (I, [P, P, I, I, I, I, I, P]),
-    "gom_swin_window_scatter_add_f32": (I, [P, P, P, I, I, I, I, I, P]),
-    "gom_swin_patch_merge_f32": (I, [P, P, I, I, I, I, P]),
-    "gom_swin_window_attention_f32": (I, [P, P, P, P, L, I, I, I, P]),
-    "gom_im2col_nhwc_f32": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P]),
-    "gom_grouped_conv3x3_nhwc_f32": (I, [P, P, P, P, P, I, P, I, I, I, I, I, I, I, P]),
-    "gom_silu_f32": (I, [P, L, P]),
-    "gom_vitae_window_gather_f32": (I, [P, P, I, I, I, I, P]),
-    "gom_vitae_window_crop_f32": (I, [P, P, P, P, I, I, I, I, P]),
-    "gom_vitae_window_attention_f32": (I, [P, P, L, I, I, P]),
-    "gom_softmax_rows_scaled_f32": (I, [P, L, I, L, F, P]),
-    "gom_transpose_f32": (I, [P, P, I, I, L, L, P]),
-    "gom_flash_attention_f32": (I, [P, P, P, P, I, I, I, I, I, I, P, P]),
-    "gom_match_workspace_floats": (L, [I, I, I, I]),
-    "gom_gather_match_f32": (I, [P, I, P, I, P, I, I, I, I, P, P, P, P]),
-    "gom_match_scores_proj_f32": (I, [P, I, P, I, P, P, P, P, P, I, I, I, I, I, P, I, P, I, I, I, I, F, F, I, F, P, L, P, P]),
-    "gom_tracker_set_projections": (I, [P, P, I]),
-    "gom_match_scores_f32": (I, [P, I, P, P, P, P, P, I, I, I, I, I, P, I, P, I, I, I, I, F, F, I, F, P, L, P, P]),
-    "gom_tracker_create": (P, [I, F, I, I, I, F, P, I, P, I, I, I, I]),
-    "gom_tracker_destroy": (None, [P]),
-    "gom_stream_create_cu_mask": (I, [P, I, P]),
-    "gom_stream_destroy": (I, [P]),
-    "gom_tracker_run": (I, [P, I, P, P, P, P, I, L, P, P, P, I, F, F, P, P, P, P]),
-    "gom_tracker_run_wh": (I, [P, I, P, P, P, P, I, L, P, P, P, I, P, P, P, P, P]),
-    "gom_linear_sum_assignment": (I, [ctypes.POINTER(ctypes.c_double), L, L, ctypes.POINTER(c_long),
-                                      ctypes.POINTER(c_long)]),
-}
-
-_lib = None
+HEADER_PATH = os.path.join(HERE, "..", "include", "gomatching_hip.h")
 
 
 class GomError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+            "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "unsigned long long": ctypes.c_ulonglong}
+_TYPE_WORDS = {"const", "void", "char", "short", "signed", "struct"}.union(*(k.split() for k in _SCALARS))
+
+
+def _ctype(words, returned=False):
+    """ctypes type of the C type spelled by `words` (`*` a word of its own): an argument's, a field's or (`returned`) a return
+    type; None for a type outside the mapping."""
+    if words[-1:] == ["*"]:                                  # any T*, const or not, is a plain address
+        return ctypes.c_char_p if returned and words == ["const", "char", "*"] else ctypes.c_void_p
+    return _SCALARS.get(" ".join(words))
+
+
+def _named(decl, symbol):
+    """`type name` (an argument of `symbol`, a field of the struct `symbol`) -> (name, ctypes type).  The name is the last word."""
+    words = decl.replace("*", " * ").split()
+    ctype = _ctype(words[:-1]) if len(words) > 1 and words[-1].isidentifier() and words[-1] not in _TYPE_WORDS else None
+    if ctype is None:
+        raise GomError("%s: `%s` is not `type name` with a type that has a ctypes mapping" % (symbol, " ".join(decl.split())))
+    return words[-1], ctype
+
+
+def parse_header(text):
+    """The C ABI stated by header text -> (signatures, structs, constants):
+      signatures  name -> (restype, argtypes) for every `ret gom_name(args);`
+      structs     name -> ctypes.Structure class for every `typedef struct gom_x { ... } gom_x;`, fields in the header's order
+      constants   NAME -> int for every `#define GOM_NAME <integer>`
+    by the type mapping of `_SCALARS`, every pointer a c_void_p (`const char*` as a return type: c_char_p), `void` as a return
+    type None.  A statement or a type outside that raises GomError and names the symbol: nothing is skipped or guessed."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b[^\n]*", "", text, flags=re.S | re.M)   # not C++ here
+    constants = {}
+    for line in re.findall(r"^[ \t]*#[^\n]*", text, flags=re.M):
+        m = re.fullmatch(r"#\s*(\w+)\s*(\w*)\s*(.*?)\s*", line.strip())
+        if not m or m.group(1) not in ("define", "include", "ifndef", "endif"):
+            raise GomError("header: cannot follow the directive `%s`" % line.strip())
+        if m.group(1) == "define" and m.group(2).startswith("GOM_") and re.fullmatch(r"-?(0|[1-9]\d*|0[xX][0-9a-fA-F]+)", m.group(3)):
+            constants[m.group(2)] = int(m.group(3), 0)
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)
+    structs = {}
+
+    def struct(m):
+        fields = [_named(f, m.group(1)) for f in m.group(2).split(";") if f.strip()]
+        structs[m.group(1)] = type(m.group(1), (ctypes.Structure,), {"_fields_": fields})
+        return ""
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", struct, text, flags=re.S)
+    signatures = {}
+    for stmt in text.split(";"):
+        if not stmt.strip():
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(gom_\w+)\s*\(([^()]*)\)\s*", stmt)
+        if not m:
+            raise GomError("header: cannot read `%s` as a declaration `ret gom_name(args)`" % " ".join(stmt.split()))
+        ret, name, args = m.groups()
+        res = _ctype(ret.replace("*", " * ").split(), returned=True)
+        if res is None and ret.split() != ["void"]:          # (`void` as a return type IS restype None)
+            raise GomError("%s: no ctypes mapping for the return type `%s`" % (name, " ".join(ret.split())))
+        argtypes = [] if args.split() == ["void"] else [_named(a, name)[1] for a in args.split(",")]
+        signatures[name] = (res, argtypes)
+    return signatures, structs, constants
+
+
+def _parse_file(path):
+    try:
+        with open(path) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise GomError("the C ABI header is missing: %s (%s)" % (path, e.strerror))
+
+
+# SIGNATURES: name -> (restype, argtypes), one entry per symbol the header declares
+SIGNATURES, STRUCTS, CONSTANTS = _parse_file(HEADER_PATH)
+OptimTensor = STRUCTS["gom_optim_tensor"]         # one row of the clipped-AdamW table
+MatcherLayer = STRUCTS["gom_matcher_layer"]       # the weights of one matcher transformer layer
+
+GOM_OK = CONSTANTS["GOM_OK"]
+_ERR_HIP_BASE = CONSTANTS["GOM_ERR_HIP_BASE"]
+_ERR = {CONSTANTS["GOM_ERR_INVALID_ARG"]: "GOM_ERR_INVALID_ARG (violated precondition)",
+        CONSTANTS["GOM_ERR_UNSUPPORTED"]: "GOM_ERR_UNSUPPORTED"}
+
+_lib = None
 
 
 def load():
@@ -248,5 +123,5 @@ def load():
 
 def check(rc, what=""):
     if rc != GOM_OK:
-        msg = _ERR.get(rc, "HIP error %d" % (rc - 1000) if rc >= 1000 else "error %d" % rc)
+        msg = _ERR.get(rc, "HIP error %d" % (rc - _ERR_HIP_BASE) if rc >= _ERR_HIP_BASE else "error %d" % rc)
         raise GomError("%s failed: %s" % (what or "libgomatching_hip call", msg))

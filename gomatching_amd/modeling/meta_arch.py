@@ -1104,7 +1104,6 @@ class GoMatching:
         mirrors of the window (carried frames + new ones), runs the batched short-term device work, and hands everything
         over in ONE call; ids come back for all new frames."""
         import ctypes
-        L = ops._L()
         start = batch_id * 100 + frame_offset
         t0 = time.time()
         base = len(instances)
@@ -1155,10 +1154,9 @@ class GoMatching:
         if lane is not None:                                     # CU-partitioned step: the recurrence runs on its own CUs
             lane.wait_stream(torch.cuda.current_stream())        # ... after the embeddings it gathers from the pool
             run_stream = lane.cuda_stream
-        ops.check(L.gom_tracker_run_wh(trk, len(window), ptr(n), ptr(boxes), ptr(rows), ptr(ids), first_new, start,
-                                       ptr(S_all), ptr(s_off), ctypes.c_void_p(self._pool.data_ptr()), self._pool.stride(0),
-                                       ptr(frame_wh), ptr(self._decay_table), ctypes.byref(idc), secs, run_stream),
-                  "gom_tracker_run_wh")
+        ops._call("gom_tracker_run_wh", trk, len(window), ptr(n), ptr(boxes), ptr(rows), ptr(ids), first_new, start, ptr(S_all),
+                  ptr(s_off), ctypes.c_void_p(self._pool.data_ptr()), self._pool.stride(0), ptr(frame_wh), ptr(self._decay_table),
+                  ctypes.byref(idc), secs, run_stream)
         if lane is not None:
             torch.cuda.current_stream().wait_stream(lane)        # the pool may be rewritten by later work on this stream
         time_cost["short_match"] += secs[0]
@@ -1210,7 +1208,7 @@ class GoMatching:
         m = self.roi_heads._matcher(False)
         if not ops.HOIST_MATCH_PROJECTIONS or not m.enc or not m.dec or self._pool is None:
             return
-        d, L = m.d, ops._L()
+        d = m.d
         cap = self._pool.shape[0]
         if getattr(self, "_proj", None) is None or self._proj.shape[0] < cap or self._proj_pool is not self._pool:
             self._proj = torch.empty((cap, 4 * d), dtype=_f32, device=self.device)
@@ -1223,7 +1221,7 @@ class GoMatching:
             ops.gemm_small_rows(self._pool[a:b], w_in, b_in, self._proj[a:b, :3 * d])
             ops.gemm_small_rows(self._pool[a:b], w_q[:d], b_q[:d], self._proj[a:b, 3 * d:])
             self._proj_done = b
-        ops.check(L.gom_tracker_set_projections(trk, self._proj.data_ptr(), self._proj.stride(0)), "gom_tracker_set_projections")
+        ops._call("gom_tracker_set_projections", trk, self._proj.data_ptr(), self._proj.stride(0))
 
     def close(self):
         """Release the native tracker handle (hipMalloc / hipHostMalloc buffers of csrc/tracker_rt.hip)."""

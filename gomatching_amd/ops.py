@@ -21,6 +21,13 @@ def _L():
     return _lib_mod.load()
 
 
+def _call(name, *args):
+    """Call the status-returning entry point `name`; a non-zero status raises GomError("<name> failed: ...")."""
+    rc = getattr(_lib_mod._lib or _L(), name)(*args)         # (the loaded handle read directly: host time per launch matters)
+    if rc:
+        check(rc, name)
+
+
 # Optional launch profiler for bench.py's roofline leg: a list that receives one (start_event, end_event, flops, bytes, label,
 # scope) per launch of every instrumented kernel (`_timed`); bench.py picks kernels by label prefix and the decoder layers by
 # scope (`profile_scope`).  None = no events recorded.
@@ -68,7 +75,7 @@ _untimed = contextlib.nullcontext()
 
 
 def _timed(cond, figures):
-    """Launch bracket of the profiler: `with _timed(cond, lambda: (flops, bytes, label)): check(launch)`.  Without a collector or
+    """Launch bracket of the profiler: `with _timed(cond, lambda: (flops, bytes, label)): _call(launch)`.  Without a collector or
     with `cond` false it is one shared no-op: no event is created and `figures` is never called."""
     return _Timed(_gemm_profile, figures) if (_gemm_profile is not None and cond) else _untimed
 
@@ -154,10 +161,10 @@ def split_weight(w, conv_shape=None, kind=None):
     if kind == "f16x3":
         planes = torch.empty((2, N, Kpad), dtype=torch.float16, device=w.device)
         inv = torch.empty((N,), dtype=_f32, device=w.device)
-        check(_L().gom_split_f16x2(_p(w), ldw, N, K, _p(planes), Kpad, _p(inv), _stream()), "gom_split_f16x2")
+        _call("gom_split_f16x2", _p(w), ldw, N, K, _p(planes), Kpad, _p(inv), _stream())
         return SplitWeight(planes, N, K, conv_shape, "f16x3", inv)
     planes = torch.empty((3, N, Kpad), dtype=torch.bfloat16, device=w.device)
-    check(_L().gom_split_bf16x3(_p(w), ldw, N, K, _p(planes), Kpad, _stream()), "gom_split_bf16x3")
+    _call("gom_split_bf16x3", _p(w), ldw, N, K, _p(planes), Kpad, _stream())
     return SplitWeight(planes, N, K, conv_shape)
 
 
@@ -236,7 +243,7 @@ def plan_rows(frames, rows_per_frame):
 def flag_nonfinite(x, flag):
     """flag |= 1 on the device when x holds an Inf / NaN (result check of the back-ends whose GEMMs carry no range flag)."""
     _chk_f32(x)
-    check(_L().gom_flag_nonfinite_f32(_p(x), x.numel(), _p(flag), _stream()), "gom_flag_nonfinite_f32")
+    _call("gom_flag_nonfinite_f32", _p(x), x.numel(), _p(flag), _stream())
 
 
 def prep_weight(w, min_n=33):
@@ -270,14 +277,12 @@ def _gemm_split(A, W, bias, scale, A2, rows, R, relu, out, M, r_cols=None, r_per
     with _timed(M > 0, lambda: (2.0 * M * N * K, 4.0 * M * K + 2.0 * pl.shape[0] * N * pl.shape[2] + 4.0 * M * N
                                 + (4.0 * (r_period or M) * rc if R is not None else 0.0), "%dx%dx%d" % (M, N, K))):
         if W.kind == "f16x3":
-            check(_L().gom_gemm_f32_f16x3_rp(_p(A), _p(rows), lda, _p(pl), pl.stride(0), pl.stride(1), _p(W.inv_scale),
-                                             _p(scale), _p(bias), _p(R), ldr, rc, int(r_period),
-                                             2 if relu == "gelu" else (1 if relu else 0), _p(out), ldc, M, N, K,
-                                             _p(range_flag(A.device)), _stream()), "gom_gemm_f32_f16x3_rp")
+            _call("gom_gemm_f32_f16x3_rp", _p(A), _p(rows), lda, _p(pl), pl.stride(0), pl.stride(1), _p(W.inv_scale), _p(scale),
+                  _p(bias), _p(R), ldr, rc, int(r_period), 2 if relu == "gelu" else (1 if relu else 0), _p(out), ldc, M, N, K,
+                  _p(range_flag(A.device)), _stream())
         else:
-            check(_L().gom_gemm_f32_bf16x6(_p(A), _p(rows), lda, _p(pl), pl.stride(0), pl.stride(1), _p(scale),
-                                           _p(bias), _p(R), ldr, rc, 1 if relu else 0, _p(out), ldc, M, N, K, _stream()),
-                  "gom_gemm_f32_bf16x6")
+            _call("gom_gemm_f32_bf16x6", _p(A), _p(rows), lda, _p(pl), pl.stride(0), pl.stride(1), _p(scale), _p(bias), _p(R), ldr,
+                  rc, 1 if relu else 0, _p(out), ldc, M, N, K, _stream())
     return out
 
 
@@ -333,8 +338,8 @@ def gemm(A, W, bias=None, scale=None, A2=None, rows=None, R=None, relu=False, ou
     # workgroups (85-95 us whatever M is; tools/skinny_bench.py)
     if small and A2 is None and M > 0:
         if (M <= SMALL_GEMM_ROWS or M * N <= SMALL_GEMM_OUTPUTS) and K % 4 == 0 and lda % 4 == 0 and ldw % 4 == 0:
-            check(_L().gom_gemm_small_f32(_p(A), _p(rows), lda, _p(W), ldw, _p(scale), _p(bias), _p(R), ldr,
-                                          1 if relu else 0, _p(out), ldc, M, N, K, _stream()), "gom_gemm_small_f32")
+            _call("gom_gemm_small_f32", _p(A), _p(rows), lda, _p(W), ldw, _p(scale), _p(bias), _p(R), ldr, 1 if relu else 0,
+                  _p(out), ldc, M, N, K, _stream())
             return out
         splitk = M <= SPLITK_MAX_ROWS                        # beyond that the partial sums cost more than they save
     if splitk is None:
@@ -342,14 +347,13 @@ def gemm(A, W, bias=None, scale=None, A2=None, rows=None, R=None, relu=False, ou
     if splitk and A2 is None and M > 0:
         nbytes = _L().gom_gemm_splitk_workspace_bytes(M, N, K)
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=A.device)
-        check(_L().gom_gemm_f32_splitk(_p(A), _p(rows), lda, _p(W), ldw, _p(scale), _p(bias), _p(R), ldr,
-                                       1 if relu else 0, _p(out), ldc, M, N, K, _p(ws), nbytes, _stream()),
-              "gom_gemm_f32_splitk")
+        _call("gom_gemm_f32_splitk", _p(A), _p(rows), lda, _p(W), ldw, _p(scale), _p(bias), _p(R), ldr, 1 if relu else 0, _p(out),
+              ldc, M, N, K, _p(ws), nbytes, _stream())
         return out
     with _timed(N > 64 and M > 0 and GEMM_MODE == "fp32", lambda: (
             2.0 * M * N * K, 4.0 * (M * K + N * K + M * N + (M * N if R is not None else 0)), "%dx%dx%d" % (M, N, K))):
-        check(_L().gom_gemm_f32(_p(A), _p(A2), _p(rows), lda, _p(W), ldw, _p(scale), _p(bias), _p(R), ldr,
-                                1 if relu else 0, _p(out), ldc, M, N, K, _stream()), "gom_gemm_f32")
+        _call("gom_gemm_f32", _p(A), _p(A2), _p(rows), lda, _p(W), ldw, _p(scale), _p(bias), _p(R), ldr, 1 if relu else 0, _p(out),
+              ldc, M, N, K, _stream())
     return out
 
 
@@ -404,14 +408,12 @@ def conv2d_nhwc(x, w_ohwi, scale=None, shift=None, R=None, relu=False, stride=1,
             if img is None:                                  # fragment-linear image of the planes, built once per weight
                 nb = _L().gom_conv3x3_patch_image_bytes(Cin, Cout)
                 img = torch.empty((nb,), dtype=torch.uint8, device=pl.device)
-                check(_L().gom_conv3x3_patch_image(_p(pl), pl.stride(0), pl.stride(1), Cin, Cout, _p(img), nb, _stream()),
-                      "gom_conv3x3_patch_image")
+                _call("gom_conv3x3_patch_image", _p(pl), pl.stride(0), pl.stride(1), Cin, Cout, _p(img), nb, _stream())
                 w_ohwi.patch_image = img
             with _timed(True, lambda: (2.0 * M * Cout * 9 * Cin, 4.0 * M * (Cin + Cout) + 4.0 * 9 * Cin * Cout,
                                        "conv3:%dx%dx%d" % (M, Cout, 9 * Cin))):
-                check(_L().gom_conv3x3_patch_f32_f16x3(_p(x), _p(img), _p(w_ohwi.inv_scale), _p(scale), _p(shift), 1 if relu else 0,
-                                                       _p(y), B, H, Wd, Cin, Cout, _p(range_flag(x.device)), _stream()),
-                      "gom_conv3x3_patch_f32_f16x3")
+                _call("gom_conv3x3_patch_f32_f16x3", _p(x), _p(img), _p(w_ohwi.inv_scale), _p(scale), _p(shift), 1 if relu else 0,
+                      _p(y), B, H, Wd, Cin, Cout, _p(range_flag(x.device)), _stream())
             return y
         if kernel == "pw_k256":
             # conv3 of the res4 bottlenecks (256 -> 1024, + BN + shortcut + ReLU): K = 256 is the row-resident kernel's shape
@@ -424,32 +426,29 @@ def conv2d_nhwc(x, w_ohwi, scale=None, shift=None, R=None, relu=False, stride=1,
                 inv = w_ohwi.inv_scale if scale is None else (w_ohwi.inv_scale * scale).contiguous()
                 nb = _L().gom_gemm_k256_image_bytes(Cout, Cin)
                 img = torch.empty((nb,), dtype=torch.uint8, device=pl.device)
-                check(_L().gom_gemm_k256_image(_p(pl), pl.stride(0), pl.stride(1), _p(inv), _p(shift), Cout, Cin, _p(img), nb,
-                                               _stream()), "gom_gemm_k256_image")
+                _call("gom_gemm_k256_image", _p(pl), pl.stride(0), pl.stride(1), _p(inv), _p(shift), Cout, Cin, _p(img), nb,
+                      _stream())
                 cache[key] = img = (img, inv, scale, shift)         # (the vectors stay referenced: ids are the cache key)
             with _timed(True, lambda: (2.0 * M * Cout * Cin, 4.0 * M * Cin + 4.0 * M * Cout * (2 if R is not None else 1) + 4.0 * Cout * Cin,
                                        "pwk256:%dx%dx%d" % (M, Cout, Cin))):
-                check(_L().gom_gemm_k256_rp_f32(_p(x), None, Cin, _p(img[0]), _p(R), Cout if R is not None else 0,
-                                                Cout if R is not None else 0, 0, 1 if relu else 0, _p(y), Cout, M, Cout, Cin, 1,
-                                                _p(range_flag(x.device)), _stream()), "gom_gemm_k256_rp_f32")
+                _call("gom_gemm_k256_rp_f32", _p(x), None, Cin, _p(img[0]), _p(R), Cout if R is not None else 0,
+                      Cout if R is not None else 0, 0, 1 if relu else 0, _p(y), Cout, M, Cout, Cin, 1, _p(range_flag(x.device)),
+                      _stream())
             return y
         if w_ohwi.kind == "f16x3":
             # a pointwise convolution IS a launch of the GEMM tile kernel (dispatch<0, 0> in csrc/gemm_f16x3.hip): bench.py's
             # roofline sample of that kernel covers these launches too (label "pw:")
             with _timed(KH == 1 and stride == 1 and pad == 0 and splits <= 1 and Cout > 64, lambda: (
                     2.0 * M * Cout * Cin, 4.0 * M * Cin + 4.0 * M * Cout * (2 if R is not None else 1) + 4.0 * Cout * Cin, "pw:%dx%dx%d" % (M, Cout, Cin))):
-                check(_L().gom_conv2d_nhwc_f32_f16x3(_p(x), _p(pl), pl.stride(0), pl.stride(1), _p(w_ohwi.inv_scale),
-                                                     _p(scale), _p(shift), _p(R), 1 if relu else 0, _p(y), B, H, Wd, Cin,
-                                                     Cout, KH, KW, stride, pad, _p(ws), nbytes, splits,
-                                                     _p(range_flag(x.device)), _stream()), "gom_conv2d_nhwc_f32_f16x3")
+                _call("gom_conv2d_nhwc_f32_f16x3", _p(x), _p(pl), pl.stride(0), pl.stride(1), _p(w_ohwi.inv_scale), _p(scale),
+                      _p(shift), _p(R), 1 if relu else 0, _p(y), B, H, Wd, Cin, Cout, KH, KW, stride, pad, _p(ws), nbytes, splits,
+                      _p(range_flag(x.device)), _stream())
             return y
-        check(_L().gom_conv2d_nhwc_f32_bf16x6_splitk(_p(x), _p(pl), pl.stride(0), pl.stride(1), _p(scale), _p(shift),
-                                                     _p(R), 1 if relu else 0, _p(y), B, H, Wd, Cin, Cout, KH, KW, stride,
-                                                     pad, _p(ws), nbytes, splits, _stream()),
-              "gom_conv2d_nhwc_f32_bf16x6_splitk")
+        _call("gom_conv2d_nhwc_f32_bf16x6_splitk", _p(x), _p(pl), pl.stride(0), pl.stride(1), _p(scale), _p(shift), _p(R),
+              1 if relu else 0, _p(y), B, H, Wd, Cin, Cout, KH, KW, stride, pad, _p(ws), nbytes, splits, _stream())
         return y
-    check(_L().gom_conv2d_nhwc_f32(_p(x), _p(w_ohwi), _p(scale), _p(shift), _p(R), 1 if relu else 0, _p(y), B, H, Wd,
-                                   Cin, Cout, KH, KW, stride, pad, _stream()), "gom_conv2d_nhwc_f32")
+    _call("gom_conv2d_nhwc_f32", _p(x), _p(w_ohwi), _p(scale), _p(shift), _p(R), 1 if relu else 0, _p(y), B, H, Wd, Cin, Cout, KH,
+          KW, stride, pad, _stream())
     return y
 
 
@@ -460,8 +459,7 @@ def layernorm(x, gamma, beta, residual=None, eps=1e-5, out=None):
     rows = x.numel() // D
     if out is None:
         out = torch.empty_like(x)
-    check(_L().gom_layernorm_f32(_p(x), _p(residual), _p(gamma), _p(beta), _p(out), rows, D, eps, _stream()),
-          "gom_layernorm_f32")
+    _call("gom_layernorm_f32", _p(x), _p(residual), _p(gamma), _p(beta), _p(out), rows, D, eps, _stream())
     return out
 
 
@@ -470,8 +468,7 @@ def groupnorm32_into(x, gamma, beta, out_view, out_batch_stride, eps=1e-5):
     _chk_f32(x, gamma, beta)
     B, HW, C = x.shape
     ws = torch.empty((B * 64,), dtype=torch.float64, device=x.device)
-    check(_L().gom_groupnorm32_nhwc_f32(_p(x), _p(gamma), _p(beta), _p(ws), _p(out_view), out_batch_stride, B, HW, C,
-                                        eps, _stream()), "gom_groupnorm32_nhwc_f32")
+    _call("gom_groupnorm32_nhwc_f32", _p(x), _p(gamma), _p(beta), _p(ws), _p(out_view), out_batch_stride, B, HW, C, eps, _stream())
 
 
 _masked_streams = {}
@@ -489,7 +486,7 @@ def masked_stream(mask_words, device):
         arr = (ctypes.c_uint32 * len(mask_words))(*key[1])
         out = ctypes.c_void_p()
         with torch.cuda.device(device):
-            check(_L().gom_stream_create_cu_mask(arr, len(mask_words), ctypes.byref(out)), "gom_stream_create_cu_mask")
+            _call("gom_stream_create_cu_mask", arr, len(mask_words), ctypes.byref(out))
         st = torch.cuda.ExternalStream(out.value, device=device)
         _masked_streams[key] = st
     return st
@@ -523,8 +520,8 @@ class K256Linear:
             raise _lib_mod.GomError("row-resident GEMM kernel does not serve N %d / K %d" % (W.N, W.K))
         pl = W.planes
         self.image = torch.empty((nbytes,), dtype=torch.uint8, device=pl.device)
-        check(_L().gom_gemm_k256_image(_p(pl), pl.stride(0), pl.stride(1), _p(W.inv_scale), _p(bias), W.N, W.K,
-                                       _p(self.image), nbytes, _stream()), "gom_gemm_k256_image")
+        _call("gom_gemm_k256_image", _p(pl), pl.stride(0), pl.stride(1), _p(W.inv_scale), _p(bias), W.N, W.K, _p(self.image),
+              nbytes, _stream())
         self.W, self.bias, self.N, self.K = W, bias, W.N, W.K
 
 
@@ -561,9 +558,8 @@ def linear(x, lin, A2=None, R=None, relu=False, r_cols=None, out=None, groups=0,
         _L().gom_gemm_k256_set_lines(0)                      # (A/B switch only: the round-2 mid-state of the kernel)
     with _timed(True, lambda: (2.0 * M * N * lin.K, 4.0 * M * lin.K * (2 if A2 is not None else 1) + lin.image.numel() + 4.0 * M * N
                                + 4.0 * (r_period or M) * rc, "k256:%dx%dx%d" % (M, N, lin.K))):
-        check(_L().gom_gemm_k256_rp_f32(_p(x), _p(A2), _ld(x), _p(lin.image), _p(R), _ld(R), rc, int(r_period), 1 if relu else 0,
-                                        _p(out), _ld(out), M, N, lin.K, groups or 1, _p(range_flag(x.device)), _stream()),
-              "gom_gemm_k256_rp_f32")
+        _call("gom_gemm_k256_rp_f32", _p(x), _p(A2), _ld(x), _p(lin.image), _p(R), _ld(R), rc, int(r_period), 1 if relu else 0,
+              _p(out), _ld(out), M, N, lin.K, groups or 1, _p(range_flag(x.device)), _stream())
     return out
 
 
@@ -584,8 +580,7 @@ class ProjLN:
         _chk_f32(bias, gamma, beta)
         pl = W.planes
         self.image = torch.empty((nbytes,), dtype=torch.uint8, device=pl.device)
-        check(_L().gom_proj_ln_image(_p(pl), pl.stride(0), pl.stride(1), W.N, W.K, _p(self.image), nbytes, _stream()),
-              "gom_proj_ln_image")
+        _call("gom_proj_ln_image", _p(pl), pl.stride(0), pl.stride(1), W.N, W.K, _p(self.image), nbytes, _stream())
         self.W, self.bias, self.gamma, self.beta, self.eps = W, bias, gamma, beta, eps
 
 
@@ -607,9 +602,8 @@ def proj_ln(x, blk, R, out=None):
         out = torch.empty((M, 256), dtype=_f32, device=x.device)
     with _timed(M > 0, lambda: (2.0 * M * 256 * 256, (12.0 if R is not None else 8.0) * M * 256 + blk.image.numel(),
                                 "projln:%dx256x256" % M)):
-        check(_L().gom_proj_ln_f32(_p(x), _ld(x), _p(blk.image), _p(blk.W.inv_scale), _p(blk.bias), _p(R), _ld(R), _p(blk.gamma),
-                                   _p(blk.beta), blk.eps, _p(out), _ld(out), M, _p(range_flag(x.device)), _stream()),
-              "gom_proj_ln_f32")
+        _call("gom_proj_ln_f32", _p(x), _ld(x), _p(blk.image), _p(blk.W.inv_scale), _p(blk.bias), _p(R), _ld(R), _p(blk.gamma),
+              _p(blk.beta), blk.eps, _p(out), _ld(out), M, _p(range_flag(x.device)), _stream())
     return out
 
 
@@ -625,9 +619,8 @@ def proj_ln_dot(x, blk, w, b):
     M = x.shape[0]
     out = torch.empty((M,), dtype=_f32, device=x.device)
     with _timed(M > 0, lambda: (2.0 * M * 256 * 257, 4.0 * M * 257 + blk.image.numel(), "projdot:%dx256x257" % M)):
-        check(_L().gom_proj_ln_dot_f32(_p(x), _ld(x), _p(blk.image), _p(blk.W.inv_scale), _p(blk.bias), _p(blk.gamma), _p(blk.beta),
-                                       blk.eps, _p(w), float(b), _p(out), M, _p(range_flag(x.device)), _stream()),
-              "gom_proj_ln_dot_f32")
+        _call("gom_proj_ln_dot_f32", _p(x), _ld(x), _p(blk.image), _p(blk.W.inv_scale), _p(blk.bias), _p(blk.gamma), _p(blk.beta),
+              blk.eps, _p(w), float(b), _p(out), M, _p(range_flag(x.device)), _stream())
     return out
 
 
@@ -662,10 +655,9 @@ class BneckFused:
             ps = ws.planes
             nbytes = _L().gom_bneck_sc_image_bytes(self.k1, self.c4, self.mp, self.ks, self.stride)
             self.image = torch.empty((nbytes,), dtype=torch.uint8, device=p3.device)
-            check(_L().gom_bneck_sc_image(_p(p3), p3.stride(0), p3.stride(1), _p(w3.inv_scale), _p(scale3), _p(shift3), _p(p1),
-                                          p1.stride(0), p1.stride(1), _p(ps), ps.stride(0), ps.stride(1), _p(ws.inv_scale),
-                                          _p(scale_s), _p(shift_s), self.k1, self.c4, self.mp, self.ks, self.stride, _p(self.image),
-                                          nbytes, _stream()), "gom_bneck_sc_image")
+            _call("gom_bneck_sc_image", _p(p3), p3.stride(0), p3.stride(1), _p(w3.inv_scale), _p(scale3), _p(shift3), _p(p1),
+                  p1.stride(0), p1.stride(1), _p(ps), ps.stride(0), ps.stride(1), _p(ws.inv_scale), _p(scale_s), _p(shift_s),
+                  self.k1, self.c4, self.mp, self.ks, self.stride, _p(self.image), nbytes, _stream())
             self.sc1 = (scale1 * w1.inv_scale).contiguous()
             self.sh1 = shift1.contiguous()
             return
@@ -675,8 +667,8 @@ class BneckFused:
             # workgroup sharing one weight ring
             nbytes = _L().gom_bneck2_image_bytes(self.k1, self.c4, self.mp)
             self.image = torch.empty((nbytes,), dtype=torch.uint8, device=p3.device)
-            check(_L().gom_bneck2_image(_p(p3), p3.stride(0), p3.stride(1), _p(w3.inv_scale), _p(scale3), _p(shift3), _p(p1), p1.stride(0),
-                                        p1.stride(1), self.k1, self.c4, self.mp, _p(self.image), nbytes, _stream()), "gom_bneck2_image")
+            _call("gom_bneck2_image", _p(p3), p3.stride(0), p3.stride(1), _p(w3.inv_scale), _p(scale3), _p(shift3), _p(p1),
+                  p1.stride(0), p1.stride(1), self.k1, self.c4, self.mp, _p(self.image), nbytes, _stream())
             self.sc1 = (scale1 * w1.inv_scale).contiguous()
             self.sh1 = shift1.contiguous()
             return
@@ -684,8 +676,8 @@ class BneckFused:
         if nbytes < 0:
             raise _lib_mod.GomError("fused bottleneck kernel does not serve %d -> %d -> %d" % (self.k1, self.c4, self.mp))
         self.image = torch.empty((nbytes,), dtype=torch.uint8, device=p3.device)
-        check(_L().gom_bneck_image(_p(p3), p3.stride(0), p3.stride(1), _p(w3.inv_scale), _p(scale3), _p(shift3), _p(p1), p1.stride(0),
-                                   p1.stride(1), self.k1, self.c4, self.mp, _p(self.image), nbytes, _stream()), "gom_bneck_image")
+        _call("gom_bneck_image", _p(p3), p3.stride(0), p3.stride(1), _p(w3.inv_scale), _p(scale3), _p(shift3), _p(p1), p1.stride(0),
+              p1.stride(1), self.k1, self.c4, self.mp, _p(self.image), nbytes, _stream())
         self.sc1 = (scale1 * w1.inv_scale).contiguous()          # exact: the row scale is a power of two (the tile kernel's product)
         self.sh1 = shift1.contiguous()
 
@@ -720,8 +712,8 @@ def _bneck_fused_sc(a, blk, S):
     # profile bytes: A and the sampled rows of S in, X and Y1 out: no residual stream
     with _timed(M > 0, lambda: (2.0 * M * blk.c4 * (blk.k1 + blk.ks + blk.mp), 4.0 * M * (blk.k1 + blk.ks + blk.c4 + blk.mp) + blk.image.numel(),
                                 "bneck:%dx%dx%dx%d+sc%d/%d" % (M, blk.k1, blk.c4, blk.mp, blk.ks, st))):
-        check(_L().gom_bneck_sc_f32(_p(a), k1, _p(blk.image), _p(S), ks, B, Hs, Ws, st, _p(blk.sc1), _p(blk.sh1), _p(X), blk.c4, _p(Y1),
-                                    blk.mp, blk.k1, blk.c4, blk.mp, blk.ks, _p(range_flag(a.device)), _stream()), "gom_bneck_sc_f32")
+        _call("gom_bneck_sc_f32", _p(a), k1, _p(blk.image), _p(S), ks, B, Hs, Ws, st, _p(blk.sc1), _p(blk.sh1), _p(X), blk.c4,
+              _p(Y1), blk.mp, blk.k1, blk.c4, blk.mp, blk.ks, _p(range_flag(a.device)), _stream())
     return X, Y1
 
 
@@ -736,11 +728,10 @@ def bneck_fused(a, blk, R):
     M = B * H * W
     X = torch.empty((B, H, W, blk.c4), dtype=_f32, device=a.device)
     Y1 = torch.empty((B, H, W, blk.mp), dtype=_f32, device=a.device)
-    fn = _L().gom_bneck2_f32 if blk.v2 else _L().gom_bneck_f32
     with _timed(M > 0, lambda: (2.0 * M * blk.c4 * (blk.k1 + blk.mp), 4.0 * M * (blk.k1 + 2 * blk.c4 + blk.mp) + blk.image.numel(),
                                 "bneck:%dx%dx%dx%d" % (M, blk.k1, blk.c4, blk.mp))):
-        check(fn(_p(a), k1, _p(blk.image), _p(R), blk.c4, _p(blk.sc1), _p(blk.sh1), _p(X), blk.c4, _p(Y1), blk.mp, M,
-                 blk.k1, blk.c4, blk.mp, _p(range_flag(a.device)), _stream()), "gom_bneck2_f32" if blk.v2 else "gom_bneck_f32")
+        _call("gom_bneck2_f32" if blk.v2 else "gom_bneck_f32", _p(a), k1, _p(blk.image), _p(R), blk.c4, _p(blk.sc1), _p(blk.sh1),
+              _p(X), blk.c4, _p(Y1), blk.mp, M, blk.k1, blk.c4, blk.mp, _p(range_flag(a.device)), _stream())
     return X, Y1
 
 
@@ -773,25 +764,23 @@ class DecAttnBlock:
         _chk_f32(in_b, out_b, gamma, beta)
         self.image = torch.empty((nbytes,), dtype=torch.uint8, device=si.planes.device)
         pi, po = si.planes, so.planes
-        check(_L().gom_dec_attn_image(_p(pi), pi.stride(0), pi.stride(1), _p(si.inv_scale), _p(in_b), _p(po), po.stride(0),
-                                      po.stride(1), _p(so.inv_scale), _p(out_b), _p(gamma), _p(beta), 1 if inter else 0,
-                                      _p(self.image), nbytes, _stream()), "gom_dec_attn_image")
+        _call("gom_dec_attn_image", _p(pi), pi.stride(0), pi.stride(1), _p(si.inv_scale), _p(in_b), _p(po), po.stride(0),
+              po.stride(1), _p(so.inv_scale), _p(out_b), _p(gamma), _p(beta), 1 if inter else 0, _p(self.image), nbytes, _stream())
         self.eps, self.inter, self.has_raw = eps, bool(inter), raw is not None
         if raw is not None:
             sr = raw[0] if isinstance(raw[0], SplitWeight) else split_weight(raw[0].contiguous(), kind="f16x3")
             assert sr.kind == "f16x3"
             _chk_f32(raw[1])
-            check(_L().gom_dec_attn_raw_image(_p(sr.planes), sr.planes.stride(0), sr.planes.stride(1), _p(sr.inv_scale), _p(raw[1]),
-                                              _p(self.image), nbytes, _stream()), "gom_dec_attn_raw_image")
+            _call("gom_dec_attn_raw_image", _p(sr.planes), sr.planes.stride(0), sr.planes.stride(1), _p(sr.inv_scale), _p(raw[1]),
+                  _p(self.image), nbytes, _stream())
         if self.form == 2:
             n2 = _L().gom_dec_attn2_raw_image_bytes() if raw is not None else _L().gom_dec_attn2_image_bytes(256, 8)
             self.image2 = torch.empty((n2,), dtype=torch.uint8, device=si.planes.device)
-            check(_L().gom_dec_attn2_image(_p(pi), pi.stride(0), pi.stride(1), _p(si.inv_scale), _p(in_b), _p(po), po.stride(0),
-                                           po.stride(1), _p(so.inv_scale), _p(out_b), _p(gamma), _p(beta), 1 if inter else 0,
-                                           _p(self.image2), n2, _stream()), "gom_dec_attn2_image")
+            _call("gom_dec_attn2_image", _p(pi), pi.stride(0), pi.stride(1), _p(si.inv_scale), _p(in_b), _p(po), po.stride(0),
+                  po.stride(1), _p(so.inv_scale), _p(out_b), _p(gamma), _p(beta), 1 if inter else 0, _p(self.image2), n2, _stream())
             if raw is not None:
-                check(_L().gom_dec_attn2_raw_image(_p(sr.planes), sr.planes.stride(0), sr.planes.stride(1), _p(sr.inv_scale), _p(raw[1]),
-                                                   _p(self.image2), n2, _stream()), "gom_dec_attn2_raw_image")
+                _call("gom_dec_attn2_raw_image", _p(sr.planes), sr.planes.stride(0), sr.planes.stride(1), _p(sr.inv_scale),
+                      _p(raw[1]), _p(self.image2), n2, _stream())
 
 
 DEC_ATTN_RAW = _switch("DEC_ATTN_RAW")      # the inter block's launch also makes the cross attention's offsets | logits
@@ -838,17 +827,15 @@ def dec_attn(x, blk, groups, group_tokens, inner=1, pos=None, out=None, raw_pos=
     if out is None:
         out = torch.empty((x.shape[0], 256), dtype=_f32, device=x.device)
     raw = torch.empty((rows, 384), dtype=_f32, device=x.device) if with_raw else None
-    L, form2 = _L(), blk.form == 2
+    form2 = blk.form == 2
     img = blk.image2 if form2 else blk.image
     with _timed(rows > 0, lambda: _dec_attn_figures(blk, groups, group_tokens, with_raw, pos is not None)):
         if with_raw:
-            check((L.gom_dec_attn2_raw_f32 if form2 else L.gom_dec_attn_raw_f32)(
-                _p(x), _ld(x), _p(img), blk.eps, _p(out), _ld(out), _p(raw_pos), _ld(raw_pos), _p(raw), 384, groups, group_tokens,
-                inner, _p(range_flag(x.device)), _stream()), "gom_dec_attn_raw_f32")
+            _call("gom_dec_attn2_raw_f32" if form2 else "gom_dec_attn_raw_f32", _p(x), _ld(x), _p(img), blk.eps, _p(out), _ld(out),
+                  _p(raw_pos), _ld(raw_pos), _p(raw), 384, groups, group_tokens, inner, _p(range_flag(x.device)), _stream())
         else:
-            check((L.gom_dec_attn2_f32 if form2 else L.gom_dec_attn_f32)(
-                _p(x), _ld(x), _p(pos), _ld(pos), _p(img), blk.eps, _p(out), _ld(out), groups, group_tokens, inner,
-                1 if blk.inter else 0, _p(range_flag(x.device)), _stream()), "gom_dec_attn_f32")
+            _call("gom_dec_attn2_f32" if form2 else "gom_dec_attn_f32", _p(x), _ld(x), _p(pos), _ld(pos), _p(img), blk.eps, _p(out),
+                  _ld(out), groups, group_tokens, inner, 1 if blk.inter else 0, _p(range_flag(x.device)), _stream())
     return (out, raw) if with_raw else out
 
 
@@ -863,8 +850,8 @@ def dec_inter_heads(x, blk, groups, group_tokens, inner, out=None):
     # profile flops: in_proj + QK^T and PV of every head
     with _timed(rows > 0, lambda: (2.0 * rows * 256 * 768 + 4.0 * rows * group_tokens * 256, 4.0 * rows * 256 * 2 + 24 * 36864,
                                    "decattn:inter-heads:%dx%d" % (groups, group_tokens))):
-        check(_L().gom_dec_inter_heads_f32(_p(x), _ld(x), _p(blk.image), _p(out), _ld(out), groups, group_tokens, inner,
-                                           _p(range_flag(x.device)), _stream()), "gom_dec_inter_heads_f32")
+        _call("gom_dec_inter_heads_f32", _p(x), _ld(x), _p(blk.image), _p(out), _ld(out), groups, group_tokens, inner,
+              _p(range_flag(x.device)), _stream())
     return out
 
 
@@ -889,9 +876,8 @@ def _ffn_image(w1, b1, w2, refusal=None, acc_order=False, into=None, off=0):
         into = torch.empty((nbytes,), dtype=torch.uint8, device=w1.device)
     assert off + nbytes <= into.numel()
     p1, p2 = s1.planes, s2.planes
-    name = "gom_ffn_fused_image_acc_order" if acc_order else "gom_ffn_fused_image"
-    check(getattr(_L(), name)(_p(p1), p1.stride(0), p1.stride(1), _p(s1.inv_scale), _p(b1), _p(p2), p2.stride(0), p2.stride(1), D_, F_,
-                              ctypes.c_void_p(into.data_ptr() + off), nbytes, _stream()), name)
+    _call("gom_ffn_fused_image_acc_order" if acc_order else "gom_ffn_fused_image", _p(p1), p1.stride(0), p1.stride(1),
+          _p(s1.inv_scale), _p(b1), _p(p2), p2.stride(0), p2.stride(1), D_, F_, ctypes.c_void_p(into.data_ptr() + off), nbytes, _stream())
     return s1.inv_scale, s2.inv_scale, into
 
 
@@ -931,8 +917,8 @@ def mlp2_fused(x, blk):
     M = x.shape[0]
     out = torch.empty((M, 256), dtype=_f32, device=x.device)
     with _timed(M > 0, lambda: (4.0 * M * blk.D * blk.F, 8.0 * M * blk.D + blk.image.numel(), "ffn-mlp2:%dx%dx%d" % (M, blk.D, blk.F))):
-        check(_L().gom_mlp2_fused_f32(_p(x), _ld(x), _p(blk.image), _p(blk.inv2), _p(blk.b2), 1 if blk.relu_out else 0, _p(out), 256,
-                                      M, blk.D, blk.F, _p(range_flag(x.device)), _stream()), "gom_mlp2_fused_f32")
+        _call("gom_mlp2_fused_f32", _p(x), _ld(x), _p(blk.image), _p(blk.inv2), _p(blk.b2), 1 if blk.relu_out else 0, _p(out), 256,
+              M, blk.D, blk.F, _p(range_flag(x.device)), _stream())
     return out
 
 
@@ -943,9 +929,8 @@ def ffn_fused_ln(x, ffn, out=None):
     if out is None:
         out = torch.empty((M, ffn.D), dtype=_f32, device=x.device)
     with _timed(M > 0, lambda: (4.0 * M * ffn.D * ffn.F, 8.0 * M * ffn.D + ffn.image.numel(), "ffn%dx%dx%d" % (M, ffn.D, ffn.F))):
-        check(_L().gom_ffn_fused_ln_f32(_p(x), _ld(x), _p(ffn.image), _p(ffn.inv2), _p(ffn.b2), _p(ffn.gamma), _p(ffn.beta), ffn.eps,
-                                        _p(out), _ld(out), M, ffn.D, ffn.F, _p(range_flag(x.device)), _stream()),
-              "gom_ffn_fused_ln_f32")
+        _call("gom_ffn_fused_ln_f32", _p(x), _ld(x), _p(ffn.image), _p(ffn.inv2), _p(ffn.b2), _p(ffn.gamma), _p(ffn.beta), ffn.eps,
+              _p(out), _ld(out), M, ffn.D, ffn.F, _p(range_flag(x.device)), _stream())
     return out
 
 
@@ -1003,8 +988,8 @@ class DecTail:
         nbytes = L.gom_dec_tail_image_bytes(self.D, self.F, 1) + lin_bytes
         self.image = torch.empty((nbytes,), dtype=torch.uint8, device=mlps[0][0].device)
         if so is not None:
-            check(L.gom_dec_tail_lin_image(_p(so.planes), so.planes.stride(0), so.planes.stride(1), _p(self.image), lin_bytes, _stream()),
-                  "gom_dec_tail_lin_image")
+            _call("gom_dec_tail_lin_image", _p(so.planes), so.planes.stride(0), so.planes.stride(1), _p(self.image), lin_bytes,
+                  _stream())
         off, invs = lin_bytes, []
         for i, (wa, ba, wb) in enumerate(mlps):
             invs.append(_ffn_image(wa, ba, wb, acc_order=i > 0 or so is not None, into=self.image, off=off)[:2])
@@ -1016,18 +1001,18 @@ class DecTail:
         """One linear weight stream per wave (csrc/dec_tail2.hip): [out_proj] | FFN | ctrl_point_coord | ref_point_head; an image
         WITHOUT ref_point_head's part serves the last layer (want_qpos=False): the streams of the two differ only in length.
         Returns the blocks' (inv_scale1, inv_scale2)."""
-        L, nw, wb = _L(), self.waves, self.wave_bytes[1]
+        nw, wb = self.waves, self.wave_bytes[1]
         self.image = torch.empty((nw * wb,), dtype=torch.uint8, device=mlps[0][0].device)
         blk_bytes = (256 // nw) * 1024                            # a wave's share of a 256 -> 256 layer or of a chunk of 128 hidden units
         off, invs = 0, []
         if so is not None:
-            check(L.gom_dec_tail2_image_lin(_p(so.planes), so.planes.stride(0), so.planes.stride(1), _p(self.image), wb, off, nw, _stream()),
-                  "gom_dec_tail2_image_lin")
+            _call("gom_dec_tail2_image_lin", _p(so.planes), so.planes.stride(0), so.planes.stride(1), _p(self.image), wb, off, nw,
+                  _stream())
             off += blk_bytes
         for wa, _, wb_ in mlps:
             sa, sb = split_weight(wa.contiguous(), kind="f16x3"), split_weight(wb_.contiguous(), kind="f16x3")
-            check(L.gom_dec_tail2_image_mlp(_p(sa.planes), sa.planes.stride(0), sa.planes.stride(1), _p(sb.planes), sb.planes.stride(0),
-                                            sb.planes.stride(1), wa.shape[0], _p(self.image), wb, off, nw, _stream()), "gom_dec_tail2_image_mlp")
+            _call("gom_dec_tail2_image_mlp", _p(sa.planes), sa.planes.stride(0), sa.planes.stride(1), _p(sb.planes),
+                  sb.planes.stride(0), sb.planes.stride(1), wa.shape[0], _p(self.image), wb, off, nw, _stream())
             off += (wa.shape[0] // 128) * blk_bytes
             invs.append((sa.inv_scale, sb.inv_scale))
         assert off == wb
@@ -1097,24 +1082,20 @@ def dec_tail(x, blk, ref, want_qpos=True, residual=None, frames=None):
     pi, pb, pg, pbe = blk.proj if blk.proj is not None else (None, None, None, None)
     with _timed(M > 0, lambda: _dec_tail_figures(blk, M, want_qpos)):
         if blk.form == 2:
-            check(_L().gom_dec_tail2_f32(_p(x), _ld(x), _p(r), _ld(r),
-                                         _p(blk.image if want_qpos else blk.image_last), blk.wave_bytes[1 if want_qpos else 0], blk.F,
-                                         _p(pi), _p(pb), _p(pg), _p(pbe), blk.eps, _p(blk.inv1), _p(blk.b1), _p(blk.inv2), _p(blk.b2),
-                                         _p(blk.gamma), _p(blk.beta), blk.eps, _p(blk.c_inv1), _p(blk.c_b1), _p(blk.c_inv2), _p(blk.c_b2),
-                                         _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t), _p(blk.q_inv1), _p(blk.q_b1), _p(blk.q_inv2),
-                                         _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M, blk.waves, _p(range_flag(x.device)), _stream()),
-                  "gom_dec_tail2_f32")
+            _call("gom_dec_tail2_f32", _p(x), _ld(x), _p(r), _ld(r), _p(blk.image if want_qpos else blk.image_last),
+                  blk.wave_bytes[1 if want_qpos else 0], blk.F, _p(pi), _p(pb), _p(pg), _p(pbe), blk.eps, _p(blk.inv1), _p(blk.b1),
+                  _p(blk.inv2), _p(blk.b2), _p(blk.gamma), _p(blk.beta), blk.eps, _p(blk.c_inv1), _p(blk.c_b1), _p(blk.c_inv2),
+                  _p(blk.c_b2), _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t), _p(blk.q_inv1), _p(blk.q_b1), _p(blk.q_inv2),
+                  _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M, blk.waves, _p(range_flag(x.device)), _stream())
         elif blk.proj is None:
-            check(_L().gom_dec_tail_f32(_p(x), _ld(x), _p(blk.image), blk.F, _p(blk.inv2), _p(blk.b2), _p(blk.gamma),
-                                        _p(blk.beta), blk.eps, _p(blk.c_inv2), _p(blk.c_b2), _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t),
-                                        _p(blk.q_inv2), _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M,
-                                        _p(range_flag(x.device)), _stream()), "gom_dec_tail_f32")
+            _call("gom_dec_tail_f32", _p(x), _ld(x), _p(blk.image), blk.F, _p(blk.inv2), _p(blk.b2), _p(blk.gamma), _p(blk.beta),
+                  blk.eps, _p(blk.c_inv2), _p(blk.c_b2), _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t), _p(blk.q_inv2),
+                  _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M, _p(range_flag(x.device)), _stream())
         else:
-            check(_L().gom_dec_tail_proj_f32(_p(x), _ld(x), _p(r), _ld(r), _p(blk.image), blk.F,
-                                             _p(pi), _p(pb), _p(pg), _p(pbe), blk.eps, _p(blk.inv2), _p(blk.b2), _p(blk.gamma), _p(blk.beta),
-                                             blk.eps, _p(blk.c_inv2), _p(blk.c_b2), _p(blk.W3), _p(blk.b3), _p(ref), _p(blk.dim_t),
-                                             _p(blk.q_inv2), _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M,
-                                             _p(range_flag(x.device)), _stream()), "gom_dec_tail_proj_f32")
+            _call("gom_dec_tail_proj_f32", _p(x), _ld(x), _p(r), _ld(r), _p(blk.image), blk.F, _p(pi), _p(pb), _p(pg), _p(pbe),
+                  blk.eps, _p(blk.inv2), _p(blk.b2), _p(blk.gamma), _p(blk.beta), blk.eps, _p(blk.c_inv2), _p(blk.c_b2), _p(blk.W3),
+                  _p(blk.b3), _p(ref), _p(blk.dim_t), _p(blk.q_inv2), _p(blk.q_b2), _p(out), 256, _p(new_ref), _p(qpos), 256, M,
+                  _p(range_flag(x.device)), _stream())
     return out, new_ref, qpos
 
 
@@ -1149,13 +1130,11 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     B, S, M, D, Lv, Lq, Pn = dims
     out = torch.empty((B, Lq, M * D), dtype=value.dtype, device=value.device)
     if code == 0:           # the 1:1 entry: the shipped shape on the wave-per-query kernel, anything else on the general one
-        check(_L().gom_ms_deform_attn_forward(_p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_loc),
-                                              _p(attn_weight), _p(out), B, S, M, D, Lv, Lq, Pn, _stream()),
-              "gom_ms_deform_attn_forward")
+        _call("gom_ms_deform_attn_forward", _p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_loc), _p(attn_weight),
+              _p(out), B, S, M, D, Lv, Lq, Pn, _stream())
     else:
-        check(_L().gom_ms_deform_attn_forward_any(code, _p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_loc),
-                                                  _p(attn_weight), _p(out), B, S, M, D, Lv, Lq, Pn, _stream()),
-              "gom_ms_deform_attn_forward_any")
+        _call("gom_ms_deform_attn_forward_any", code, _p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_loc),
+              _p(attn_weight), _p(out), B, S, M, D, Lv, Lq, Pn, _stream())
     return out
 
 
@@ -1164,9 +1143,8 @@ def ms_deform_attn_forward_any(value, spatial_shapes, level_start_index, samplin
     code, dims = _msda_args(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     B, S, M, D, Lv, Lq, Pn = dims
     out = torch.empty((B, Lq, M * D), dtype=value.dtype, device=value.device)
-    check(_L().gom_ms_deform_attn_forward_any(code, _p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_loc),
-                                              _p(attn_weight), _p(out), B, S, M, D, Lv, Lq, Pn, _stream()),
-          "gom_ms_deform_attn_forward_any")
+    _call("gom_ms_deform_attn_forward_any", code, _p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_loc),
+          _p(attn_weight), _p(out), B, S, M, D, Lv, Lq, Pn, _stream())
     return out
 
 
@@ -1177,10 +1155,8 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     if grad_output.numel() != B * Lq * M * D:
         raise _lib_mod.GomError("ms_deform_attn_backward: grad_output must hold [B, Lq, M*D] elements")
     gv, gl, gw = torch.empty_like(value), torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
-    check(_L().gom_ms_deform_attn_backward(code, _p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_loc),
-                                           _p(attn_weight), _p(grad_output), _p(gv), _p(gl), _p(gw), B, S, M, D, Lv, Lq, Pn,
-                                           _stream()),
-          "gom_ms_deform_attn_backward")
+    _call("gom_ms_deform_attn_backward", code, _p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_loc),
+          _p(attn_weight), _p(grad_output), _p(gv), _p(gl), _p(gw), B, S, M, D, Lv, Lq, Pn, _stream())
     return gv, gl, gw
 
 
@@ -1188,9 +1164,8 @@ def ms_deform_attn_forward_strided(value2d, batch_stride, shapes, lsi, loc, w, B
     """value2d: [B*S, 256] column slice (stride(1)==1) of a wider buffer; reads it in place."""
     assert value2d.stride(1) == 1
     out = torch.empty((B * Lq, 256), dtype=_f32, device=value2d.device)
-    check(_L().gom_ms_deform_attn_forward_strided(_p(value2d), batch_stride, value2d.stride(0), _p(shapes), _p(lsi),
-                                                  _p(loc), _p(w), _p(out), B, Lq, _stream()),
-          "gom_ms_deform_attn_forward_strided")
+    _call("gom_ms_deform_attn_forward_strided", _p(value2d), batch_stride, value2d.stride(0), _p(shapes), _p(lsi), _p(loc), _p(w),
+          _p(out), B, Lq, _stream())
     return out
 
 
@@ -1252,13 +1227,11 @@ def msda_fused(raw, ref, value2d, batch_stride, shapes, lsi, B, Lq, valid_ratios
     # output (fp32)
     with _timed(True, lambda: (2.0 * B * Lq * 8 * 16 * 4 * 32, 4.0 * (S_rows * 256 + B * Lq * (384 + 256)), "msda:%dx%d" % (B, Lq))):
         if frame_valid_ratios is not None:
-            check(_L().gom_msda_fused_forward_vr_frames(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride,
-                                                        value2d.stride(0), _p(shapes), _p(lsi), _p(frame_valid_ratios), _p(out),
-                                                        B, Lq, _stream()), "gom_msda_fused_forward_vr_frames")
+            _call("gom_msda_fused_forward_vr_frames", _p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride, value2d.stride(0),
+                  _p(shapes), _p(lsi), _p(frame_valid_ratios), _p(out), B, Lq, _stream())
         elif valid_ratios is not None:
-            check(_L().gom_msda_fused_forward_vr(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride,
-                                                 value2d.stride(0), _p(shapes), _p(lsi), _p(valid_ratios), _p(out), B, Lq,
-                                                 _stream()), "gom_msda_fused_forward_vr")
+            _call("gom_msda_fused_forward_vr", _p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride, value2d.stride(0),
+                  _p(shapes), _p(lsi), _p(valid_ratios), _p(out), B, Lq, _stream())
         elif encoder_hw0 is not None and MSDA_WINDOW and MSDA_LANES:
             mask = (3 if MSDA_WINDOW_L1 else 1) | (4 if MSDA_WINDOW_OVERLAP else 0) | (8 if MSDA_WINDOW_LANES4 else 0)
             if _msda_window_set[0] != mask:
@@ -1269,15 +1242,15 @@ def msda_fused(raw, ref, value2d, batch_stride, shapes, lsi, B, Lq, valid_ratios
                 fallback_counter.zero_()
                 _L().gom_msda_window_count_fallbacks(_p(fallback_counter))
             try:
-                check(_L().gom_msda_fused_forward_encoder(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride, value2d.stride(0),
-                                                          _p(shapes), _p(lsi), _p(out), B, Lq, int(encoder_hw0[0]), int(encoder_hw0[1]),
-                                                          h1, w1, _stream()), "gom_msda_fused_forward_encoder")
+                _call("gom_msda_fused_forward_encoder", _p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride,
+                      value2d.stride(0), _p(shapes), _p(lsi), _p(out), B, Lq, int(encoder_hw0[0]), int(encoder_hw0[1]), h1, w1,
+                      _stream())
             finally:
                 if fallback_counter is not None:
                     _L().gom_msda_window_count_fallbacks(None)
         else:
-            check(_L().gom_msda_fused_forward(_p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride, value2d.stride(0),
-                                              _p(shapes), _p(lsi), _p(out), B, Lq, _stream()), "gom_msda_fused_forward")
+            _call("gom_msda_fused_forward", _p(raw), raw.stride(0), _p(ref), _p(value2d), batch_stride, value2d.stride(0),
+                  _p(shapes), _p(lsi), _p(out), B, Lq, _stream())
     return out
 
 
@@ -1287,23 +1260,21 @@ def msda_prepare(raw, ref, spatial_shapes, ref_levels=1):
     Q = raw.shape[0]
     loc = torch.empty((Q, 8, 4, 4, 2), dtype=_f32, device=raw.device)
     w = torch.empty((Q, 8, 4, 4), dtype=_f32, device=raw.device)
-    check(_L().gom_msda_prepare(_p(raw), raw.stride(0), _p(ref), ref_levels, _p(spatial_shapes), _p(loc), _p(w), Q,
-                                _stream()), "gom_msda_prepare")
+    _call("gom_msda_prepare", _p(raw), raw.stride(0), _p(ref), ref_levels, _p(spatial_shapes), _p(loc), _p(w), Q, _stream())
     return loc, w
 
 
 # ------------------------------------------------------------------------------------------ attention
 def mha_core(q, k, v, out, outer, inner, heads, head_dim, Lq, Lk, strides):
     arr = (ctypes.c_long * 12)(*[int(s) for s in strides])
-    check(_L().gom_mha_core_f32(_p(q), _p(k), _p(v), _p(out), outer, inner, heads, head_dim, Lq, Lk, arr, _stream()),
-          "gom_mha_core_f32")
+    _call("gom_mha_core_f32", _p(q), _p(k), _p(v), _p(out), outer, inner, heads, head_dim, Lq, Lk, arr, _stream())
     return out
 
 
 def mha_core_segments(q, k, v, out, segments, num_segments, heads, head_dim, ld_q, ld_k, ld_v, ld_o, max_Lq, max_Lk):
     """Ragged batch: segments int32 [S,4] (device) = (first query row, Lq, first key row, Lk) over shared matrices."""
-    check(_L().gom_mha_core_segments_f32(_p(q), _p(k), _p(v), _p(out), _p(segments), num_segments, heads, head_dim,
-                                         ld_q, ld_k, ld_v, ld_o, max_Lq, max_Lk, _stream()), "gom_mha_core_segments_f32")
+    _call("gom_mha_core_segments_f32", _p(q), _p(k), _p(v), _p(out), _p(segments), num_segments, heads, head_dim, ld_q, ld_k, ld_v,
+          ld_o, max_Lq, max_Lk, _stream())
     return out
 
 
@@ -1315,7 +1286,7 @@ def preprocess(images, mean, std):
     out = torch.empty((B, H, W, 4), dtype=_f32, device=images.device)
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    check(_L().gom_preprocess_nchw_to_nhwc4(_p(images), m, s, _p(out), B, H, W, _stream()), "gom_preprocess")
+    _call("gom_preprocess_nchw_to_nhwc4", _p(images), m, s, _p(out), B, H, W, _stream())
     return out
 
 
@@ -1328,7 +1299,7 @@ def _build_resample_tables(in_size, out_size, device):
         raise ValueError("bad resample sizes %d -> %d" % (in_size, out_size))
     bounds = torch.empty((out_size, 2), dtype=torch.int32)
     kk = torch.empty((out_size, ks), dtype=torch.int32)
-    check(_L().gom_resample_coeffs_bilinear(in_size, out_size, _p(bounds), _p(kk), ks), "gom_resample_coeffs")
+    _call("gom_resample_coeffs_bilinear", in_size, out_size, _p(bounds), _p(kk), ks)
     return (bounds.to(device), kk.to(device), ks)
 
 
@@ -1355,8 +1326,8 @@ def resize_u8(frames, out_h, out_w, flip=False):
     xb, xk, xks = resample_tables(W, out_w, frames.device)
     yb, yk, yks = resample_tables(H, out_h, frames.device)
     out = torch.empty((B, out_h, out_w, 3), dtype=torch.uint8, device=frames.device)
-    check(_L().gom_resize_bilinear_u8_hwc3(_p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, _p(out),
-                                           out_h, out_w, int(flip), _stream()), "gom_resize_bilinear_u8_hwc3")
+    _call("gom_resize_bilinear_u8_hwc3", _p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, _p(out), out_h, out_w,
+          int(flip), _stream())
     return out
 
 
@@ -1369,8 +1340,8 @@ def ingest(frames, out_h, out_w, mean, std, flip):
     out = torch.empty((B, out_h, out_w, 4), dtype=_f32, device=frames.device)
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    check(_L().gom_ingest_u8_hwc3_to_nhwc4(_p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, m, s,
-                                           _p(out), out_h, out_w, int(flip), _stream()), "gom_ingest_u8_hwc3_to_nhwc4")
+    _call("gom_ingest_u8_hwc3_to_nhwc4", _p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, m, s, _p(out), out_h, out_w,
+          int(flip), _stream())
     return out
 
 
@@ -1413,9 +1384,8 @@ def resize_crop_u8(frames, scaled_hw, window, flip=False):
     xb, xk, xks = _crop_resample_tables(W, SW, frames.device)
     yb, yk, yks = _crop_resample_tables(H, SH, frames.device)
     out = torch.empty((B, OH, OW, 3), dtype=torch.uint8, device=frames.device)
-    check(_L().gom_resize_crop_bilinear_u8_hwc3(_p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, _p(out),
-                                                SH, SW, y0, x0, OH, OW, int(flip), _stream()),
-          "gom_resize_crop_bilinear_u8_hwc3")
+    _call("gom_resize_crop_bilinear_u8_hwc3", _p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, _p(out), SH, SW, y0,
+          x0, OH, OW, int(flip), _stream())
     return out
 
 
@@ -1430,13 +1400,12 @@ def ingest_crop(frames, scaled_hw, window, mean, std, flip):
     out = torch.empty((B, OH, OW, 4), dtype=_f32, device=frames.device)
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    check(_L().gom_ingest_crop_u8_hwc3_to_nhwc4(_p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, m, s,
-                                                _p(out), SH, SW, y0, x0, OH, OW, int(flip), _stream()),
-          "gom_ingest_crop_u8_hwc3_to_nhwc4")
+    _call("gom_ingest_crop_u8_hwc3_to_nhwc4", _p(frames), B, H, W, _p(xb), _p(xk), xks, _p(yb), _p(yk), yks, m, s, _p(out), SH, SW,
+          y0, x0, OH, OW, int(flip), _stream())
     return out
 
 
-INGEST_MOTION_MAX_FRAMES = 16       # GOM_INGEST_MOTION_MAX_FRAMES (include/gomatching_hip.h)
+INGEST_MOTION_MAX_FRAMES = _lib_mod.CONSTANTS["GOM_INGEST_MOTION_MAX_FRAMES"]
 
 
 def motion_tables(H, W, frames):
@@ -1458,7 +1427,7 @@ def motion_tables(H, W, frames):
                 raise ValueError("bad resample sizes %d -> %d" % (in_size, out_size))
             bounds = torch.empty((out_size, 2), dtype=torch.int32)
             kk = torch.empty((out_size, ks), dtype=torch.int32)
-            check(L.gom_resample_coeffs_bilinear(in_size, out_size, _p(bounds), _p(kk), ks), "gom_resample_coeffs")
+            _call("gom_resample_coeffs_bilinear", in_size, out_size, _p(bounds), _p(kk), ks)
             hit = (ks, words, words + bounds.numel())
             words += bounds.numel() + kk.numel()
             parts.extend((bounds.view(-1), kk.view(-1)))
@@ -1494,12 +1463,12 @@ def ingest_motion(src, frames, mean, std, flip, out=None):
     tab = tables.to(src.device)
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    check(_L().gom_ingest_motion_u8_hwc3_to_nhwc4(_p(src), H, W, _p(tab), tab.numel(), _p(desc), T, m, s, _p(out), PH, PW,
-                                                  int(flip), _stream()), "gom_ingest_motion_u8_hwc3_to_nhwc4")
+    _call("gom_ingest_motion_u8_hwc3_to_nhwc4", _p(src), H, W, _p(tab), tab.numel(), _p(desc), T, m, s, _p(out), PH, PW, int(flip),
+          _stream())
     return out
 
 
-RESULT_ROWS_WORDS = 234             # GOM_RESULT_ROWS_WORDS (include/gomatching_hip.h)
+RESULT_ROWS_WORDS = _lib_mod.CONSTANTS["GOM_RESULT_ROWS_WORDS"]
 
 
 def result_rows(bd, recs, voc_size, track_ids=None):
@@ -1518,12 +1487,11 @@ def result_rows(bd, recs, voc_size, track_ids=None):
     track_ids = None if track_ids is None else track_ids.contiguous()
     out = torch.empty((n, RESULT_ROWS_WORDS), dtype=torch.int32, device=bd.device)
     with torch.cuda.device(bd.device):
-        check(_L().gom_result_rows_i32(_p(bd), _p(recs), _p(track_ids), n, int(voc_size), _p(out), RESULT_ROWS_WORDS,
-                                       _stream()), "gom_result_rows_i32")
+        _call("gom_result_rows_i32", _p(bd), _p(recs), _p(track_ids), n, int(voc_size), _p(out), RESULT_ROWS_WORDS, _stream())
     return out
 
 
-RESULT_ROWS_DESC_WORDS = 6          # GOM_RR_DESC_WORDS
+RESULT_ROWS_DESC_WORDS = _lib_mod.CONSTANTS["GOM_RR_DESC_WORDS"]
 
 
 def result_rows_desc(rows, track_ids, sx, sy):
@@ -1563,8 +1531,8 @@ def result_rows_gather(bd, recs, desc, voc_size, upload=None):
     with torch.cuda.device(bd.device):
         desc = np.ascontiguousarray(desc)
         desc_d = upload(desc) if upload is not None else torch.from_numpy(desc).to(bd.device)
-        check(_L().gom_result_rows_gather_i32(_p(bd), _p(recs), cap, _p(desc_d), n, int(voc_size), _p(out), RESULT_ROWS_WORDS,
-                                              _stream()), "gom_result_rows_gather_i32")
+        _call("gom_result_rows_gather_i32", _p(bd), _p(recs), cap, _p(desc_d), n, int(voc_size), _p(out), RESULT_ROWS_WORDS,
+              _stream())
     return out
 
 
@@ -1578,7 +1546,7 @@ def quad_bezier(quads, hw):
         raise ValueError("hw must be [n,2] for quads [n,8]")
     out = torch.empty((n, 16), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(_L().gom_quad_bezier_i32(_p(quads), _p(hw), n, _p(out), _stream()), "gom_quad_bezier_i32")
+        _call("gom_quad_bezier_i32", _p(quads), _p(hw), n, _p(out), _stream())
     return out
 
 
@@ -1604,13 +1572,13 @@ def quad_pairs(gt_quads, det_quads, gt_off, det_off, gt_key, det_key, measure, t
     args = (_p(gt_quads), _p(det_quads), _p(gt_off), _p(det_off), _p(gt_key), _p(det_key), G, D, F, int(pairs), int(measure),
             float(threshold))
     with torch.cuda.device(dev):
-        check(_L().gom_quad_pairs_count_f64(*args, _p(counts), _stream()), "gom_quad_pairs_count_f64")
+        _call("gom_quad_pairs_count_f64", *args, _p(counts), _stream())
         ends = torch.cumsum(counts, 0, dtype=torch.int64)
         total = int(ends[-1]) if G else 0
         scan = ends - counts
         det = torch.empty((total,), dtype=torch.int32, device=dev)
         val = torch.empty((total,), dtype=torch.float64, device=dev)
-        check(_L().gom_quad_pairs_emit_f64(*args, _p(scan), total, _p(det), _p(val), _stream()), "gom_quad_pairs_emit_f64")
+        _call("gom_quad_pairs_emit_f64", *args, _p(scan), total, _p(det), _p(val), _stream())
     return counts, det, val
 
 
@@ -1639,9 +1607,8 @@ def quad_det_match(gt_quads, det_quads, gt_off, det_off, gt_care, iou_thr=0.5, a
     match = torch.empty((G,), dtype=torch.int32, device=dev)
     stats = torch.empty((F, 3), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(_L().gom_quad_det_match_f64(_p(gt_quads), _p(det_quads), _p(gt_off), _p(det_off), _p(gt_care), G, D, F,
-                                          float(iou_thr), float(area_thr), _p(det_care), _p(match), _p(stats), _stream()),
-              "gom_quad_det_match_f64")
+        _call("gom_quad_det_match_f64", _p(gt_quads), _p(det_quads), _p(gt_off), _p(det_off), _p(gt_care), G, D, F, float(iou_thr),
+              float(area_thr), _p(det_care), _p(match), _p(stats), _stream())
     return det_care, match, stats
 
 
@@ -1683,9 +1650,8 @@ def mask_fill_polygons(points, contour_off, mask_coff, boxes, word_off, H, W, wo
     if C < 0 or mask_coff.shape[0] != N + 1:
         raise ValueError("contour_off must be [C+1] and mask_coff [N+1]")
     with torch.cuda.device(boxes.device):
-        check(_L().gom_mask_fill_polygons_u32(_p(points), P, _p(contour_off), C, _p(mask_coff), _p(boxes), _p(word_off), N, nwords,
-                                              _p(sel), M, int(H), int(W), _p(words), _p(area), _stream()),
-              "gom_mask_fill_polygons_u32")
+        _call("gom_mask_fill_polygons_u32", _p(points), P, _p(contour_off), C, _p(mask_coff), _p(boxes), _p(word_off), N, nwords,
+              _p(sel), M, int(H), int(W), _p(words), _p(area), _stream())
     return words, area
 
 
@@ -1697,8 +1663,8 @@ def mask_fill_rle(ends, run_off, boxes, word_off, H, W, words, area, sel=None):
     if run_off.shape[0] != N + 1:
         raise ValueError("run_off must be [N+1]")
     with torch.cuda.device(boxes.device):
-        check(_L().gom_mask_fill_rle_u32(_p(ends), ends.shape[0], _p(run_off), _p(boxes), _p(word_off), N, nwords, _p(sel), M,
-                                         int(H), int(W), _p(words), _p(area), _stream()), "gom_mask_fill_rle_u32")
+        _call("gom_mask_fill_rle_u32", _p(ends), ends.shape[0], _p(run_off), _p(boxes), _p(word_off), N, nwords, _p(sel), M, int(H),
+              int(W), _p(words), _p(area), _stream())
     return words, area
 
 
@@ -1726,17 +1692,17 @@ def mask_pairs(gt_words, gt_boxes, gt_woff, gt_area, det_words, det_boxes, det_w
     args = (_p(gt_words), _p(gt_boxes), _p(gt_woff), _p(gt_area), gt_words.shape[0], _p(det_words), _p(det_boxes), _p(det_woff),
             _p(det_area), det_words.shape[0], _p(gt_off), _p(det_off), _p(gt_key), _p(det_key), G, D, F, int(pairs), float(threshold))
     with torch.cuda.device(dev):
-        check(_L().gom_mask_pairs_count_f64(*args, _p(counts), _stream()), "gom_mask_pairs_count_f64")
+        _call("gom_mask_pairs_count_f64", *args, _p(counts), _stream())
         ends = torch.cumsum(counts, 0, dtype=i64)
         total = int(ends[-1]) if G else 0
         scan = ends - counts
         det = torch.empty((total,), dtype=i32, device=dev)
         val = torch.empty((total,), dtype=torch.float64, device=dev)
-        check(_L().gom_mask_pairs_emit_f64(*args, _p(scan), total, _p(det), _p(val), _stream()), "gom_mask_pairs_emit_f64")
+        _call("gom_mask_pairs_emit_f64", *args, _p(scan), total, _p(det), _p(val), _stream())
     return counts, det, val
 
 
-LEXICON_MAX_LEN = 64                 # GOM_LEXICON_MAX_LEN of include/gomatching_hip.h
+LEXICON_MAX_LEN = _lib_mod.CONSTANTS["GOM_LEXICON_MAX_LEN"]
 
 
 def lexicon_match(q_chars, q_off, q_seg, w_chars, w_off, seg_off, max_len=None, out=None):
@@ -1764,13 +1730,12 @@ def lexicon_match(q_chars, q_off, q_seg, w_chars, w_off, seg_off, max_len=None, 
     else:
         _chk_i(dev, ("out", out, i32, (2, S)))
     with torch.cuda.device(dev):
-        check(_L().gom_lexicon_match_u32(_p(q_chars), q_chars.shape[0], _p(q_off), _p(q_seg), S, _p(w_chars), w_chars.shape[0],
-                                         _p(w_off), W, _p(seg_off), n_seg, int(max_len), _p(out[0]), _p(out[1]), _stream()),
-              "gom_lexicon_match_u32")
+        _call("gom_lexicon_match_u32", _p(q_chars), q_chars.shape[0], _p(q_off), _p(q_seg), S, _p(w_chars), w_chars.shape[0],
+              _p(w_off), W, _p(seg_off), n_seg, int(max_len), _p(out[0]), _p(out[1]), _stream())
     return out[0], out[1]
 
 
-JPEG_MAX_WIDTH, JPEG_MAX_HEIGHT = 4096, 65535   # GOM_JPEG_MAX_WIDTH / GOM_JPEG_MAX_HEIGHT of include/gomatching_hip.h
+JPEG_MAX_WIDTH, JPEG_MAX_HEIGHT = _lib_mod.CONSTANTS["GOM_JPEG_MAX_WIDTH"], _lib_mod.CONSTANTS["GOM_JPEG_MAX_HEIGHT"]
 
 
 def jpeg_encode(frames, quality=95, bgr=True):
@@ -1794,13 +1759,11 @@ def jpeg_encode(frames, quality=95, bgr=True):
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     off_dev = torch.empty((F + 1,), dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        check(_L().gom_jpeg_encode_scan_u8(_p(frames), F, H, W, 1 if bgr else 0, quality, _p(ws), nbytes, _p(off_dev),
-                                           _stream()), "gom_jpeg_encode_scan_u8")
+        _call("gom_jpeg_encode_scan_u8", _p(frames), F, H, W, 1 if bgr else 0, quality, _p(ws), nbytes, _p(off_dev), _stream())
         offsets = off_dev.cpu()
         total = int(offsets[F])
         payload = torch.empty(((total + 3) // 4 * 4,), dtype=torch.uint8, device=dev)
-        check(_L().gom_jpeg_encode_pack_u8(_p(ws), nbytes, F, H, W, total, _p(payload), payload.shape[0], _stream()),
-              "gom_jpeg_encode_pack_u8")
+        _call("gom_jpeg_encode_pack_u8", _p(ws), nbytes, F, H, W, total, _p(payload), payload.shape[0], _stream())
     return payload[:total], offsets
 
 
@@ -1823,9 +1786,8 @@ def mask_outline_polygons(points, contour_off, mask_coff, boxes, word_off, H, W,
     if int(H) < 1 or int(W) < 1 or int(H) * int(W) > 2 ** 31 - 1:
         raise ValueError("H x W must lie in [1, 2^31 - 1]")
     with torch.cuda.device(dev):
-        check(_L().gom_mask_outline_polygons_u32(_p(points), P, _p(contour_off), C, _p(mask_coff), _p(boxes), _p(word_off), N,
-                                                 words.shape[0], _p(sel), N if sel is None else sel.shape[0], int(H), int(W),
-                                                 _p(words), _stream()), "gom_mask_outline_polygons_u32")
+        _call("gom_mask_outline_polygons_u32", _p(points), P, _p(contour_off), C, _p(mask_coff), _p(boxes), _p(word_off), N,
+              words.shape[0], _p(sel), N if sel is None else sel.shape[0], int(H), int(W), _p(words), _stream())
     return words
 
 
@@ -1860,10 +1822,9 @@ def overlay_compose(frames, face_words, outline_words, boxes, word_off, inst_off
         if out.shape != frames.shape or out.device != dev:
             raise ValueError("out must have the shape and the device of frames")
     with torch.cuda.device(dev):
-        check(_L().gom_overlay_compose_u8(_p(frames), _p(out), F, H, W, _p(face_words), _p(outline_words), _p(boxes), _p(word_off),
-                                          N, face_words.shape[0], _p(inst_off), _p(inst_rgb), _p(label_off), _p(label_pos),
-                                          _p(label_glyph), _p(label_rgb), L, _p(glyph_wh), _p(glyph_woff), _p(glyph_words), G,
-                                          glyph_words.shape[0], int(a_face), int(a_box), _stream()), "gom_overlay_compose_u8")
+        _call("gom_overlay_compose_u8", _p(frames), _p(out), F, H, W, _p(face_words), _p(outline_words), _p(boxes), _p(word_off), N,
+              face_words.shape[0], _p(inst_off), _p(inst_rgb), _p(label_off), _p(label_pos), _p(label_glyph), _p(label_rgb), L,
+              _p(glyph_wh), _p(glyph_woff), _p(glyph_words), G, glyph_words.shape[0], int(a_face), int(a_box), _stream())
     return out
 
 
@@ -1882,8 +1843,8 @@ def stem_conv_pool(x, w, scale=None, shift=None):
     PH, PW = (OH + 2 - 3) // 2 + 1, (OW + 2 - 3) // 2 + 1
     y = torch.empty((B, PH, PW, 64), dtype=_f32, device=x.device)
     pl = w.planes
-    check(_L().gom_stem_conv_pool_f32(_p(x), _p(pl), pl.stride(0), pl.stride(1), _p(w.inv_scale), _p(scale), _p(shift), _p(y),
-                                      B, H, Wd, _p(range_flag(x.device)), _stream()), "gom_stem_conv_pool_f32")
+    _call("gom_stem_conv_pool_f32", _p(x), _p(pl), pl.stride(0), pl.stride(1), _p(w.inv_scale), _p(scale), _p(shift), _p(y), B, H,
+          Wd, _p(range_flag(x.device)), _stream())
     return y
 
 
@@ -1897,24 +1858,23 @@ def maxpool3x3s2(x):
     B, H, W, C = x.shape
     OH, OW = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
     y = torch.empty((B, OH, OW, C), dtype=_f32, device=x.device)
-    check(_L().gom_maxpool3x3s2_nhwc_f32(_p(x), _p(y), B, H, W, C, _stream()), "gom_maxpool3x3s2")
+    _call("gom_maxpool3x3s2_nhwc_f32", _p(x), _p(y), B, H, W, C, _stream())
     return y
 
 
 def pos_encoding_into(dim_t, level_embed_row, out_view, H, W, valid_hw=None):
     if valid_hw is not None:
-        check(_L().gom_pos_encoding_2d_valid_f32(_p(dim_t), _p(level_embed_row), _p(out_view), H, W, int(valid_hw[0]),
-                                                 int(valid_hw[1]), _stream()), "gom_pos_encoding_2d_valid_f32")
+        _call("gom_pos_encoding_2d_valid_f32", _p(dim_t), _p(level_embed_row), _p(out_view), H, W, int(valid_hw[0]),
+              int(valid_hw[1]), _stream())
         return
-    check(_L().gom_pos_encoding_2d_f32(_p(dim_t), _p(level_embed_row), _p(out_view), H, W, _stream()),
-          "gom_pos_encoding_2d_f32")
+    _call("gom_pos_encoding_2d_f32", _p(dim_t), _p(level_embed_row), _p(out_view), H, W, _stream())
 
 
 def point_pos_embed(pts, dim_t):
     _chk_f32(pts, dim_t)
     Q = pts.numel() // 2
     out = torch.empty((Q, 256), dtype=_f32, device=pts.device)
-    check(_L().gom_point_pos_embed_f32(_p(pts), _p(dim_t), _p(out), Q, _stream()), "gom_point_pos_embed_f32")
+    _call("gom_point_pos_embed_f32", _p(pts), _p(dim_t), _p(out), Q, _stream())
     return out
 
 
@@ -1922,8 +1882,7 @@ def ref_sigmoid(delta, ref, C):
     _chk_f32(ref)
     Q = ref.numel() // 2
     out = torch.empty((Q, C), dtype=_f32, device=ref.device)
-    check(_L().gom_ref_sigmoid_f32(_p(delta), delta.stride(0), _p(ref), _p(out), Q, C, _stream()),
-          "gom_ref_sigmoid_f32")
+    _call("gom_ref_sigmoid_f32", _p(delta), delta.stride(0), _p(ref), _p(out), Q, C, _stream())
     return out
 
 
@@ -1947,30 +1906,29 @@ def ref_update(h, last, ref, dim_t, scale=None, want_pos=True, frame_scales=None
         if B <= 0 or Q % B:
             raise _lib_mod.GomError("frame_scales: %d points do not divide into %s frames" % (Q, B))
         _chk_frame_desc(frame_scales, B, (2,), _f32, "frame_scales")
-        check(_L().gom_ref_update_frames_f32(_p(h), _ld(h), _p(W3), _p(b3), _p(ref), _p(dim_t), _p(frame_scales), Q // B,
-                                             _p(new_ref), _p(pos), Q, _stream()), "gom_ref_update_frames_f32")
+        _call("gom_ref_update_frames_f32", _p(h), _ld(h), _p(W3), _p(b3), _p(ref), _p(dim_t), _p(frame_scales), Q // B, _p(new_ref),
+              _p(pos), Q, _stream())
         return new_ref, pos
     sx, sy = scale if scale is not None else (1.0, 1.0)
-    check(_L().gom_ref_update_f32(_p(h), _ld(h), _p(W3), _p(b3), _p(ref), _p(dim_t), float(sx), float(sy),
-                                  _p(new_ref), _p(pos), Q, _stream()), "gom_ref_update_f32")
+    _call("gom_ref_update_f32", _p(h), _ld(h), _p(W3), _p(b3), _p(ref), _p(dim_t), float(sx), float(sy), _p(new_ref), _p(pos), Q,
+          _stream())
     return new_ref, pos
 
 
 def proposal_valid(shapes, lsi, S, vshapes=None):
     out = torch.empty((S,), dtype=torch.uint8, device=shapes.device)
     if vshapes is not None:
-        check(_L().gom_proposal_valid_masked(_p(shapes), _p(lsi), shapes.shape[0], _p(vshapes), _p(out), S, _stream()),
-              "gom_proposal_valid_masked")
+        _call("gom_proposal_valid_masked", _p(shapes), _p(lsi), shapes.shape[0], _p(vshapes), _p(out), S, _stream())
         return out
-    check(_L().gom_proposal_valid(_p(shapes), _p(lsi), shapes.shape[0], _p(out), S, _stream()), "gom_proposal_valid")
+    _call("gom_proposal_valid", _p(shapes), _p(lsi), shapes.shape[0], _p(out), S, _stream())
     return out
 
 
 def zero_padded_tokens_(buf, col0, ncols, shapes, lsi, vshapes, B, S):
     """buf [B*S, ld]: zero columns [col0, col0+ncols) of the tokens outside their level's valid region."""
     _chk_f32(buf)
-    check(_L().gom_zero_padded_tokens_f32(_p(buf), buf.stride(0), col0, ncols, _p(shapes), _p(lsi), _p(vshapes),
-                                          shapes.shape[0], B, S, _stream()), "gom_zero_padded_tokens_f32")
+    _call("gom_zero_padded_tokens_f32", _p(buf), buf.stride(0), col0, ncols, _p(shapes), _p(lsi), _p(vshapes), shapes.shape[0], B,
+          S, _stream())
     return buf
 
 
@@ -1978,8 +1936,8 @@ def zero_padded_tokens_frames_(buf, col0, ncols, shapes, lsi, frame_vshapes, B, 
     """`zero_padded_tokens_` with frame tok // S's valid extents: frame_vshapes [B,L,2] int64."""
     _chk_f32(buf)
     _chk_frame_desc(frame_vshapes, B, (shapes.shape[0], 2), torch.int64, "frame_vshapes")
-    check(_L().gom_zero_padded_tokens_frames_f32(_p(buf), buf.stride(0), col0, ncols, _p(shapes), _p(lsi), _p(frame_vshapes),
-                                                 shapes.shape[0], B, S, _stream()), "gom_zero_padded_tokens_frames_f32")
+    _call("gom_zero_padded_tokens_frames_f32", _p(buf), buf.stride(0), col0, ncols, _p(shapes), _p(lsi), _p(frame_vshapes),
+          shapes.shape[0], B, S, _stream())
     return buf
 
 
@@ -1995,19 +1953,17 @@ def padded_geometry(dim_t, level_embed, shapes, lsi, frame_vshapes, B, S):
     lvl_pos = torch.empty((B, S, 256), dtype=_f32, device=dev)
     ref = torch.empty((B, S, 2), dtype=_f32, device=dev)
     valid = torch.empty((B, S), dtype=torch.uint8, device=dev)
-    check(_L().gom_padded_geometry_f32(_p(dim_t), _p(level_embed), _p(shapes), _p(lsi), _p(frame_vshapes), L, B, S, _p(lvl_pos),
-                                       _p(ref), _p(valid), _stream()), "gom_padded_geometry_f32")
+    _call("gom_padded_geometry_f32", _p(dim_t), _p(level_embed), _p(shapes), _p(lsi), _p(frame_vshapes), L, B, S, _p(lvl_pos),
+          _p(ref), _p(valid), _stream())
     return lvl_pos, ref, valid
 
 
 def encoder_reference_points(shapes, lsi, S, vshapes=None):
     out = torch.empty((S, 2), dtype=_f32, device=shapes.device)
     if vshapes is not None:
-        check(_L().gom_encoder_reference_points_masked(_p(shapes), _p(lsi), _p(vshapes), shapes.shape[0], _p(out), S,
-                                                       _stream()), "gom_encoder_reference_points_masked")
+        _call("gom_encoder_reference_points_masked", _p(shapes), _p(lsi), _p(vshapes), shapes.shape[0], _p(out), S, _stream())
         return out
-    check(_L().gom_encoder_reference_points(_p(shapes), _p(lsi), shapes.shape[0], _p(out), S, _stream()),
-          "gom_encoder_reference_points")
+    _call("gom_encoder_reference_points", _p(shapes), _p(lsi), shapes.shape[0], _p(out), S, _stream())
     return out
 
 
@@ -2019,25 +1975,22 @@ def bezier_reference_points(coord_raw, topk_idx, shapes, lsi, bern, B, S, nq, P,
     if frame_vshapes is not None:
         assert vshapes is None, "vshapes and frame_vshapes are exclusive"
         _chk_frame_desc(frame_vshapes, B, (shapes.shape[0], 2), torch.int64, "frame_vshapes")
-        check(_L().gom_bezier_reference_points_frames(_p(coord_raw), _p(topk_idx), _p(shapes), _p(lsi), _p(frame_vshapes),
-                                                      shapes.shape[0], _p(bern), _p(out), B, S, nq, P,
-                                                      1 if compact else 0, _stream()), "gom_bezier_reference_points_frames")
+        _call("gom_bezier_reference_points_frames", _p(coord_raw), _p(topk_idx), _p(shapes), _p(lsi), _p(frame_vshapes),
+              shapes.shape[0], _p(bern), _p(out), B, S, nq, P, 1 if compact else 0, _stream())
         return out
     if vshapes is not None:
-        check(_L().gom_bezier_reference_points_masked(_p(coord_raw), _p(topk_idx), _p(shapes), _p(lsi), _p(vshapes),
-                                                      shapes.shape[0], _p(bern), _p(out), B, S, nq, P,
-                                                      1 if compact else 0, _stream()), "gom_bezier_reference_points_masked")
+        _call("gom_bezier_reference_points_masked", _p(coord_raw), _p(topk_idx), _p(shapes), _p(lsi), _p(vshapes), shapes.shape[0],
+              _p(bern), _p(out), B, S, nq, P, 1 if compact else 0, _stream())
         return out
-    check(_L().gom_bezier_reference_points(_p(coord_raw), _p(topk_idx), _p(shapes), _p(lsi), shapes.shape[0],
-                                           _p(bern), _p(out), B, S, nq, P, 1 if compact else 0, _stream()),
-          "gom_bezier_reference_points")
+    _call("gom_bezier_reference_points", _p(coord_raw), _p(topk_idx), _p(shapes), _p(lsi), shapes.shape[0], _p(bern), _p(out), B, S,
+          nq, P, 1 if compact else 0, _stream())
     return out
 
 
 def scale_xy_(x, sx, sy):
     """In-place scaling of interleaved (x, y) pairs of a contiguous tensor."""
     _chk_f32(x)
-    check(_L().gom_scale_xy_f32(_p(x), x.numel() // 2, float(sx), float(sy), _stream()), "gom_scale_xy_f32")
+    _call("gom_scale_xy_f32", _p(x), x.numel() // 2, float(sx), float(sy), _stream())
     return x
 
 
@@ -2049,7 +2002,7 @@ def scale_xy_frames_(x, frame_scales):
     if B <= 0 or n % B:
         raise _lib_mod.GomError("frame_scales: %d pairs do not divide into %s frames" % (n, B))
     _chk_frame_desc(frame_scales, B, (2,), _f32, "frame_scales")
-    check(_L().gom_scale_xy_frames_f32(_p(x), n, _p(frame_scales), n // B, _stream()), "gom_scale_xy_frames_f32")
+    _call("gom_scale_xy_frames_f32", _p(x), n, _p(frame_scales), n // B, _stream())
     return x
 
 
@@ -2057,21 +2010,21 @@ def copy_words(src, dst):
     """dst <- src over 32-bit words by a kernel (src: pinned host tensor or device tensor of the same byte size)."""
     nbytes = src.numel() * src.element_size()
     assert nbytes == dst.numel() * dst.element_size() and nbytes % 4 == 0 and src.is_contiguous() and dst.is_contiguous()
-    check(_L().gom_copy_words(src.data_ptr(), dst.data_ptr(), nbytes // 4, _stream()), "gom_copy_words")
+    _call("gom_copy_words", src.data_ptr(), dst.data_ptr(), nbytes // 4, _stream())
     return dst
 
 
 def add(a, b):
     _chk_f32(a, b)
     out = torch.empty_like(a)
-    check(_L().gom_add_f32(_p(a), _p(b), _p(out), a.numel(), _stream()), "gom_add_f32")
+    _call("gom_add_f32", _p(a), _p(b), _p(out), a.numel(), _stream())
     return out
 
 
 def broadcast_rows(src, B):
     _chk_f32(src)
     out = torch.empty((B,) + tuple(src.shape), dtype=_f32, device=src.device)
-    check(_L().gom_broadcast_rows_f32(_p(src), _p(out), src.numel(), B, _stream()), "gom_broadcast_rows_f32")
+    _call("gom_broadcast_rows_f32", _p(src), _p(out), src.numel(), B, _stream())
     return out
 
 
@@ -2085,18 +2038,18 @@ def topk_tokens(logits, B, S, k, valid=None, invalid_logit=None, with_rows=False
     if frame_valid is not None:
         assert valid is None, "valid and frame_valid are exclusive"
         _chk_frame_desc(frame_valid, B, (S,), torch.uint8, "frame_valid")
-        check(_L().gom_topk_tokens_frames(_p(logits), logits.stride(0), _p(frame_valid), _p(invalid_logit), B, S, k, _p(ws),
-                                          _p(idx), _p(rows), _stream()), "gom_topk_tokens_frames")
+        _call("gom_topk_tokens_frames", _p(logits), logits.stride(0), _p(frame_valid), _p(invalid_logit), B, S, k, _p(ws), _p(idx),
+              _p(rows), _stream())
         return (idx, rows) if with_rows else idx
-    check(_L().gom_topk_tokens(_p(logits), logits.stride(0), _p(valid), _p(invalid_logit), B, S, k, _p(ws), _p(idx),
-                               _p(rows), _stream()), "gom_topk_tokens")
+    _call("gom_topk_tokens", _p(logits), logits.stride(0), _p(valid), _p(invalid_logit), B, S, k, _p(ws), _p(idx), _p(rows),
+          _stream())
     return (idx, rows) if with_rows else idx
 
 
 def argmax_rows(x):
     rows, V = x.shape
     out = torch.empty((rows,), dtype=torch.int32, device=x.device)
-    check(_L().gom_argmax_rows_f32(_p(x), x.stride(0), V, rows, _p(out), _stream()), "gom_argmax_rows_f32")
+    _call("gom_argmax_rows_f32", _p(x), x.stride(0), V, rows, _p(out), _stream())
     return out
 
 
@@ -2119,17 +2072,13 @@ def detect_post(cls, recls, ctrl, bd, recs, B, nq, P, img_h, img_w, det_thr, nms
     if frame_sizes is not None:
         assert img_h is None and img_w is None, "img_h / img_w and frame_sizes are exclusive"
         _chk_frame_desc(frame_sizes, B, (2,), _f32, "frame_sizes")
-        check(_L().gom_detect_post_sizes(_p(cls), cls.stride(0), _p(recls), recls.stride(0) if recls is not None else 0,
-                                         _p(ctrl), _p(bd), _p(recs), B, nq, P, _p(frame_sizes), float(det_thr),
-                                         float(nms_thr), float(asso_thr), _p(out["count"]), _p(out["keep_idx"]),
-                                         _p(out["scores"]), _p(out["boxes"]), _p(out["ctrl"]), _p(out["bd"]), _p(out["recs"]),
-                                         _stream()), "gom_detect_post_sizes")
+        _call("gom_detect_post_sizes", _p(cls), cls.stride(0), _p(recls), recls.stride(0) if recls is not None else 0, _p(ctrl),
+              _p(bd), _p(recs), B, nq, P, _p(frame_sizes), float(det_thr), float(nms_thr), float(asso_thr), _p(out["count"]),
+              _p(out["keep_idx"]), _p(out["scores"]), _p(out["boxes"]), _p(out["ctrl"]), _p(out["bd"]), _p(out["recs"]), _stream())
         return out
-    check(_L().gom_detect_post(_p(cls), cls.stride(0), _p(recls), recls.stride(0) if recls is not None else 0,
-                               _p(ctrl), _p(bd), _p(recs), B, nq, P, float(img_h), float(img_w), float(det_thr),
-                               float(nms_thr), float(asso_thr), _p(out["count"]), _p(out["keep_idx"]),
-                               _p(out["scores"]), _p(out["boxes"]), _p(out["ctrl"]), _p(out["bd"]), _p(out["recs"]),
-                               _stream()), "gom_detect_post")
+    _call("gom_detect_post", _p(cls), cls.stride(0), _p(recls), recls.stride(0) if recls is not None else 0, _p(ctrl), _p(bd),
+          _p(recs), B, nq, P, float(img_h), float(img_w), float(det_thr), float(nms_thr), float(asso_thr), _p(out["count"]),
+          _p(out["keep_idx"]), _p(out["scores"]), _p(out["boxes"]), _p(out["ctrl"]), _p(out["bd"]), _p(out["recs"]), _stream())
     return out
 
 
@@ -2145,14 +2094,13 @@ def layernorm_any(x, gamma, beta, eps=1e-5):
     _chk_f32(x, gamma, beta)
     D = x.shape[-1]
     out = torch.empty_like(x)
-    check(_L().gom_layernorm_any_f32(_p(x), _p(gamma), _p(beta), _p(out), x.numel() // D, D, eps, _stream()),
-          "gom_layernorm_any_f32")
+    _call("gom_layernorm_any_f32", _p(x), _p(gamma), _p(beta), _p(out), x.numel() // D, D, eps, _stream())
     return out
 
 
 def gelu_(x):
     _chk_f32(x)
-    check(_L().gom_gelu_f32(_p(x), x.numel(), _stream()), "gom_gelu_f32")
+    _call("gom_gelu_f32", _p(x), x.numel(), _stream())
     return x
 
 
@@ -2162,7 +2110,7 @@ def swin_patchify(img):
     B, H, W, _ = img.shape
     Hp, Wp = (H + 3) // 4, (W + 3) // 4
     out = torch.empty((B * Hp * Wp, 64), dtype=_f32, device=img.device)
-    check(_L().gom_swin_patchify_f32(_p(img), _p(out), B, H, W, _stream()), "gom_swin_patchify_f32")
+    _call("gom_swin_patchify_f32", _p(img), _p(out), B, H, W, _stream())
     return out, Hp, Wp
 
 
@@ -2171,7 +2119,7 @@ def swin_window_gather(x, B, H, W, shift):
     C = x.shape[-1]
     Hp, Wp = (H + 6) // 7 * 7, (W + 6) // 7 * 7
     out = torch.empty((B * Hp * Wp, C), dtype=_f32, device=x.device)
-    check(_L().gom_swin_window_gather_f32(_p(x), _p(out), B, H, W, C, shift, _stream()), "gom_swin_window_gather_f32")
+    _call("gom_swin_window_gather_f32", _p(x), _p(out), B, H, W, C, shift, _stream())
     return out
 
 
@@ -2179,8 +2127,7 @@ def swin_window_scatter_add(windows, shortcut, B, H, W, shift):
     _chk_f32(windows, shortcut)
     C = shortcut.shape[-1]
     out = torch.empty_like(shortcut)
-    check(_L().gom_swin_window_scatter_add_f32(_p(windows), _p(shortcut), _p(out), B, H, W, C, shift, _stream()),
-          "gom_swin_window_scatter_add_f32")
+    _call("gom_swin_window_scatter_add_f32", _p(windows), _p(shortcut), _p(out), B, H, W, C, shift, _stream())
     return out
 
 
@@ -2189,7 +2136,7 @@ def swin_patch_merge(x, B, H, W):
     C = x.shape[-1]
     H2, W2 = (H + 1) // 2, (W + 1) // 2
     out = torch.empty((B * H2 * W2, 4 * C), dtype=_f32, device=x.device)
-    check(_L().gom_swin_patch_merge_f32(_p(x), _p(out), B, H, W, C, _stream()), "gom_swin_patch_merge_f32")
+    _call("gom_swin_patch_merge_f32", _p(x), _p(out), B, H, W, C, _stream())
     return out, H2, W2
 
 
@@ -2197,8 +2144,8 @@ def swin_window_attention(qkv, bias, mask, windows_per_image, heads):
     _chk_f32(qkv, bias, mask)
     C = qkv.shape[1] // 3
     out = torch.empty((qkv.shape[0], C), dtype=_f32, device=qkv.device)
-    check(_L().gom_swin_window_attention_f32(_p(qkv), _p(out), _p(bias), _p(mask), qkv.shape[0] // 49, windows_per_image,
-                                             heads, C, _stream()), "gom_swin_window_attention_f32")
+    _call("gom_swin_window_attention_f32", _p(qkv), _p(out), _p(bias), _p(mask), qkv.shape[0] // 49, windows_per_image, heads, C,
+          _stream())
     return out
 
 
@@ -2210,8 +2157,7 @@ def im2col(x, KH, KW, stride, pad, dilation, ldo):
     OH = (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1
     OW = (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
     out = torch.empty((B * OH * OW, ldo), dtype=_f32, device=x.device)
-    check(_L().gom_im2col_nhwc_f32(_p(x), _p(out), B, H, W, C, KH, KW, stride, pad, dilation, ldo, _stream()),
-          "gom_im2col_nhwc_f32")
+    _call("gom_im2col_nhwc_f32", _p(x), _p(out), B, H, W, C, KH, KW, stride, pad, dilation, ldo, _stream())
     return out, OH, OW
 
 
@@ -2225,14 +2171,14 @@ def grouped_conv3x3(x, w, scale, shift, groups, stride=1, silu=False, R=None):
     y = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, Cout), dtype=_f32, device=x.device)
     if R is not None:
         assert R.numel() == y.numel()
-    check(_L().gom_grouped_conv3x3_nhwc_f32(_p(x), _p(w), _p(scale), _p(shift), _p(R), 3 if silu else 0, _p(y), B, H, W,
-                                            Cin, Cout, groups, stride, _stream()), "gom_grouped_conv3x3_nhwc_f32")
+    _call("gom_grouped_conv3x3_nhwc_f32", _p(x), _p(w), _p(scale), _p(shift), _p(R), 3 if silu else 0, _p(y), B, H, W, Cin, Cout,
+          groups, stride, _stream())
     return y
 
 
 def silu_(x):
     _chk_f32(x)
-    check(_L().gom_silu_f32(_p(x), x.numel(), _stream()), "gom_silu_f32")
+    _call("gom_silu_f32", _p(x), x.numel(), _stream())
     return x
 
 
@@ -2242,7 +2188,7 @@ def vitae_window_gather(x, B, H, W):
     C = x.shape[-1]
     Hp, Wp = -(-H // 7) * 7, -(-W // 7) * 7
     out = torch.empty((B * Hp * Wp, C), dtype=_f32, device=x.device)
-    check(_L().gom_vitae_window_gather_f32(_p(x), _p(out), B, H, W, C, _stream()), "gom_vitae_window_gather_f32")
+    _call("gom_vitae_window_gather_f32", _p(x), _p(out), B, H, W, C, _stream())
     return out
 
 
@@ -2251,8 +2197,7 @@ def vitae_window_crop(windows, B, H, W, R1=None, R2=None):
     _chk_f32(windows, R1, R2)
     C = windows.shape[-1]
     out = torch.empty((B * H * W, C), dtype=_f32, device=windows.device)
-    check(_L().gom_vitae_window_crop_f32(_p(windows), _p(R1), _p(R2), _p(out), B, H, W, C, _stream()),
-          "gom_vitae_window_crop_f32")
+    _call("gom_vitae_window_crop_f32", _p(windows), _p(R1), _p(R2), _p(out), B, H, W, C, _stream())
     return out
 
 
@@ -2260,23 +2205,21 @@ def vitae_window_attention(qkv, heads):
     _chk_f32(qkv)
     C = qkv.shape[1] // 3
     out = torch.empty((qkv.shape[0], C), dtype=_f32, device=qkv.device)
-    check(_L().gom_vitae_window_attention_f32(_p(qkv), _p(out), qkv.shape[0] // 49, heads, C, _stream()),
-          "gom_vitae_window_attention_f32")
+    _call("gom_vitae_window_attention_f32", _p(qkv), _p(out), qkv.shape[0] // 49, heads, C, _stream())
     return out
 
 
 def softmax_rows_scaled_(x, cols, scale):
     """In place over the first `cols` columns of a 2-D row-strided view."""
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == _f32
-    check(_L().gom_softmax_rows_scaled_f32(_p(x), x.shape[0], cols, x.stride(0), float(scale), _stream()),
-          "gom_softmax_rows_scaled_f32")
+    _call("gom_softmax_rows_scaled_f32", _p(x), x.shape[0], cols, x.stride(0), float(scale), _stream())
     return x
 
 
 def relu_backward(dy, y):
     _chk_f32(dy, y)
     dx = torch.empty_like(dy)
-    check(_L().gom_relu_backward_f32(_p(dy), _p(y), _p(dx), dy.numel(), _stream()), "gom_relu_backward_f32")
+    _call("gom_relu_backward_f32", _p(dy), _p(y), _p(dx), dy.numel(), _stream())
     return dx
 
 
@@ -2284,8 +2227,7 @@ def softmax_rows_backward(P, dP, cols, scale):
     """dS = scale * P * (dP - rowsum(dP * P)) over the first `cols` columns of same-shape row-strided matrices."""
     assert P.shape == dP.shape and P.stride() == dP.stride() and P.stride(1) == 1
     dS = torch.zeros_like(P)
-    check(_L().gom_softmax_rows_backward_f32(_p(P), _p(dP), _p(dS), P.shape[0], cols, P.stride(0), float(scale), _stream()),
-          "gom_softmax_rows_backward_f32")
+    _call("gom_softmax_rows_backward_f32", _p(P), _p(dP), _p(dS), P.shape[0], cols, P.stride(0), float(scale), _stream())
     return dS
 
 
@@ -2319,8 +2261,8 @@ def dropout(x, stream, residual=None, out=None):
     rv = None if residual is None else _row_view(residual)
     assert ov.shape == xv.shape and (rv is None or rv.shape == xv.shape)
     ld = lambda t: max(t.stride(0), cols) if rows > 1 else cols
-    check(_L().gom_dropout_f32(_p(xv), ld(xv), _p(rv), 0 if rv is None else ld(rv), _p(ov), ld(ov), rows, cols,
-                               *dropout_args(*stream), _stream()), "gom_dropout_f32")
+    _call("gom_dropout_f32", _p(xv), ld(xv), _p(rv), 0 if rv is None else ld(rv), _p(ov), ld(ov), rows, cols,
+          *dropout_args(*stream), _stream())
     return out
 
 
@@ -2328,8 +2270,7 @@ def relu_backward_scaled(dy, y, scale):
     """dx = y > 0 ? dy * scale : 0 (ReLU's backward behind a dropout whose output y was saved)."""
     _chk_f32(dy, y)
     dx = torch.empty_like(dy)
-    check(_L().gom_relu_backward_scaled_f32(_p(dy), _p(y), _p(dx), dy.numel(), float(scale), _stream()),
-          "gom_relu_backward_scaled_f32")
+    _call("gom_relu_backward_scaled_f32", _p(dy), _p(y), _p(dx), dy.numel(), float(scale), _stream())
     return dx
 
 
@@ -2340,8 +2281,8 @@ def softmax_dropout_rows_(x, cols, scale, stream, elem0=0):
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == _f32
     pd = torch.zeros_like(x)
     assert pd.stride() == x.stride()
-    check(_L().gom_softmax_dropout_rows_f32(_p(x), _p(pd), x.shape[0], cols, x.stride(0), float(scale), int(elem0),
-                                            *dropout_args(*stream), _stream()), "gom_softmax_dropout_rows_f32")
+    _call("gom_softmax_dropout_rows_f32", _p(x), _p(pd), x.shape[0], cols, x.stride(0), float(scale), int(elem0),
+          *dropout_args(*stream), _stream())
     return pd
 
 
@@ -2350,9 +2291,8 @@ def softmax_dropout_rows_backward(P, dPd, cols, scale, stream, elem0=0):
     assert P.shape == dPd.shape and P.stride() == dPd.stride() and P.stride(1) == 1
     dS = torch.zeros_like(P)
     assert dS.stride() == P.stride()
-    check(_L().gom_softmax_dropout_rows_backward_f32(_p(P), _p(dPd), _p(dS), P.shape[0], cols, P.stride(0), float(scale),
-                                                     int(elem0), *dropout_args(*stream), _stream()),
-          "gom_softmax_dropout_rows_backward_f32")
+    _call("gom_softmax_dropout_rows_backward_f32", _p(P), _p(dPd), _p(dS), P.shape[0], cols, P.stride(0), float(scale), int(elem0),
+          *dropout_args(*stream), _stream())
     return dS
 
 
@@ -2370,8 +2310,8 @@ def asso_ce(logits, frame_offsets, gt, want_loss=True, grad_scale=None):
         # no address and the entry refuses a null pointer -- one float stands in for both
         anchor = torch.zeros((1,), dtype=_f32, device=logits.device)
         lp, dp = _p(anchor), (None if dl is None else _p(anchor))
-    check(_L().gom_asso_ce_f32(lp, logits.shape[1] if logits.dim() == 2 else 0, _p(frame_offsets), T, _p(gt), R,
-                               _p(loss), _p(grad_scale), dp, _stream()), "gom_asso_ce_f32")
+    _call("gom_asso_ce_f32", lp, logits.shape[1] if logits.dim() == 2 else 0, _p(frame_offsets), T, _p(gt), R, _p(loss),
+          _p(grad_scale), dp, _stream())
     return loss, dl
 
 
@@ -2379,8 +2319,7 @@ def sigmoid_focal(x, target, alpha, gamma, want_loss=True, want_grad=True):
     _chk_f32(x, target)
     loss = torch.empty_like(x) if want_loss else None
     dx = torch.empty_like(x) if want_grad else None
-    check(_L().gom_sigmoid_focal_f32(_p(x), _p(target), float(alpha), float(gamma), x.numel(), _p(loss), _p(dx), _stream()),
-          "gom_sigmoid_focal_f32")
+    _call("gom_sigmoid_focal_f32", _p(x), _p(target), float(alpha), float(gamma), x.numel(), _p(loss), _p(dx), _stream())
     return loss, dx
 
 
@@ -2409,8 +2348,8 @@ def clipped_adamw_step(rows, beta1, beta2, eps, clip_value, workspace=None, norm
         workspace = torch.empty((max(n, 1),), dtype=_f32, device=dev)
     if norm_out is None or norm_out.device != dev:
         norm_out = torch.empty((2,), dtype=_f32, device=dev)
-    check(_L().gom_clipped_adamw_step(table, len(rows), float(beta1), float(beta2), float(eps), float(clip_value), _p(workspace),
-                                      workspace.numel(), _p(norm_out), _stream()), "gom_clipped_adamw_step")
+    _call("gom_clipped_adamw_step", table, len(rows), float(beta1), float(beta2), float(eps), float(clip_value), _p(workspace),
+          workspace.numel(), _p(norm_out), _stream())
     return norm_out, workspace
 
 
@@ -2418,8 +2357,7 @@ def transpose_into(x, out):
     """out[c, r] = x[r, c] for 2-D row-strided views (out may be wider than x has rows)."""
     assert x.dim() == 2 and out.dim() == 2 and x.stride(1) == 1 and out.stride(1) == 1
     assert out.shape[0] == x.shape[1] and out.shape[1] >= x.shape[0]
-    check(_L().gom_transpose_f32(_p(x), _p(out), x.shape[0], x.shape[1], x.stride(0), out.stride(0), _stream()),
-          "gom_transpose_f32")
+    _call("gom_transpose_f32", _p(x), _p(out), x.shape[0], x.shape[1], x.stride(0), out.stride(0), _stream())
     return out
 
 
@@ -2431,8 +2369,8 @@ def flash_attention(qkv, B, N, heads):
     C = qkv.shape[1] // 3
     out = torch.empty((B * N, C), dtype=_f32, device=qkv.device)
     f = qkv.view(-1)
-    check(_L().gom_flash_attention_f32(_p(f), _p(f[C:]), _p(f[2 * C:]), _p(out), B, N, heads, C // heads, 3 * C, C,
-                                       _p(range_flag(qkv.device)), _stream()), "gom_flash_attention_f32")
+    _call("gom_flash_attention_f32", _p(f), _p(f[C:]), _p(f[2 * C:]), _p(out), B, N, heads, C // heads, 3 * C, C,
+          _p(range_flag(qkv.device)), _stream())
     return out
 
 
@@ -2440,7 +2378,7 @@ def flash_attention(qkv, B, N, heads):
 def gather_rows(src, rows):
     n, D = rows.numel(), src.shape[1]
     out = torch.empty((n, D), dtype=_f32, device=src.device)
-    check(_L().gom_gather_rows_f32(_p(src), _p(rows), _p(out), n, D, _stream()), "gom_gather_rows_f32")
+    _call("gom_gather_rows_f32", _p(src), _p(rows), _p(out), n, D, _stream())
     return out
 
 
@@ -2450,16 +2388,14 @@ def asso_activate(logits, offsets, T, out=None):
     n_k, N = logits.shape
     if out is None:
         out = torch.empty((n_k, N), dtype=_f32, device=logits.device)
-    check(_L().gom_asso_activate_f32(_p(logits), _ld(logits), _p(offsets), T, n_k, _p(out), _ld(out), _stream()),
-          "gom_asso_activate_f32")
+    _call("gom_asso_activate_f32", _p(logits), _ld(logits), _p(offsets), T, n_k, _p(out), _ld(out), _stream())
     return out
 
 
 def track_score(act, meta, decay, boxes, img_w, img_h, n_k, Np, M, with_iou, max_center_dist, out=None):
     traj = torch.empty((n_k, M), dtype=_f32, device=act.device) if out is None else out
-    check(_L().gom_track_score_f32(_p(act), _ld(act), _p(meta), _p(decay), _p(boxes), float(img_w), float(img_h),
-                                   n_k, Np, M, 1 if with_iou else 0, float(max_center_dist), _p(traj), _stream()),
-          "gom_track_score_f32")
+    _call("gom_track_score_f32", _p(act), _ld(act), _p(meta), _p(decay), _p(boxes), float(img_w), float(img_h), n_k, Np, M,
+          1 if with_iou else 0, float(max_center_dist), _p(traj), _stream())
     return traj
 
 
@@ -2467,9 +2403,8 @@ def asso_score(logits, offsets, T, meta, decay, boxes, img_w, img_h, n_k, Np, M,
     """asso_activate + track_score of one match as ONE launch (the form the native matcher runs for N <= 16 384): logits
     [n_k, N = Np + n_k], rows `logits.stride(0)` apart -> traj [n_k, M], the same values as the two launches."""
     traj = torch.empty((n_k, M), dtype=_f32, device=logits.device) if out is None else out
-    check(_L().gom_asso_score_f32(_p(logits), _ld(logits), _p(offsets), T, _p(meta), _p(decay), _p(boxes), float(img_w),
-                                  float(img_h), n_k, Np, M, 1 if with_iou else 0, float(max_center_dist), _p(traj), _stream()),
-          "gom_asso_score_f32")
+    _call("gom_asso_score_f32", _p(logits), _ld(logits), _p(offsets), T, _p(meta), _p(decay), _p(boxes), float(img_w), float(img_h),
+          n_k, Np, M, 1 if with_iou else 0, float(max_center_dist), _p(traj), _stream())
     return traj
 
 
@@ -2479,10 +2414,9 @@ def pack_records(pool, row_base, det, frames, nq, feature_dim, num_points, image
     out = torch.empty((frames, nq + 1, D), dtype=_f32, device=pool.device)
     recs = det["recs"]
     assert recs.dtype == torch.int64 and recs.is_contiguous() and det["ctrl"].is_contiguous() and det["bd"].is_contiguous()
-    check(_L().gom_pack_records_f32(_p(pool), pool.stride(0), int(row_base), _p(det["count"]), _p(det["boxes"]),
-                                    _p(det["scores"]), _p(det["ctrl"]), _p(det["bd"]), _p(recs), frames, nq, feature_dim,
-                                    num_points, float(image_size[0]), float(image_size[1]), _p(out), _stream()),
-          "gom_pack_records_f32")
+    _call("gom_pack_records_f32", _p(pool), pool.stride(0), int(row_base), _p(det["count"]), _p(det["boxes"]), _p(det["scores"]),
+          _p(det["ctrl"]), _p(det["bd"]), _p(recs), frames, nq, feature_dim, num_points, float(image_size[0]), float(image_size[1]),
+          _p(out), _stream())
     return out
 
 
@@ -2493,19 +2427,13 @@ SHORT_TERM_MAX_PREV = 320
 def short_term_pairs(tgt, memory, pairs, row_pair, boxes, img_w, img_h, with_iou, total_rows, max_prev, s_floats, out=None):
     """All pairs' S = max(softmax-with-background(q.k^T), IoU) in one launch; returns the packed fp32 buffer (`out`: a caller's)."""
     S = torch.empty((max(s_floats, 1),), dtype=_f32, device=tgt.device) if out is None else out
-    check(_L().gom_short_term_pairs_f32(_p(tgt), _p(memory), tgt.shape[1], _p(pairs), _p(row_pair), _p(boxes),
-                                        float(img_w), float(img_h), 1 if with_iou else 0, total_rows, max_prev, _p(S),
-                                        _stream()), "gom_short_term_pairs_f32")
+    _call("gom_short_term_pairs_f32", _p(tgt), _p(memory), tgt.shape[1], _p(pairs), _p(row_pair), _p(boxes), float(img_w),
+          float(img_h), 1 if with_iou else 0, total_rows, max_prev, _p(S), _stream())
     return S
 
 
 NATIVE_TRACKER = True      # the per-frame id recurrence of a track_frames call in native code (tracker_rt.hip); False: Python loop
 NATIVE_MATCHER = True      # False: compose the match from per-kernel calls in Python (kept for the A/B parity test)
-
-
-class MatcherLayer(ctypes.Structure):
-    """Mirror of `gom_matcher_layer` (include/gomatching_hip.h)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("in_w", "in_b", "out_w", "out_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b")]
 
 
 def gemm_small_rows(A, W, bias, out):
@@ -2521,15 +2449,15 @@ def gemm_small_rows(A, W, bias, out):
     lda, ldw, ldc = _ld(A), _ld(W), _ld(out)
     for a in range(0, M, step):
         m = min(step, M - a)
-        check(_L().gom_gemm_small_f32(_p(A[a:]), None, lda, _p(W), ldw, None, _p(bias), None, 0, 0, _p(out[a:]), ldc, m, N, K,
-                                      _stream()), "gom_gemm_small_f32")
+        _call("gom_gemm_small_f32", _p(A[a:]), None, lda, _p(W), ldw, None, _p(bias), None, 0, 0, _p(out[a:]), ldc, m, N, K,
+              _stream())
     return out
 
 
 def matcher_layers(layers):
     """layers: list of dicts {"in": (w, b), "out": (w, b), ["lin1": (w, b), "lin2": (w, b)]} of fp32 CUDA tensors ->
     ctypes array for gom_match_scores_f32 (the tensors must outlive it: the caller keeps `layers`)."""
-    arr = (MatcherLayer * max(len(layers), 1))()
+    arr = (_lib_mod.MatcherLayer * max(len(layers), 1))()
     for i, L in enumerate(layers):
         for key in ("in", "out", "lin1", "lin2"):
             w, b = L.get(key, (None, None))
@@ -2547,10 +2475,9 @@ def match_scores(pool, rows, frame_offsets, meta, boxes, decay, N, T, lo, hi, nu
     nws = _L().gom_match_workspace_floats(N, n_k, d, ffn)
     ws = torch.empty((nws,), dtype=_f32, device=pool.device)
     traj = torch.empty((n_k, num_tracks), dtype=_f32, device=pool.device)
-    check(_L().gom_match_scores_f32(_p(pool), pool.stride(0), _p(rows), _p(frame_offsets), _p(meta), _p(boxes),
-                                    _p(decay), N, T, lo, hi, num_tracks, enc, n_enc, dec, n_dec, d, heads, ffn,
-                                    float(img_w), float(img_h), 1 if with_iou else 0, float(max_center_dist), _p(ws),
-                                    nws, _p(traj), _stream()), "gom_match_scores_f32")
+    _call("gom_match_scores_f32", _p(pool), pool.stride(0), _p(rows), _p(frame_offsets), _p(meta), _p(boxes), _p(decay), N, T, lo,
+          hi, num_tracks, enc, n_enc, dec, n_dec, d, heads, ffn, float(img_w), float(img_h), 1 if with_iou else 0,
+          float(max_center_dist), _p(ws), nws, _p(traj), _stream())
     return traj
 
 
@@ -2562,10 +2489,9 @@ def match_scores_proj(pool, proj, rows, frame_offsets, meta, boxes, decay, N, T,
     nws = _L().gom_match_workspace_floats(N, n_k, d, ffn)
     ws = torch.empty((nws,), dtype=_f32, device=pool.device)
     traj = torch.empty((n_k, num_tracks), dtype=_f32, device=pool.device)
-    check(_L().gom_match_scores_proj_f32(_p(pool), pool.stride(0), _p(proj), proj.stride(0), _p(rows), _p(frame_offsets),
-                                         _p(meta), _p(boxes), _p(decay), N, T, lo, hi, num_tracks, enc, n_enc, dec, n_dec, d,
-                                         heads, ffn, float(img_w), float(img_h), 1 if with_iou else 0, float(max_center_dist),
-                                         _p(ws), nws, _p(traj), _stream()), "gom_match_scores_proj_f32")
+    _call("gom_match_scores_proj_f32", _p(pool), pool.stride(0), _p(proj), proj.stride(0), _p(rows), _p(frame_offsets), _p(meta),
+          _p(boxes), _p(decay), N, T, lo, hi, num_tracks, enc, n_enc, dec, n_dec, d, heads, ffn, float(img_w), float(img_h),
+          1 if with_iou else 0, float(max_center_dist), _p(ws), nws, _p(traj), _stream())
     return traj
 
 
