@@ -32,6 +32,11 @@ Deliberate differences:
   * `--lexicon FILE|DIR [--lexicon-pairs FILE] [--lexicon-max-dist N] [--lexicon-unmatched keep|drop]` runs
     `gomatching_amd.lexicon.correct_results` over OUT after the videos are written (those of earlier, resumed runs included)
     and writes OUT/lexicon/{jsons,preds}; without it the command issues the launches and writes the bytes it always did;
+  * `--device-decode` reads file bytes on the pool and decodes baseline JPEG frames on the GPU (csrc/jpeg_decode.hip, byte-equal
+    to Pillow's decode, so the result files do not change), per 100-frame chunk offline and per push with `--online`: host
+    memory holds bytes, device memory one chunk of pixels.  Files with another extension, files `jpeg.parse` refuses and files
+    whose status word is set go through Pillow per file; the run prints the count of every route.  Not with `--host-ingest`
+    (status 2); without a GPU status 1.  With `--show` the drawing step still reads its frames through Pillow;
   * frames are decoded with Pillow (`convert("RGB")`, reversed to the BGR order `read_image(format="BGR")` yields).
     OpenCV is not available here, so the parity of the decoded pixels with `cv2.imread` (JPEG decoders differ in their
     IDCT and chroma upsampling) is UNPINNED, as is the parity of `results.min_area_rect` with `cv2.minAreaRect`.
@@ -74,6 +79,9 @@ def get_parser(drawing=False):
                    help="resize and normalise frames on the host (default: on the GPU, bit-exact with the host path)")
     p.add_argument("--host-rows", action="store_true",
                    help="build result rows per frame on the host (default: one kernel launch and one copy per clip)")
+    p.add_argument("--device-decode", action="store_true",
+                   help="decode baseline JPEG frames on the GPU (the same bytes as Pillow's): the pool reads file bytes, host "
+                        "memory holds no pixels; any other file goes through Pillow, per file (not with --host-ingest)")
     p.add_argument("--online", action="store_true",
                    help="run every video as a stream: frames are decoded one push ahead, rows are written as their tracks "
                         "settle, memory does not grow with the video; the files are the same (not with --show / --host-rows)")
@@ -149,6 +157,71 @@ def read_frame(path):
         return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
 
 
+def read_bytes(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
+DECODE_ROUTES = ("device", "refused", "flagged", "other")
+
+
+def decode_frames(paths, blobs, counts, device):
+    """`--device-decode`: the files' bytes -> one CUDA u8 [H,W,3] tensor per frame, in BGR order as `read_frame` yields.
+    `.jpg` / `.jpeg` files that `jpeg.parse` accepts are decoded on the GPU, one `ops.jpeg_decode` call per geometry (a
+    video's frames share one); a file with another extension ("other"), one the parser refuses ("refused") and one whose
+    status word comes back set ("flagged") go through `read_frame`, per file, and are uploaded beside the others.  `counts`
+    is incremented per route."""
+    import torch
+    from . import jpeg as _jpeg
+    from . import ops
+    out = [None] * len(paths)
+    groups = {}
+    for i, (path, blob) in enumerate(zip(paths, blobs)):
+        if os.path.splitext(path)[1].lower() not in (".jpg", ".jpeg"):
+            counts["other"] += 1
+            continue
+        info = _jpeg.parse(blob)
+        if isinstance(info, _jpeg.Refusal):
+            counts["refused"] += 1
+            continue
+        groups.setdefault(info.key, []).append((i, info))
+    for items in groups.values():
+        pixels, status = ops.jpeg_decode(_jpeg.plan([blobs[i] for i, _ in items], [info for _, info in items]), True, device)
+        status = status.cpu().numpy()
+        for j, (i, _) in enumerate(items):
+            if status[j] == 0:
+                out[i] = pixels[j]
+                counts["device"] += 1
+            else:
+                counts["flagged"] += 1
+    for i, path in enumerate(paths):
+        if out[i] is None:                                 # Pillow raises or decodes exactly as without the flag
+            out[i] = torch.from_numpy(read_frame(path)).to(device)
+    return out
+
+
+def spot_video_device_decode(spotter, pool, paths, time_cost, counts, device, batch=100):
+    """`results.spot_video` for `--device-decode`: the pool reads the bytes of one chunk ahead, the chunk's frames are decoded
+    into device memory and go to the predictor as they are.  Host memory holds file bytes only, device memory one chunk of
+    pixels.  -> (per-frame results, seconds inside the timed window, seconds reading and decoding)."""
+    chunks = [paths[i:i + batch] for i in range(0, len(paths), batch)]
+    instances, id_count, seconds, read = [], 0, 0.0, 0.0
+    ahead = [pool.submit(read_bytes, p) for p in chunks[0]]
+    for batch_id, chunk in enumerate(chunks):
+        t0 = time.time()
+        blobs = [f.result() for f in ahead]
+        ahead = [pool.submit(read_bytes, p) for p in chunks[batch_id + 1]] if batch_id + 1 < len(chunks) else []
+        frames = decode_frames(chunk, blobs, counts, device)
+        del blobs
+        read += time.time() - t0
+        instances, id_count, dt = spotter(frames, instances, batch_id, id_count, batch_id == len(chunks) - 1, time_cost,
+                                          return_time=True)
+        del frames
+        seconds += dt
+        time_cost["total_time"] += dt
+    return instances, seconds, read
+
+
 def load_weights(path):
     """-> canonical state dict, or None when `path` is empty or no file."""
     if not path or not os.path.isfile(path):
@@ -158,7 +231,7 @@ def load_weights(path):
     return normalize_state_dict(torch.load(path, map_location="cpu"))
 
 
-def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost):
+def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, counts=None):
     """One video through `online.OnlineSpotter`: the pool decodes one push ahead, rows go to the incremental writer as they
     settle.  -> seconds reading / inside the timed window / building rows and writing, and the session's wait figures."""
     from .online import OnlineSpotter
@@ -169,12 +242,15 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
     writer = _results.VideoResultWriter(video_name, data_type, args.output)
     read, write = 0.0, 0.0
     chunks = [paths[i:i + push] for i in range(0, len(paths), push)]
+    reader = read_bytes if counts is not None else read_frame      # --device-decode: bytes ahead, pixels made on the GPU
     try:
-        ahead = [pool.submit(read_frame, p) for p in chunks[0]]
+        ahead = [pool.submit(reader, p) for p in chunks[0]]
         for c in range(len(chunks)):
             t0 = time.time()
             frames = [f.result() for f in ahead]
-            ahead = [pool.submit(read_frame, p) for p in chunks[c + 1]] if c + 1 < len(chunks) else []
+            ahead = [pool.submit(reader, p) for p in chunks[c + 1]] if c + 1 < len(chunks) else []
+            if counts is not None:
+                frames = decode_frames(chunks[c], frames, counts, model.device)
             read += time.time() - t0
             settled = session.push(frames)
             del frames
@@ -216,6 +292,14 @@ def main(argv=None):
     if args.push is not None and (not args.online or args.push < 1):
         sys.stderr.write("error: --push N (N >= 1) goes with --online\n")
         return 2
+    if args.device_decode and args.host_ingest:
+        sys.stderr.write("error: --device-decode leaves the frames in device memory: it does not go with --host-ingest\n")
+        return 2
+    if args.device_decode:
+        import torch
+        if not torch.cuda.is_available():
+            sys.stderr.write("error: --device-decode needs a GPU: the decoder runs in csrc/jpeg_decode.hip\n")
+            return 1
     if (args.config_file is None) == (args.builtin is None):
         sys.stderr.write("error: give exactly one of --config-file and --builtin\n")
         return 2
@@ -258,6 +342,7 @@ def main(argv=None):
         spotter = GoMBatchPredictor(cfg, model, device_ingest=not args.host_ingest)
         decoder = TextDecoder(cfg.MODEL.TRANSFORMER.VOC_SIZE, cfg.MODEL.TRANSFORMER.CUSTOM_DICT)
     total_frame, read_seconds, rows_seconds, draw_seconds = 0, 0.0, 0.0, 0.0
+    routes = {k: 0 for k in DECODE_ROUTES} if args.device_decode else None
     if args.show:
         from . import show as _show
         atlas = _show.Atlas(args.font)
@@ -269,7 +354,7 @@ def main(argv=None):
             if args.online:
                 if not paths:
                     continue
-                stats = spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost)
+                stats = spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, routes)
                 read_seconds += stats["read"]
                 rows_seconds += stats["rows"]
                 total_frame += len(paths)
@@ -278,11 +363,22 @@ def main(argv=None):
                 print("online: largest wait ", stats["max_wait"], " frames (bound ", stats["bound"], "), gather launches ",
                       stats["launches"])
                 continue
-            frames = list(pool.map(read_frame, paths))
-            read_seconds += time.time() - t0
-            if not frames:
-                continue
-            preds, per_video_time = _results.spot_video(spotter, frames, time_cost)
+            if routes is not None:
+                if not paths:
+                    continue
+                preds, per_video_time, read = spot_video_device_decode(spotter, pool, paths, time_cost, routes, model.device)
+                read_seconds += read
+                frames = paths                              # (counted below; the pixels are gone)
+                if args.show:                               # the drawing step takes host frames: read through Pillow, as ever
+                    t0 = time.time()
+                    frames = list(pool.map(read_frame, paths))
+                    read_seconds += time.time() - t0
+            else:
+                frames = list(pool.map(read_frame, paths))
+                read_seconds += time.time() - t0
+                if not frames:
+                    continue
+                preds, per_video_time = _results.spot_video(spotter, frames, time_cost)
             total_frame += len(frames)
             t0 = time.time()
             annotation = _results.write_video(preds, video_name, data_type, args.output, decoder,
@@ -304,6 +400,9 @@ def main(argv=None):
     print(time_cost)
     print("host seconds outside the timed window: reading frames ", read_seconds, ", building rows and writing files ",
           rows_seconds, ", videos processed: ", len(videos))
+    if routes is not None:
+        print("device decode: ", routes["device"], " files decoded on the GPU; through Pillow: ", routes["other"],
+              " with another extension, ", routes["refused"], " refused by the parser, ", routes["flagged"], " with a status word set")
     if args.show:
         print("host seconds drawing and encoding frames: ", draw_seconds)
     if args.lexicon is not None:                            # every video under OUT, those of earlier (resumed) runs included

@@ -1767,6 +1767,43 @@ def jpeg_encode(frames, quality=95, bgr=True):
     return payload[:total], offsets
 
 
+def jpeg_decode(plan, bgr=True, device=None):
+    """Baseline JPEG files -> u8 [F,H,W,3] on the device, four launches (csrc/jpeg_decode.hip; the integer rule is in
+    include/gomatching_hip.h).  `plan` = `jpeg.plan(files)`: the packed entropy bytes, the segment descriptors and the distinct
+    table sets, three uploads.  -> (pixels, status int32 [F] on the device): a frame whose status word is not 0 holds no
+    picture and its file goes through Pillow.  A geometry the decoder refuses raises before any launch."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    F, nseg = int(plan.F), int(plan.desc.shape[0])
+    if F == 0:
+        raise ValueError("no files")
+    geo = (F, int(plan.H), int(plan.W), int(plan.ncomp), int(plan.hs), int(plan.vs))
+    nbytes = _L().gom_jpeg_decode_workspace_bytes(*geo)
+    if nbytes < 0:
+        raise _lib_mod.GomError("gom_jpeg_decode_entropy_i16 refused: GOM_ERR_UNSUPPORTED (%d x %d frames of %d components, "
+                                "sampling %dx%d; at most %d wide and %d high, one component or 4:4:4 / 4:2:2 / 4:2:0, are decoded)"
+                                % (geo[2], geo[1], geo[3], geo[4], geo[5], JPEG_MAX_WIDTH, JPEG_MAX_HEIGHT))
+    if plan.desc.shape != (nseg, _lib_mod.CONSTANTS["GOM_JPEG_DECODE_DESC_WORDS"]) or plan.seg_off.shape != (F + 1,) or \
+            plan.frame_set.shape != (F,) or plan.sets.ndim != 2 or plan.sets.shape[1] != _lib_mod.CONSTANTS["GOM_JPEG_DECODE_SET_WORDS"]:
+        raise ValueError("a plan whose arrays do not fit its frame count")
+    data = np.zeros(((len(plan.data) + 3) // 4 * 4 or 4,), dtype=np.uint8)          # whole words, and never empty
+    data[:len(plan.data)] = plan.data
+    small = np.concatenate([plan.seg_off.astype(np.int32), plan.frame_set.astype(np.int32),
+                            np.ascontiguousarray(plan.sets, dtype=np.int32).reshape(-1)])
+    data_d = torch.from_numpy(data).to(dev)
+    desc_d = torch.from_numpy(np.ascontiguousarray(plan.desc, dtype=np.int64)).to(dev)
+    small_d = torch.from_numpy(small).to(dev)
+    seg_off, frame_set, sets = small_d[:F + 1], small_d[F + 1:2 * F + 1], small_d[2 * F + 1:]
+    nsets = int(plan.sets.shape[0])
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    status = torch.empty((nseg + F,), dtype=torch.int32, device=dev)
+    out = torch.empty((F, geo[1], geo[2], 3), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _call("gom_jpeg_decode_entropy_i16", _p(data_d), len(plan.data), _p(desc_d), nseg, _p(seg_off), _p(sets), nsets, *geo,
+              _p(ws), nbytes, _p(status[:nseg]), _p(status[nseg:]), _stream())
+        _call("gom_jpeg_decode_pixels_u8", _p(sets), nsets, _p(frame_set), *geo, 1 if bgr else 0, _p(ws), nbytes, _p(out), _stream())
+    return out, status[nseg:]
+
+
 def mask_outline_polygons(points, contour_off, mask_coff, boxes, word_off, H, W, words, sel=None):
     """`mask_fill_polygons` for the outlines alone (csrc/overlay.hip): writes Boundary of the rasterisation rule, without
     Fill and without areas, into `words` (int32 [nwords]) for every mask, or for the masks `sel` names.  -> words."""

@@ -79,7 +79,7 @@ class GoMBatchPredictor:
         inputs = []
         for x in original_frames:
             h, w = x.shape[:2]
-            t = torch.as_tensor(np.ascontiguousarray(x))
+            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))   # (a tensor: decoded on the device)
             if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
                 raise ValueError("frames must be HxWx3 uint8 arrays")
             inputs.append({"frame_u8": t, "resize_hw": resized_shape(h, w, self.min_size, self.max_size),

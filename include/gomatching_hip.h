@@ -848,6 +848,78 @@ int gom_jpeg_encode_scan_u8(const uint8_t* frames, int F, int H, int W, int bgr,
                             long workspace_bytes, int64_t* frame_off, void* stream);
 int gom_jpeg_encode_pack_u8(const void* workspace, long workspace_bytes, int F, int H, int W, long total, uint8_t* payload,
                             long payload_bytes, void* stream);
+/* ---- JPEG decoding of source frames (csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h; gomatching_amd/jpeg.py; eval --device-decode)
+ * File bytes go up, u8 [F,H,W,3] pixels stay in HBM.  THE RULE, in integers only, is libjpeg's published arithmetic, so that the
+ * kernels, the numpy path (jpeg.decode_host), the plain-Python statement (tests/jpeg_decode_statement.py) and Pillow's
+ * `Image.open(p).convert("RGB")` (libjpeg-turbo: the `islow` IDCT, fancy upsampling) agree byte for byte.  `>>` is the
+ * arithmetic shift (floor).
+ *   Accepted  : SOF0, 8 bits; one component (sampling 1x1), or three components Y Cb Cr (a JFIF marker, or an Adobe marker with
+ *               transform 1, or neither and component ids 1, 2, 3) with luminance sampling (h, v) in {(1,1), (2,1), (2,2)} and
+ *               chrominance (1,1); one interleaved scan (Ss 0, Se 63, Ah Al 0); 8-bit DQT; DC and AC Huffman tables 0 and 1 of any
+ *               content (DC categories up to 11); any DRI; width up to GOM_JPEG_MAX_WIDTH, height up to 65535.
+ *   Refused   : by jpeg.parse on the host, with a reason, before anything is uploaded: SOF1 / SOF2 / lossless / arithmetic
+ *               coding, 12 bits, four components, another Adobe transform, any other sampling, several scans, DNL, 16-bit
+ *               quantisation tables, a table the scan names but no segment defines, a header cut short.  Pillow reads those.
+ *   Geometry  : an MCU is h x v luminance blocks (left to right, top to bottom), then Cb, then Cr; MW = ceil(W / 8h) MCUs a row,
+ *               MH = ceil(H / 8v) rows.  Component c has a grid of (MH v_c) x (MW h_c) blocks; coefficients are int16
+ *               [frame][component][block of the grid, row-major][64] in natural (row-major) order, planes are u8 of 8 x the grid.
+ *   Segments  : the host cuts the entropy-coded segment at every 0xFF 0xD0..0xD7 (a vectorised scan).  Segment s of a frame
+ *               holds MCUs [s R, min((s + 1) R, MH MW)) for restart interval R (one segment without DRI) and must be followed
+ *               by RSTn with n = s mod 8, the last one by the end of the scan.  Predictors start at 0 in every segment.
+ *   Bits      : bytes fill a 32-bit accumulator from the most significant bit; 0xFF 0x00 is the byte 0xFF; any other 0xFF, or
+ *               the segment's end, ends the data: zero bits follow, and taking one of them is status 1.
+ *   Walk      : per block the DC category (Huffman), its amplitude bits (a value v of s bits with its top bit clear is
+ *               v - 2^s + 1), the predictor's sum wrapped to 16 bits; then k = 1: a symbol RS, R = RS >> 4, S = RS & 15:
+ *               S > 0: k += R, k > 63 is status 3, else coefficient zigzag[k] = the amplitude, k += 1; S = 0 and R = 15: k += 16
+ *               (k > 63 is status 3); S = 0 otherwise: end of block.  A Huffman code is looked up by its first 8 bits, longer ones
+ *               by length against the largest code of each length; no code of 16 bits or fewer is status 2.
+ *   Status    : per segment 0 = clean, else the first that happened of 1 ran past the segment, 2 invalid code (or a DC category
+ *               above 11), 3 coefficient index above 63; a segment walked cleanly is then 5 when whole bytes are left over,
+ *               else 4 when the RSTn behind it is wrong or missing (or bytes follow the last segment).  The frame's word is that
+ *               of its first segment that is not clean.  The caller sends a flagged file through Pillow.
+ *   Dequantise: coefficient x its quantiser (natural order).
+ *   IDCT      : jidctint.c, CONST_BITS 13, PASS1_BITS 2, constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995
+ *               25172 (FIX(0.298631336) .. FIX(3.072711026)).  One pass over d0 .. d7:
+ *                 z1 = (d2 + d6) 4433; t2 = z1 - d6 15137; t3 = z1 + d2 6270; t0 = (d0 + d4) << 13; t1 = (d0 - d4) << 13
+ *                 e0 = t0 + t3; e3 = t0 - t3; e1 = t1 + t2; e2 = t1 - t2
+ *                 o0 = d7; o1 = d5; o2 = d3; o3 = d1; z1 = o0 + o3; z2 = o1 + o2; z3 = o0 + o2; z4 = o1 + o3; z5 = (z3 + z4) 9633
+ *                 o0 *= 2446; o1 *= 16819; o2 *= 25172; o3 *= 12299; z1 *= -7373; z2 *= -20995; z3 = z5 - z3 16069; z4 = z5 - z4 3196
+ *                 o0 += z1 + z3; o1 += z2 + z4; o2 += z2 + z3; o3 += z1 + z4
+ *                 out 0..7 = e0 + o3, e1 + o2, e2 + o1, e3 + o0, e3 - o0, e2 - o1, e1 - o2, e0 - o3, each (x + 2^(n-1)) >> n
+ *               down the columns with n = 11, then along the rows with n = 18; sample = clamp(value + 128, 0, 255).  (libjpeg's
+ *               shortcut for a column without AC terms gives the same value.)  32-bit accumulators.
+ *   Upsample  : a chrominance plane has ch = ceil(H / v) rows of cw = ceil(W / h) real samples.  h = 1: none.  cw <= 2:
+ *               replication (libjpeg switches the triangle filter off there).  Otherwise, with c the sample over the pixel
+ *               (row y >> 1 for v = 2, column x >> 1) and the neighbour index clamped into the real samples:
+ *                 h2v1: odd x: (3 c + right + 2) >> 2, even x: (3 c + left + 1) >> 2
+ *                 h2v2: s(column) = 3 c + (the row below for odd y, above for even y); odd x: (3 s + s(right) + 7) >> 4,
+ *                       even x: (3 s + s(left) + 8) >> 4
+ *   Colour    : with cb = Cb - 128, cr = Cr - 128: R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768)
+ *               >> 16), B = Y + ((116130 cb + 32768) >> 16), each clamped to 0 .. 255.  One component: R = G = B = Y.
+ * What the host uploads (jpeg.plan): the files' entropy bytes packed; per segment GOM_JPEG_DECODE_DESC_WORDS int64: first byte,
+ * end (the marker excluded), the end of its frame's bytes, first MCU, MCUs, frame, table set, the RSTn byte expected behind it
+ * (0: the frame's end); seg_off int32 [F+1]; the distinct table sets, GOM_JPEG_DECODE_SET_WORDS int32 each: four Huffman
+ * tables (DC 0, DC 1, AC 0, AC 1) of 548 words (look[256] = length << 8 | symbol by the first 8 bits, maxcode[18], valoff[18],
+ * huffval[256]), the DC table (0, 1) of components 0..3, the AC table (2, 3) of components 0..3, the quantisers [3][64].
+ * All of it is data the device does not trust: every byte read is bounded by the segment's end, every offset, MCU, frame and
+ * table index is checked or clamped before use, every coefficient and block index before the store.
+ *   gom_jpeg_decode_workspace_bytes : coefficients (128 bytes a block) + planes (64 bytes a block), or -1 for sizes it refuses.
+ *   gom_jpeg_decode_entropy_i16     : a wavefront per segment: lane 0 walks the bits into LDS, the 64 lanes store the block's
+ *                                     coefficients as one 128-byte row (which also zero-fills it); then a launch that folds
+ *                                     seg_status int32 [nseg] into frame_status int32 [F].
+ *   gom_jpeg_decode_pixels_u8       : dequantise + IDCT into planes (8 lanes a block), then upsampling + colour into out u8
+ *                                     [F,H,W,3] (bgr = 1: B G R); a thread owns four pixels (three 32-bit words).
+ * No atomics, no scratch, one writer per output byte: bitwise reproducible.  GOM_ERR_UNSUPPORTED before any HIP call: W above
+ * GOM_JPEG_MAX_WIDTH, H above GOM_JPEG_MAX_HEIGHT, components or sampling outside the accepted set.  GOM_ERR_INVALID_ARG: null
+ * pointers, negative counts, a workspace too small or not 256-byte aligned, bgr outside {0, 1}.  F == 0: GOM_OK, no launch. */
+#define GOM_JPEG_DECODE_DESC_WORDS 8
+#define GOM_JPEG_DECODE_SET_WORDS 2392
+long gom_jpeg_decode_workspace_bytes(int F, int H, int W, int ncomp, int hs, int vs);
+int gom_jpeg_decode_entropy_i16(const uint8_t* bytes, long nbytes, const int64_t* desc, int nseg, const int32_t* seg_off,
+                                const int32_t* sets, int nsets, int F, int H, int W, int ncomp, int hs, int vs, void* workspace,
+                                long workspace_bytes, int32_t* seg_status, int32_t* frame_status, void* stream);
+int gom_jpeg_decode_pixels_u8(const int32_t* sets, int nsets, const int32_t* frame_set, int F, int H, int W, int ncomp, int hs,
+                              int vs, int bgr, void* workspace, long workspace_bytes, uint8_t* out, void* stream);
 int gom_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 /* out [H*W, 256] = PositionalEncoding2D(normalize=True) + level_embed, for an unpadded H x W level. */
 int gom_pos_encoding_2d_f32(const float* dim_t128, const float* level_embed256, float* out, int H, int W,
