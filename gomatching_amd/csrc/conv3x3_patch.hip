@@ -58,11 +58,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(const PArgs p) {
     const int fn = lane & 15, fg = lane >> 4;
 
     const int tiles_n = p.N / BN;
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = gom_xcd_contiguous_block(blockIdx.x, gridDim.x);
     const int tn = bid % tiles_n;
     int tm = bid / tiles_n;
     const int tx = tm % p.tiles_x;

@@ -64,12 +64,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgs p) {
 
     // ---- XCD-aware tile order (bijective for any grid size) -------------------------------
     const int tiles_n = (p.N + BN - 1) / BN;
-    const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = gom_xcd_contiguous_block(blockIdx.x, gridDim.x);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
 

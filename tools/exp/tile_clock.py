@@ -1,4 +1,4 @@
-"""Diagnostic build of the 128x128 tile kernel (gemm_f16x3.hip, three workgroups per CU): where does a wave's lifetime go?
+"""Diagnostic build of the 128x128 tile kernel (common.h's tile frame with gemm_f16x3.hip's policy, three workgroups per CU): where does a wave's lifetime go?
 Stamps (s_memtime) around the k-loop's phases -- issue loads + LDS reads + MFMAs | barrier | wait for the loads, split, LDS
 stores | barrier -- summed over the k-tiles, plus prologue and epilogue; in-kernel clock from s_memrealtime.  Generated from the
 product source; the product kernel carries no stamps.  Shapes: a 3x3 convolution of ResNet-50's layer2 on the BASELINE frames and
@@ -15,14 +15,17 @@ SO = os.path.join(HERE, "libtile_clock.so")
 
 
 def build():
-    src = open(os.path.join(ROOT, "gomatching_amd", "csrc", "gemm_f16x3.hip")).read()
+    csrc = os.path.join(ROOT, "gomatching_amd", "csrc")
 
     def once(s, a, b):
         assert s.count(a) == 1, a
         return s.replace(a, b)
-    src = once(src, 'template <int BM, int BN, int KH, int KW, int OCC>\n__global__ __launch_bounds__(256, OCC) void gemm_f16x3_kernel(const Args p) {',
+    # the loop lives in the shared tile frame (common.h): the stamped frame, then the f16x3 policy and entry points, as one file
+    src = once(open(os.path.join(csrc, "common.h")).read(), '#include "../../include/gomatching_hip.h"', '#include "gomatching_hip.h"')
+    src += once(open(os.path.join(csrc, "gemm_f16x3.hip")).read(), '#include "common.h"', '')
+    src = once(src, 'template <class P, int BM, int BN, int KH, int KW>\n__device__ __forceinline__ void gom_tile_gemm(const GomTileArgs p) {',
                '__device__ unsigned long long g_stamp[16384 * 10];\n#define NOW() __builtin_amdgcn_s_memtime()\n'
-               'template <int BM, int BN, int KH, int KW, int OCC>\n__global__ __launch_bounds__(256, OCC) void gemm_f16x3_kernel(const Args p) {\n'
+               'template <class P, int BM, int BN, int KH, int KW>\n__device__ __forceinline__ void gom_tile_gemm(const GomTileArgs p) {\n'
                '    const unsigned long long t_start = NOW(), r_start = __builtin_amdgcn_s_memrealtime();\n'
                '    unsigned long long t_comp = 0, t_b1 = 0, t_store = 0, t_b2 = 0, t_loop0 = 0;\n')
     src = once(src, '''        __syncthreads();
