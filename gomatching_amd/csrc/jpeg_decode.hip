@@ -1,5 +1,5 @@
 // Baseline JPEG decoding of source frames: file bytes go up, u8 [F,H,W,3] stays in HBM.  Contract and THE RULE:
-// include/gomatching_hip.h (`gom_jpeg_decode_*`); the walk shared with the host check: jpeg_decode_core.h; the numpy twin:
+// include/gomatching_hip.h (`gom_jpeg_decode_*`); the walks shared with the host checks: jpeg_decode_core.h, jpeg_decode_chunks.h; the numpy twin:
 // gomatching_amd/jpeg.py (decode_host); the per-bit statement: tests/jpeg_decode_statement.py.  Integers only, no atomics, no
 // scratch, one writer per output byte, nothing depends on launch order.
 //
@@ -11,6 +11,9 @@
 //                               2 KiB LDS window of the segment that the wave refills (32-bit loads) between two blocks once
 //                               less than 1 KiB of it lies ahead -- a block's code is at most ~0.5 KiB, so the walk stays inside
 //                               it; a read outside it goes to HBM.  A walk that stops leaves the remaining blocks zero.
+//   jpeg_decode_chunks_kernel   gom_jpeg_decode_entropy_chunks_i16 only, in front of the kernel above (which then skips the
+//                               segments this one finished): a 256-thread workgroup per segment, a lane per chunk of its bytes;
+//                               cold walk, settling, scans, write walk per span of chunks (jpeg_decode_chunks.h; below).
 //   jpeg_decode_status_kernel   a thread per frame: the status of its first segment that is not clean.
 //   jpeg_decode_idct_kernel     eight lanes per block: lane c dequantises and transforms column c (strided 16-bit loads), the
 //                               block's 8 x 8 intermediate goes through LDS (rows padded to 9 words), lane r transforms row r,
@@ -19,8 +22,10 @@
 //                               sample, the two upsampled chrominance samples, the colour matrix, clamp.
 #include "common.h"
 #include "jpeg_decode_core.h"
+#include "jpeg_decode_chunks.h"
 
 #define JD_WIN_BYTES 2048
+#define JC_THREADS GOM_JC_MAX_LANES
 #define JD_IDCT_THREADS 256
 #define JD_COLOUR_THREADS 256
 
@@ -49,13 +54,15 @@ inline int jd_layout(int F, int H, int W, int ncomp, int hs, int vs, JdLayout& L
 __global__ __launch_bounds__(64) void jpeg_decode_entropy_kernel(const uint8_t* __restrict__ bytes, long nbytes,
                                                                  const int64_t* __restrict__ desc, const int32_t* __restrict__ sets,
                                                                  int nsets, int F, GomJdGeom g, int16_t* __restrict__ coef,
-                                                                 int32_t* __restrict__ seg_status) {
+                                                                 int32_t* __restrict__ seg_status,
+                                                                 const int32_t* __restrict__ seg_info) {
     __shared__ int32_t s_set[GOM_JD_SET_WORDS];
     __shared__ uint32_t s_win[JD_WIN_BYTES / 4];
     __shared__ int16_t s_blk[64];
     __shared__ long s_pos;
     const int lane = threadIdx.x;
     const long seg = blockIdx.x;
+    if (seg_info && seg_info[2 * seg] == 0) return;                     // the chunk walk finished this segment
     const GomJdDesc d = gom_jd_desc(desc + seg * GOM_JD_DESC_WORDS);
     if (d.frame < 0 || d.frame >= F || d.set < 0 || d.set >= nsets) {  // a descriptor that names no frame or no table set
         if (lane == 0) seg_status[seg] = GOM_JD_PAST_END;
@@ -95,6 +102,164 @@ __global__ __launch_bounds__(64) void jpeg_decode_entropy_kernel(const uint8_t* 
     };
     const int status = gom_jd_walk_segment(bytes, nbytes, d, s_set, g, lane == 0, s_blk, begin, emit);
     if (lane == 0) seg_status[seg] = status;
+}
+
+// ---- launch 1c: the chunked entropy walk, a workgroup per segment, a lane per chunk (jpeg_decode_chunks.h) -----------------------
+// A span is `lanes` chunks; its bytes are staged in LDS, chunk t at word t (chunk_bytes / 4 + 1): the odd stride spreads the
+// lanes' byte reads, which advance at about the same pace, over the banks.  A lane's window is its own chunk; what it reads beyond
+// it (the end of a symbol, the end of a block it began) comes from HBM.  Exit states travel through LDS; a lane whose entry did not
+// change does not walk again, and a wave of such lanes skips the pass.
+__device__ __forceinline__ int jc_pack(const GomJcPoint& a) { return a.bit | (a.slot << 3) | (a.k << 6); }
+
+__global__ __launch_bounds__(JC_THREADS) void jpeg_decode_chunks_kernel(const uint8_t* __restrict__ bytes, long nbytes,
+                                                                        const int64_t* __restrict__ desc, const int32_t* __restrict__ sets,
+                                                                        int nsets, int F, GomJdGeom g, int16_t* __restrict__ coef,
+                                                                        int32_t* __restrict__ seg_status, int32_t* __restrict__ seg_info,
+                                                                        int chunk_bytes, int lanes) {
+    __shared__ int32_t s_set[GOM_JD_SET_WORDS];
+    __shared__ uint32_t s_stage[GOM_JC_STAGE_BYTES / 4 + GOM_JC_MAX_LANES];
+    __shared__ long s_exit_byte[GOM_JC_MAX_LANES];
+    __shared__ int s_exit_w[GOM_JC_MAX_LANES];
+    __shared__ uint32_t s_wave[JC_THREADS / 64][4];
+    __shared__ int s_bad, s_closed;
+    const int tid = threadIdx.x;
+    const long seg = blockIdx.x;
+    const GomJdDesc d = gom_jd_desc(desc + seg * GOM_JD_DESC_WORDS);
+    GomJcSeg sg;
+    if (d.frame < 0 || d.frame >= F || d.set < 0 || d.set >= nsets || !gom_jc_segment(sg, bytes, nbytes, d, s_set, g)) {
+        if (tid == 0) {                                                 // the serial walk says what is wrong with it
+            seg_info[2 * seg] = 1;
+            seg_info[2 * seg + 1] = 0;
+        }
+        return;
+    }
+    for (int i = tid; i < GOM_JD_SET_WORDS; i += JC_THREADS) s_set[i] = sets[d.set * GOM_JD_SET_WORDS + i];
+    if (tid == 0) {
+        s_bad = 0;
+        s_closed = -1;
+    }
+    __syncthreads();
+    const int row = chunk_bytes / 4 + 1, shift = 31 - __clz(chunk_bytes / 4);
+    const long nchunks = gom_jc_chunks(sg, chunk_bytes);
+    GomJcPoint truth = {sg.start, 0, 0, 0};
+    long carry_blocks = 0;
+    uint32_t carry_dc0 = 0, carry_dc1 = 0, carry_dc2 = 0;
+    int passes = 0;
+    bool bad = false;
+    for (long c0 = 0; c0 < nchunks && carry_blocks < sg.blocks && !bad; c0 += lanes) {
+        const int act = nchunks - c0 < lanes ? (int)(nchunks - c0) : lanes;
+        const long span = sg.base + c0 * chunk_bytes;
+        for (int w = tid; w < act << shift; w += JC_THREADS) {          // staging: coalesced 32-bit loads (`bytes` is 4-byte aligned)
+            const long at = span + 4L * w;
+            if (at >= sg.end) break;
+            uint32_t v = 0;
+            if (at + 4 <= nbytes) {
+                v = *reinterpret_cast<const uint32_t*>(bytes + at);
+            } else {
+                for (int b = 0; b < 4; ++b)
+                    if (at + b < nbytes) v |= (uint32_t)bytes[at + b] << (8 * b);
+            }
+            s_stage[(w >> shift) * row + (w & ((1 << shift) - 1))] = v;
+        }
+        __syncthreads();
+        const bool active = tid < act;
+        const long lo = span + (long)tid * chunk_bytes;
+        const long stop = lo + chunk_bytes < sg.end ? lo + chunk_bytes : sg.end;
+        const uint8_t* win = reinterpret_cast<const uint8_t*>(s_stage + (active ? tid : 0) * row);
+        GomJcPoint entry = truth, exit = truth;
+        GomJcTotals tot = {0, 0u, 0u, 0u};
+        GomJcWrite w;
+        int status = GOM_JD_OK, closed = -1;
+        if (active) {                                                   // (a) the cold walk
+            if (tid > 0) entry = gom_jc_guess(sg, lo);
+            gom_jc_walk<false>(sg, g, win, lo, lo + chunk_bytes, entry, stop, exit, tot, w, status, closed);
+            s_exit_byte[tid] = exit.byte;
+            s_exit_w[tid] = jc_pack(exit);
+        }
+        __syncthreads();
+        int p = 0;
+        for (int pass = 0; pass < GOM_JC_MAX_LANES; ++pass) {           // (b) settling: after pass p the first p + 1 chunks are exact
+            GomJcPoint nx = entry;
+            if (active && tid > 0) {
+                const int ew = s_exit_w[tid - 1];
+                nx.byte = s_exit_byte[tid - 1];
+                nx.bit = ew & 7;
+                nx.slot = (ew >> 3) & 7;
+                nx.k = ew >> 6;
+            }
+            const bool changed = !gom_jc_same(nx, entry);
+            if (!__syncthreads_or(changed)) break;                      // (every lane has read before any lane writes)
+            ++p;
+            if (changed) {
+                entry = nx;
+                gom_jc_walk<false>(sg, g, win, lo, lo + chunk_bytes, entry, stop, exit, tot, w, status, closed);
+                s_exit_byte[tid] = exit.byte;
+                s_exit_w[tid] = jc_pack(exit);
+            }
+            __syncthreads();
+        }
+        passes = p > passes ? p : passes;
+        {                                                               // the next span's true entry
+            const int ew = s_exit_w[act - 1];
+            truth.byte = s_exit_byte[act - 1];
+            truth.bit = ew & 7;
+            truth.slot = (ew >> 3) & 7;
+            truth.k = ew >> 6;
+        }
+        // (c), (d) exclusive scans of the blocks begun and the DC sums: within the wave by shuffles, across the waves through LDS
+        uint32_t inc[4] = {active ? (uint32_t)tot.blocks : 0u, active ? tot.dc0 : 0u, active ? tot.dc1 : 0u, active ? tot.dc2 : 0u};
+        const uint32_t own[4] = {inc[0], inc[1], inc[2], inc[3]};
+        const int wl = tid & 63, wv = tid >> 6;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int dlt = 1; dlt < 64; dlt <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)inc[q], dlt, 64);
+                if (wl >= dlt) inc[q] += up;
+            }
+            if (wl == 63) s_wave[wv][q] = inc[q];
+        }
+        __syncthreads();
+        uint32_t before[4], all[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            before[q] = inc[q] - own[q];
+            all[q] = 0;
+#pragma unroll
+            for (int v = 0; v < JC_THREADS / 64; ++v) {
+                const uint32_t t = s_wave[v][q];
+                if (v < wv) before[q] += t;
+                all[q] += t;
+            }
+        }
+        if (active) {                                                   // (e) the write walk, from the truth
+            w.ordinal = carry_blocks + before[0];
+            w.pred0 = carry_dc0 + before[1];
+            w.pred1 = carry_dc1 + before[2];
+            w.pred2 = carry_dc2 + before[3];
+            w.m0 = d.m0;
+            w.limit = d.limit;
+            w.rst = d.rst;
+            w.out = coef + d.frame * g.nblk * 64;
+            GomJcPoint e;
+            GomJcTotals x;
+            gom_jc_walk<true>(sg, g, win, lo, lo + chunk_bytes, entry, stop, e, x, w, status, closed);
+            if (status != GOM_JD_OK) s_bad = 1;
+            if (closed != -1) s_closed = closed;                        // (one lane ends the last block)
+        }
+        carry_blocks += all[0];
+        carry_dc0 += all[1];
+        carry_dc1 += all[2];
+        carry_dc2 += all[3];
+        __syncthreads();                                                // the stage, the exit words and s_wave are free again
+        bad = s_bad != 0;
+    }
+    if (tid == 0) {
+        const int route = (!bad && s_closed == GOM_JD_OK) ? 0 : 1;
+        seg_info[2 * seg] = route;
+        seg_info[2 * seg + 1] = passes;
+        if (route == 0) seg_status[seg] = GOM_JD_OK;
+    }
 }
 
 // ---- launch 2: segment status words -> frame status words ------------------------------------------------------------------------
@@ -279,7 +444,33 @@ extern "C" int gom_jpeg_decode_entropy_i16(const uint8_t* bytes, long nbytes, co
     unsigned char* ws = (unsigned char*)workspace;
     if (nseg > 0)
         hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((unsigned)nseg), dim3(64), 0, (hipStream_t)stream, bytes, nbytes, desc, sets,
-                           nsets, F, L.g, (int16_t*)(ws + L.coef), seg_status);
+                           nsets, F, L.g, (int16_t*)(ws + L.coef), seg_status, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(jpeg_decode_status_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, (hipStream_t)stream, seg_status, seg_off,
+                       nseg, F, frame_status);
+    return gom_launch_status();
+}
+
+extern "C" int gom_jpeg_decode_entropy_chunks_i16(const uint8_t* bytes, long nbytes, const int64_t* desc, int nseg, const int32_t* seg_off,
+                                                  const int32_t* sets, int nsets, int F, int H, int W, int ncomp, int hs, int vs,
+                                                  void* workspace, long workspace_bytes, int32_t* seg_status, int32_t* frame_status,
+                                                  int chunk_bytes, int32_t* seg_info, void* stream) {
+    JdLayout L;
+    const int rc = jd_layout(F, H, W, ncomp, hs, vs, L);
+    if (rc != GOM_OK) return rc;
+    GOM_CHECK_ARG(nbytes >= 0 && nseg >= 0 && nsets >= 0 && GOM_JC_CHUNK_OK(chunk_bytes));
+    if (F == 0) return GOM_OK;
+    GOM_CHECK_ARG(bytes && desc && seg_off && sets && nsets >= 1 && workspace && seg_status && frame_status && (seg_info || nseg == 0));
+    GOM_CHECK_ARG(((uintptr_t)bytes & 3) == 0 && workspace_bytes >= L.total && ((uintptr_t)workspace & 255) == 0);
+    unsigned char* ws = (unsigned char*)workspace;
+    if (nseg > 0) {
+        // the zeros in front: what a clean walk does not store is zero (a marked segment's blocks are all stored again below)
+        const hipError_t e = hipMemsetAsync(ws + L.coef, 0, (size_t)F * L.g.nblk * 128, (hipStream_t)stream);
+        if (e != hipSuccess) return GOM_ERR_HIP_BASE + (int)e;
+        hipLaunchKernelGGL(jpeg_decode_chunks_kernel, dim3((unsigned)nseg), dim3(JC_THREADS), 0, (hipStream_t)stream, bytes, nbytes, desc,
+                           sets, nsets, F, L.g, (int16_t*)(ws + L.coef), seg_status, seg_info, chunk_bytes, GOM_JC_LANES(chunk_bytes));
+        hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((unsigned)nseg), dim3(64), 0, (hipStream_t)stream, bytes, nbytes, desc, sets,
+                           nsets, F, L.g, (int16_t*)(ws + L.coef), seg_status, (const int32_t*)seg_info);
+    }
     hipLaunchKernelGGL(jpeg_decode_status_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, (hipStream_t)stream, seg_status, seg_off,
                        nseg, F, frame_status);
     return gom_launch_status();

@@ -32,6 +32,9 @@ Deliberate differences:
   * `--lexicon FILE|DIR [--lexicon-pairs FILE] [--lexicon-max-dist N] [--lexicon-unmatched keep|drop]` runs
     `gomatching_amd.lexicon.correct_results` over OUT after the videos are written (those of earlier, resumed runs included)
     and writes OUT/lexicon/{jsons,preds}; without it the command issues the launches and writes the bytes it always did;
+  * `--decode-walk {auto,segments,chunks}` (with `--device-decode`; default auto) picks the decoder's entropy walk: a wavefront per
+    restart segment, or a lane per chunk of a segment for files without restart markers; the pixels are the same, and the run prints
+    how many segments went which way.  Without `--device-decode` status 2;
   * `--device-decode` reads file bytes on the pool and decodes baseline JPEG frames on the GPU (csrc/jpeg_decode.hip, byte-equal
     to Pillow's decode, so the result files do not change), per 100-frame chunk offline and per push with `--online`: host
     memory holds bytes, device memory one chunk of pixels.  Files with another extension, files `jpeg.parse` refuses and files
@@ -82,6 +85,10 @@ def get_parser(drawing=False):
     p.add_argument("--device-decode", action="store_true",
                    help="decode baseline JPEG frames on the GPU (the same bytes as Pillow's): the pool reads file bytes, host "
                         "memory holds no pixels; any other file goes through Pillow, per file (not with --host-ingest)")
+    p.add_argument("--decode-walk", choices=("auto", "segments", "chunks"), default=None,
+                   help="with --device-decode: the entropy walk -- a wavefront per restart segment, a lane per chunk of a segment "
+                        "(files without restart markers), or auto (default): chunks where a call's segments are long; the same "
+                        "pixels either way")
     p.add_argument("--online", action="store_true",
                    help="run every video as a stream: frames are decoded one push ahead, rows are written as their tracks "
                         "settle, memory does not grow with the video; the files are the same (not with --show / --host-rows)")
@@ -163,14 +170,17 @@ def read_bytes(path):
 
 
 DECODE_ROUTES = ("device", "refused", "flagged", "other")
+DECODE_WALK_ROUTES = ("chunks", "serial")                      # segments the chunk walk finished / walked by one lane
 
 
-def decode_frames(paths, blobs, counts, device):
+def decode_frames(paths, blobs, counts, device, walk="segments"):
     """`--device-decode`: the files' bytes -> one CUDA u8 [H,W,3] tensor per frame, in BGR order as `read_frame` yields.
     `.jpg` / `.jpeg` files that `jpeg.parse` accepts are decoded on the GPU, one `ops.jpeg_decode` call per geometry (a
     video's frames share one); a file with another extension ("other"), one the parser refuses ("refused") and one whose
     status word comes back set ("flagged") go through `read_frame`, per file, and are uploaded beside the others.  `counts`
-    is incremented per route."""
+    is incremented per route.  `walk`: jpeg.decode_device's ("auto" resolves per call); the segments that went through the
+    chunk walk and through the serial one are counted under DECODE_WALK_ROUTES ("serial": every segment of a call that took
+    the segment walk, and the segments the chunk walk marked -- it is no count of damaged segments)."""
     import torch
     from . import jpeg as _jpeg
     from . import ops
@@ -186,7 +196,16 @@ def decode_frames(paths, blobs, counts, device):
             continue
         groups.setdefault(info.key, []).append((i, info))
     for items in groups.values():
-        pixels, status = ops.jpeg_decode(_jpeg.plan([blobs[i] for i, _ in items], [info for _, info in items]), True, device)
+        plan = _jpeg.plan([blobs[i] for i, _ in items], [info for _, info in items])
+        nseg = int(plan.desc.shape[0])
+        if _jpeg.resolve_walk(walk, plan) == "chunks":
+            pixels, status, seg_info = ops.jpeg_decode(plan, True, device, walk="chunks", return_info=True)
+            by_chunks = int((seg_info[:, 0] == 0).sum().item())
+        else:
+            pixels, status = ops.jpeg_decode(plan, True, device)
+            by_chunks = 0
+        counts["chunks"] = counts.get("chunks", 0) + by_chunks
+        counts["serial"] = counts.get("serial", 0) + nseg - by_chunks
         status = status.cpu().numpy()
         for j, (i, _) in enumerate(items):
             if status[j] == 0:
@@ -200,7 +219,7 @@ def decode_frames(paths, blobs, counts, device):
     return out
 
 
-def spot_video_device_decode(spotter, pool, paths, time_cost, counts, device, batch=100):
+def spot_video_device_decode(spotter, pool, paths, time_cost, counts, device, batch=100, walk="segments"):
     """`results.spot_video` for `--device-decode`: the pool reads the bytes of one chunk ahead, the chunk's frames are decoded
     into device memory and go to the predictor as they are.  Host memory holds file bytes only, device memory one chunk of
     pixels.  -> (per-frame results, seconds inside the timed window, seconds reading and decoding)."""
@@ -211,7 +230,7 @@ def spot_video_device_decode(spotter, pool, paths, time_cost, counts, device, ba
         t0 = time.time()
         blobs = [f.result() for f in ahead]
         ahead = [pool.submit(read_bytes, p) for p in chunks[batch_id + 1]] if batch_id + 1 < len(chunks) else []
-        frames = decode_frames(chunk, blobs, counts, device)
+        frames = decode_frames(chunk, blobs, counts, device, walk)
         del blobs
         read += time.time() - t0
         instances, id_count, dt = spotter(frames, instances, batch_id, id_count, batch_id == len(chunks) - 1, time_cost,
@@ -250,7 +269,7 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
             frames = [f.result() for f in ahead]
             ahead = [pool.submit(reader, p) for p in chunks[c + 1]] if c + 1 < len(chunks) else []
             if counts is not None:
-                frames = decode_frames(chunks[c], frames, counts, model.device)
+                frames = decode_frames(chunks[c], frames, counts, model.device, args.decode_walk)
             read += time.time() - t0
             settled = session.push(frames)
             del frames
@@ -292,6 +311,11 @@ def main(argv=None):
     if args.push is not None and (not args.online or args.push < 1):
         sys.stderr.write("error: --push N (N >= 1) goes with --online\n")
         return 2
+    if args.decode_walk is not None and not args.device_decode:
+        sys.stderr.write("error: --decode-walk goes with --device-decode\n")
+        return 2
+    if args.device_decode and args.decode_walk is None:
+        args.decode_walk = "auto"
     if args.device_decode and args.host_ingest:
         sys.stderr.write("error: --device-decode leaves the frames in device memory: it does not go with --host-ingest\n")
         return 2
@@ -366,7 +390,8 @@ def main(argv=None):
             if routes is not None:
                 if not paths:
                     continue
-                preds, per_video_time, read = spot_video_device_decode(spotter, pool, paths, time_cost, routes, model.device)
+                preds, per_video_time, read = spot_video_device_decode(spotter, pool, paths, time_cost, routes, model.device,
+                                                                       walk=args.decode_walk)
                 read_seconds += read
                 frames = paths                              # (counted below; the pixels are gone)
                 if args.show:                               # the drawing step takes host frames: read through Pillow, as ever
@@ -403,6 +428,8 @@ def main(argv=None):
     if routes is not None:
         print("device decode: ", routes["device"], " files decoded on the GPU; through Pillow: ", routes["other"],
               " with another extension, ", routes["refused"], " refused by the parser, ", routes["flagged"], " with a status word set")
+        print("device decode walk (--decode-walk ", args.decode_walk, "): ", routes.get("chunks", 0), " segments by the chunk walk, ",
+              routes.get("serial", 0), " by the serial walk (those of calls that took the segment walk, and those the chunk walk marked)")
     if args.show:
         print("host seconds drawing and encoding frames: ", draw_seconds)
     if args.lexicon is not None:                            # every video under OUT, those of earlier (resumed) runs included

@@ -27,6 +27,11 @@ import numpy as np
 from .lib import CONSTANTS as _ABI
 
 MAX_WIDTH = _ABI["GOM_JPEG_MAX_WIDTH"]
+# The chunked entropy walk (THE RULE of `gom_jpeg_decode_entropy_chunks_i16`): the default chunk and the mean segment length from
+# which walk="auto" takes it, both measured (profiles/jpeg_decode_chunks_bench.log) and stated in include/gomatching_hip.h.
+CHUNK_BYTES = _ABI["GOM_JPEG_DECODE_CHUNK_BYTES"]
+AUTO_SEGMENT_BYTES = _ABI["GOM_JPEG_DECODE_AUTO_SEGMENT_BYTES"]
+WALKS = ("auto", "segments", "chunks")
 MAX_HEIGHT = 65535                                         # SOF0 holds 16 bits
 
 # natural index of the k-th coefficient in zigzag order
@@ -775,12 +780,31 @@ def decode_host(files, bgr=True, return_status=False, return_coefficients=False)
     return res if len(res) > 1 else out
 
 
-def decode_device(files, bgr=True, return_status=False):
+def resolve_walk(walk, plan):
+    """The entropy walk of one decode call: "segments" and "chunks" stand; "auto" gives "chunks" when the plan's segments are
+    at least AUTO_SEGMENT_BYTES long in the mean (files without restart markers: one segment each), else "segments".  Pure."""
+    if walk not in WALKS:
+        raise ValueError("walk must be one of %s, not %r" % (", ".join(WALKS), walk))
+    if walk != "auto":
+        return walk
+    nseg = int(plan.desc.shape[0])
+    mean = float((plan.desc[:, 1] - plan.desc[:, 0]).sum()) / nseg if nseg else 0.0
+    return "chunks" if mean >= AUTO_SEGMENT_BYTES else "segments"
+
+
+def decode_device(files, bgr=True, return_status=False, walk="segments", chunk_bytes=None):
     """`decode_host` through csrc/jpeg_decode.hip: three uploads (bytes, descriptors, table sets), the pixels stay on the
-    device.  -> CUDA u8 [F,H,W,3] (and the status words as a host int32 array)."""
+    device.  -> CUDA u8 [F,H,W,3] (and the status words as a host int32 array).  walk: "segments", "chunks" (with
+    `chunk_bytes`, None = CHUNK_BYTES) or "auto" (`resolve_walk`): `ops.jpeg_decode`'s, the same pixels either way."""
+    if walk not in WALKS:
+        raise ValueError("walk must be one of %s, not %r" % (", ".join(WALKS), walk))
+    if walk == "segments" and chunk_bytes is not None:
+        raise ValueError("chunk_bytes belongs to walk=\"chunks\" (or \"auto\", where it counts when the chunk walk is taken)")
     import torch
     from . import ops
     if not torch.cuda.is_available():
         raise RuntimeError("no GPU: the decoder runs in csrc/jpeg_decode.hip (decode_host is the numpy path)")
-    out, status = ops.jpeg_decode(plan(files), bgr)
+    p = plan(files)
+    walk = resolve_walk(walk, p)
+    out, status = ops.jpeg_decode(p, bgr, walk=walk, chunk_bytes=chunk_bytes if walk == "chunks" else None)
     return (out, status.cpu().numpy()) if return_status else out

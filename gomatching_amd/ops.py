@@ -1767,11 +1767,28 @@ def jpeg_encode(frames, quality=95, bgr=True):
     return payload[:total], offsets
 
 
-def jpeg_decode(plan, bgr=True, device=None):
+JPEG_DECODE_CHUNK_BYTES = _lib_mod.CONSTANTS["GOM_JPEG_DECODE_CHUNK_BYTES"]
+JPEG_DECODE_WALKS = ("segments", "chunks")
+
+
+def jpeg_decode(plan, bgr=True, device=None, walk="segments", chunk_bytes=None, return_info=False):
     """Baseline JPEG files -> u8 [F,H,W,3] on the device, four launches (csrc/jpeg_decode.hip; the integer rule is in
     include/gomatching_hip.h).  `plan` = `jpeg.plan(files)`: the packed entropy bytes, the segment descriptors and the distinct
     table sets, three uploads.  -> (pixels, status int32 [F] on the device): a frame whose status word is not 0 holds no
-    picture and its file goes through Pillow.  A geometry the decoder refuses raises before any launch."""
+    picture and its file goes through Pillow.  A geometry the decoder refuses raises before any launch.
+    walk="segments": a wavefront per restart segment (`gom_jpeg_decode_entropy_i16`).  walk="chunks": a lane per `chunk_bytes`
+    (a power of two in 16 .. 4096; None: the measured default) of a segment, for files without restart markers
+    (`gom_jpeg_decode_entropy_chunks_i16`); the same pixels and status words.  return_info (chunks only) appends seg_info int32
+    [nseg, 2] on the device: per segment the route (0 = the chunk walk, 1 = marked and walked serially) and the most settling
+    passes of one of its spans."""
+    if walk not in JPEG_DECODE_WALKS:
+        raise ValueError("walk must be one of %s, not %r" % (", ".join(JPEG_DECODE_WALKS), walk))
+    if walk == "segments" and (chunk_bytes is not None or return_info):
+        raise ValueError("chunk_bytes and return_info belong to walk=\"chunks\"")
+    if walk == "chunks":
+        chunk_bytes = JPEG_DECODE_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+        if not (16 <= chunk_bytes <= 4096 and chunk_bytes & (chunk_bytes - 1) == 0):
+            raise ValueError("chunk_bytes must be a power of two in 16 .. 4096, not %d" % chunk_bytes)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     F, nseg = int(plan.F), int(plan.desc.shape[0])
     if F == 0:
@@ -1797,11 +1814,16 @@ def jpeg_decode(plan, bgr=True, device=None):
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     status = torch.empty((nseg + F,), dtype=torch.int32, device=dev)
     out = torch.empty((F, geo[1], geo[2], 3), dtype=torch.uint8, device=dev)
+    info = torch.empty((nseg, 2), dtype=torch.int32, device=dev) if walk == "chunks" else None
     with torch.cuda.device(dev):
-        _call("gom_jpeg_decode_entropy_i16", _p(data_d), len(plan.data), _p(desc_d), nseg, _p(seg_off), _p(sets), nsets, *geo,
-              _p(ws), nbytes, _p(status[:nseg]), _p(status[nseg:]), _stream())
+        if walk == "chunks":
+            _call("gom_jpeg_decode_entropy_chunks_i16", _p(data_d), len(plan.data), _p(desc_d), nseg, _p(seg_off), _p(sets), nsets,
+                  *geo, _p(ws), nbytes, _p(status[:nseg]), _p(status[nseg:]), chunk_bytes, _p(info), _stream())
+        else:
+            _call("gom_jpeg_decode_entropy_i16", _p(data_d), len(plan.data), _p(desc_d), nseg, _p(seg_off), _p(sets), nsets, *geo,
+                  _p(ws), nbytes, _p(status[:nseg]), _p(status[nseg:]), _stream())
         _call("gom_jpeg_decode_pixels_u8", _p(sets), nsets, _p(frame_set), *geo, 1 if bgr else 0, _p(ws), nbytes, _p(out), _stream())
-    return out, status[nseg:]
+    return (out, status[nseg:], info) if return_info else (out, status[nseg:])
 
 
 def mask_outline_polygons(points, contour_off, mask_coff, boxes, word_off, H, W, words, sel=None):

@@ -920,6 +920,57 @@ int gom_jpeg_decode_entropy_i16(const uint8_t* bytes, long nbytes, const int64_t
                                 long workspace_bytes, int32_t* seg_status, int32_t* frame_status, void* stream);
 int gom_jpeg_decode_pixels_u8(const int32_t* sets, int nsets, const int32_t* frame_set, int F, int H, int W, int ncomp, int hs,
                               int vs, int bgr, void* workspace, long workspace_bytes, uint8_t* out, void* stream);
+/* ---- The chunked entropy walk (csrc/jpeg_decode_chunks.h, csrc/jpeg_decode.hip; tools/jpeg_decode_chunks_hostcheck.cpp)
+ * gom_jpeg_decode_entropy_i16 with many lanes per segment, for files without restart markers (one segment a file).  Huffman codes
+ * are self-synchronising: a walk begun at a wrong place falls into step with the true one.  THE RULE:
+ *   Chunks    : a segment's stuffed bytes [start, end) are cut every chunk_bytes (a power of two in 16 .. 4096) counted from
+ *               start rounded down to 4 (the staging loads whole words), so chunk 0 may be up to 3 bytes short.
+ *   State     : at a symbol boundary, everything the rest of the walk depends on: the stuffed byte that holds the next unread bit
+ *               and the bits of it already read (0xFF 0x00 is one byte, named by its 0xFF), the block slot within the MCU
+ *               (0 .. hs vs + 1; 0 for one component), the zigzag index (0: a DC symbol is next).  Not in it: the DC predictors
+ *               and the count of blocks, which are sums and are scanned.  A chunk's exit state is the state at the first symbol
+ *               boundary at or behind its end; it is the next chunk's entry.
+ *   Span      : min(256, 65536 / chunk_bytes) consecutive chunks, a lane each, settled together; a workgroup takes the spans of
+ *               a segment in order, the exit of a span's last chunk being the next span's true entry.  Per span:
+ *               (a) cold walk: a lane walks its chunk from a guess -- its first bit (a 0x00 behind the previous chunk's 0xFF is
+ *                   skipped), slot 0, index 0; chunk 0 from the true entry.  For a guess an invalid code costs one bit, a DC
+ *                   category is taken mod 16, an index above 63 ends the block: no error, the guess is discarded unless it was true.
+ *               (b) settling: lane i takes lane i - 1's exit as its entry; where that differs from the entry it last walked from,
+ *                   it walks again; until no entry changed.  After pass p the first p + 1 chunks are exact, so at most 256 passes,
+ *                   the loop's constant bound.  Equal entries give equal walks: the result is exactly the serial walk's.
+ *               (c) totals: the walk also counts the blocks that begin in the chunk (a block belongs to the chunk that holds its
+ *                   first bit) and sums their DC differences per component;
+ *               (d) which are scanned exclusively over the span, with the carry of the spans before, in 32 bits (the stored DC
+ *                   wraps to 16 bits as in the serial walk);
+ *               (e) write walk: from the true entry, first block ordinal and predictors a lane stores the coefficients of the
+ *                   blocks that begin in its chunk, walking behind the chunk's end to finish the last; ordinal o is slot
+ *                   o mod (blocks of an MCU) of MCU first + o / (blocks of an MCU), at the serial walk's block index.
+ *   End       : the walk ends with the last block of the segment's MCUs; what lies behind is judged as in the serial walk
+ *               (left-over bytes, the RSTn that must follow).  What no walk stores is zero (cleared in front).
+ *   Route     : anything but a clean walk is not this kernel's business: a status other than 0 in a write walk, blocks that do
+ *               not add up to the segment's MCUs, a closing check other than 0 mark the segment, seg_info[s][0] = 1, and leave its
+ *               coefficients unspecified.  The block count is held through the closing check: the check is made by the lane
+ *               that ends block (MCUs x blocks of an MCU) - 1 and a segment nobody closed is marked, which catches too few
+ *               blocks; no write walk begins a block of a higher ordinal, and bytes that would hold more are left over (status
+ *               5), which catches too many.  (The counts of sub-step (c) may run past the last block into the padding bits;
+ *               they only number the blocks.)  Behind the chunk launch, in the same call, gom_jpeg_decode_entropy_i16's kernel runs
+ *               over all segments, returns at once for those with route 0 and walks the marked ones as it always does: a damaged
+ *               stream has exactly the serial walk's status words and coefficients.  seg_info[s][1] = the most settling passes
+ *               of one of its spans (0 for a segment marked before any walk).
+ * One writer per coefficient, no atomics, no scratch; bitwise reproducible, and independent of chunk_bytes, the span and the pass
+ * count.  Same workspace and status words as gom_jpeg_decode_entropy_i16, so gom_jpeg_decode_pixels_u8 follows unchanged.
+ * GOM_ERR_INVALID_ARG before any launch: as there, and a chunk_bytes that is no power of two in 16 .. 4096, a null seg_info.
+ * GOM_JPEG_DECODE_CHUNK_BYTES: the default, and GOM_JPEG_DECODE_AUTO_SEGMENT_BYTES: the mean segment length from which
+ * jpeg.decode_device(walk="auto") takes this walk -- both measured (profiles/jpeg_decode_chunks_bench.log, 100 files of 1280 x
+ * 720): without restart markers the entropy launch takes 38.3 / 24.4 / 16.7 / 22.1 / 35.7 ms at chunks of 64 / 128 / 256 / 512 /
+ * 1024 bytes against 143.8 ms for the segment walk, so 256; the segment walk wins at segments of 4 061 bytes in the mean (7.7 ms
+ * against 19.6 at best) and loses at 30 459 (27.7 ms against 8.9 .. 9.3), so 16 384, between the two. */
+#define GOM_JPEG_DECODE_CHUNK_BYTES 256
+#define GOM_JPEG_DECODE_AUTO_SEGMENT_BYTES 16384
+int gom_jpeg_decode_entropy_chunks_i16(const uint8_t* bytes, long nbytes, const int64_t* desc, int nseg, const int32_t* seg_off,
+                                       const int32_t* sets, int nsets, int F, int H, int W, int ncomp, int hs, int vs,
+                                       void* workspace, long workspace_bytes, int32_t* seg_status, int32_t* frame_status,
+                                       int chunk_bytes, int32_t* seg_info, void* stream);
 int gom_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 /* out [H*W, 256] = PositionalEncoding2D(normalize=True) + level_embed, for an unpadded H x W level. */
 int gom_pos_encoding_2d_f32(const float* dim_t128, const float* level_embed256, float* out, int H, int W,
