@@ -35,6 +35,13 @@ Deliberate differences:
   * `--decode-walk {auto,segments,chunks}` (with `--device-decode`; default auto) picks the decoder's entropy walk: a wavefront per
     restart segment, or a lane per chunk of a segment for files without restart markers; the pixels are the same, and the run prints
     how many segments went which way.  Without `--device-decode` status 2;
+  * `--device-write` formats the text of jsons/<video>.json and preds/res_<video>.xml on the GPU (csrc/result_text.hip; the rule
+    is in include/gomatching_hip.h, `gom_result_text_*`), from the rows where `ops.result_rows` / `result_rows_gather` left them:
+    only the words `results.finish_points` needs come back, the eight rectangle points go up, and the text comes back as bytes,
+    at most 100 frames per call offline and per gather with `--online`.  The files are byte-identical (always UTF-8; the host
+    writer opens the XML in the locale's encoding).  With `--show` the row lists are still built, for the drawing only; `--lexicon`
+    reads the files afterwards; goes with `--device-decode`.  With `--host-rows` status 2; without a GPU status 1 (a choice, not a
+    fall-back).  Without the flag the command issues the launches and writes the bytes it always did;
   * `--device-decode` reads file bytes on the pool and decodes baseline JPEG frames on the GPU (csrc/jpeg_decode.hip, byte-equal
     to Pillow's decode, so the result files do not change), per 100-frame chunk offline and per push with `--online`: host
     memory holds bytes, device memory one chunk of pixels.  Files with another extension, files `jpeg.parse` refuses and files
@@ -89,6 +96,9 @@ def get_parser(drawing=False):
                    help="with --device-decode: the entropy walk -- a wavefront per restart segment, a lane per chunk of a segment "
                         "(files without restart markers), or auto (default): chunks where a call's segments are long; the same "
                         "pixels either way")
+    p.add_argument("--device-write", action="store_true",
+                   help="format the text of jsons/*.json and preds/res_*.xml on the GPU, from the rows where they lie "
+                        "(csrc/result_text.hip); the same bytes (not with --host-rows)")
     p.add_argument("--online", action="store_true",
                    help="run every video as a stream: frames are decoded one push ahead, rows are written as their tracks "
                         "settle, memory does not grow with the video; the files are the same (not with --show / --host-rows)")
@@ -257,7 +267,9 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
     step = model.frames_per_step
     push = args.push if args.push is not None else 4 * step
     push = (push + step - 1) // step * step
-    session = OnlineSpotter(cfg, model, decoder, device_ingest=not args.host_ingest, time_cost=time_cost)
+    session = OnlineSpotter(cfg, model, decoder, device_ingest=not args.host_ingest, time_cost=time_cost,
+                            device_text=args.device_write)
+    add = (lambda item: writer.add_text(*item)) if args.device_write else (lambda item: writer.add(*item))
     writer = _results.VideoResultWriter(video_name, data_type, args.output)
     read, write = 0.0, 0.0
     chunks = [paths[i:i + push] for i in range(0, len(paths), push)]
@@ -274,13 +286,13 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
             settled = session.push(frames)
             del frames
             t0 = time.time()
-            for index, rows in settled:
-                writer.add(index, rows)
+            for item in settled:
+                add(item)
             write += time.time() - t0
         settled = session.close()
         t0 = time.time()
-        for index, rows in settled:
-            writer.add(index, rows)
+        for item in settled:
+            add(item)
         assert writer.frames == len(paths), (writer.frames, len(paths))
         writer.close()
         write += time.time() - t0
@@ -323,6 +335,14 @@ def main(argv=None):
         import torch
         if not torch.cuda.is_available():
             sys.stderr.write("error: --device-decode needs a GPU: the decoder runs in csrc/jpeg_decode.hip\n")
+            return 1
+    if args.device_write and args.host_rows:
+        sys.stderr.write("error: --device-write formats the rows where they lie on the GPU: it does not go with --host-rows\n")
+        return 2
+    if args.device_write:
+        import torch
+        if not torch.cuda.is_available():
+            sys.stderr.write("error: --device-write needs a GPU: the text is formatted in csrc/result_text.hip\n")
             return 1
     if (args.config_file is None) == (args.builtin is None):
         sys.stderr.write("error: give exactly one of --config-file and --builtin\n")
@@ -407,7 +427,7 @@ def main(argv=None):
             total_frame += len(frames)
             t0 = time.time()
             annotation = _results.write_video(preds, video_name, data_type, args.output, decoder,
-                                              device_rows=not args.host_rows)
+                                              device_rows=not args.host_rows, device_text=args.device_write, rows=args.show)
             rows_seconds += time.time() - t0
             if args.show:
                 t0 = time.time()

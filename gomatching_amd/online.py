@@ -139,10 +139,15 @@ class OnlineSpotter:
 
     Per push, for the frames that settled: ONE descriptor upload, ONE `ops.result_rows_gather` launch, ONE copy back, then
     `results.finish_rows` on the host -- the function the offline path ends in.  (A single push of more steps than the ring
-    has room for gathers in between.)"""
+    has room for gathers in between.)
 
-    def __init__(self, cfg, model, decoder, device_ingest=True, time_cost=None, min_extent=5):
+    device_text=True: the gathered words stay on the device.  Only the words `results.finish_points` needs come back, the
+    rectangle points go up, `ops.result_text` formats the settled frames (csrc/result_text.hip) and `push` / `close()` return
+    `[(first frame, frame count, json bytes, xml bytes), ...]` for `VideoResultWriter.add_text` instead of row lists."""
+
+    def __init__(self, cfg, model, decoder, device_ingest=True, time_cost=None, min_extent=5, device_text=False):
         import torch
+        self.device_text = bool(device_text)
         from .predictor import GoMBatchPredictor, new_time_cost
         self.cfg, self.model, self.decoder, self.min_extent = cfg, model, decoder, min_extent
         self.predictor = GoMBatchPredictor(cfg, model, device_ingest=device_ingest)
@@ -278,6 +283,35 @@ class OnlineSpotter:
             self.instances[i] = None
         self._released = max(self._released, stop)
 
+    def _gather_text(self, ready, counts, rows, ids, sxs, sys_, t0):
+        """`_gather` for device_text=True: the same upload and launch, then the text of the settled frames, at most
+        `results.TEXT_FRAMES_PER_CALL` frames per `ops.result_text` call."""
+        from . import ops, results
+        first = ready[0][0]
+        assert [f for f, _ in ready] == list(range(first, first + len(ready))), "settled frames leave in frame order"
+        words_d = None
+        if sum(counts):
+            desc = ops.result_rows_desc(np.concatenate(rows), np.concatenate(ids), np.concatenate(sxs), np.concatenate(sys_))
+            words_d = ops.result_rows_gather(self.ring_bd, self.ring_recs, desc, self.decoder.voc_size, upload=self.model._h2d)
+            self.gather_launches += 1
+            dt = time.time() - t0
+            self.time_cost["post_process"] += dt
+            if not self._in_run:
+                self.seconds += dt
+        t0 = time.time()
+        step = results.TEXT_FRAMES_PER_CALL
+        offsets = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+        for a in range(0, len(ready), step):
+            b = min(a + step, len(ready))
+            r0, r1 = int(offsets[a]), int(offsets[b])
+            if r1 > r0:                                          # (the copy of the text back waits for the launches: the ring
+                js, xs = results.rows_text(words_d[r0:r1], offsets[a:b + 1] - r0, first + a, self.decoder, self.min_extent)
+            else:                                                #  slots may be rewritten afterwards)
+                js, xs = results.host_text_of_empty_frames(first + a, b - a)
+            self._out.append((first + a, b - a, js, xs))
+        self.rows_seconds += time.time() - t0
+        self._ring_tail = ready[-1][0] + 1
+
     def _gather(self):
         """Rows of every settled frame: one upload, one launch, one copy back; then their ring slots are free."""
         from . import ops, results
@@ -296,6 +330,9 @@ class OnlineSpotter:
             sys_.append(np.full((len(k),), sy, np.float32))
         total = sum(counts)
         lines = []
+        if self.device_text:
+            self._gather_text(ready, counts, rows, ids, sxs, sys_, t0)
+            return
         if total:
             desc = ops.result_rows_desc(np.concatenate(rows), np.concatenate(ids), np.concatenate(sxs), np.concatenate(sys_))
             words_d = ops.result_rows_gather(self.ring_bd, self.ring_recs, desc, self.decoder.voc_size, upload=self.model._h2d)

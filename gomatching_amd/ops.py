@@ -1536,6 +1536,66 @@ def result_rows_gather(bd, recs, desc, voc_size, upload=None):
     return out
 
 
+RESULT_TEXT_ENTRY_BYTES = _lib_mod.CONSTANTS["GOM_RT_ENTRY_BYTES"]
+RESULT_TEXT_SCAN_BLOCK = _lib_mod.CONSTANTS["GOM_RT_SCAN_BLOCK"]
+
+
+def result_text(words, pts, keep, frame_rows, first_frame, tables):
+    """The JSON and XML text of the frames of one call, formatted on the GPU (csrc/result_text.hip; THE RULE is in
+    include/gomatching_hip.h, `gom_result_text_*`): words int32 [n, >= RESULT_ROWS_WORDS] as `result_rows` /
+    `result_rows_gather` left them, pts int64 [n, 8] and keep uint8 [n] (`results.finish_points`), all CUDA; frame_rows: host
+    int32 [F + 1], the CSR offsets of the rows over the call's frames; first_frame: the absolute 0-based index of the call's first
+    frame; tables: the (json, xml) pair of uint8 [voc_size - 1, 8] CUDA tensors (`results.text_tables`).
+    -> (json u8 tensor, xml u8 tensor, json_frame_off, xml_frame_off): the bytes between the files' header and footer, and int64
+    [F + 1] offsets of every frame in each.  Three launches (count and scan, then emit) around ONE synchronising read, the two
+    totals, from which the buffers are allocated.  F == 0 gives empty tensors and n == 0 frames without rows, both without a
+    launch.  An emitted character id outside the tables raises GomError: nothing was read through it."""
+    if not words.is_cuda or words.dtype != torch.int32 or words.dim() != 2 or words.shape[1] < RESULT_ROWS_WORDS or \
+            words.stride(1) != 1 and words.shape[0] > 0:
+        raise ValueError("words must be a CUDA int32 [n, >= %d] tensor with unit column stride" % RESULT_ROWS_WORDS)
+    dev, n = words.device, words.shape[0]
+    _chk_i(dev, ("pts", pts, torch.int64, (n, 8)), ("keep", keep, torch.uint8, (n,)))
+    json_tab, xml_tab = tables
+    ntab = json_tab.shape[0]
+    _chk_i(dev, ("json table", json_tab, torch.uint8, (ntab, RESULT_TEXT_ENTRY_BYTES)),
+           ("xml table", xml_tab, torch.uint8, (ntab, RESULT_TEXT_ENTRY_BYTES)))
+    frame_rows = np.ascontiguousarray(frame_rows, dtype=np.int32).reshape(-1)
+    F = frame_rows.shape[0] - 1
+    first_frame = int(first_frame)
+    if F < 0 or frame_rows[0] != 0 or frame_rows[-1] != n or (np.diff(frame_rows) < 0).any():
+        raise ValueError("frame_rows must be non-decreasing offsets from 0 to n = %d" % n)
+    if first_frame < 0 or first_frame + F > 2 ** 31 - 2:
+        raise ValueError("first_frame + F must fit 31 bits")
+    if F == 0 or n == 0:
+        from . import results as _results
+        js, xs = _results.host_text_of_empty_frames(first_frame, F)
+        joff = np.cumsum([0] + [len(_results.host_text_of_empty_frames(f, 1)[0]) for f in range(first_frame, first_frame + F)])
+        xoff = np.cumsum([0] + [len(_results.host_text_of_empty_frames(f, 1)[1]) for f in range(first_frame, first_frame + F)])
+        u8 = lambda b: torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()).to(dev)
+        return u8(js), u8(xs), torch.from_numpy(joff.astype(np.int64)).to(dev), torch.from_numpy(xoff.astype(np.int64)).to(dev)
+    if ntab < 1:
+        raise ValueError("empty tables")
+    ld = words.stride(0) if n > 1 else words.shape[1]
+    with torch.cuda.device(dev):
+        frame_rows_d = torch.from_numpy(frame_rows).to(dev)
+        row_len = torch.empty((2, n), dtype=torch.int32, device=dev)
+        row_off = torch.empty((2, n + 1), dtype=torch.int64, device=dev)
+        row_kept = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+        frame_off = torch.empty((2, F + 1), dtype=torch.int64, device=dev)
+        totals = torch.empty((_lib_mod.CONSTANTS["GOM_RT_TOTALS"],), dtype=torch.int64, device=dev)
+        common = (_p(words), ld, _p(pts), _p(keep), n, _p(frame_rows_d), F, first_frame, _p(json_tab), _p(xml_tab), ntab)
+        _call("gom_result_text_count_scan", *common, _p(row_len), _p(row_off), _p(row_kept), _p(frame_off), _p(totals), _stream())
+        jt, xt, status, _ = totals.tolist()                  # the one synchronising read
+        if status:
+            raise _lib_mod.GomError("result_text: an emitted character id lies outside the %d-entry tables (status %d)"
+                                    % (ntab, status))
+        js = torch.empty((jt,), dtype=torch.uint8, device=dev)
+        xs = torch.empty((xt,), dtype=torch.uint8, device=dev)
+        _call("gom_result_text_emit", *common, _p(row_len), _p(row_off), _p(row_kept), _p(frame_off), _p(js), jt, _p(xs), xt,
+              _stream())
+    return js, xs, frame_off[0], frame_off[1]
+
+
 def quad_bezier(quads, hw):
     """quads int32 [n,8] (x1,y1,..,x4,y4), hw int32 [n,2] (each quad's image H, W), both CUDA -> int32 [n,16]: the control points
     of the two Bezier curves of every quad, one launch (csrc/prepare.hip; the rule is in include/gomatching_hip.h)."""

@@ -559,6 +559,73 @@ int gom_result_rows_i32(const float* bd, const int64_t* recs, const int64_t* tra
 #define GOM_RR_DESC_WORDS 6
 int gom_result_rows_gather_i32(const float* bd, const int64_t* recs, long cap, const int32_t* desc, int n, int voc_size,
                                int32_t* out, int ld, void* stream);
+/* ---- Result text (csrc/result_text.hip, csrc/result_text_core.h; results.write_video(device_text=True); eval --device-write)
+ * The bytes of <out>/jsons/<video>.json and <out>/preds/res_<video>.xml, made from the rows where they lie on the device.
+ * THE RULE: the bytes are those `results.write_video_results` / `VideoResultWriter` write, that is json.dumps(indent=4,
+ * ensure_ascii=False) of the annotation and minidom's toprettyxml(indent="  "); spelled out below so that the kernels, the
+ * shared core (built for the host by tools/result_text_hostcheck.cpp) and the plain-Python statement
+ * (tests/result_text_statement.py) agree byte for byte.  Bytes are UTF-8.  <k> is k spaces, \n is one byte 0x0A.
+ * A call covers frames first_frame .. first_frame + F - 1 of a video (0-based; frame f is written under the key f + 1).
+ * A ROW is one row of gom_result_rows_i32 / gom_result_rows_gather_i32 (words) with its eight rectangle points pts[r][0..7]
+ * (int64, finished on the host: results.finish_points) and keep[r]; a row with keep[r] == 0 writes nothing and counts nothing.
+ * Frame f of the call owns rows frame_rows[f] .. frame_rows[f+1] - 1.
+ *   JSON, frame f : ",\n" unless f == 0 (the ABSOLUTE index: first_frame + the frame's place in the call), then
+ *                   <4>"<f+1>": [] for a frame without kept rows, else <4>"<f+1>": [\n, the rows joined by ",\n", \n<4>]
+ *   JSON, row     : <8>{\n
+ *                   <12>"points": [\n   <16>P0,\n <16>P1,\n ... <16>P7\n   <12>],\n
+ *                   <12>"ID": I,\n
+ *                   <12>"transcription": "T",\n
+ *                   <12>"segmentation": [\n <16>[\n
+ *                       50 times  <20>[\n <24>X,\n <24>Y\n <20>]   joined by ",\n"
+ *                   \n<16>]\n <12>]\n <8>}
+ *                   (spaces between the pieces above only separate them; the bytes are the pieces, one after another)
+ *   The host writes "{\n" before frame 0 and "\n}" after the last frame; a video without frames is "{}".
+ *   XML, frame f  : <2><frame ID="f+1"/>\n without kept rows, else <2><frame ID="f+1">\n, the objects, <2></frame>\n
+ *   XML, object   : <4><object ID="I" Transcription="T">\n
+ *                   4 times <6><Point x="P2i" y="P2i+1"/>\n
+ *                   <4></object>\n
+ *   The host writes <?xml version="1.0" ?>\n<Frames>\n before frame 0 and </Frames>\n at the end (a video without frames:
+ *   the declaration line alone).
+ *   Integers      : plain decimal, '-' in front of a negative one, no other sign, no leading zero.  P0..P7 = pts (int64),
+ *                   I = the int64 in words GOM_RR_TRACK_ID (low), +1 (high), X Y = words GOM_RR_POLY_I32 + 2p, + 2p + 1 (int32).
+ *                   INT64_MIN is -9223372036854775808.
+ *   T             : for c = 0 .. 24 in order, where bit c of word GOM_RR_EMIT is set: the table entry of id = word
+ *                   GOM_RR_RECS + c.  A table is [ntab][GOM_RT_ENTRY_BYTES] u8 with ntab = voc_size - 1: byte 0 = the
+ *                   entry's length L (0 .. 7; a larger byte counts as 7), bytes 1 .. L = the character as the writer
+ *                   escapes it -- json_tab for the JSON stream, xml_tab for the XML stream (results.text_tables builds both
+ *                   from json.dumps and minidom themselves).  An emitted id outside [0, ntab) is never used as an index: its
+ *                   row is left out of both streams and totals[GOM_RT_STATUS] is set to GOM_RT_BAD_ID (the wrapper raises).
+ * Two calls, because the size of the text is a result:
+ *   gom_result_text_count_scan : `count` (one wavefront per row: the JSON and XML byte lengths of every row, 0 for a dropped one,
+ *                   -1 for a bad id) and `scan` (ONE block: exclusive int64 scans over the rows, then over the frames with their
+ *                   wrappers and row separators).  Leaves row_len int32 [2][n], row_off int64 [2][n+1] (bytes of the kept rows
+ *                   before row r, wrappers and separators not counted), row_kept int32 [n+1] (kept rows before row r),
+ *                   frame_off int64 [2][F+1] (frame f's first byte in the JSON / XML stream of this call) and totals int64
+ *                   [GOM_RT_TOTALS] = {JSON bytes, XML bytes, status, 0}: the one thing the caller reads back.
+ *   gom_result_text_emit       : `emit`, with buffers of json_cap / xml_cap bytes (the totals, as the caller read them): one
+ *                   wavefront per row formats the row into LDS (the same core functions that counted it, a lane per piece: a
+ *                   polygon point, a rectangle point, the id, the transcription; a wave scan places them) and stores it; one
+ *                   wavefront per frame writes the frame's wrappers.  Every store index is checked against the length the count
+ *                   pass left and against the cap: a byte that does not fit is not written.  The arrays must be the ones the
+ *                   count_scan call left for the same inputs.
+ * No atomics, no scratch, one writer per output byte, plain and vector stores only; the result depends on nothing but the
+ * input: bitwise reproducible.  frame_rows must be non-decreasing with frame_rows[0] = 0 and frame_rows[F] = n (the wrapper
+ * checks it on the host; the kernels clamp what they read into [0, n], so nothing is read or written out of bounds either way).
+ * GOM_ERR_INVALID_ARG before any HIP call: n < 1, F < 1, ld < GOM_RESULT_ROWS_WORDS, ntab < 1, first_frame < 0 or
+ * first_frame + F > 2^31 - 2, a negative cap, a null pointer. */
+#define GOM_RT_ENTRY_BYTES 8
+#define GOM_RT_TOTALS 4
+#define GOM_RT_STATUS 2
+#define GOM_RT_BAD_ID 1
+#define GOM_RT_SCAN_BLOCK 256
+int gom_result_text_count_scan(const int32_t* words, int ld, const int64_t* pts, const uint8_t* keep, int n,
+                               const int32_t* frame_rows, int F, long first_frame, const uint8_t* json_tab,
+                               const uint8_t* xml_tab, int ntab, int32_t* row_len, int64_t* row_off, int32_t* row_kept,
+                               int64_t* frame_off, int64_t* totals, void* stream);
+int gom_result_text_emit(const int32_t* words, int ld, const int64_t* pts, const uint8_t* keep, int n,
+                         const int32_t* frame_rows, int F, long first_frame, const uint8_t* json_tab, const uint8_t* xml_tab,
+                         int ntab, const int32_t* row_len, const int64_t* row_off, const int32_t* row_kept,
+                         const int64_t* frame_off, uint8_t* json, long json_cap, uint8_t* xml, long xml_cap, void* stream);
 /* ---- Quad -> Bezier control points (csrc/prepare.hip; python -m gomatching_amd.prepare) ------------------------
  * What datasets/vts.py:154-162 derives from a `poly` quad on every load (polygon2rbox -> LinearRing.is_ccw -> cpt_bezier_pts),
  * computed once per dataset: quads int32 [n,8] (x1,y1,..,x4,y4), hw int32 [n,2] (the quad's image H, W), out int32 [n,16]
