@@ -42,6 +42,12 @@ Deliberate differences:
     writer opens the XML in the locale's encoding).  With `--show` the row lists are still built, for the drawing only; `--lexicon`
     reads the files afterwards; goes with `--device-decode`.  With `--host-rows` status 2; without a GPU status 1 (a choice, not a
     fall-back).  Without the flag the command issues the launches and writes the bytes it always did;
+  * `--device-vote` (with `--device-write`; without it status 2, without a GPU status 1) votes preds/res_<video>.txt on the GPU as
+    well (csrc/track_vote.hip; the rule is in include/gomatching_hip.h, `gom_track_vote_*`): every call's rows leave a 112-byte
+    record each in a device log that lives as long as the video, and when the video's other two files are closed the log is
+    ordered by track, voted and formatted, offline and with `--online`.  The end-of-run host step skips those files and still
+    parses the XMLs this run did not write (a resumed run); the run prints both counts.  The bytes are the same.  Without the
+    flag the command issues the launches and writes the bytes it always did, `--device-write` alone included;
   * `--device-decode` reads file bytes on the pool and decodes baseline JPEG frames on the GPU (csrc/jpeg_decode.hip, byte-equal
     to Pillow's decode, so the result files do not change), per 100-frame chunk offline and per push with `--online`: host
     memory holds bytes, device memory one chunk of pixels.  Files with another extension, files `jpeg.parse` refuses and files
@@ -99,6 +105,9 @@ def get_parser(drawing=False):
     p.add_argument("--device-write", action="store_true",
                    help="format the text of jsons/*.json and preds/res_*.xml on the GPU, from the rows where they lie "
                         "(csrc/result_text.hip); the same bytes (not with --host-rows)")
+    p.add_argument("--device-vote", action="store_true",
+                   help="with --device-write: vote every video's track transcriptions (preds/res_*.txt) on the GPU as well, from "
+                        "the same rows (csrc/track_vote.hip); the same bytes")
     p.add_argument("--online", action="store_true",
                    help="run every video as a stream: frames are decoded one push ahead, rows are written as their tracks "
                         "settle, memory does not grow with the video; the files are the same (not with --show / --host-rows)")
@@ -268,7 +277,7 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
     push = args.push if args.push is not None else 4 * step
     push = (push + step - 1) // step * step
     session = OnlineSpotter(cfg, model, decoder, device_ingest=not args.host_ingest, time_cost=time_cost,
-                            device_text=args.device_write)
+                            device_text=args.device_write, device_vote=args.device_vote)
     add = (lambda item: writer.add_text(*item)) if args.device_write else (lambda item: writer.add(*item))
     writer = _results.VideoResultWriter(video_name, data_type, args.output)
     read, write = 0.0, 0.0
@@ -294,7 +303,7 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
         for item in settled:
             add(item)
         assert writer.frames == len(paths), (writer.frames, len(paths))
-        writer.close()
+        writer.close(session.track_txt)                     # (None without --device-vote: no txt is written here)
         write += time.time() - t0
     except BaseException:
         writer.abort()
@@ -339,10 +348,15 @@ def main(argv=None):
     if args.device_write and args.host_rows:
         sys.stderr.write("error: --device-write formats the rows where they lie on the GPU: it does not go with --host-rows\n")
         return 2
+    if args.device_vote and not args.device_write:
+        sys.stderr.write("error: --device-vote votes over the rows --device-write leaves on the GPU: it goes with --device-write\n")
+        return 2
     if args.device_write:
         import torch
         if not torch.cuda.is_available():
-            sys.stderr.write("error: --device-write needs a GPU: the text is formatted in csrc/result_text.hip\n")
+            sys.stderr.write("error: --device-write needs a GPU: the text is formatted in csrc/result_text.hip\n" if not args.device_vote
+                             else "error: --device-write --device-vote need a GPU: the text is formatted in csrc/result_text.hip, "
+                                  "the tracks are voted in csrc/track_vote.hip\n")
             return 1
     if (args.config_file is None) == (args.builtin is None):
         sys.stderr.write("error: give exactly one of --config-file and --builtin\n")
@@ -387,6 +401,7 @@ def main(argv=None):
         decoder = TextDecoder(cfg.MODEL.TRANSFORMER.VOC_SIZE, cfg.MODEL.TRANSFORMER.CUSTOM_DICT)
     total_frame, read_seconds, rows_seconds, draw_seconds = 0, 0.0, 0.0, 0.0
     routes = {k: 0 for k in DECODE_ROUTES} if args.device_decode else None
+    voted = []                                              # --device-vote: the XMLs whose txt the GPU wrote in this run
     if args.show:
         from . import show as _show
         atlas = _show.Atlas(args.font)
@@ -399,6 +414,8 @@ def main(argv=None):
                 if not paths:
                     continue
                 stats = spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, routes)
+                if args.device_vote:
+                    voted.append("res_%s.xml" % _results.result_names(video_name, data_type)[0])
                 read_seconds += stats["read"]
                 rows_seconds += stats["rows"]
                 total_frame += len(paths)
@@ -427,7 +444,10 @@ def main(argv=None):
             total_frame += len(frames)
             t0 = time.time()
             annotation = _results.write_video(preds, video_name, data_type, args.output, decoder,
-                                              device_rows=not args.host_rows, device_text=args.device_write, rows=args.show)
+                                              device_rows=not args.host_rows, device_text=args.device_write, rows=args.show,
+                                              device_vote=args.device_vote)
+            if args.device_vote:
+                voted.append("res_%s.xml" % _results.result_names(video_name, data_type)[0])
             rows_seconds += time.time() - t0
             if args.show:
                 t0 = time.time()
@@ -437,7 +457,12 @@ def main(argv=None):
             print("Video: ", video_name, "per_img_time: ", per_video_time / len(frames), ", FPS: ",
                   len(frames) / per_video_time)
     t0 = time.time()
-    _results.write_track_transcriptions(xml_dir)
+    if args.device_vote:                                    # XMLs this run did not write (a resumed run) stay with the host
+        by_host = [n for n in os.listdir(xml_dir) if ".txt" not in n and "ipynb" not in n and n not in voted]
+        _results.write_track_transcriptions(xml_dir, skip=voted)
+        print("track transcriptions: ", len(voted), " txt files voted on the GPU, ", len(by_host), " by the host from their XML")
+    else:
+        _results.write_track_transcriptions(xml_dir)
     rows_seconds += time.time() - t0
     if total_frame:
         print("total_time: ", time_cost["total_time"], ", per_video_time: ", time_cost["total_time"] / len(videos),

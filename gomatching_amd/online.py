@@ -143,11 +143,22 @@ class OnlineSpotter:
 
     device_text=True: the gathered words stay on the device.  Only the words `results.finish_points` needs come back, the
     rectangle points go up, `ops.result_text` formats the settled frames (csrc/result_text.hip) and `push` / `close()` return
-    `[(first frame, frame count, json bytes, xml bytes), ...]` for `VideoResultWriter.add_text` instead of row lists."""
+    `[(first frame, frame count, json bytes, xml bytes), ...]` for `VideoResultWriter.add_text` instead of row lists.
 
-    def __init__(self, cfg, model, decoder, device_ingest=True, time_cost=None, min_extent=5, device_text=False):
+    device_vote=True (with device_text=True): every gather's words and keep flags also go to a `results.TrackVote` -- only
+    settled rows reach it, the rows the offline path keeps -- and `close()` leaves the bytes of preds/res_<video>.txt in
+    `track_txt` for `VideoResultWriter.close`.  The vote's log, 112 bytes per row, is the one thing a session holds that grows
+    with the video."""
+
+    def __init__(self, cfg, model, decoder, device_ingest=True, time_cost=None, min_extent=5, device_text=False,
+                 device_vote=False):
         import torch
         self.device_text = bool(device_text)
+        if device_vote and not device_text:
+            raise ValueError("device_vote=True votes over the rows device_text=True leaves on the GPU: it needs device_text=True")
+        from . import results as _results
+        self._vote = _results.TrackVote(decoder) if device_vote else None
+        self.track_txt = None                                    # device_vote=True: the txt file's bytes, from `close()` on
         from .predictor import GoMBatchPredictor, new_time_cost
         self.cfg, self.model, self.decoder, self.min_extent = cfg, model, decoder, min_extent
         self.predictor = GoMBatchPredictor(cfg, model, device_ingest=device_ingest)
@@ -218,6 +229,10 @@ class OnlineSpotter:
         self._ready.extend(self.settler.close())
         self._gather()
         self.instances = []
+        if self._vote is not None:
+            t0 = time.time()
+            self.track_txt = self._vote.finish()
+            self.rows_seconds += time.time() - t0
         return self._take()
 
     # ---------------------------------------------------------------------------------------- inside
@@ -305,7 +320,8 @@ class OnlineSpotter:
             b = min(a + step, len(ready))
             r0, r1 = int(offsets[a]), int(offsets[b])
             if r1 > r0:                                          # (the copy of the text back waits for the launches: the ring
-                js, xs = results.rows_text(words_d[r0:r1], offsets[a:b + 1] - r0, first + a, self.decoder, self.min_extent)
+                js, xs = results.rows_text(words_d[r0:r1], offsets[a:b + 1] - r0, first + a, self.decoder, self.min_extent,
+                                           vote=self._vote)
             else:                                                #  slots may be rewritten afterwards)
                 js, xs = results.host_text_of_empty_frames(first + a, b - a)
             self._out.append((first + a, b - a, js, xs))

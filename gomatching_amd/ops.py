@@ -1596,6 +1596,76 @@ def result_text(words, pts, keep, frame_rows, first_frame, tables):
     return js, xs, frame_off[0], frame_off[1]
 
 
+TRACK_VOTE_RECORD_WORDS = _lib_mod.CONSTANTS["GOM_TV_RECORD_WORDS"]
+TRACK_VOTE_ENTRY_MAX = _lib_mod.CONSTANTS["GOM_TV_ENTRY_MAX"]
+TRACK_VOTE_BLOCK = _lib_mod.CONSTANTS["GOM_TV_BLOCK"]
+
+
+def track_vote_records(words, keep, table):
+    """One record per row of a call (csrc/track_vote.hip; THE RULE is in include/gomatching_hip.h, `gom_track_vote_*`): words
+    int32 [n, >= RESULT_ROWS_WORDS] as `result_rows` / `result_rows_gather` left them, keep uint8 [n], table uint8
+    [voc_size - 1, 8] (`results.txt_table`), all CUDA -> int32 [n, TRACK_VOTE_RECORD_WORDS]: track id low / high, the text's byte
+    length (-1: the row does not vote, -2: an emitted id outside the table), 25 words of text bytes.  One launch, no read back."""
+    if not words.is_cuda or words.dtype != torch.int32 or words.dim() != 2 or words.shape[1] < RESULT_ROWS_WORDS or \
+            words.stride(1) != 1 and words.shape[0] > 0:
+        raise ValueError("words must be a CUDA int32 [n, >= %d] tensor with unit column stride" % RESULT_ROWS_WORDS)
+    dev, n = words.device, words.shape[0]
+    ntab = table.shape[0]
+    _chk_i(dev, ("keep", keep, torch.uint8, (n,)), ("txt table", table, torch.uint8, (ntab, RESULT_TEXT_ENTRY_BYTES)))
+    records = torch.empty((n, TRACK_VOTE_RECORD_WORDS), dtype=torch.int32, device=dev)
+    if n == 0:
+        return records
+    if ntab < 1:
+        raise ValueError("an empty table")
+    ld = words.stride(0) if n > 1 else words.shape[1]
+    with torch.cuda.device(dev):
+        _call("gom_track_vote_records_i32", _p(words), ld, _p(keep), n, _p(table), ntab, _p(records), _stream())
+    return records
+
+
+def track_vote(records):
+    """The vote over a video's log: records int32 [m, TRACK_VOTE_RECORD_WORDS] (CUDA, contiguous; `track_vote_records` of every
+    call, in file order) -> (text u8 tensor, track ids int64 [T], winner int32 [T], count int32 [T]): the bytes of
+    preds/res_<video>.txt, and per line the track's id, the log position of the winning row and how many of the track's rows
+    have its text.  The log is ordered by (track id, log position) with a stable sort and cut into tracks here (plumbing); the
+    vote, the line lengths and their scan are two launches, the lines a third, around ONE read of {bytes, status}.  A log
+    without a voting row gives empty tensors without a launch.  A record flagged for a character id outside the table raises
+    GomError."""
+    if not records.is_cuda or records.dtype != torch.int32 or records.dim() != 2 or \
+            records.shape[1] != TRACK_VOTE_RECORD_WORDS or not records.is_contiguous():
+        raise ValueError("records must be a contiguous CUDA int32 [m, %d] tensor" % TRACK_VOTE_RECORD_WORDS)
+    dev, m = records.device, records.shape[0]
+    if m > 2 ** 31 - 1:
+        raise ValueError("a log of more than 2^31 - 1 records")
+    C = _lib_mod.CONSTANTS
+    with torch.cuda.device(dev):
+        ids = records[:, :2].contiguous().view(torch.int64).reshape(m)
+        voters = torch.nonzero(records[:, C["GOM_TV_LEN"]] != C["GOM_TV_LEN_DROPPED"]).reshape(-1)
+        nv = voters.shape[0]
+        if nv == 0:
+            return (torch.empty((0,), dtype=torch.uint8, device=dev), torch.empty((0,), dtype=torch.int64, device=dev),
+                    torch.empty((0,), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev))
+        sorted_ids, perm = torch.sort(ids[voters], stable=True)
+        order = voters[perm].to(torch.int32)
+        track_ids, sizes = torch.unique_consecutive(sorted_ids, return_counts=True)
+        T = track_ids.shape[0]
+        seg = torch.zeros((T + 1,), dtype=torch.int32, device=dev)
+        seg[1:] = torch.cumsum(sizes, 0)
+        winner = torch.empty((T, C["GOM_TV_WINNER_WORDS"]), dtype=torch.int32, device=dev)
+        line_off = torch.empty((T + 1,), dtype=torch.int64, device=dev)
+        totals = torch.empty((C["GOM_TV_TOTALS"],), dtype=torch.int64, device=dev)
+        _call("gom_track_vote_count_scan", _p(records), m, _p(order), nv, _p(seg), T, _p(winner), _p(line_off), _p(totals),
+              _stream())
+        total, status = totals.tolist()                      # the one synchronising read of the vote
+        if status:
+            raise _lib_mod.GomError("track_vote: %s (status %d)" % (
+                "an emitted character id lies outside the table" if status & C["GOM_TV_BAD_ID"] else
+                "the ordering of the log is not a cut into tracks", status))
+        out = torch.empty((total,), dtype=torch.uint8, device=dev)
+        _call("gom_track_vote_emit", _p(records), m, _p(winner), _p(line_off), T, _p(out), total, _stream())
+    return out, track_ids, winner[:, 0], winner[:, 1]
+
+
 def quad_bezier(quads, hw):
     """quads int32 [n,8] (x1,y1,..,x4,y4), hw int32 [n,2] (each quad's image H, W), both CUDA -> int32 [n,16]: the control points
     of the two Bezier curves of every quad, one launch (csrc/prepare.hip; the rule is in include/gomatching_hip.h)."""

@@ -626,6 +626,69 @@ int gom_result_text_emit(const int32_t* words, int ld, const int64_t* pts, const
                          const int32_t* frame_rows, int F, long first_frame, const uint8_t* json_tab, const uint8_t* xml_tab,
                          int ntab, const int32_t* row_len, const int64_t* row_off, const int32_t* row_kept,
                          const int64_t* frame_off, uint8_t* json, long json_cap, uint8_t* xml, long xml_cap, void* stream);
+/* ---- Track vote (csrc/track_vote.hip, csrc/track_vote_core.h; results.TrackVote; eval --device-write --device-vote) --------
+ * The bytes of <out>/preds/res_<video>.txt, one line per track with the track's majority transcription, made from the rows
+ * where they lie on the device.  THE RULE: the bytes are those `results.write_track_transcriptions` writes after parsing the
+ * video's XML (eval.py:182-210, getid_text); spelled out below so that the kernels, the shared core (built for the host by
+ * tools/track_vote_hostcheck.cpp) and the plain-Python statement (tests/track_vote_statement.py) agree byte for byte.
+ *   Which rows vote : a video's voting rows are its kept rows in file order: frame ascending, row order within the frame.  A row
+ *                   with keep == 0 (the min-extent drop of results.finish_points) is not in the XML and does not vote.
+ *   A row's text    : for c = 0 .. 24 in order, where bit c of word GOM_RR_EMIT is set: the txt-table entry of id = word
+ *                   GOM_RR_RECS + c.  The txt table is [ntab][GOM_RT_ENTRY_BYTES] u8 with ntab = voc_size - 1, byte 0 = the
+ *                   entry's length L (0 .. 4; a larger byte counts as 4), bytes 1 .. L = the character as the host function
+ *                   reads it back from the XML (results.txt_table: minidom's attribute serialisation, then the parser of
+ *                   write_track_transcriptions), UTF-8.  A text is therefore at most 100 bytes.
+ *   The vote        : two rows of a track agree when their text BYTES are equal (different ids may share an entry; ids are not
+ *                   compared).  A row's count is the number of rows of its track, itself included, that agree with it.  The
+ *                   winner of a track is the first row, in file order, with the greatest count: max(txts, key=txts.count).
+ *                   Equality is exact: the length and every byte are compared, no hash stands in for them.
+ *   The output      : for each track id that has a voting row, ascending as an int64: the line  "I","W"\n  -- I the id in plain
+ *                   decimal ('-' in front of a negative one, INT64_MIN is -9223372036854775808), W the winner's text bytes as
+ *                   they are, nothing escaped, \n one byte 0x0A.  A video without voting rows gives no bytes.
+ *   Bad ids         : an emitted id outside [0, ntab) is never used as an index: its row gets the length GOM_TV_LEN_BAD, does
+ *                   not vote, and totals[GOM_TV_STATUS] of the vote that sees it is GOM_TV_BAD_ID (the wrapper raises).
+ * A RECORD is GOM_TV_RECORD_WORDS int32 words: the track id's low and high word, the text's byte length (GOM_TV_LEN:
+ * GOM_TV_LEN_DROPPED for a row that does not vote, GOM_TV_LEN_BAD for a bad id; the text words of both are 0), then
+ * GOM_TV_TEXT_WORDS words of text from GOM_TV_TEXT on, byte b in bits 8 * (b % 4) .. of word b / 4, zero after the last byte: two
+ * texts are equal iff their length words and all their text words are.
+ *   gom_track_vote_records_i32 : one lane per row of a call: records [n][GOM_TV_RECORD_WORDS] from words (rows of
+ *                   gom_result_rows_i32 / gom_result_rows_gather_i32, leading dimension ld) and keep [n].  Python appends every
+ *                   call's records to the video's LOG; a record's log position is its place in file order.
+ *   gom_track_vote_count_scan  : the vote over a log of m records.  order int32 [nv]: the log positions of the records with a
+ *                   length other than GOM_TV_LEN_DROPPED, sorted by (track id, log position); seg int32 [T + 1]: track t owns
+ *                   order[seg[t] .. seg[t+1] - 1] (the ordering itself is a stable sort, done by the caller).  One workgroup of
+ *                   GOM_TV_BLOCK lanes per track: a lane holds its record in registers and walks the track's records, every
+ *                   lane reading the same one (streamed from L2; a track need not fit LDS, nor have one row per frame); the
+ *                   winner is the workgroup's maximum of count << 32 | (0xFFFFFFFF - place in the track).  Leaves winner
+ *                   int32 [T][GOM_TV_WINNER_WORDS] = {the winner's log position, its count, the line's byte length, status}.
+ *                   Then ONE block: exclusive int64 scans of the line lengths in tiles of the block -> line_off int64 [T + 1],
+ *                   and totals int64 [GOM_TV_TOTALS] = {bytes, status}: the one thing the caller reads back.
+ *   gom_track_vote_emit        : one wavefront per track writes its line, a lane per byte, into out [cap] (cap = the bytes read
+ *                   back).  The arrays must be the ones the count_scan call left for the same log.
+ * No atomics, no scratch, one writer per output word and byte; every store index is checked (a line that does not lie inside
+ * [0, cap) or whose length is not the one the scan saw is not written); an order or seg entry outside its array is clamped or
+ * skipped and sets GOM_TV_BAD_ORDER, it is never used as an index unchecked.  The result depends on nothing but the input:
+ * bitwise reproducible.  GOM_ERR_INVALID_ARG before any HIP call: n < 1, ld < GOM_RESULT_ROWS_WORDS, ntab < 1, m < 1 or
+ * m > 2^31 - 1, nv < 1 or nv > m, T < 1 or T > nv, a negative cap, a null pointer. */
+#define GOM_TV_RECORD_WORDS 28
+#define GOM_TV_LEN 2
+#define GOM_TV_TEXT 3
+#define GOM_TV_TEXT_WORDS 25
+#define GOM_TV_ENTRY_MAX 4
+#define GOM_TV_LEN_DROPPED -1
+#define GOM_TV_LEN_BAD -2
+#define GOM_TV_WINNER_WORDS 4
+#define GOM_TV_TOTALS 2
+#define GOM_TV_STATUS 1
+#define GOM_TV_BAD_ID 1
+#define GOM_TV_BAD_ORDER 2
+#define GOM_TV_BLOCK 256
+int gom_track_vote_records_i32(const int32_t* words, int ld, const uint8_t* keep, int n, const uint8_t* txt_tab, int ntab,
+                               int32_t* records, void* stream);
+int gom_track_vote_count_scan(const int32_t* records, long m, const int32_t* order, long nv, const int32_t* seg, int T,
+                              int32_t* winner, int64_t* line_off, int64_t* totals, void* stream);
+int gom_track_vote_emit(const int32_t* records, long m, const int32_t* winner, const int64_t* line_off, int T, uint8_t* out,
+                        long cap, void* stream);
 /* ---- Quad -> Bezier control points (csrc/prepare.hip; python -m gomatching_amd.prepare) ------------------------
  * What datasets/vts.py:154-162 derives from a `poly` quad on every load (polygon2rbox -> LinearRing.is_ccw -> cpt_bezier_pts),
  * computed once per dataset: quads int32 [n,8] (x1,y1,..,x4,y4), hw int32 [n,2] (the quad's image H, W), out int32 [n,16]
