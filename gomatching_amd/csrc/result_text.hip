@@ -15,20 +15,54 @@
 // count pass left for the row (and the stage size), a global byte or word against the row's extent clipped to the cap.
 #include "common.h"
 #include "result_text_core.h"
+#include "lexicon_rows_core.h"
 
 #define RT_WAVES 4
 
 namespace {
 
+// the operands of the `_ov` entries (THE RULE: include/gomatching_hip.h, `gom_lexicon_rows_*`): the per-row override, the keep
+// flags the apply step left, and the display tables of the two streams over the lexicon's W words
+struct RtOv {
+    const int32_t* ov;
+    const unsigned char* keep_out;
+    const unsigned char* json_disp;
+    const int32_t* json_doff;
+    long json_dbytes;
+    const unsigned char* xml_disp;
+    const int32_t* xml_doff;
+    long xml_dbytes;
+    int W;
+};
+
+// OV = false: the row of the tables alone (the override pointers are null constants: the branch on them folds away)
+template <bool OV>
 __device__ __forceinline__ GomRtRow rt_row(const int32_t* words, int ld, const int64_t* pts, const unsigned char* jt,
-                                           const unsigned char* xt, int ntab, long r) {
+                                           const unsigned char* xt, int ntab, long r, const RtOv& v) {
     GomRtRow row;
     row.words = words + r * (long)ld;
     row.pts = pts + r * 8;
     row.json_tab = jt;
     row.xml_tab = xt;
     row.ntab = ntab;
+    row.json_ov = row.xml_ov = nullptr;
+    row.json_ov_len = row.xml_ov_len = 0;
+    if (OV) {
+        const int i = v.ov[r];
+        if (i >= 0) {                                      // (an index outside [0, W) reads nothing: the empty form)
+            long at;
+            row.json_ov_len = lr_display(v.json_doff, v.W, v.json_dbytes, i, 25 * (GOM_RT_ENTRY_BYTES - 1), at);
+            row.json_ov = v.json_disp + at;
+            row.xml_ov_len = lr_display(v.xml_doff, v.W, v.xml_dbytes, i, 25 * (GOM_RT_ENTRY_BYTES - 1), at);
+            row.xml_ov = v.xml_disp + at;
+        }
+    }
     return row;
+}
+
+template <bool OV>
+__device__ __forceinline__ bool rt_keeps(const unsigned char* keep, const RtOv& v, long r) {
+    return keep[r] && (!OV || v.keep_out[r]);
 }
 
 template <typename T>
@@ -47,18 +81,17 @@ __device__ __forceinline__ int wave_sum(int v) {
 
 __device__ __forceinline__ int clamp_row(int v, int n) { return v < 0 ? 0 : (v > n ? n : v); }
 
-__global__ __launch_bounds__(64 * RT_WAVES) void result_text_count_kernel(const int32_t* __restrict__ words, int ld,
-                                                                          const int64_t* __restrict__ pts,
-                                                                          const unsigned char* __restrict__ keep, int n,
-                                                                          const unsigned char* __restrict__ jt,
-                                                                          const unsigned char* __restrict__ xt, int ntab,
-                                                                          int32_t* __restrict__ row_len) {
+template <bool OV>
+__device__ __forceinline__ void result_text_count_body(const int32_t* __restrict__ words, int ld, const int64_t* __restrict__ pts,
+                                                       const unsigned char* __restrict__ keep, int n,
+                                                       const unsigned char* __restrict__ jt, const unsigned char* __restrict__ xt,
+                                                       int ntab, int32_t* __restrict__ row_len, const RtOv& v) {
     const int lane = threadIdx.x & 63;
     const long r = (long)blockIdx.x * RT_WAVES + (threadIdx.x >> 6);
     if (r >= n) return;                                   // (whole waves leave; nothing below needs the block)
     int lj = 0, lx = 0;
-    if (keep[r]) {
-        const GomRtRow row = rt_row(words, ld, pts, jt, xt, ntab, r);
+    if (rt_keeps<OV>(keep, v, r)) {
+        const GomRtRow row = rt_row<OV>(words, ld, pts, jt, xt, ntab, r, v);
         GomRtOut o = {nullptr, 0, 0};
         if (lane < GOM_RT_JSON_PIECES) rt_json_piece(o, row, lane, false);
         const int pj = (int)o.pos;
@@ -74,6 +107,24 @@ __global__ __launch_bounds__(64 * RT_WAVES) void result_text_count_kernel(const 
         row_len[r] = lj;
         row_len[(long)n + r] = lx;
     }
+}
+
+__global__ __launch_bounds__(64 * RT_WAVES) void result_text_count_kernel(const int32_t* __restrict__ words, int ld,
+                                                                          const int64_t* __restrict__ pts,
+                                                                          const unsigned char* __restrict__ keep, int n,
+                                                                          const unsigned char* __restrict__ jt,
+                                                                          const unsigned char* __restrict__ xt, int ntab,
+                                                                          int32_t* __restrict__ row_len) {
+    result_text_count_body<false>(words, ld, pts, keep, n, jt, xt, ntab, row_len, RtOv{});
+}
+
+__global__ __launch_bounds__(64 * RT_WAVES) void result_text_count_ov_kernel(const int32_t* __restrict__ words, int ld,
+                                                                             const int64_t* __restrict__ pts,
+                                                                             const unsigned char* __restrict__ keep, int n,
+                                                                             const unsigned char* __restrict__ jt,
+                                                                             const unsigned char* __restrict__ xt, int ntab,
+                                                                             int32_t* __restrict__ row_len, RtOv v) {
+    result_text_count_body<true>(words, ld, pts, keep, n, jt, xt, ntab, row_len, v);
 }
 
 // exclusive scan of one chunk of the block: -> this thread's exclusive prefix (carry included); the carry moves on
@@ -182,12 +233,13 @@ __device__ __forceinline__ void wave_store(unsigned char* __restrict__ out, long
     for (long i = a1 + lane; i < end; i += 64) out[i] = stage[i - dst + shift];
 }
 
-__global__ __launch_bounds__(64 * RT_WAVES) void result_text_emit_kernel(
+template <bool OV>
+__device__ __forceinline__ void result_text_emit_body(
     const int32_t* __restrict__ words, int ld, const int64_t* __restrict__ pts, const unsigned char* __restrict__ keep, int n,
     const int32_t* __restrict__ frame_rows, int F, long first_frame, const unsigned char* __restrict__ jt, const unsigned char* __restrict__ xt, int ntab,
     const int32_t* __restrict__ row_len, const int64_t* __restrict__ row_off, const int32_t* __restrict__ row_kept,
     const int64_t* __restrict__ frame_off, unsigned char* __restrict__ json, long json_cap, unsigned char* __restrict__ xml,
-    long xml_cap) {
+    long xml_cap, const RtOv& v) {
     __shared__ __attribute__((aligned(16))) unsigned char stage_all[RT_WAVES][GOM_RT_STAGE_BYTES];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     unsigned char* stage = stage_all[w];
@@ -228,11 +280,12 @@ __global__ __launch_bounds__(64 * RT_WAVES) void result_text_emit_kernel(
     int lj = 0, lx = 0;
     long dj = 0, dx = 0;
     bool sep = false;
-    GomRtRow row = rt_row(words, ld, pts, jt, xt, ntab, r);
+    GomRtRow row = rt_row<false>(words, ld, pts, jt, xt, ntab, r, v);
     if (is_row) {
+        if (OV) row = rt_row<true>(words, ld, pts, jt, xt, ntab, r, v);
         lj = row_len[r];
         lx = row_len[(long)n + r];
-        if (lj <= 0 || lx <= 0 || !keep[r]) lj = lx = 0;    // dropped, or flagged for an id outside the table
+        if (lj <= 0 || lx <= 0 || !rt_keeps<OV>(keep, v, r)) lj = lx = 0;    // dropped, or flagged for an id outside the table
     }
     if (lj > 0) {
         int lo = 0, hi = F - 1;                            // the frame that owns row r: the last f with frame_rows[f] <= r
@@ -290,10 +343,35 @@ __global__ __launch_bounds__(64 * RT_WAVES) void result_text_emit_kernel(
     }
 }
 
+__global__ __launch_bounds__(64 * RT_WAVES) void result_text_emit_kernel(
+    const int32_t* __restrict__ words, int ld, const int64_t* __restrict__ pts, const unsigned char* __restrict__ keep, int n,
+    const int32_t* __restrict__ frame_rows, int F, long first_frame, const unsigned char* __restrict__ jt, const unsigned char* __restrict__ xt, int ntab,
+    const int32_t* __restrict__ row_len, const int64_t* __restrict__ row_off, const int32_t* __restrict__ row_kept,
+    const int64_t* __restrict__ frame_off, unsigned char* __restrict__ json, long json_cap, unsigned char* __restrict__ xml,
+    long xml_cap) {
+    result_text_emit_body<false>(words, ld, pts, keep, n, frame_rows, F, first_frame, jt, xt, ntab, row_len, row_off, row_kept,
+                                 frame_off, json, json_cap, xml, xml_cap, RtOv{});
+}
+
+__global__ __launch_bounds__(64 * RT_WAVES) void result_text_emit_ov_kernel(
+    const int32_t* __restrict__ words, int ld, const int64_t* __restrict__ pts, const unsigned char* __restrict__ keep, int n,
+    const int32_t* __restrict__ frame_rows, int F, long first_frame, const unsigned char* __restrict__ jt, const unsigned char* __restrict__ xt, int ntab,
+    const int32_t* __restrict__ row_len, const int64_t* __restrict__ row_off, const int32_t* __restrict__ row_kept,
+    const int64_t* __restrict__ frame_off, unsigned char* __restrict__ json, long json_cap, unsigned char* __restrict__ xml,
+    long xml_cap, RtOv v) {
+    result_text_emit_body<true>(words, ld, pts, keep, n, frame_rows, F, first_frame, jt, xt, ntab, row_len, row_off, row_kept,
+                                frame_off, json, json_cap, xml, xml_cap, v);
+}
+
 bool rt_args_ok(const void* words, int ld, const void* pts, const void* keep, int n, const void* frame_rows, int F,
                 long first_frame, const void* jt, const void* xt, int ntab) {
     return n >= 1 && F >= 1 && ld >= GOM_RESULT_ROWS_WORDS && ntab >= 1 && first_frame >= 0 &&
            first_frame + F <= 2147483646L && words && pts && keep && frame_rows && jt && xt;
+}
+
+bool rt_ov_ok(const RtOv& v) {
+    return v.ov && v.keep_out && v.json_disp && v.json_doff && v.xml_disp && v.xml_doff && v.W >= 0 && v.json_dbytes >= 0 &&
+           v.xml_dbytes >= 0;
 }
 
 }  // namespace
@@ -321,5 +399,40 @@ extern "C" int gom_result_text_emit(const int32_t* words, int ld, const int64_t*
     hipLaunchKernelGGL(result_text_emit_kernel, dim3((unsigned)cdiv((long)n + F, (long)RT_WAVES)), dim3(64 * RT_WAVES), 0,
                        (hipStream_t)stream, words, ld, pts, keep, n, frame_rows, F, first_frame, json_tab, xml_tab, ntab, row_len,
                        row_off, row_kept, frame_off, json, json_cap, xml, xml_cap);
+    return gom_launch_status();
+}
+
+// ---- the `_ov` forms (lexicon correction of rows): the same launches with the override operands
+extern "C" int gom_result_text_count_scan_ov(const int32_t* words, int ld, const int64_t* pts, const uint8_t* keep, int n,
+                                             const int32_t* frame_rows, int F, long first_frame, const uint8_t* json_tab,
+                                             const uint8_t* xml_tab, int ntab, const int32_t* ov, const uint8_t* keep_out,
+                                             const uint8_t* json_disp, const int32_t* json_doff, long json_dbytes,
+                                             const uint8_t* xml_disp, const int32_t* xml_doff, long xml_dbytes, int W,
+                                             int32_t* row_len, int64_t* row_off, int32_t* row_kept, int64_t* frame_off,
+                                             int64_t* totals, void* stream) {
+    const RtOv v = {ov, keep_out, json_disp, json_doff, json_dbytes, xml_disp, xml_doff, xml_dbytes, W};
+    GOM_CHECK_ARG(rt_args_ok(words, ld, pts, keep, n, frame_rows, F, first_frame, json_tab, xml_tab, ntab) && rt_ov_ok(v));
+    GOM_CHECK_ARG(row_len && row_off && row_kept && frame_off && totals);
+    hipLaunchKernelGGL(result_text_count_ov_kernel, dim3((unsigned)cdiv((long)n, (long)RT_WAVES)), dim3(64 * RT_WAVES), 0,
+                       (hipStream_t)stream, words, ld, pts, keep, n, json_tab, xml_tab, ntab, row_len, v);
+    hipLaunchKernelGGL(result_text_scan_kernel, dim3(1), dim3(GOM_RT_SCAN_BLOCK), 0, (hipStream_t)stream,
+                       (const int32_t*)row_len, n, frame_rows, F, first_frame, row_off, row_kept, frame_off, totals);
+    return gom_launch_status();
+}
+
+extern "C" int gom_result_text_emit_ov(const int32_t* words, int ld, const int64_t* pts, const uint8_t* keep, int n,
+                                       const int32_t* frame_rows, int F, long first_frame, const uint8_t* json_tab,
+                                       const uint8_t* xml_tab, int ntab, const int32_t* ov, const uint8_t* keep_out,
+                                       const uint8_t* json_disp, const int32_t* json_doff, long json_dbytes,
+                                       const uint8_t* xml_disp, const int32_t* xml_doff, long xml_dbytes, int W,
+                                       const int32_t* row_len, const int64_t* row_off, const int32_t* row_kept,
+                                       const int64_t* frame_off, uint8_t* json, long json_cap, uint8_t* xml, long xml_cap,
+                                       void* stream) {
+    const RtOv v = {ov, keep_out, json_disp, json_doff, json_dbytes, xml_disp, xml_doff, xml_dbytes, W};
+    GOM_CHECK_ARG(rt_args_ok(words, ld, pts, keep, n, frame_rows, F, first_frame, json_tab, xml_tab, ntab) && rt_ov_ok(v));
+    GOM_CHECK_ARG(row_len && row_off && row_kept && frame_off && json && xml && json_cap >= 0 && xml_cap >= 0);
+    hipLaunchKernelGGL(result_text_emit_ov_kernel, dim3((unsigned)cdiv((long)n + F, (long)RT_WAVES)), dim3(64 * RT_WAVES), 0,
+                       (hipStream_t)stream, words, ld, pts, keep, n, frame_rows, F, first_frame, json_tab, xml_tab, ntab, row_len,
+                       row_off, row_kept, frame_off, json, json_cap, xml, xml_cap, v);
     return gom_launch_status();
 }

@@ -34,6 +34,12 @@ struct GomRtRow {
     const unsigned char* json_tab;                             // [ntab][GOM_RT_ENTRY_BYTES]
     const unsigned char* xml_tab;
     int ntab;
+    // a lexicon override (`gom_result_text_*_ov`): with a non-null pointer the transcription piece is these bytes as they are, the
+    // row's display form for that stream; null (what `GomRtRow{words, pts, json_tab, xml_tab, ntab}` leaves): the tables, as ever
+    const unsigned char* json_ov;
+    int json_ov_len;
+    const unsigned char* xml_ov;
+    int xml_ov_len;
 };
 
 GOM_RT_FN void rt_put(GomRtOut& o, unsigned char c) {
@@ -124,6 +130,12 @@ GOM_RT_FN void rt_transcription(GomRtOut& o, const GomRtRow& r, const unsigned c
     }
 }
 
+// an override's bytes: a display form of the lexicon, escaped on the host, at most 25 * (GOM_RT_ENTRY_BYTES - 1) of them
+GOM_RT_FN void rt_override(GomRtOut& o, const unsigned char* b, int len) {
+    if (len > 25 * (GOM_RT_ENTRY_BYTES - 1)) len = 25 * (GOM_RT_ENTRY_BYTES - 1);
+    for (int i = 0; i < len; ++i) rt_put(o, b[i]);
+}
+
 // ---- JSON: piece s of a row, in stream order.  `sep`: the row is not the first kept row of its frame.
 GOM_RT_FN void rt_json_piece(GomRtOut& o, const GomRtRow& r, int s, bool sep) {
     if (s == 0) {
@@ -146,7 +158,8 @@ GOM_RT_FN void rt_json_piece(GomRtOut& o, const GomRtRow& r, int s, bool sep) {
         rt_spaces(o, 12);
         rt_str(o, "\"transcription\": \"");
     } else if (s == 10) {
-        rt_transcription(o, r, r.json_tab);
+        if (r.json_ov) rt_override(o, r.json_ov, r.json_ov_len);
+        else rt_transcription(o, r, r.json_tab);
     } else if (s == 11) {
         rt_str(o, "\",\n");
         rt_spaces(o, 12);
@@ -184,7 +197,8 @@ GOM_RT_FN void rt_xml_piece(GomRtOut& o, const GomRtRow& r, int s) {
         rt_i64(o, rt_track_id(r));
         rt_str(o, "\" Transcription=\"");
     } else if (s == 1) {
-        rt_transcription(o, r, r.xml_tab);
+        if (r.xml_ov) rt_override(o, r.xml_ov, r.xml_ov_len);
+        else rt_transcription(o, r, r.xml_tab);
     } else if (s == 2) {
         rt_str(o, "\">\n");
     } else if (s < 7) {

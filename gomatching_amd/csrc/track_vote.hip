@@ -15,6 +15,7 @@
 // the log before it is used as an index, every output byte against the line's extent and the cap.
 #include "common.h"
 #include "track_vote_core.h"
+#include "lexicon_rows_core.h"
 
 #define TV_WAVES (GOM_TV_BLOCK / 64)
 
@@ -27,6 +28,21 @@ __global__ __launch_bounds__(GOM_TV_BLOCK) void track_vote_records_kernel(const 
     const long r = (long)blockIdx.x * GOM_TV_BLOCK + threadIdx.x;
     if (r >= n) return;
     tv_record(words + r * (long)ld, keep[r] != 0, tab, ntab, records + r * GOM_TV_RECORD_WORDS);
+}
+
+// the `_ov` form: a row with ov[r] >= 0 takes its text from the txt display table of the lexicon's W words (an index or an offset
+// outside the table gives the empty text); keep_out is what the apply step left of keep
+__global__ __launch_bounds__(GOM_TV_BLOCK) void track_vote_records_ov_kernel(
+    const int32_t* __restrict__ words, int ld, const unsigned char* __restrict__ keep, int n, const unsigned char* __restrict__ tab,
+    int ntab, const int32_t* __restrict__ ov, const unsigned char* __restrict__ keep_out, const unsigned char* __restrict__ disp,
+    const int32_t* __restrict__ doff, long dbytes, int W, int32_t* __restrict__ records) {
+    const long r = (long)blockIdx.x * GOM_TV_BLOCK + threadIdx.x;
+    if (r >= n) return;
+    const int i = ov[r];
+    long at = 0;
+    const int len = i >= 0 ? lr_display(doff, W, dbytes, i, 4 * GOM_TV_TEXT_WORDS, at) : 0;
+    tv_record_ov(words + r * (long)ld, keep[r] != 0 && keep_out[r] != 0, tab, ntab, i >= 0 ? disp + at : nullptr, len,
+                 records + r * GOM_TV_RECORD_WORDS);
 }
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -176,6 +192,17 @@ extern "C" int gom_track_vote_records_i32(const int32_t* words, int ld, const ui
     GOM_CHECK_ARG(n >= 1 && ld >= GOM_RESULT_ROWS_WORDS && ntab >= 1 && words && keep && txt_tab && records);
     hipLaunchKernelGGL(track_vote_records_kernel, dim3((unsigned)cdiv((long)n, (long)GOM_TV_BLOCK)), dim3(GOM_TV_BLOCK), 0,
                        (hipStream_t)stream, words, ld, keep, n, txt_tab, ntab, records);
+    return gom_launch_status();
+}
+
+extern "C" int gom_track_vote_records_ov_i32(const int32_t* words, int ld, const uint8_t* keep, int n, const uint8_t* txt_tab,
+                                             int ntab, const int32_t* ov, const uint8_t* keep_out, const uint8_t* txt_disp,
+                                             const int32_t* txt_doff, long txt_dbytes, int W, int32_t* records, void* stream) {
+    GOM_CHECK_ARG(n >= 1 && ld >= GOM_RESULT_ROWS_WORDS && ntab >= 1 && words && keep && txt_tab && records);
+    GOM_CHECK_ARG(ov && keep_out && txt_disp && txt_doff && txt_dbytes >= 0 && W >= 0);
+    hipLaunchKernelGGL(track_vote_records_ov_kernel, dim3((unsigned)cdiv((long)n, (long)GOM_TV_BLOCK)), dim3(GOM_TV_BLOCK), 0,
+                       (hipStream_t)stream, words, ld, keep, n, txt_tab, ntab, ov, keep_out, txt_disp, txt_doff, txt_dbytes, W,
+                       records);
     return gom_launch_status();
 }
 

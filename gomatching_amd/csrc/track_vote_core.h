@@ -24,7 +24,10 @@ GOM_TV_FN void tv_store(int32_t* rec, int at, int32_t v) {
 }
 
 // ---- the record of one row.  `row`: the GOM_RESULT_ROWS_WORDS words of the row; `rec`: GOM_TV_RECORD_WORDS words, all written.
-GOM_TV_FN void tv_record(const int32_t* row, bool keep, const unsigned char* tab, int ntab, int32_t* rec) {
+// `ovb` non-null (`gom_track_vote_records_ov_i32`): the text is the `ovlen` bytes there, the txt display form of the word a lexicon
+// put in the row's place, instead of the table's entries; the flags (dropped, bad id) are the row's own either way.
+GOM_TV_FN void tv_record_ov(const int32_t* row, bool keep, const unsigned char* tab, int ntab, const unsigned char* ovb, int ovlen,
+                            int32_t* rec) {
     tv_store(rec, 0, row[GOM_RR_TRACK_ID]);
     tv_store(rec, 1, row[GOM_RR_TRACK_ID + 1]);
     const uint32_t emit = (uint32_t)row[GOM_RR_EMIT];
@@ -35,7 +38,17 @@ GOM_TV_FN void tv_record(const int32_t* row, bool keep, const unsigned char* tab
     }
     int len = 0, word_at = GOM_TV_TEXT;                        // bytes so far; the next text word to store
     uint32_t word = 0;
-    if (keep && !bad) {
+    if (keep && !bad && ovb) {
+        if (ovlen > 4 * GOM_TV_TEXT_WORDS) ovlen = 4 * GOM_TV_TEXT_WORDS;
+        for (int i = 0; i < ovlen; ++i) {
+            word |= (uint32_t)ovb[i] << (8 * (len & 3));
+            ++len;
+            if ((len & 3) == 0) {
+                tv_store(rec, word_at++, (int32_t)word);
+                word = 0;
+            }
+        }
+    } else if (keep && !bad) {
         for (int c = 0; c < 25; ++c) {
             if (!((emit >> c) & 1u)) continue;
             const unsigned char* e = tab + (long)row[GOM_RR_RECS + c] * GOM_RT_ENTRY_BYTES;
@@ -54,6 +67,10 @@ GOM_TV_FN void tv_record(const int32_t* row, bool keep, const unsigned char* tab
     tv_store(rec, GOM_TV_LEN, !keep ? GOM_TV_LEN_DROPPED : (bad ? GOM_TV_LEN_BAD : len));
     if (len & 3) tv_store(rec, word_at++, (int32_t)word);
     for (; word_at < GOM_TV_RECORD_WORDS; ++word_at) tv_store(rec, word_at, 0);
+}
+
+GOM_TV_FN void tv_record(const int32_t* row, bool keep, const unsigned char* tab, int ntab, int32_t* rec) {
+    tv_record_ov(row, keep, tab, ntab, nullptr, 0, rec);
 }
 
 GOM_TV_FN int64_t tv_track_id(const int32_t* rec) {

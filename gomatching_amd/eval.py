@@ -32,6 +32,16 @@ Deliberate differences:
   * `--lexicon FILE|DIR [--lexicon-pairs FILE] [--lexicon-max-dist N] [--lexicon-unmatched keep|drop]` runs
     `gomatching_amd.lexicon.correct_results` over OUT after the videos are written (those of earlier, resumed runs included)
     and writes OUT/lexicon/{jsons,preds}; without it the command issues the launches and writes the bytes it always did;
+  * `--device-lexicon` (with `--lexicon`, `--device-write` and `--device-vote`; without all three status 2, before anything is
+    created; without a GPU status 1) corrects the rows where they lie instead (csrc/lexicon_rows.hip; the rule is in
+    include/gomatching_hip.h, `gom_lexicon_rows_*`): every call -- a 100-frame chunk offline, a push with `--online` -- writes the
+    original text under OUT/ as ever and the corrected text under OUT/lexicon/{jsons,preds}, the corrected txt voted over the
+    corrected words when the video closes, byte-identical to the end-of-run host step, which then skips those videos and still
+    corrects the ones this run did not write (a resumed run); the run prints both counts and the kept, accepted and dropped
+    rows of the device path (`distinct` and `changed` are not computed there).  A display form above 175 bytes in the JSON or
+    XML file or 100 bytes in the txt file is refused with status 2 before a model is built or anything is created
+    (`device_lexicons`): those stay with the host step; a transcription above 64 code points ends the run with status 2 too.  Without
+    the flag the command issues the launches and writes the bytes it always did;
   * `--decode-walk {auto,segments,chunks}` (with `--device-decode`; default auto) picks the decoder's entropy walk: a wavefront per
     restart segment, or a lane per chunk of a segment for files without restart markers; the pixels are the same, and the run prints
     how many segments went which way.  Without `--device-decode` status 2;
@@ -131,6 +141,11 @@ def get_parser(drawing=False):
                    help="with --lexicon: accept a word at an edit distance of at most N (default 1)")
     p.add_argument("--lexicon-unmatched", choices=("keep", "drop"), default="keep",
                    help="with --lexicon: keep a transcription without an accepted word (default) or remove its row")
+    p.add_argument("--device-lexicon", action="store_true",
+                   help="with --lexicon, --device-write and --device-vote: correct the rows on the GPU, in the call that formats "
+                        "them (csrc/lexicon_rows.hip), offline and with --online; OUT/lexicon/ gets the same bytes, nothing is "
+                        "parsed or dumped at the end.  The figures are the kept, accepted and dropped rows: `distinct` and "
+                        "`changed` are not computed on the device path")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER,
                    help="modify config options using the command-line 'KEY VALUE' pairs")
     return p
@@ -260,6 +275,19 @@ def spot_video_device_decode(spotter, pool, paths, time_cost, counts, device, ba
     return instances, seconds, read
 
 
+def device_lexicons(lexicon, pairs, input_dir, done=()):
+    """`--device-lexicon`: the Lexicon (`--lexicon FILE`) or {video: Lexicon} (`--lexicon DIR`) of the videos this run will spot,
+    every one with its display tables built -- on the host, before a model is built or anything is uploaded or created.  A
+    missing per-video lexicon, a word without a pair and a display form above the device path's limits (175 bytes in the JSON
+    or XML file, 100 in the txt file) raise `lexicon.LexiconError` here: status 2."""
+    from . import lexicon as _lexicon
+    data_type, videos = list_videos(input_dir, done=done)
+    lexicons = _lexicon.load_lexicons(lexicon, pairs, [_results.result_names(v, data_type)[1] for v, d in videos if os.listdir(d)])
+    for lex in ([lexicons] if isinstance(lexicons, _lexicon.Lexicon) else lexicons.values()):
+        _lexicon.checked_display_tables(lex)
+    return lexicons
+
+
 def load_weights(path):
     """-> canonical state dict, or None when `path` is empty or no file."""
     if not path or not os.path.isfile(path):
@@ -269,7 +297,7 @@ def load_weights(path):
     return normalize_state_dict(torch.load(path, map_location="cpu"))
 
 
-def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, counts=None):
+def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, counts=None, fix=None):
     """One video through `online.OnlineSpotter`: the pool decodes one push ahead, rows go to the incremental writer as they
     settle.  -> seconds reading / inside the timed window / building rows and writing, and the session's wait figures."""
     from .online import OnlineSpotter
@@ -277,9 +305,12 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
     push = args.push if args.push is not None else 4 * step
     push = (push + step - 1) // step * step
     session = OnlineSpotter(cfg, model, decoder, device_ingest=not args.host_ingest, time_cost=time_cost,
-                            device_text=args.device_write, device_vote=args.device_vote)
-    add = (lambda item: writer.add_text(*item)) if args.device_write else (lambda item: writer.add(*item))
+                            device_text=args.device_write, device_vote=args.device_vote, device_lexicon=fix)
+    add = (lambda item: writer.add_text(*item[:4])) if args.device_write else (lambda item: writer.add(*item))
     writer = _results.VideoResultWriter(video_name, data_type, args.output)
+    fixed = _results.VideoResultWriter(video_name, data_type, os.path.join(args.output, "lexicon")) if fix is not None else None
+    if fixed is not None:                                   # --device-lexicon: an item carries the corrected text as well
+        add = lambda item: (writer.add_text(*item[:4]), fixed.add_text(item[0], item[1], item[4], item[5]))
     read, write = 0.0, 0.0
     chunks = [paths[i:i + push] for i in range(0, len(paths), push)]
     reader = read_bytes if counts is not None else read_frame      # --device-decode: bytes ahead, pixels made on the GPU
@@ -304,9 +335,13 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
             add(item)
         assert writer.frames == len(paths), (writer.frames, len(paths))
         writer.close(session.track_txt)                     # (None without --device-vote: no txt is written here)
+        if fixed is not None:
+            fixed.close(session.lexicon_txt)
         write += time.time() - t0
     except BaseException:
         writer.abort()
+        if fixed is not None:
+            fixed.abort()
         raise
     time_cost["total_time"] += session.seconds
     return {"read": read, "window": session.seconds, "rows": session.rows_seconds + write, "max_wait": session.max_wait,
@@ -314,6 +349,18 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
 
 
 def main(argv=None):
+    """The command.  A `lexicon.LexiconError` from anywhere in the run -- the device path raises it inside the video loop for a
+    transcription above the length limit, as the host step does at the end -- ends it with a message and status 2; the
+    writers of the video at hand have dropped their unfinished files by then."""
+    from . import lexicon as _lexicon
+    try:
+        return run(argv)
+    except _lexicon.LexiconError as e:
+        sys.stderr.write("error: lexicon: %s\n" % e)
+        return 2
+
+
+def run(argv=None):
     args = get_parser(drawing=True).parse_args(argv)
     if args.online and (getattr(args, "show", False) or args.host_rows):
         sys.stderr.write("error: --online builds rows on the GPU and draws nothing: it takes neither --show nor --host-rows "
@@ -351,6 +398,10 @@ def main(argv=None):
     if args.device_vote and not args.device_write:
         sys.stderr.write("error: --device-vote votes over the rows --device-write leaves on the GPU: it goes with --device-write\n")
         return 2
+    if args.device_lexicon and not (args.lexicon is not None and args.device_write and args.device_vote):
+        sys.stderr.write("error: --device-lexicon corrects the rows --device-write and --device-vote leave on the GPU by the "
+                         "vocabulary of --lexicon: it goes with all three\n")
+        return 2
     if args.device_write:
         import torch
         if not torch.cuda.is_available():
@@ -378,6 +429,14 @@ def main(argv=None):
         sys.stderr.write("error: --lexicon %r / --lexicon-pairs %r not found, or a negative --lexicon-max-dist\n"
                          % (args.lexicon, args.lexicon_pairs))
         return 2
+    if args.device_lexicon:                                 # the limits of the device path, before anything is built or created
+        from . import lexicon as _lexicon
+        try:
+            lexicons = device_lexicons(args.lexicon, args.lexicon_pairs, args.input,
+                                       done=written_videos(os.path.join(args.output, "preds")))
+        except _lexicon.LexiconError as e:
+            sys.stderr.write("error: lexicon: %s\n" % e)
+            return 2
     cfg = _config.setup_cfg(config_file=args.config_file, opts=args.opts, builtin=args.builtin)
     state_dict = load_weights(cfg.MODEL.WEIGHTS)
     if state_dict is None:
@@ -402,6 +461,20 @@ def main(argv=None):
     total_frame, read_seconds, rows_seconds, draw_seconds = 0, 0.0, 0.0, 0.0
     routes = {k: 0 for k in DECODE_ROUTES} if args.device_decode else None
     voted = []                                              # --device-vote: the XMLs whose txt the GPU wrote in this run
+    corrected, fix_rows = [], [0, 0, 0]                     # --device-lexicon: the videos corrected on the GPU; kept, accepted, dropped
+
+    def row_correction(video_name):                         # (per-video lexicons: one DeviceLexicon per video)
+        if not args.device_lexicon:
+            return None
+        lex = lexicons if isinstance(lexicons, _lexicon.Lexicon) else lexicons[_results.result_names(video_name, data_type)[1]]
+        return _lexicon.RowCorrection(_lexicon.DeviceLexicon.of(lex, decoder, model.device), args.lexicon_max_dist,
+                                      args.lexicon_unmatched, video=video_name)
+
+    def corrected_video(video_name, fix):
+        if fix is not None:
+            corrected.append(_results.result_names(video_name, data_type)[1])
+            for k, v in enumerate((fix.rows, fix.accepted, fix.dropped)):
+                fix_rows[k] += v
     if args.show:
         from . import show as _show
         atlas = _show.Atlas(args.font)
@@ -413,7 +486,9 @@ def main(argv=None):
             if args.online:
                 if not paths:
                     continue
-                stats = spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, routes)
+                fix = row_correction(video_name)
+                stats = spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, routes, fix)
+                corrected_video(video_name, fix)
                 if args.device_vote:
                     voted.append("res_%s.xml" % _results.result_names(video_name, data_type)[0])
                 read_seconds += stats["read"]
@@ -443,9 +518,11 @@ def main(argv=None):
                 preds, per_video_time = _results.spot_video(spotter, frames, time_cost)
             total_frame += len(frames)
             t0 = time.time()
+            fix = row_correction(video_name)
             annotation = _results.write_video(preds, video_name, data_type, args.output, decoder,
                                               device_rows=not args.host_rows, device_text=args.device_write, rows=args.show,
-                                              device_vote=args.device_vote)
+                                              device_vote=args.device_vote, lexicon=fix)
+            corrected_video(video_name, fix)
             if args.device_vote:
                 voted.append("res_%s.xml" % _results.result_names(video_name, data_type)[0])
             rows_seconds += time.time() - t0
@@ -482,10 +559,13 @@ def main(argv=None):
         t0 = time.time()
         try:
             figures = _lexicon.correct_results(args.output, None, args.lexicon, args.lexicon_pairs, args.lexicon_max_dist,
-                                               args.lexicon_unmatched)
+                                               args.lexicon_unmatched, skip=corrected)
         except _lexicon.LexiconError as e:
             sys.stderr.write("error: lexicon: %s\n" % e)
             return 2
+        if args.device_lexicon:
+            print("device lexicon: ", len(corrected), " videos corrected on the GPU (", fix_rows[0], " kept rows, ", fix_rows[1],
+                  " accepted, ", fix_rows[2], " dropped), ", figures["videos"], " by the host from their json")
         print("lexicon: ", figures["rows"], " rows, ", figures["distinct"], " distinct strings matched, ", figures["changed"],
               " changed, ", figures["dropped"], " dropped -> ", figures["output"], ", seconds: ", time.time() - t0)
     return 0

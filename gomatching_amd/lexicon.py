@@ -20,6 +20,11 @@ pairs of the WHOLE result set go up in ONE upload, are matched by ONE `gom_lexic
 come back in ONE copy; `--host-match` runs `host_match`, the same rule in numpy vectorised over a segment's words, and
 writes the same bytes.
 
+`eval --device-lexicon` does not go through the files at all: `DeviceLexicon` (the words, the decoder's table of upper-cased
+code points and the three display tables of a Lexicon, uploaded once) and `RowCorrection` are what `results.rows_text` takes to
+correct a call's rows where they lie on the GPU (csrc/lexicon_rows.hip; the rule is in include/gomatching_hip.h,
+`gom_lexicon_rows_*`), and `correct_results(skip=)` leaves the videos corrected that way alone.  The bytes are the same.
+
 Deliberate differences: the correction applies per instance and the track vote is retaken (the reference has no tracks at
 that point); unmatched detections are kept by default, `--unmatched drop` removes their rows as the reference's `*_full` files
 do; strong lexicons are per video, not per image; blank lexicon lines are skipped (the reference would look up '').
@@ -214,6 +219,136 @@ def match_strings(items, lexicons, host=False):
     return (host_match if host else device_match)(q_chars, q_off, q_seg, w_chars, w_off, seg_off)
 
 
+# ------------------------------------------------------------------------------------------------- rows on the device
+NORM_WORDS = _ABI["GOM_LR_NORM_WORDS"]
+DISPLAY_TEXT_MAX = 25 * (_ABI["GOM_RT_ENTRY_BYTES"] - 1)         # a JSON or XML display form: no longer than 25 table entries
+DISPLAY_TXT_MAX = 4 * _ABI["GOM_TV_TEXT_WORDS"]                   # a txt display form: what a vote record holds
+
+
+def norm_table(decoder):
+    """The per-vocabulary table of the device queries (include/gomatching_hip.h, `gom_lexicon_rows_*`), int32 [voc_size - 1, 4]:
+    a count and the code points of label.upper().  `str.upper` works character by character (tests/test_lexicon_rows_cpu.py), so
+    the query of a row is its characters' entries, one after another.  A label that is not one character, or whose upper-case
+    form has more than 3 code points, is a ValueError naming the entry."""
+    labels = list(decoder.labels)
+    tab = np.zeros((len(labels), NORM_WORDS), dtype=np.int32)
+    for i, ch in enumerate(labels):
+        up = norm(ch)
+        if len(ch) != 1 or len(up) > NORM_WORDS - 1:
+            raise ValueError("dictionary entry %d (%r) is upper-cased to %d code points, a norm-table entry holds %d"
+                             % (i, ch, len(up), NORM_WORDS - 1))
+        tab[i, 0] = len(up)
+        tab[i, 1:1 + len(up)] = [ord(c) for c in up]
+    return tab
+
+
+def txt_form(text):
+    """`text` as `results.write_track_transcriptions` reads it back from the XML minidom wrote it into (the round trip of
+    `results.txt_table`, over a whole string)."""
+    import xml.etree.ElementTree as ET
+    parser = ET.XMLParser(encoding="utf-8")
+    parser.feed(('<a v="%s"/>' % _results._xml_attribute(text)).encode("utf-8"))
+    return parser.close().attrib["v"]
+
+
+def display_tables(lex, shortcut=True):
+    """The three display tables of a Lexicon, each (bytes uint8 [>= 1], offsets int32 [W + 1], bytes in use): entry i is the
+    display form of word i as the JSON writer, the XML writer and the txt reader have it, over the whole form.  A form above
+    its stream's limit, or one a writer cannot take, is a LexiconError naming the file and the word.
+    The libraries are asked once per distinct character whether all three leave it as it is (they work character by character:
+    `results.text_tables`, `results.txt_table`); a form of such characters alone is its own UTF-8 bytes in all three tables, any
+    other form goes through the libraries whole.  shortcut=False sends every form through the libraries whole: the same tables
+    (tests/test_lexicon_rows_cpu.py compares the two)."""
+    forms = [[], [], []]
+    plain = {}
+
+    def is_plain(ch):
+        if ch not in plain:
+            try:
+                ch.encode("utf-8")
+                plain[ch] = json.dumps(ch, ensure_ascii=False)[1:-1] == ch and _results._xml_attribute(ch) == ch and txt_form(ch) == ch
+            except Exception:
+                plain[ch] = False
+        return plain[ch]
+
+    for i in range(len(lex)):
+        d = str(lex.display(i))
+        try:
+            if shortcut and all(is_plain(ch) for ch in d):
+                data = [d.encode("utf-8")] * 3
+            else:
+                texts = (json.dumps(d, ensure_ascii=False)[1:-1], _results._xml_attribute(d), txt_form(d))
+                data = [t.encode("utf-8") for t in texts]
+        except Exception as e:                                   # (the XML parser's own error type, UnicodeEncodeError, ...)
+            raise LexiconError("%s: word %d (%r): the display form %r cannot be written (%s)" % (lex.path, i + 1, lex.words[i], d, e))
+        for b, limit, name in zip(data, (DISPLAY_TEXT_MAX, DISPLAY_TEXT_MAX, DISPLAY_TXT_MAX), ("JSON", "XML", "txt")):
+            if len(b) > limit:
+                raise LexiconError("%s: word %d (%r): the display form %r is %d bytes in the %s file, the device path takes at "
+                                   "most %d (run without --device-lexicon)" % (lex.path, i + 1, lex.words[i], d, len(b), name, limit))
+        for k in range(3):
+            forms[k].append(data[k])
+    out = []
+    for items in forms:
+        off = np.zeros(len(items) + 1, dtype=np.int64)
+        np.cumsum([len(b) for b in items], out=off[1:])
+        if off[-1] > 2 ** 31 - 1:
+            raise LexiconError("%s: more than 2^31 - 1 bytes of display forms" % lex.path)
+        data = np.frombuffer(b"".join(items) or b"\0", dtype=np.uint8).copy()
+        out.append((data, off.astype(np.int32), int(off[-1])))
+    return out
+
+
+def checked_display_tables(lex):
+    """`display_tables(lex)`, built once per Lexicon and kept on it: the host check of the device path's limits (a command
+    runs it for every lexicon it needs before it builds or uploads anything) and what `DeviceLexicon` uploads."""
+    if "_display_tables" not in lex.__dict__:
+        lex.__dict__["_display_tables"] = display_tables(lex)
+    return lex.__dict__["_display_tables"]
+
+
+class DeviceLexicon:
+    """One Lexicon on one device, for `results.rows_text(lexicon=...)`: the words' code points (CSR, one segment), the three
+    display tables and the decoder's norm table, uploaded once.  `DeviceLexicon.of` caches per (lexicon, decoder, device); the
+    limits of the display forms are checked here, before any upload."""
+
+    def __init__(self, lex, decoder, device):
+        import torch
+        if not torch.cuda.is_available():
+            raise NoDeviceError("no GPU: rows are corrected by csrc/lexicon_rows.hip")
+        self.lexicon, self.decoder, self.device = lex, decoder, device
+        tables = checked_display_tables(lex)                     # (raises before anything is uploaded)
+        norm_tab = norm_table(decoder)
+        w_chars, w_off = pack(lex.normal)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        self.W = len(lex)
+        self.w_chars, self.w_off = up(w_chars), up(w_off)
+        self.seg_off = up(np.asarray([0, self.W], dtype=np.int32))
+        self.norm_tab = up(norm_tab)
+        self.json_disp, self.xml_disp, self.txt_disp = [(up(d), up(o), nb) for d, o, nb in tables]
+
+    @classmethod
+    def of(cls, lex, decoder, device):
+        cache = lex.__dict__.setdefault("_device", {})
+        key = (tuple(decoder.labels), str(device))               # (the vocabulary itself: an id may be reused)
+        if key not in cache:
+            cache[key] = cls(lex, decoder, device)
+        return cache[key]
+
+
+class RowCorrection:
+    """What `results.rows_text` needs to correct a call's rows: a DeviceLexicon, the acceptance (`max_dist`, `unmatched`), the
+    `results.TrackVote` of the corrected words, and where the rows come from (for the error that names video and frame).  The
+    figures of the device path add up in `rows` (kept rows in), `accepted` and `dropped`."""
+
+    def __init__(self, device_lexicon, max_dist=1, unmatched="keep", vote=None, video="<video>"):
+        if unmatched not in ("keep", "drop"):
+            raise ValueError("unmatched must be 'keep' or 'drop', not %r" % (unmatched,))
+        if max_dist < 0:
+            raise ValueError("max_dist must not be negative")
+        self.lexicon, self.max_dist, self.unmatched, self.vote, self.video = device_lexicon, int(max_dist), unmatched, vote, video
+        self.rows = self.accepted = self.dropped = 0
+
+
 # ------------------------------------------------------------------------------------------------- annotations
 def correct_annotations(annotations, lexicons, max_dist=1, unmatched="keep", host=False):
     """annotations {video: {frame: [rows]}} (rows as `results.write_video_results` takes them), lexicons {video: Lexicon} or
@@ -315,17 +450,22 @@ def load_lexicons(lexicon, pairs, videos):
     return load_lexicon(lexicon, pairs)
 
 
-def correct_results(results_dir, out_dir=None, lexicon=None, pairs=None, max_dist=1, unmatched="keep", host=False):
+def correct_results(results_dir, out_dir=None, lexicon=None, pairs=None, max_dist=1, unmatched="keep", host=False, skip=()):
     """RES/jsons/*.json -> OUT/jsons, OUT/preds (xml and txt) with corrected transcriptions; -> the figures of
-    `correct_annotations`.  One match call for the whole directory."""
+    `correct_annotations`.  One match call for the whole directory.  `skip`: videos (the json stems) that are left alone -- those
+    whose corrected files, the txt included, the device path wrote already (`results.rows_text(lexicon=)`); their files are
+    neither read nor written, and the figures do not count them."""
     json_dir, xml_dir = os.path.join(results_dir, "jsons"), os.path.join(results_dir, "preds")
     for d in (results_dir, json_dir, xml_dir):
         if not os.path.isdir(d):
             raise LexiconError("%s: no such directory" % d)
     if out_dir is None:
         out_dir = os.path.join(results_dir, "lexicon")
+    skip = frozenset(skip)
     videos = sorted(f[:-len(".json")] for f in os.listdir(json_dir) if f.endswith(".json"))
     stems = {v: xml_stem(v, xml_dir) for v in videos}
+    skipped_xml = ["res_%s.xml" % stems[v] for v in videos if v in skip]
+    videos = [v for v in videos if v not in skip]
     lexicons = load_lexicons(lexicon, pairs, videos)
     annotations = {v: read_annotation(os.path.join(json_dir, v + ".json")) for v in videos}
     fixed, figures = correct_annotations(annotations, lexicons, max_dist, unmatched, host)
@@ -334,7 +474,7 @@ def correct_results(results_dir, out_dir=None, lexicon=None, pairs=None, max_dis
     os.makedirs(out_xml, exist_ok=True)
     for v in videos:
         _results.write_video_results(fixed[v], os.path.join(out_json, v + ".json"), os.path.join(out_xml, "res_%s.xml" % stems[v]))
-    _results.write_track_transcriptions(out_xml)
+    _results.write_track_transcriptions(out_xml, skip=skipped_xml)
     figures["output"] = out_dir
     return figures
 

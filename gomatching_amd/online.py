@@ -148,17 +148,28 @@ class OnlineSpotter:
     device_vote=True (with device_text=True): every gather's words and keep flags also go to a `results.TrackVote` -- only
     settled rows reach it, the rows the offline path keeps -- and `close()` leaves the bytes of preds/res_<video>.txt in
     `track_txt` for `VideoResultWriter.close`.  The vote's log, 112 bytes per row, is the one thing a session holds that grows
-    with the video."""
+    with the video.
+
+    device_lexicon=a `lexicon.RowCorrection` (with device_text=True and device_vote=True): every gather's rows are also corrected
+    by the video's lexicon where they lie (csrc/lexicon_rows.hip: the correction is per row, only the vote waits for `close()`);
+    the items `push` / `close()` return carry the corrected json and xml bytes as a fifth and sixth element, for a second
+    `VideoResultWriter` rooted at <out>/lexicon, and `close()` leaves the vote over the corrected words in `lexicon_txt`."""
 
     def __init__(self, cfg, model, decoder, device_ingest=True, time_cost=None, min_extent=5, device_text=False,
-                 device_vote=False):
+                 device_vote=False, device_lexicon=None):
         import torch
         self.device_text = bool(device_text)
         if device_vote and not device_text:
             raise ValueError("device_vote=True votes over the rows device_text=True leaves on the GPU: it needs device_text=True")
+        if device_lexicon is not None and not (device_text and device_vote):
+            raise ValueError("device_lexicon corrects the rows on the GPU: it needs device_text=True and device_vote=True")
         from . import results as _results
         self._vote = _results.TrackVote(decoder) if device_vote else None
         self.track_txt = None                                    # device_vote=True: the txt file's bytes, from `close()` on
+        self._lexicon = device_lexicon
+        self.lexicon_txt = None                                  # device_lexicon: the corrected txt file's bytes, from `close()` on
+        if device_lexicon is not None:
+            device_lexicon.vote = _results.TrackVote(decoder)
         from .predictor import GoMBatchPredictor, new_time_cost
         self.cfg, self.model, self.decoder, self.min_extent = cfg, model, decoder, min_extent
         self.predictor = GoMBatchPredictor(cfg, model, device_ingest=device_ingest)
@@ -232,6 +243,8 @@ class OnlineSpotter:
         if self._vote is not None:
             t0 = time.time()
             self.track_txt = self._vote.finish()
+            if self._lexicon is not None:
+                self.lexicon_txt = self._lexicon.vote.finish()
             self.rows_seconds += time.time() - t0
         return self._take()
 
@@ -320,11 +333,11 @@ class OnlineSpotter:
             b = min(a + step, len(ready))
             r0, r1 = int(offsets[a]), int(offsets[b])
             if r1 > r0:                                          # (the copy of the text back waits for the launches: the ring
-                js, xs = results.rows_text(words_d[r0:r1], offsets[a:b + 1] - r0, first + a, self.decoder, self.min_extent,
-                                           vote=self._vote)
+                text = results.rows_text(words_d[r0:r1], offsets[a:b + 1] - r0, first + a, self.decoder, self.min_extent,
+                                         vote=self._vote, lexicon=self._lexicon)
             else:                                                #  slots may be rewritten afterwards)
-                js, xs = results.host_text_of_empty_frames(first + a, b - a)
-            self._out.append((first + a, b - a, js, xs))
+                text = results.host_text_of_empty_frames(first + a, b - a) * (2 if self._lexicon is not None else 1)
+            self._out.append((first + a, b - a) + tuple(text))
         self.rows_seconds += time.time() - t0
         self._ring_tail = ready[-1][0] + 1
 

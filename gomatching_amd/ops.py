@@ -1540,7 +1540,16 @@ RESULT_TEXT_ENTRY_BYTES = _lib_mod.CONSTANTS["GOM_RT_ENTRY_BYTES"]
 RESULT_TEXT_SCAN_BLOCK = _lib_mod.CONSTANTS["GOM_RT_SCAN_BLOCK"]
 
 
-def result_text(words, pts, keep, frame_rows, first_frame, tables):
+def _chk_display(dev, name, table, W):
+    """A display table of `lexicon.DeviceLexicon`: (bytes uint8 [>= 1] CUDA, offsets int32 [W + 1] CUDA, the bytes in use)."""
+    data, off, nbytes = table
+    _chk_i(dev, (name + " display bytes", data, torch.uint8, (None,)), (name + " display offsets", off, torch.int32, (W + 1,)))
+    if data.shape[0] < 1 or not 0 <= int(nbytes) <= data.shape[0]:
+        raise ValueError("%s display table: %d bytes in use of %d (at least one is allocated)" % (name, nbytes, data.shape[0]))
+    return _p(data), _p(off), int(nbytes)
+
+
+def result_text(words, pts, keep, frame_rows, first_frame, tables, ov=None, read_with=None):
     """The JSON and XML text of the frames of one call, formatted on the GPU (csrc/result_text.hip; THE RULE is in
     include/gomatching_hip.h, `gom_result_text_*`): words int32 [n, >= RESULT_ROWS_WORDS] as `result_rows` /
     `result_rows_gather` left them, pts int64 [n, 8] and keep uint8 [n] (`results.finish_points`), all CUDA; frame_rows: host
@@ -1549,7 +1558,12 @@ def result_text(words, pts, keep, frame_rows, first_frame, tables):
     -> (json u8 tensor, xml u8 tensor, json_frame_off, xml_frame_off): the bytes between the files' header and footer, and int64
     [F + 1] offsets of every frame in each.  Three launches (count and scan, then emit) around ONE synchronising read, the two
     totals, from which the buffers are allocated.  F == 0 gives empty tensors and n == 0 frames without rows, both without a
-    launch.  An emitted character id outside the tables raises GomError: nothing was read through it."""
+    launch.  An emitted character id outside the tables raises GomError: nothing was read through it.
+    ov = (ov int32 [n], keep_out uint8 [n], json display table, xml display table): the `_ov` entries (the rule of
+    `gom_lexicon_rows_*`) -- a row with ov[r] >= 0 takes its transcription from that entry of the display tables
+    (`lexicon.DeviceLexicon`), a row writes iff keep[r] and keep_out[r].
+    read_with = an int64 CUDA vector that comes back in the SAME copy as the totals (the apply step's counts: no second
+    synchronising read); its values are then a fifth element of the result, a list."""
     if not words.is_cuda or words.dtype != torch.int32 or words.dim() != 2 or words.shape[1] < RESULT_ROWS_WORDS or \
             words.stride(1) != 1 and words.shape[0] > 0:
         raise ValueError("words must be a CUDA int32 [n, >= %d] tensor with unit column stride" % RESULT_ROWS_WORDS)
@@ -1566,13 +1580,19 @@ def result_text(words, pts, keep, frame_rows, first_frame, tables):
         raise ValueError("frame_rows must be non-decreasing offsets from 0 to n = %d" % n)
     if first_frame < 0 or first_frame + F > 2 ** 31 - 2:
         raise ValueError("first_frame + F must fit 31 bits")
+    if ov is not None:
+        ov_t, keep_out, json_disp, xml_disp = ov
+        W = json_disp[1].shape[0] - 1
+        _chk_i(dev, ("ov", ov_t, torch.int32, (n,)), ("keep_out", keep_out, torch.uint8, (n,)))
+        ov_args = (_p(ov_t), _p(keep_out)) + _chk_display(dev, "json", json_disp, W) + _chk_display(dev, "xml", xml_disp, W) + (W,)
     if F == 0 or n == 0:
         from . import results as _results
         js, xs = _results.host_text_of_empty_frames(first_frame, F)
         joff = np.cumsum([0] + [len(_results.host_text_of_empty_frames(f, 1)[0]) for f in range(first_frame, first_frame + F)])
         xoff = np.cumsum([0] + [len(_results.host_text_of_empty_frames(f, 1)[1]) for f in range(first_frame, first_frame + F)])
         u8 = lambda b: torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()).to(dev)
-        return u8(js), u8(xs), torch.from_numpy(joff.astype(np.int64)).to(dev), torch.from_numpy(xoff.astype(np.int64)).to(dev)
+        out = (u8(js), u8(xs), torch.from_numpy(joff.astype(np.int64)).to(dev), torch.from_numpy(xoff.astype(np.int64)).to(dev))
+        return out if read_with is None else out + (read_with.tolist(),)
     if ntab < 1:
         raise ValueError("empty tables")
     ld = words.stride(0) if n > 1 else words.shape[1]
@@ -1584,15 +1604,26 @@ def result_text(words, pts, keep, frame_rows, first_frame, tables):
         frame_off = torch.empty((2, F + 1), dtype=torch.int64, device=dev)
         totals = torch.empty((_lib_mod.CONSTANTS["GOM_RT_TOTALS"],), dtype=torch.int64, device=dev)
         common = (_p(words), ld, _p(pts), _p(keep), n, _p(frame_rows_d), F, first_frame, _p(json_tab), _p(xml_tab), ntab)
-        _call("gom_result_text_count_scan", *common, _p(row_len), _p(row_off), _p(row_kept), _p(frame_off), _p(totals), _stream())
-        jt, xt, status, _ = totals.tolist()                  # the one synchronising read
+        sfx = ""
+        if ov is not None:
+            common, sfx = common + ov_args, "_ov"
+        _call("gom_result_text_count_scan" + sfx, *common, _p(row_len), _p(row_off), _p(row_kept), _p(frame_off), _p(totals),
+              _stream())
+        if read_with is not None:
+            _chk_i(dev, ("read_with", read_with, torch.int64, (None,)))
+            both = torch.cat((totals, read_with)).tolist()   # the one synchronising read, the caller's counts riding along
+            (jt, xt, status, _), rode = both[:4], both[4:]
+        else:
+            jt, xt, status, _ = totals.tolist()              # the one synchronising read
         if status:
             raise _lib_mod.GomError("result_text: an emitted character id lies outside the %d-entry tables (status %d)"
                                     % (ntab, status))
         js = torch.empty((jt,), dtype=torch.uint8, device=dev)
         xs = torch.empty((xt,), dtype=torch.uint8, device=dev)
-        _call("gom_result_text_emit", *common, _p(row_len), _p(row_off), _p(row_kept), _p(frame_off), _p(js), jt, _p(xs), xt,
+        _call("gom_result_text_emit" + sfx, *common, _p(row_len), _p(row_off), _p(row_kept), _p(frame_off), _p(js), jt, _p(xs), xt,
               _stream())
+    if read_with is not None:
+        return js, xs, frame_off[0], frame_off[1], rode
     return js, xs, frame_off[0], frame_off[1]
 
 
@@ -1601,11 +1632,13 @@ TRACK_VOTE_ENTRY_MAX = _lib_mod.CONSTANTS["GOM_TV_ENTRY_MAX"]
 TRACK_VOTE_BLOCK = _lib_mod.CONSTANTS["GOM_TV_BLOCK"]
 
 
-def track_vote_records(words, keep, table):
+def track_vote_records(words, keep, table, ov=None):
     """One record per row of a call (csrc/track_vote.hip; THE RULE is in include/gomatching_hip.h, `gom_track_vote_*`): words
     int32 [n, >= RESULT_ROWS_WORDS] as `result_rows` / `result_rows_gather` left them, keep uint8 [n], table uint8
     [voc_size - 1, 8] (`results.txt_table`), all CUDA -> int32 [n, TRACK_VOTE_RECORD_WORDS]: track id low / high, the text's byte
-    length (-1: the row does not vote, -2: an emitted id outside the table), 25 words of text bytes.  One launch, no read back."""
+    length (-1: the row does not vote, -2: an emitted id outside the table), 25 words of text bytes.  One launch, no read back.
+    ov = (ov int32 [n], keep_out uint8 [n], txt display table): `gom_track_vote_records_ov_i32` -- a row with ov[r] >= 0 takes
+    its text from that entry of the display table, a row votes iff keep[r] and keep_out[r]."""
     if not words.is_cuda or words.dtype != torch.int32 or words.dim() != 2 or words.shape[1] < RESULT_ROWS_WORDS or \
             words.stride(1) != 1 and words.shape[0] > 0:
         raise ValueError("words must be a CUDA int32 [n, >= %d] tensor with unit column stride" % RESULT_ROWS_WORDS)
@@ -1619,7 +1652,14 @@ def track_vote_records(words, keep, table):
         raise ValueError("an empty table")
     ld = words.stride(0) if n > 1 else words.shape[1]
     with torch.cuda.device(dev):
-        _call("gom_track_vote_records_i32", _p(words), ld, _p(keep), n, _p(table), ntab, _p(records), _stream())
+        if ov is not None:
+            ov_t, keep_out, disp = ov
+            W = disp[1].shape[0] - 1
+            _chk_i(dev, ("ov", ov_t, torch.int32, (n,)), ("keep_out", keep_out, torch.uint8, (n,)))
+            _call("gom_track_vote_records_ov_i32", _p(words), ld, _p(keep), n, _p(table), ntab, _p(ov_t), _p(keep_out),
+                  *(_chk_display(dev, "txt", disp, W) + (W, _p(records), _stream())))
+        else:
+            _call("gom_track_vote_records_i32", _p(words), ld, _p(keep), n, _p(table), ntab, _p(records), _stream())
     return records
 
 
@@ -1863,6 +1903,59 @@ def lexicon_match(q_chars, q_off, q_seg, w_chars, w_off, seg_off, max_len=None, 
         _call("gom_lexicon_match_u32", _p(q_chars), q_chars.shape[0], _p(q_off), _p(q_seg), S, _p(w_chars), w_chars.shape[0],
               _p(w_off), W, _p(seg_off), n_seg, int(max_len), _p(out[0]), _p(out[1]), _stream())
     return out[0], out[1]
+
+
+LEXICON_ROWS_NORM_WORDS = _lib_mod.CONSTANTS["GOM_LR_NORM_WORDS"]
+LEXICON_ROWS_TOTALS = _lib_mod.CONSTANTS["GOM_LR_TOTALS"]
+
+
+def lexicon_rows_queries(words, keep, norm_tab):
+    """The lexicon queries of a call's rows (csrc/lexicon_rows.hip; THE RULE is in include/gomatching_hip.h, `gom_lexicon_rows_*`):
+    words int32 [n, >= RESULT_ROWS_WORDS], keep uint8 [n], norm_tab int32 [voc_size - 1, 4] (`lexicon.norm_table`: a count and the
+    code points of label.upper()), all CUDA -> (q_chars int32 [64 n], q_off int32 [n + 1], q_len int32 [n], q_status int32 [2]):
+    the code points of every row's query as `lexicon_match` takes them (CSR; the buffer is sized by the limit, so nothing is read
+    back), the lengths (-1: above the limit) and {status, first row above the limit}.  Three launches, no read back."""
+    if not words.is_cuda or words.dtype != torch.int32 or words.dim() != 2 or words.shape[1] < RESULT_ROWS_WORDS or \
+            words.stride(1) != 1 and words.shape[0] > 0:
+        raise ValueError("words must be a CUDA int32 [n, >= %d] tensor with unit column stride" % RESULT_ROWS_WORDS)
+    dev, n = words.device, words.shape[0]
+    ntab = norm_tab.shape[0]
+    _chk_i(dev, ("keep", keep, torch.uint8, (n,)), ("norm table", norm_tab, torch.int32, (ntab, LEXICON_ROWS_NORM_WORDS)))
+    if ntab < 1:
+        raise ValueError("an empty norm table")
+    if n > _lib_mod.CONSTANTS["GOM_LR_MAX_ROWS"]:
+        raise ValueError("more than %d rows in one call" % _lib_mod.CONSTANTS["GOM_LR_MAX_ROWS"])
+    q_cap = n * LEXICON_MAX_LEN
+    q_chars = torch.empty((q_cap,), dtype=torch.int32, device=dev)
+    q_off = torch.zeros((n + 1,), dtype=torch.int32, device=dev)
+    q_len = torch.empty((n,), dtype=torch.int32, device=dev)
+    q_status = torch.zeros((2,), dtype=torch.int32, device=dev)
+    ld = words.stride(0) if n > 1 else words.shape[1]
+    with torch.cuda.device(dev):
+        _call("gom_lexicon_rows_queries_u32", _p(words), ld, _p(keep), n, _p(norm_tab), ntab, _p(q_len), _p(q_off), _p(q_status),
+              _p(q_chars), q_cap, _stream())
+    return q_chars, q_off, q_len, q_status
+
+
+def lexicon_rows_apply(keep, q_len, q_status, best_index, best_dist, W, max_dist=1, drop=False):
+    """The apply step of `gom_lexicon_rows_*`: keep uint8 [n], q_len int32 [n], q_status int32 [2] (`lexicon_rows_queries`),
+    best_index / best_dist int32 [n] (`lexicon_match`), all CUDA; W = the lexicon's words -> (ov int32 [n]: the accepted word's
+    index or -1, keep_out uint8 [n], totals int64 [5] = {kept rows in, accepted, dropped, status, first row above the limit}),
+    on the device.  One launch, no read back."""
+    dev, n = keep.device, keep.shape[0]
+    _chk_i(dev, ("keep", keep, torch.uint8, (n,)), ("q_len", q_len, torch.int32, (n,)), ("q_status", q_status, torch.int32, (2,)),
+           ("best_index", best_index, torch.int32, (n,)), ("best_dist", best_dist, torch.int32, (n,)))
+    if W < 0 or max_dist < 0:
+        raise ValueError("W and max_dist must not be negative")
+    ov = torch.empty((n,), dtype=torch.int32, device=dev)
+    keep_out = torch.empty((n,), dtype=torch.uint8, device=dev)
+    totals = torch.zeros((LEXICON_ROWS_TOTALS,), dtype=torch.int64, device=dev)
+    if n == 0:
+        totals[_lib_mod.CONSTANTS["GOM_LR_FIRST_LONG"]] = -1
+    with torch.cuda.device(dev):
+        _call("gom_lexicon_rows_apply_i32", _p(keep), _p(q_len), _p(q_status), _p(best_index), _p(best_dist), n, int(W),
+              int(max_dist), 1 if drop else 0, _p(ov), _p(keep_out), _p(totals), _stream())
+    return ov, keep_out, totals
 
 
 JPEG_MAX_WIDTH, JPEG_MAX_HEIGHT = _lib_mod.CONSTANTS["GOM_JPEG_MAX_WIDTH"], _lib_mod.CONSTANTS["GOM_JPEG_MAX_HEIGHT"]

@@ -914,6 +914,80 @@ int gom_overlay_compose_u8(const uint8_t* frames, uint8_t* out, int F, int H, in
 int gom_lexicon_match_u32(const uint32_t* q_chars, long q_nchars, const int32_t* q_off, const int32_t* q_seg, int S,
                           const uint32_t* w_chars, long w_nchars, const int32_t* w_off, int W, const int32_t* seg_off,
                           int n_seg, int max_len, int32_t* best_index, int32_t* best_dist, void* stream);
+/* ---- Lexicon correction of rows on the device (csrc/lexicon_rows.hip, csrc/lexicon_rows_core.h; eval --device-lexicon) ------
+ * The corrected files OUT/lexicon/{jsons,preds} made from the rows where they lie, in the call that formats the original files:
+ * nothing is parsed and nothing is dumped.  THE RULE: the bytes are those `lexicon.correct_results` writes from the original
+ * files; spelled out below so that the kernels, the shared core (built for the host by tools/lexicon_rows_hostcheck.cpp) and
+ * the plain-Python statement (tests/lexicon_rows_statement.py) agree byte for byte.
+ *   Query of a row : for c = 0 .. 24 in order, where bit c of word GOM_RR_EMIT is set: the entry of id = word GOM_RR_RECS + c in
+ *                   the norm table, uint32 [ntab][GOM_LR_NORM_WORDS] with ntab = voc_size - 1: word 0 = a count 0 .. 3 (a larger
+ *                   one counts as 3), then the code points of label.upper() (`str.upper` works character by character and gives
+ *                   at most 3 code points: lexicon.norm_table builds the entries from it and refuses anything else).  The query
+ *                   is those code points one after another: lexicon.norm of the row's text.  A row with keep == 0 has the empty
+ *                   query and its match is ignored.  An emitted id outside [0, ntab) is never used as an index: its row has the
+ *                   empty query (the result text flags it: GOM_RT_BAD_ID).  A kept row whose query has more than
+ *                   GOM_LEXICON_MAX_LEN code points has the length GOM_LR_LEN_LONG, is matched as the empty query, is never
+ *                   accepted and sets q_status = {GOM_LR_TOO_LONG, the first such row} ({0, -1} otherwise); the wrapper raises.
+ *   Match          : gom_lexicon_match_u32 as it is, one segment per call (the video's lexicon), a query per row: equal strings
+ *                   are not deduplicated.
+ *   Apply          : a row is accepted when keep and 0 <= index < W and dist <= max_dist.  ov[r] = index (the word's index
+ *                   within its lexicon) for an accepted row, -1 for any other.  keep_out[r] = keep[r] and accepted with
+ *                   drop = 1 (`unmatched = drop`), keep[r] with drop = 0.  totals int64 [GOM_LR_TOTALS] = {kept rows in,
+ *                   accepted, dropped, q_status[0], q_status[1]}.
+ *   Text of a row  : with ov[r] < 0 exactly what it is without a lexicon (the character tables).  With ov[r] = i entry i of the
+ *                   stream's DISPLAY TABLE, as it is: a CSR byte table over the lexicon's W words, u8 bytes [dbytes] and int32
+ *                   off [W + 1], built on the host from the libraries themselves over the WHOLE display form d = pairs[norm(w_i)]:
+ *                   JSON json.dumps(d, ensure_ascii=False) without its quotes, XML minidom's attribute value, txt that value as
+ *                   write_track_transcriptions' parser reads it back.  A JSON or XML form is at most 175 bytes (25 *
+ *                   (GOM_RT_ENTRY_BYTES - 1): a row is no longer than the longest one without a lexicon), a txt form at most 100
+ *                   (4 * GOM_TV_TEXT_WORDS); the host refuses a longer one before any upload, the kernels cut it.  An index or
+ *                   an offset outside its table gives the empty form.  The vote still compares text bytes: an accepted row and
+ *                   one that is not, with equal bytes, agree.
+ * gom_lexicon_rows_queries_u32: count (a lane per row) / scan (ONE block, tiles of GOM_LR_BLOCK) / emit (a lane per row, one writer
+ *   per word): q_len int32 [n], q_off int32 [n + 1] (CSR over q_chars; rows flagged GOM_LR_LEN_LONG own nothing), q_status int32
+ *   [2], q_chars uint32 [q_cap] with q_cap >= n * GOM_LEXICON_MAX_LEN, so that no size has to be read back.  The offsets are
+ *   int32: GOM_LR_MAX_ROWS is the largest n with n * GOM_LEXICON_MAX_LEN <= INT32_MAX.
+ * gom_lexicon_rows_apply_i32: ONE block; ov int32 [n], keep_out u8 [n], totals.
+ * gom_result_text_count_scan_ov / gom_result_text_emit_ov / gom_track_vote_records_ov_i32: the entries without `_ov` (their
+ *   contracts, launches and checks) with ov, keep_out (a row writes and votes iff keep[r] and keep_out[r]) and the display
+ *   table(s); with ov all -1 and keep_out = keep they leave the bytes of the entries without `_ov`.
+ * No atomics, no scratch, plain stores, one writer per output word and byte; every index made from device data is checked or
+ * clamped, every store checked against the counted extent and the cap; bitwise reproducible.  GOM_ERR_INVALID_ARG before any
+ * HIP call: a null pointer, n < 0 or n > GOM_LR_MAX_ROWS, ld < GOM_RESULT_ROWS_WORDS, ntab < 1, q_cap < n * GOM_LEXICON_MAX_LEN,
+ * W < 0, max_dist < 0, drop outside {0, 1}, a negative dbytes.  n == 0 is GOM_OK without a launch (the `_ov` text entries keep
+ * n >= 1, as the entries without `_ov` do). */
+#define GOM_LR_NORM_WORDS 4
+#define GOM_LR_LEN_LONG -1
+#define GOM_LR_TOO_LONG 1
+#define GOM_LR_BLOCK 256
+#define GOM_LR_MAX_ROWS 33554431
+#define GOM_LR_TOTALS 5
+#define GOM_LR_KEPT 0
+#define GOM_LR_ACCEPTED 1
+#define GOM_LR_DROPPED 2
+#define GOM_LR_STATUS 3
+#define GOM_LR_FIRST_LONG 4
+int gom_lexicon_rows_queries_u32(const int32_t* words, int ld, const uint8_t* keep, int n, const uint32_t* norm_tab, int ntab,
+                                 int32_t* q_len, int32_t* q_off, int32_t* q_status, uint32_t* q_chars, long q_cap,
+                                 void* stream);
+int gom_lexicon_rows_apply_i32(const uint8_t* keep, const int32_t* q_len, const int32_t* q_status, const int32_t* best_index,
+                               const int32_t* best_dist, int n, int W, int max_dist, int drop, int32_t* ov, uint8_t* keep_out,
+                               int64_t* totals, void* stream);
+int gom_result_text_count_scan_ov(const int32_t* words, int ld, const int64_t* pts, const uint8_t* keep, int n,
+                                  const int32_t* frame_rows, int F, long first_frame, const uint8_t* json_tab,
+                                  const uint8_t* xml_tab, int ntab, const int32_t* ov, const uint8_t* keep_out,
+                                  const uint8_t* json_disp, const int32_t* json_doff, long json_dbytes, const uint8_t* xml_disp,
+                                  const int32_t* xml_doff, long xml_dbytes, int W, int32_t* row_len, int64_t* row_off,
+                                  int32_t* row_kept, int64_t* frame_off, int64_t* totals, void* stream);
+int gom_result_text_emit_ov(const int32_t* words, int ld, const int64_t* pts, const uint8_t* keep, int n,
+                            const int32_t* frame_rows, int F, long first_frame, const uint8_t* json_tab, const uint8_t* xml_tab,
+                            int ntab, const int32_t* ov, const uint8_t* keep_out, const uint8_t* json_disp,
+                            const int32_t* json_doff, long json_dbytes, const uint8_t* xml_disp, const int32_t* xml_doff,
+                            long xml_dbytes, int W, const int32_t* row_len, const int64_t* row_off, const int32_t* row_kept,
+                            const int64_t* frame_off, uint8_t* json, long json_cap, uint8_t* xml, long xml_cap, void* stream);
+int gom_track_vote_records_ov_i32(const int32_t* words, int ld, const uint8_t* keep, int n, const uint8_t* txt_tab, int ntab,
+                                  const int32_t* ov, const uint8_t* keep_out, const uint8_t* txt_disp, const int32_t* txt_doff,
+                                  long txt_dbytes, int W, int32_t* records, void* stream);
 /* ---- JPEG encoding of drawn frames (csrc/jpeg.hip; gomatching_amd/jpeg.py; show --device-encode) -------------------
  * Baseline sequential DCT, 8 bits, three components at 4:2:0 (sampling (2,2), (1,1), (1,1)) in a JFIF 1.01 container: the
  * layout of Pillow's `save(quality=q)`, with a restart interval per MCU row so that every MCU row is coded independently.
