@@ -14,6 +14,9 @@
 // is read once and written once by its own lane, so `out` may be `frames`, and the result does not depend on the launch
 // geometry.  Rows are 3 W bytes and start at any byte alignment: a lane moves its 12 bytes as three dwords where they are
 // 4-byte aligned (lanes are 12 bytes apart, so a wave's lanes agree) and byte by byte otherwise and at the ragged end of a row.
+// compose_gather_kernel is the same body with one other source address: frame f is read from slot slots[f] of a ring of frames
+// (the online session's pending frames, online.py) and written to a dense `out` -- one launch whatever the ring's wrap, and no
+// index_select pass over F H W 3 bytes first.  The slot is clamped into the ring; the `wide` test stays per address.
 // Offsets, boxes, positions and atlas indices are device data the host cannot vouch for: every index made from them is clamped
 // or tested against its buffer.
 #include "common.h"
@@ -64,9 +67,14 @@ __global__ __launch_bounds__(OV_FILL_THREADS) void outline_polygon_kernel(
 // blend(p, c, a) = (p (255 - a) + c a + 127) / 255
 __device__ __forceinline__ int blend(int p, int c, int a) { return (p * (255 - a) + c * a + 127) / 255; }
 
-__global__ __launch_bounds__(64 * OV_WAVES) void compose_kernel(
-    const unsigned char* frames, unsigned char* out, int F, int H, int W, const unsigned* __restrict__ face_words,
-    const unsigned* __restrict__ outline_words, const int* __restrict__ boxes, const long long* __restrict__ word_off, int N,
+// The body of both compose kernels.  GATHER = false: frame f is read from frames[f] (the dense entry, `out` may be `frames`).
+// GATHER = true: `frames` is a ring of `cap` frames and frame f is read from ring[slots[f]], the slot clamped into the ring;
+// `out` is dense and never the ring, so every live pixel is written.  Only the source address differs.
+template <bool GATHER>
+__device__ __forceinline__ void compose_body(
+    const unsigned char* frames, int cap, const int* __restrict__ slots, unsigned char* out, int F, int H, int W,
+    const unsigned* __restrict__ face_words, const unsigned* __restrict__ outline_words, const int* __restrict__ boxes,
+    const long long* __restrict__ word_off, int N,
     long long nwords, const int* __restrict__ inst_off, const unsigned char* __restrict__ inst_rgb,
     const int* __restrict__ label_off, const int* __restrict__ label_pos, const int* __restrict__ label_glyph,
     const unsigned char* __restrict__ label_rgb, int L, const int* __restrict__ glyph_wh,
@@ -84,17 +92,18 @@ __global__ __launch_bounds__(64 * OV_WAVES) void compose_kernel(
         const int wlo = (OV_SEG >> 5) * cg, whi = wlo + (OV_SEG >> 5); // the segment's word columns
         const int live = clampi(W - x, 0, OV_PX);
         const long long pix = 3 * (((long long)f * H + y) * W + x);
+        const long long spix = GATHER ? 3 * (((long long)clampi(slots[f], 0, cap - 1) * H + y) * W + x) : pix;   // the source
         // 12 bytes as three dwords where they are 4-byte aligned (every lane of a wave, or none: lanes are 12 bytes apart)
-        const bool wide = live == OV_PX && (((uintptr_t)(frames + pix) | (uintptr_t)(out + pix)) & 3) == 0;
+        const bool wide = live == OV_PX && (((uintptr_t)(frames + spix) | (uintptr_t)(out + pix)) & 3) == 0;
         int v[OV_PX][3];
         if (wide) {
-            const unsigned* src = reinterpret_cast<const unsigned*>(frames + pix);
+            const unsigned* src = reinterpret_cast<const unsigned*>(frames + spix);
             const unsigned d[3] = {src[0], src[1], src[2]};
 #pragma unroll
             for (int i = 0; i < 3 * OV_PX; ++i) v[i / 3][i % 3] = d[i >> 2] >> (8 * (i & 3)) & 255u;
         } else {
 #pragma unroll
-            for (int i = 0; i < 3 * OV_PX; ++i) v[i / 3][i % 3] = i < 3 * live ? frames[pix + i] : 0;
+            for (int i = 0; i < 3 * OV_PX; ++i) v[i / 3][i % 3] = i < 3 * live ? frames[spix + i] : 0;
         }
         bool touched = false;
 
@@ -167,7 +176,7 @@ __global__ __launch_bounds__(64 * OV_WAVES) void compose_kernel(
             }
         }
 
-        if (live > 0 && (touched || out != frames)) {
+        if (live > 0 && (GATHER || touched || out != frames)) {
             if (wide) {
                 unsigned d[3] = {0u, 0u, 0u};
 #pragma unroll
@@ -183,6 +192,28 @@ __global__ __launch_bounds__(64 * OV_WAVES) void compose_kernel(
             }
         }
     }
+}
+
+#define OV_COMPOSE_PARAMS                                                                                                        \
+    int F, int H, int W, const unsigned *__restrict__ face_words, const unsigned *__restrict__ outline_words,                    \
+        const int *__restrict__ boxes, const long long *__restrict__ word_off, int N, long long nwords,                          \
+        const int *__restrict__ inst_off, const unsigned char *__restrict__ inst_rgb, const int *__restrict__ label_off,         \
+        const int *__restrict__ label_pos, const int *__restrict__ label_glyph, const unsigned char *__restrict__ label_rgb,     \
+        int L, const int *__restrict__ glyph_wh, const long long *__restrict__ glyph_woff,                                       \
+        const unsigned *__restrict__ glyph_words, int G, long long glyph_nwords, int a_face, int a_box
+#define OV_COMPOSE_ARGS                                                                                                          \
+    F, H, W, face_words, outline_words, boxes, word_off, N, nwords, inst_off, inst_rgb, label_off, label_pos, label_glyph,       \
+        label_rgb, L, glyph_wh, glyph_woff, glyph_words, G, glyph_nwords, a_face, a_box
+
+__global__ __launch_bounds__(64 * OV_WAVES) void compose_kernel(const unsigned char* frames, unsigned char* out,
+                                                                OV_COMPOSE_PARAMS) {
+    compose_body<false>(frames, 0, nullptr, out, OV_COMPOSE_ARGS);
+}
+
+__global__ __launch_bounds__(64 * OV_WAVES) void compose_gather_kernel(const unsigned char* ring, int cap,
+                                                                       const int* __restrict__ slots, unsigned char* out,
+                                                                       OV_COMPOSE_PARAMS) {
+    compose_body<true>(ring, cap, slots, out, OV_COMPOSE_ARGS);
 }
 
 }  // namespace
@@ -230,5 +261,38 @@ extern "C" int gom_overlay_compose_u8(const uint8_t* frames, uint8_t* out, int F
                        boxes, (const long long*)word_off, N, (long long)nwords, inst_off, inst_rgb, label_off, label_pos,
                        label_glyph, label_rgb, L, glyph_wh, (const long long*)glyph_woff, (const unsigned*)glyph_words, G,
                        (long long)glyph_nwords, a_face, a_box);
+    return gom_launch_status();
+}
+
+extern "C" int gom_overlay_compose_gather_u8(const uint8_t* ring, int cap, const int32_t* slots, uint8_t* out, int F, int H, int W,
+                                             const uint32_t* face_words, const uint32_t* outline_words, const int32_t* boxes,
+                                             const int64_t* word_off, int N, long nwords, const int32_t* inst_off,
+                                             const uint8_t* inst_rgb, const int32_t* label_off, const int32_t* label_pos,
+                                             const int32_t* label_glyph, const uint8_t* label_rgb, int L, const int32_t* glyph_wh,
+                                             const int64_t* glyph_woff, const uint32_t* glyph_words, int G, long glyph_nwords,
+                                             int a_face, int a_box, void* stream) {
+    GOM_CHECK_ARG(F >= 0 && N >= 0 && L >= 0 && G >= 0 && nwords >= 0 && glyph_nwords >= 0 && cap >= 1);
+    GOM_CHECK_ARG(H >= 1 && W >= 1 && (long)H * (long)W <= 2147483647L);
+    GOM_CHECK_ARG(a_face >= 0 && a_face <= 255 && a_box >= 0 && a_box <= 255);
+    GOM_CHECK_ARG(((uintptr_t)boxes & 15) == 0);                       // a box is read as one 16-byte word
+    if (F == 0) return GOM_OK;
+    GOM_CHECK_ARG(ring && slots && out && inst_off && label_off);
+    {                                                                  // the ring is only read: `out` lies wholly outside it
+        const uintptr_t frame = 3u * (uintptr_t)H * (uintptr_t)W;
+        const uintptr_t r0 = (uintptr_t)ring, r1 = r0 + (uintptr_t)cap * frame, o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)F * frame;
+        GOM_CHECK_ARG(o1 <= r0 || r1 <= o0);
+    }
+    if (N > 0) GOM_CHECK_ARG(boxes && word_off && inst_rgb);
+    if (N > 0 && nwords > 0) GOM_CHECK_ARG(face_words && outline_words);
+    if (L > 0) GOM_CHECK_ARG(G > 0 && label_pos && label_glyph && label_rgb);
+    if (G > 0) GOM_CHECK_ARG(glyph_wh && glyph_woff);
+    if (glyph_nwords > 0) GOM_CHECK_ARG(glyph_words);
+    const long waves = (long)F * (long)H * (long)((W + OV_SEG - 1) / OV_SEG);
+    const long blocks = (waves + OV_WAVES - 1) / OV_WAVES;
+    hipLaunchKernelGGL(compose_gather_kernel, dim3((unsigned)(blocks < OV_MAX_BLOCKS ? blocks : OV_MAX_BLOCKS)),
+                       dim3(64 * OV_WAVES), 0, (hipStream_t)stream, ring, cap, slots, out, F, H, W, (const unsigned*)face_words,
+                       (const unsigned*)outline_words, boxes, (const long long*)word_off, N, (long long)nwords, inst_off, inst_rgb,
+                       label_off, label_pos, label_glyph, label_rgb, L, glyph_wh, (const long long*)glyph_woff,
+                       (const unsigned*)glyph_words, G, (long long)glyph_nwords, a_face, a_box);
     return gom_launch_status();
 }

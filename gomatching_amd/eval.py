@@ -22,8 +22,12 @@ Deliberate differences:
     the model as soon as their tracks have settled (at most 20 frames after the frame was tracked with the shipped configs) and
     go straight to `results.VideoResultWriter`, and host and device memory do not grow with the length of the video.  The
     three files per video are byte-identical to a run without the flag, which issues the launches it always issued.
-    `--online` draws nothing and builds rows on the GPU only: with `--show` or `--host-rows` the command exits with status 2
-    (`python -m gomatching_amd.show` draws from OUT/jsons afterwards, as it does for resumed runs);
+    `--online` builds rows on the GPU only and collects no pixels on the host: with `--host-rows`, or with `--show` alone, the
+    command exits with status 2 (`python -m gomatching_amd.show` draws from OUT/jsons afterwards, as it does for resumed
+    runs).  `--online --show --device-decode` draws: the frames are born in device memory, the session keeps the pending ones
+    in a pixel ring beside its rows (`OnlineSpotter(draw=...)`), draws the frames that settle with one gather-compose launch
+    per push and every drawn chunk is written as `show.draw_video` writes it -- the pictures of a run without `--online`, byte
+    for byte; under `--device-encode` only compressed bytes come back.  Not with `--host-draw` (status 2);
   * `--show` draws with csrc/overlay.hip by an integer rule instead of matplotlib (`gomatching_amd.show`: colours by track
     id, Pillow's glyphs, no antialiasing); without it the command does what it did before the flag existed, launch for launch.
     A resumed run skips finished videos, pictures included: `python -m gomatching_amd.show` draws them from OUT/jsons.
@@ -62,7 +66,10 @@ Deliberate differences:
     to Pillow's decode, so the result files do not change), per 100-frame chunk offline and per push with `--online`: host
     memory holds bytes, device memory one chunk of pixels.  Files with another extension, files `jpeg.parse` refuses and files
     whose status word is set go through Pillow per file; the run prints the count of every route.  Not with `--host-ingest`
-    (status 2); without a GPU status 1.  With `--show` the drawing step still reads its frames through Pillow;
+    (status 2); without a GPU status 1.  With `--show` the drawing step decodes the video a second time, chunk by chunk, on the
+    GPU as well (`show.DecodedChunks`) and draws every chunk where it lies: tens of milliseconds per chunk, against holding the
+    video's pixels in either memory.  Those decodes are counted apart and printed on a line of their own ("drawing decode:");
+    the "device decode:" line counts the spotting decode only.  The pictures do not change: the decoder is byte-equal to Pillow;
   * frames are decoded with Pillow (`convert("RGB")`, reversed to the BGR order `read_image(format="BGR")` yields).
     OpenCV is not available here, so the parity of the decoded pixels with `cv2.imread` (JPEG decoders differ in their
     IDCT and chroma upsampling) is UNPINNED, as is the parity of `results.min_area_rect` with `cv2.minAreaRect`.
@@ -120,7 +127,8 @@ def get_parser(drawing=False):
                         "the same rows (csrc/track_vote.hip); the same bytes")
     p.add_argument("--online", action="store_true",
                    help="run every video as a stream: frames are decoded one push ahead, rows are written as their tracks "
-                        "settle, memory does not grow with the video; the files are the same (not with --show / --host-rows)")
+                        "settle, memory does not grow with the video; the files are the same (not with --host-rows; with --show "
+                        "only together with --device-decode)")
     p.add_argument("--push", type=int, default=None, metavar="N",
                    help="with --online: frames per push, rounded up to whole detector steps (default 4 steps)")
     if drawing:
@@ -297,15 +305,40 @@ def load_weights(path):
     return normalize_state_dict(torch.load(path, map_location="cpu"))
 
 
-def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, counts=None, fix=None):
+def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, counts=None, fix=None, draw=None):
     """One video through `online.OnlineSpotter`: the pool decodes one push ahead, rows go to the incremental writer as they
-    settle.  -> seconds reading / inside the timed window / building rows and writing, and the session's wait figures."""
+    settle.  -> seconds reading / inside the timed window / building rows and writing, and the session's wait figures.
+    draw = (atlas, encode, quality) (`--online --show`, with `--device-decode`): the session draws the frames that settle from
+    its ring of pending frames, and every drawn chunk is written to OUT/results/<video>/<frame file> through the functions
+    `show.draw_video` uses -- `show._write_encoded` under --device-encode (only compressed bytes come back) / --host-encode,
+    `show.write_frame` otherwise: the pictures of a run without --online; "draw" = seconds encoding and writing them."""
     from .online import OnlineSpotter
     step = model.frames_per_step
     push = args.push if args.push is not None else 4 * step
     push = (push + step - 1) // step * step
     session = OnlineSpotter(cfg, model, decoder, device_ingest=not args.host_ingest, time_cost=time_cost,
-                            device_text=args.device_write, device_vote=args.device_vote, device_lexicon=fix)
+                            device_text=args.device_write, device_vote=args.device_vote, device_lexicon=fix,
+                            draw=draw[0] if draw is not None else None)
+    drawing = [0.0]
+
+    def write_drawn():
+        if draw is None:
+            return
+        from . import show as _show
+        t0 = time.time()
+        for first, drawn in session.take_drawn():
+            targets = [os.path.join(save_dir, os.path.basename(p)) for p in paths[first:first + int(drawn.shape[0])]]
+            try:
+                if draw[1] is not None:
+                    _show._write_encoded(drawn if draw[1] == "device" else drawn.cpu().numpy(), targets, pool, draw[1], draw[2])
+                else:
+                    list(pool.map(_show.write_frame, drawn.cpu().numpy(), targets))
+            except _show.ShowError as e:
+                raise _show.ShowError("video %s: %s" % (video_name, e))
+        drawing[0] += time.time() - t0
+    if draw is not None:
+        save_dir = os.path.join(args.output, "results", video_name)
+        os.makedirs(save_dir, exist_ok=True)
     add = (lambda item: writer.add_text(*item[:4])) if args.device_write else (lambda item: writer.add(*item))
     writer = _results.VideoResultWriter(video_name, data_type, args.output)
     fixed = _results.VideoResultWriter(video_name, data_type, os.path.join(args.output, "lexicon")) if fix is not None else None
@@ -329,7 +362,9 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
             for item in settled:
                 add(item)
             write += time.time() - t0
+            write_drawn()
         settled = session.close()
+        write_drawn()
         t0 = time.time()
         for item in settled:
             add(item)
@@ -345,7 +380,7 @@ def spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, a
         raise
     time_cost["total_time"] += session.seconds
     return {"read": read, "window": session.seconds, "rows": session.rows_seconds + write, "max_wait": session.max_wait,
-            "bound": session.latency_bound, "launches": session.gather_launches}
+            "bound": session.latency_bound, "launches": session.gather_launches, "draw": drawing[0]}
 
 
 def main(argv=None):
@@ -353,18 +388,26 @@ def main(argv=None):
     transcription above the length limit, as the host step does at the end -- ends it with a message and status 2; the
     writers of the video at hand have dropped their unfinished files by then."""
     from . import lexicon as _lexicon
+    from . import show as _show
     try:
         return run(argv)
     except _lexicon.LexiconError as e:
         sys.stderr.write("error: lexicon: %s\n" % e)
         return 2
+    except _show.ShowError as e:                            # frames the drawing step cannot draw (a clip of mixed sizes)
+        sys.stderr.write("error: %s\n" % e)
+        return 2
 
 
 def run(argv=None):
     args = get_parser(drawing=True).parse_args(argv)
-    if args.online and (getattr(args, "show", False) or args.host_rows):
-        sys.stderr.write("error: --online builds rows on the GPU and draws nothing: it takes neither --show nor --host-rows "
+    if args.online and ((args.show and not args.device_decode) or args.host_rows):
+        sys.stderr.write("error: --online builds rows on the GPU and collects no pixels on the host: it does not take --host-rows, "
+                         "and it takes --show only together with --device-decode, which leaves the frames in device memory "
                          "(python -m gomatching_amd.show draws from OUT/jsons afterwards)\n")
+        return 2
+    if args.online and args.show and args.host_draw:
+        sys.stderr.write("error: --online --show draws the frames where they lie on the GPU: it does not go with --host-draw\n")
         return 2
     encode, quality = None, 95
     if getattr(args, "device_encode", False) or getattr(args, "host_encode", False) or getattr(args, "jpeg_quality", None) is not None:
@@ -460,6 +503,7 @@ def run(argv=None):
         decoder = TextDecoder(cfg.MODEL.TRANSFORMER.VOC_SIZE, cfg.MODEL.TRANSFORMER.CUSTOM_DICT)
     total_frame, read_seconds, rows_seconds, draw_seconds = 0, 0.0, 0.0, 0.0
     routes = {k: 0 for k in DECODE_ROUTES} if args.device_decode else None
+    draw_routes = {k: 0 for k in DECODE_ROUTES}             # --show --device-decode: the decodes made for drawing, counted apart
     voted = []                                              # --device-vote: the XMLs whose txt the GPU wrote in this run
     corrected, fix_rows = [], [0, 0, 0]                     # --device-lexicon: the videos corrected on the GPU; kept, accepted, dropped
 
@@ -487,7 +531,9 @@ def run(argv=None):
                 if not paths:
                     continue
                 fix = row_correction(video_name)
-                stats = spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, routes, fix)
+                stats = spot_video_online(cfg, model, decoder, pool, paths, video_name, data_type, args, time_cost, routes, fix,
+                                          draw=(atlas, encode, quality) if args.show else None)
+                draw_seconds += stats["draw"]
                 corrected_video(video_name, fix)
                 if args.device_vote:
                     voted.append("res_%s.xml" % _results.result_names(video_name, data_type)[0])
@@ -506,10 +552,6 @@ def run(argv=None):
                                                                        walk=args.decode_walk)
                 read_seconds += read
                 frames = paths                              # (counted below; the pixels are gone)
-                if args.show:                               # the drawing step takes host frames: read through Pillow, as ever
-                    t0 = time.time()
-                    frames = list(pool.map(read_frame, paths))
-                    read_seconds += time.time() - t0
             else:
                 frames = list(pool.map(read_frame, paths))
                 read_seconds += time.time() - t0
@@ -528,7 +570,10 @@ def run(argv=None):
             rows_seconds += time.time() - t0
             if args.show:
                 t0 = time.time()
-                _show.draw_video(frames, annotation, paths, video_name, args.output, cfg.MODEL.TRANSFORMER.VOC_SIZE, pool, atlas,
+                source = frames
+                if routes is not None:                      # decoded on the GPU a second time, chunk by chunk, and drawn there
+                    source = _show.DecodedChunks(paths, pool, draw_routes, model.device, args.decode_walk)
+                _show.draw_video(source, annotation, paths, video_name, args.output, cfg.MODEL.TRANSFORMER.VOC_SIZE, pool, atlas,
                                  host=args.host_draw, encode=encode, quality=quality)
                 draw_seconds += time.time() - t0
             print("Video: ", video_name, "per_img_time: ", per_video_time / len(frames), ", FPS: ",
@@ -552,6 +597,8 @@ def run(argv=None):
               " with another extension, ", routes["refused"], " refused by the parser, ", routes["flagged"], " with a status word set")
         print("device decode walk (--decode-walk ", args.decode_walk, "): ", routes.get("chunks", 0), " segments by the chunk walk, ",
               routes.get("serial", 0), " by the serial walk (those of calls that took the segment walk, and those the chunk walk marked)")
+    if args.show and routes is not None:                    # the frames drawn: decoded a second time offline, the pushes' own online
+        _show.print_draw_routes(routes if args.online else draw_routes, args.decode_walk, shared=args.online)
     if args.show:
         print("host seconds drawing and encoding frames: ", draw_seconds)
     if args.lexicon is not None:                            # every video under OUT, those of earlier (resumed) runs included

@@ -153,12 +153,36 @@ class OnlineSpotter:
     device_lexicon=a `lexicon.RowCorrection` (with device_text=True and device_vote=True): every gather's rows are also corrected
     by the video's lexicon where they lie (csrc/lexicon_rows.hip: the correction is per row, only the vote waits for `close()`);
     the items `push` / `close()` return carry the corrected json and xml bytes as a fifth and sixth element, for a second
-    `VideoResultWriter` rooted at <out>/lexicon, and `close()` leaves the vote over the corrected words in `lexicon_txt`."""
+    `VideoResultWriter` rooted at <out>/lexicon, and `close()` leaves the vote over the corrected words in `lexicon_txt`.
+
+    draw=a `show.Atlas`, or True for a fresh one (with device_ingest=True): the session also draws.  A pixel ring `ring_px` u8
+    `[cap_frames,H,W,3]` is allocated once, when the first frame's size is known (41 slots at the shipped configs with 8 frames
+    per step: 113 MB at 1280x720), beside `ring_bd` / `ring_recs` and under their rule: slot f % cap_frames, the same tail,
+    never overwritten.  A frame of another size is refused with a `show.ShowError` before the push runs anything.  Every step
+    copies its frames' source pixels (`inputs[j]["frame_u8"]`: device to device for frames decoded on the GPU, an upload for
+    host tensors) into their slots, ordered with the step's other ring copies.  For the frames that settle, the gather builds
+    their scene from their finished rows with `show._scene_of_rows`, the offline function (under device_text=True the row
+    lists are built for the drawing only), and runs the fill and outline launches and ONE `gom_overlay_compose_gather_u8`
+    launch from the ring into a dense tensor; the next copy into the ring waits for that launch's event.  `take_drawn()`
+    hands the drawn frames out, `[(first frame, CUDA u8 [n,H,W,3]), ...]`, covering exactly the frames whose rows or text the
+    same `push` / `close()` returned -- `show.draw_clip` of those frames and rows, byte for byte.  What `push` / `close()`
+    return does not change, and encoding is the caller's choice.  Without `draw` the session allocates, launches and returns
+    what it always did."""
 
     def __init__(self, cfg, model, decoder, device_ingest=True, time_cost=None, min_extent=5, device_text=False,
-                 device_vote=False, device_lexicon=None):
+                 device_vote=False, device_lexicon=None, draw=None):
         import torch
         self.device_text = bool(device_text)
+        self._atlas = None                                       # draw: the label bitmaps, carried from gather to gather
+        if draw is not None and draw is not False:
+            from . import show as _show
+            if not device_ingest:
+                raise ValueError("draw takes the frames' source pixels from the inputs' frame_u8: it needs device_ingest=True")
+            self._atlas = _show.Atlas() if draw is True else draw
+        self.ring_px = None                                      # draw: u8 [cap_frames,H,W,3], allocated with the first frame
+        self._drawn = []                                         # draw: (first frame, CUDA u8 [n,H,W,3]) not yet taken
+        self._px_free = None                                     # draw: event after the last launch that read ring slots
+        self._main, self._sources = None, None
         if device_vote and not device_text:
             raise ValueError("device_vote=True votes over the rows device_text=True leaves on the GPU: it needs device_text=True")
         if device_lexicon is not None and not (device_text and device_vote):
@@ -221,6 +245,8 @@ class OnlineSpotter:
     def push_inputs(self, inputs):
         if self.closed:
             raise RuntimeError("the session is closed")
+        if self._atlas is not None:
+            self._check_sizes(inputs)
         self._buffer.extend(inputs)
         self.frames_seen += len(inputs)
         full = len(self._buffer) // self.step * self.step
@@ -248,16 +274,61 @@ class OnlineSpotter:
             self.rows_seconds += time.time() - t0
         return self._take()
 
+    def take_drawn(self):
+        """draw: the frames that settled since the last call with their tracked text drawn on them, as
+        `[(first frame, CUDA u8 [n,H,W,3]), ...]` in frame order -- exactly the frames whose rows or text `push` / `close()`
+        returned since.  The tensors are the caller's: encoding and writing them is the caller's choice."""
+        out, self._drawn = self._drawn, []
+        return out
+
     # ---------------------------------------------------------------------------------------- inside
     def _take(self):
         out, self._out = self._out, []
         return out
+
+    def _check_sizes(self, inputs):
+        """draw: every frame of a session has the size of its first one -- refused before the push runs anything -- and the
+        pixel ring is allocated once, when that size is known: cap_frames slots, slot f % cap_frames for frame f, the tail
+        and the never-overwritten guarantee of `ring_bd` / `ring_recs`."""
+        import torch
+        from .show import ShowError
+        for x in inputs:
+            src = x.get("frame_u8")
+            if src is None or src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3:
+                raise ValueError("draw needs every input's source pixels: frame_u8, a uint8 [H,W,3] tensor")
+            hw = tuple(int(v) for v in src.shape[:2])
+            if self.ring_px is None:
+                self.ring_px = torch.empty((self.cap_frames,) + hw + (3,), dtype=torch.uint8, device=self.model.device)
+            if hw != tuple(self.ring_px.shape[1:3]):
+                raise ShowError("the frames of a clip must share one size: a frame of %d x %d in a stream of %d x %d"
+                                % (hw[1], hw[0], self.ring_px.shape[2], self.ring_px.shape[1]))
+
+    def _draw(self, first, rows_per_frame):
+        """draw: frames first .. first + len(rows_per_frame) - 1 have settled -- their scene from their finished rows (the
+        offline function), the fill and outline launches and ONE gather-compose launch from their ring slots into a dense
+        tensor.  An event after the launch is what the next copy into the ring waits for, whichever stream it runs on."""
+        import torch
+        from . import show as _show
+        t0 = time.time()
+        slots = [(first + i) % self.cap_frames for i in range(len(rows_per_frame))]
+        drawn = _show.draw_gather_resident(self.ring_px, slots, rows_per_frame, self.cfg.MODEL.TRANSFORMER.VOC_SIZE, self._atlas)
+        self._px_free = torch.cuda.Event()
+        self._px_free.record()
+        if self._main is not None:                               # (a gather inside a step runs on the tracker stream)
+            drawn.record_stream(self._main)
+        self._drawn.append((first, drawn))
+        self.rows_seconds += time.time() - t0
 
     def _run(self, inputs):
         import torch
         t0 = time.time()
         self._sizes = [(x["height"], x["width"]) for x in inputs]
         self._frame0 = len(self.instances)
+        if self._atlas is not None:                              # draw: `_on_step` copies the frames' source pixels
+            self._sources = [x["frame_u8"] for x in inputs]
+            self._main = torch.cuda.current_stream()
+            self._src_ready = torch.cuda.Event()                 # the frames were made on this stream (a decode, an upload)
+            self._src_ready.record()
         with torch.no_grad():
             self._in_run = True
             try:
@@ -265,6 +336,7 @@ class OnlineSpotter:
                                                                              self.time_cost, on_step=self._on_step)
             finally:
                 self._in_run = False
+                self._sources = None
         self.seconds += time.time() - t0
 
     def _on_step(self, dets, first):
@@ -291,6 +363,12 @@ class OnlineSpotter:
                 self.ring_bd[s0 * nq:(s0 + m) * nq].copy_(bd[done * nq:(done + m) * nq])
                 self.ring_recs[s0 * nq:(s0 + m) * nq].copy_(recs[done * nq:(done + m) * nq])
                 done += m
+        if self._atlas is not None:                              # draw: the frames' source pixels, beside their rows
+            torch.cuda.current_stream().wait_event(self._src_ready)
+            if self._px_free is not None:                        # (what read these slots last has been launched: order it)
+                torch.cuda.current_stream().wait_event(self._px_free)
+            for j in range(B):                                   # device to device for frames decoded on the GPU
+                self.ring_px[(first + j) % cap_f].copy_(self._sources[first - self._frame0 + j], non_blocking=True)
         for j, d in enumerate(dets):
             f, n = first + j, len(d)
             if n > nq:
@@ -338,6 +416,10 @@ class OnlineSpotter:
             else:                                                #  slots may be rewritten afterwards)
                 text = results.host_text_of_empty_frames(first + a, b - a) * (2 if self._lexicon is not None else 1)
             self._out.append((first + a, b - a) + tuple(text))
+        if self._atlas is not None:                              # the row lists, for the drawing only (as `write_video` does)
+            lines = results.finish_rows(self.model._d2h(words_d), self.decoder, self.min_extent) if words_d is not None else []
+            self._draw(first, [[r for r in lines[int(offsets[i]):int(offsets[i + 1])] if r is not None]
+                               for i in range(len(ready))])
         self.rows_seconds += time.time() - t0
         self._ring_tail = ready[-1][0] + 1
 
@@ -374,8 +456,11 @@ class OnlineSpotter:
             t0 = time.time()
             lines = results.finish_rows(words, self.decoder, self.min_extent)
             self.rows_seconds += time.time() - t0
-        o = 0
+        o, first = 0, len(self._out)
         for (f, _), c in zip(ready, counts):
             self._out.append((f, [r for r in lines[o:o + c] if r is not None]))
             o += c
+        if self._atlas is not None:
+            assert [f for f, _ in ready] == list(range(ready[0][0], ready[0][0] + len(ready))), "settled frames leave in frame order"
+            self._draw(ready[0][0], [rows for _, rows in self._out[first:]])
         self._ring_tail = ready[-1][0] + 1

@@ -2074,12 +2074,15 @@ def mask_outline_polygons(points, contour_off, mask_coff, boxes, word_off, H, W,
 
 
 def overlay_compose(frames, face_words, outline_words, boxes, word_off, inst_off, inst_rgb, label_off, label_pos, label_glyph,
-                    label_rgb, glyph_wh, glyph_woff, glyph_words, a_face, a_box, out=None):
+                    label_rgb, glyph_wh, glyph_woff, glyph_words, a_face, a_box, out=None, slots=None):
     """Draw instances and labels over u8 frames [F,H,W,3] (csrc/overlay.hip; the integer rule is in
     include/gomatching_hip.h): two mask sets over one set of boxes and word offsets (what `mask_fill_polygons` and
     `mask_outline_polygons` leave), inst_off int32 [F+1], inst_rgb u8 [N,3], the labels (label_off int32 [F+1], label_pos int32
     [L,2], label_glyph int32 [L], label_rgb u8 [L,3]) and the atlas (glyph_wh int32 [G,2], glyph_woff int64 [G+1], glyph_words
-    int32, the uint32 bitmap rows), all CUDA.  `out` may be `frames` (in place); default a new tensor.  -> out."""
+    int32, the uint32 bitmap rows), all CUDA.  `out` may be `frames` (in place); default a new tensor.  -> out.
+    With `slots` (int32 [F], CUDA) `frames` is a ring u8 [cap,H,W,3] that is only read, frame f is drawn from
+    frames[slots[f]] into a dense `out` [F,H,W,3] (default a new tensor; it must not share memory with the ring) by ONE
+    `gom_overlay_compose_gather_u8` launch: what the dense call gives for frames[slots].  A slot outside [0, cap) raises."""
     _chk_frames(frames)
     dev = frames.device
     i32, i64, u8 = torch.int32, torch.int64, torch.uint8
@@ -2089,6 +2092,14 @@ def overlay_compose(frames, face_words, outline_words, boxes, word_off, inst_off
            ("label_glyph", label_glyph, i32, (None,)), ("label_rgb", label_rgb, u8, (None, 3)), ("glyph_wh", glyph_wh, i32, (None, 2)),
            ("glyph_woff", glyph_woff, i64, (None,)), ("glyph_words", glyph_words, i32, (None,)))
     F, H, W, _ = frames.shape
+    cap = F
+    if slots is not None:
+        _chk_i(dev, ("slots", slots, i32, (None,)))
+        F = slots.shape[0]
+        if cap < 1:
+            raise ValueError("a ring of no frames")
+        if F and (int(slots.min()) < 0 or int(slots.max()) >= cap):
+            raise ValueError("slots must lie in [0, %d), the ring's frames" % cap)
     N, L, G = boxes.shape[0], label_pos.shape[0], glyph_wh.shape[0]
     if inst_off.shape[0] != F + 1 or label_off.shape[0] != F + 1 or word_off.shape[0] != N + 1 or inst_rgb.shape[0] != N or \
             outline_words.shape[0] != face_words.shape[0] or label_glyph.shape[0] != L or label_rgb.shape[0] != L or \
@@ -2097,6 +2108,21 @@ def overlay_compose(frames, face_words, outline_words, boxes, word_off, inst_off
                          "label arrays [L] and glyph_woff [G+1]")
     if boxes.data_ptr() % 16:
         raise ValueError("boxes must be 16-byte aligned")
+    if slots is not None:
+        if out is None:
+            out = torch.empty((F, H, W, 3), dtype=u8, device=dev)
+        else:
+            _chk_frames(out)
+            if tuple(out.shape) != (F, H, W, 3) or out.device != dev:
+                raise ValueError("out must be [len(slots),H,W,3] on the device of the ring")
+            if out.data_ptr() < frames.data_ptr() + frames.numel() and frames.data_ptr() < out.data_ptr() + out.numel():
+                raise ValueError("out must not share memory with the ring: the ring is only read")
+        with torch.cuda.device(dev):
+            _call("gom_overlay_compose_gather_u8", _p(frames), cap, _p(slots), _p(out), F, H, W, _p(face_words), _p(outline_words),
+                  _p(boxes), _p(word_off), N, face_words.shape[0], _p(inst_off), _p(inst_rgb), _p(label_off), _p(label_pos),
+                  _p(label_glyph), _p(label_rgb), L, _p(glyph_wh), _p(glyph_woff), _p(glyph_words), G, glyph_words.shape[0],
+                  int(a_face), int(a_box), _stream())
+        return out
     if out is None:
         out = torch.empty_like(frames)
     elif out is not frames:

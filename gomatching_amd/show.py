@@ -3,6 +3,7 @@ wrote -- the counterpart of the reference's `eval.py --show` (eval.py:364-369, t
 
     python -m gomatching_amd.show --input DIR --results OUT [--output DIR] [--font FILE] [--host-draw]
                                   [--device-encode | --host-encode] [--jpeg-quality N]
+                                  [--device-decode [--decode-walk {auto,segments,chunks}]]
                                   [--voc-size N | --config-file F | --builtin NAME]
       -> DIR/results/<video name>/<basename of the source frame>   (DIR defaults to OUT)
 
@@ -41,6 +42,21 @@ libjpeg's bytes:
   --host-encode     `jpeg.encode_host`, the same rule in numpy: the same files.  With --host-draw the command needs no GPU.
   --jpeg-quality N  1 .. 100, default 95; only with one of the two.
 Frames of any other extension go through Pillow as before, and with neither flag nothing changes.
+
+Reading.  By default a pool of four threads decodes the whole video through Pillow into host arrays, which are uploaded chunk
+by chunk.  One opt-in flag keeps the pixels off the host:
+  --device-decode   the pool reads file BYTES, one chunk (100 frames) ahead; `eval.decode_frames` makes the chunk's pixels in
+                    device memory (csrc/jpeg_decode.hip, byte-equal to Pillow; files of another extension, files the parser
+                    refuses and flagged files go through Pillow, per file, as in `eval`), the chunk is drawn IN PLACE and goes
+                    to the writers as ever.  Nothing is uploaded, and no more than one chunk of pixels is ever held; with
+                    --device-encode a frame enters the GPU as entropy bytes and leaves it as entropy bytes.  The run prints the
+                    route counts.  Not with --host-draw (status 2); without a GPU status 1.
+  --decode-walk W   with --device-decode: the decoder's entropy walk, as in `eval` (default auto); alone status 2.
+The same drawing functions serve frames that already lie in device memory elsewhere: `draw_chunk_resident` / `compose_resident`
+take a CUDA u8 [F,H,W,3] tensor and draw it where it lies, `draw_gather_resident` draws frames that wait in a ring through
+one `gom_overlay_compose_gather_u8` launch (`online.OnlineSpotter(draw=...)`, `eval --online --show --device-decode`), and
+`draw_video` takes a function that yields the video chunk by chunk (`DecodedChunks`; `eval --show --device-decode`).  The
+frames of a video must share one size: a chunk of mixed sizes ends the run with "the frames of a clip must share one size".
 """
 import argparse
 import colorsys
@@ -289,26 +305,68 @@ def device_arrays(scene, dev):
     return up, face, line, area
 
 
-def launch(frames_dev, scene, arrays, a_face=A_FACE, a_box=A_BOX, out=None):
-    """The three launches of a chunk over resident inputs: fill, outline, compose (in place unless `out` is given)."""
+def launch(frames_dev, scene, arrays, a_face=A_FACE, a_box=A_BOX, out=None, slots=None):
+    """The three launches of a chunk over resident inputs: fill, outline, compose (in place unless `out` is given).  With
+    `slots` (int32 [F], CUDA) `frames_dev` is a ring that is only read and frame f is drawn from frames_dev[slots[f]] into a
+    dense tensor (`out`, default a new one): the gather form of the compose launch, still one launch."""
     from . import ops
     (points, coff, mcoff, boxes, woff, inst_off, inst_rgb, label_off, label_pos, label_glyph, label_rgb, gwh, gwoff,
      gwords), face, line, area = arrays
     ops.mask_fill_polygons(points, coff, mcoff, boxes, woff, scene.H, scene.W, face, area)
     ops.mask_outline_polygons(points, coff, mcoff, boxes, woff, scene.H, scene.W, line)
+    if slots is not None:
+        return ops.overlay_compose(frames_dev, face, line, boxes, woff, inst_off, inst_rgb, label_off, label_pos, label_glyph,
+                                   label_rgb, gwh, gwoff, gwords, a_face, a_box, out=out, slots=slots)
     return ops.overlay_compose(frames_dev, face, line, boxes, woff, inst_off, inst_rgb, label_off, label_pos, label_glyph,
                                label_rgb, gwh, gwoff, gwords, a_face, a_box, out=frames_dev if out is None else out)
 
 
+def is_resident(frames):
+    """Whether `frames` is a CUDA tensor: frames that already lie in device memory (decoded there, or a session's ring)."""
+    if isinstance(frames, (list, tuple, np.ndarray)):
+        return False
+    import torch
+    return isinstance(frames, torch.Tensor) and frames.is_cuda
+
+
+def _resident_frames(frames):
+    import torch
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("resident frames must be a contiguous CUDA u8 [F,H,W,3] tensor")
+    return frames
+
+
 def compose_resident(frames, scene, a_face=A_FACE, a_box=A_BOX):
     """`compose_host` through csrc/overlay.hip, the drawn frames LEFT on the device: one upload of the frames and one of the
-    description, the fill, outline and compose launches.  -> a CUDA u8 tensor [F,H,W,3]."""
+    description, the fill, outline and compose launches.  -> a CUDA u8 tensor [F,H,W,3].  Frames that are a CUDA u8
+    [F,H,W,3] tensor already are used where they lie -- no upload -- and drawn IN PLACE: the result is that tensor."""
     import torch
+    if is_resident(frames):
+        fr = _resident_frames(frames)
+        assert tuple(fr.shape[:3]) == (scene.F, scene.H, scene.W)
+        with torch.cuda.device(fr.device):
+            return launch(fr, scene, device_arrays(scene, fr.device), a_face, a_box)
     if not torch.cuda.is_available():
         raise ShowError("no GPU: drawing runs in csrc/overlay.hip (use --host-draw for the numpy path)")
     dev = torch.device("cuda", torch.cuda.current_device())
     fr = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).to(dev)
     return launch(fr, scene, device_arrays(scene, dev), a_face, a_box)
+
+
+def compose_gather_resident(ring, slots, scene, a_face=A_FACE, a_box=A_BOX):
+    """`compose_resident` for frames that lie in a ring: `ring` a CUDA u8 [cap,H,W,3] tensor that is only read, `slots` the
+    ring slot of each of the scene's frames (a sequence of ints; a slot may repeat).  One upload of the description and of
+    the slot table, the fill and outline launches and ONE gather-compose launch.  -> a new dense CUDA u8 tensor [F,H,W,3]."""
+    import torch
+    ring = _resident_frames(ring)
+    slots = np.asarray(slots, dtype=np.int32).reshape(-1)
+    if len(slots) != scene.F or tuple(ring.shape[1:3]) != (scene.H, scene.W):
+        raise ValueError("%d slots for a scene of %d frames, or a ring of another frame size" % (len(slots), scene.F))
+    if len(slots) and (slots.min() < 0 or slots.max() >= ring.shape[0]):
+        raise ValueError("slots must lie in [0, %d), the ring's frames" % ring.shape[0])
+    with torch.cuda.device(ring.device):
+        return launch(ring, scene, device_arrays(scene, ring.device), a_face, a_box,
+                      slots=torch.from_numpy(slots).to(ring.device))
 
 
 def compose_device(frames, scene, a_face=A_FACE, a_box=A_BOX):
@@ -352,10 +410,24 @@ def _chunk_scene(frames_u8, rows_per_frame, voc_size, atlas, bgr):
 
 
 def draw_chunk_resident(frames_u8, rows_per_frame, voc_size, atlas, bgr=True):
-    """One chunk of `draw_clip` on the GPU, the drawn frames left there for the encoder: -> a CUDA u8 tensor [F,H,W,3]."""
+    """One chunk of `draw_clip` on the GPU, the drawn frames left there for the encoder: -> a CUDA u8 tensor [F,H,W,3].
+    `frames_u8` may be a CUDA u8 [F,H,W,3] tensor (frames decoded on the GPU): it is drawn where it lies, in place, and
+    returned; host frames are uploaded as ever."""
     if len(rows_per_frame) != len(frames_u8) or not len(frames_u8):
         raise ValueError("%d frames but rows for %d" % (len(frames_u8), len(rows_per_frame)))
+    if is_resident(frames_u8):
+        fr = _resident_frames(frames_u8)
+        return compose_resident(fr, _scene_of_rows(rows_per_frame, voc_size, atlas, fr.shape[1], fr.shape[2], bgr))
     return compose_resident(*_chunk_scene(frames_u8, rows_per_frame, voc_size, atlas, bgr))
+
+
+def draw_gather_resident(ring, slots, rows_per_frame, voc_size, atlas, bgr=True):
+    """`draw_chunk_resident` for frames that wait in a ring (`online.OnlineSpotter`'s pending frames): frame i of the result
+    is ring[slots[i]] with rows_per_frame[i] drawn on it.  The ring is only read.  -> a new dense CUDA u8 tensor [F,H,W,3]."""
+    if len(rows_per_frame) != len(slots) or not len(slots):
+        raise ValueError("%d slots but rows for %d" % (len(slots), len(rows_per_frame)))
+    scene = _scene_of_rows(rows_per_frame, voc_size, atlas, ring.shape[1], ring.shape[2], bgr)
+    return compose_gather_resident(ring, slots, scene)
 
 
 def draw_clip(frames_u8, rows_per_frame, voc_size, font=None, host=False, chunk=CHUNK, bgr=True, atlas=None):
@@ -434,19 +506,34 @@ def draw_video(frames, annotation, paths, video_name, out_dir, voc_size, pool, a
     """Draw a whole video (BGR frames, `annotation` = {1-based frame id as str: rows}) chunk by chunk and write
     out_dir/results/<video name>/<basename of the frame's source path> through `pool`.  encode = None: Pillow writes every
     file; "device" / "host": the JPEG frames go through csrc/jpeg.hip (the drawn chunk never leaves the GPU) / through
-    `jpeg.encode_host`, at `quality`."""
-    if len(annotation) != len(frames):
-        raise ShowError("video %s: %d frames but results for %d" % (video_name, len(frames), len(annotation)))
+    `jpeg.encode_host`, at `quality`.
+    `frames` may be, instead of the list of host frames, a function `frames(f0, f1)` that returns frames f0 .. f1 - 1 of the
+    video (one per path) as ONE CUDA u8 [f1 - f0,H,W,3] tensor, called once per chunk of at most CHUNK frames in order (a
+    `DecodedChunks`): the chunk is drawn where it lies and no more than one chunk of pixels is ever held.  It raises
+    `ShowError` for frames of a chunk that differ in size."""
+    provider = frames if callable(frames) else None
+    count = len(paths) if provider is not None else len(frames)
+    if len(annotation) != count:
+        raise ShowError("video %s: %d frames but results for %d" % (video_name, count, len(annotation)))
     save_dir = os.path.join(out_dir, "results", video_name)
     os.makedirs(save_dir, exist_ok=True)
     try:
-        rows = [annotation[str(i + 1)] for i in range(len(frames))]
+        rows = [annotation[str(i + 1)] for i in range(count)]
     except KeyError as e:
         raise ShowError("video %s: no results for frame %s" % (video_name, e))
-    for f0 in range(0, len(frames), CHUNK):
+    for f0 in range(0, count, CHUNK):
         targets = [os.path.join(save_dir, os.path.basename(p)) for p in paths[f0:f0 + CHUNK]]
         try:
-            if encode == "device":
+            if provider is not None:
+                part = provider(f0, min(f0 + CHUNK, count))
+                if host:                                    # (the numpy rule on frames decoded on the GPU: one copy back)
+                    drawn = draw_clip(part.cpu().numpy(), rows[f0:f0 + CHUNK], voc_size, host=True, atlas=atlas)
+                else:
+                    drawn = draw_chunk_resident(part, rows[f0:f0 + CHUNK], voc_size, atlas)
+                    if encode != "device":
+                        drawn = drawn.cpu().numpy()
+                del part
+            elif encode == "device":
                 drawn = draw_chunk_resident(frames[f0:f0 + CHUNK], rows[f0:f0 + CHUNK], voc_size, atlas)
             else:
                 drawn = draw_clip(frames[f0:f0 + CHUNK], rows[f0:f0 + CHUNK], voc_size, host=host, atlas=atlas)
@@ -456,6 +543,48 @@ def draw_video(frames, annotation, paths, video_name, out_dir, voc_size, pool, a
             raise ShowError("video %s: %s" % (video_name, e))
         if encode is None:
             list(pool.map(write_frame, drawn, targets))
+
+
+class DecodedChunks:
+    """The frames of one video for `draw_video`, decoded on the GPU chunk by chunk (`--device-decode`): `pool` reads the
+    files' bytes one chunk ahead, `eval.decode_frames` makes the chunk's pixels in device memory -- baseline JPEG files in
+    csrc/jpeg_decode.hip, files of another extension, refused files and flagged files through Pillow, per file, `counts`
+    incremented per route -- and the chunk is handed over as ONE CUDA u8 [n,H,W,3] tensor.  Host memory holds file bytes only,
+    device memory one chunk.  Called with consecutive ranges, in order."""
+
+    def __init__(self, paths, pool, counts, device, walk="auto", chunk=CHUNK):
+        self.paths, self.pool, self.counts, self.device, self.walk, self.chunk = paths, pool, counts, device, walk, int(chunk)
+        self._next = 0
+        self._ahead = self._read(0)
+
+    def _read(self, f0):
+        from . import eval as _eval
+        return [self.pool.submit(_eval.read_bytes, p) for p in self.paths[f0:f0 + self.chunk]]
+
+    def __call__(self, f0, f1):
+        import torch
+        from . import eval as _eval
+        if f0 != self._next or not f0 < f1 <= f0 + self.chunk:
+            raise ValueError("chunks are taken in order, at most %d frames each: asked for %d .. %d at frame %d"
+                             % (self.chunk, f0, f1, self._next))
+        blobs = [f.result() for f in self._ahead][:f1 - f0]
+        self._next = f1
+        self._ahead = self._read(f1)
+        frames = _eval.decode_frames(self.paths[f0:f1], blobs, self.counts, self.device, self.walk)
+        del blobs
+        if any(tuple(f.shape) != tuple(frames[0].shape) for f in frames):
+            raise ShowError("the frames of a clip must share one size")
+        return torch.stack(frames)
+
+
+def print_draw_routes(counts, walk, shared=False):
+    """The route counts of the decodes made for drawing, on a line of their own; shared=True: the frames drawn are the ones
+    the spotter's own decode made (an online run), counted by the route they took there."""
+    print("drawing decode: ", counts["device"], " files decoded on the GPU ",
+          "once, for spotting and drawing" if shared else "for drawing", "; through Pillow: ", counts["other"],
+          " with another extension, ", counts["refused"], " refused by the parser, ", counts["flagged"],
+          " with a status word set; walk (--decode-walk ", walk, "): ", counts.get("chunks", 0), " segments by the chunk walk, ",
+          counts.get("serial", 0), " by the serial walk")
 
 
 def rows_of_json(tracks):
@@ -517,6 +646,12 @@ def get_parser():
     p.add_argument("--font", default=None, metavar="FILE", help="a TrueType font for the labels (default: Pillow's built-in font)")
     p.add_argument("--host-draw", action="store_true", help="draw in numpy on the host (default: on the GPU, the same bytes)")
     add_encode_arguments(p)
+    p.add_argument("--device-decode", action="store_true",
+                   help="decode baseline JPEG frames on the GPU (the same bytes as Pillow's) and draw them where they lie: the "
+                        "pool reads file bytes one chunk ahead, nothing is uploaded; any other file goes through Pillow, per "
+                        "file (not with --host-draw)")
+    p.add_argument("--decode-walk", choices=("auto", "segments", "chunks"), default=None,
+                   help="with --device-decode: the decoder's entropy walk, as in gomatching_amd.eval (default auto)")
     p.add_argument("--voc-size", type=int, default=None, metavar="N",
                    help="vocabulary size of the model: 37 upper-cases the labels (default 37)")
     p.add_argument("--config-file", default=None, metavar="FILE", help="take the vocabulary size from a config file")
@@ -541,10 +676,26 @@ def main(argv=None):
     if not os.path.isdir(args.input):
         sys.stderr.write("error: input directory %r not found\n" % args.input)
         return 2
+    if args.decode_walk is not None and not args.device_decode:
+        sys.stderr.write("error: --decode-walk goes with --device-decode\n")
+        return 2
+    if args.device_decode and args.host_draw:
+        sys.stderr.write("error: --device-decode leaves the frames in device memory, where they are drawn: it does not go with "
+                         "--host-draw\n")
+        return 2
     encode, quality, status, message = encode_choice(args)
     if status:
         sys.stderr.write("error: %s\n" % message)
         return status
+    routes = None
+    if args.device_decode:
+        import torch
+        if not torch.cuda.is_available():
+            sys.stderr.write("error: --device-decode needs a GPU: the decoder runs in csrc/jpeg_decode.hip\n")
+            return 1
+        routes = {k: 0 for k in _eval.DECODE_ROUTES}
+        walk = args.decode_walk or "auto"
+        device = torch.device("cuda", torch.cuda.current_device())
     voc_size = 37 if args.voc_size is None else args.voc_size
     if args.config_file is not None or args.builtin is not None:
         voc_size = _config.setup_cfg(config_file=args.config_file, opts=[], builtin=args.builtin).MODEL.TRANSFORMER.VOC_SIZE
@@ -566,12 +717,17 @@ def main(argv=None):
                 if any(len(row) < 11 for rows in annotation.values() for row in rows):
                     raise ShowError("video %s: result rows without a segmentation cannot be drawn" % video_name)
                 print("drawing {}...".format(video_name))
-                frames = list(readers.map(_eval.read_frame, paths))
+                if routes is not None:                      # bytes one chunk ahead, pixels made and drawn on the GPU
+                    frames = DecodedChunks(paths, readers, routes, device, walk)
+                else:
+                    frames = list(readers.map(_eval.read_frame, paths))
                 draw_video(frames, annotation, paths, video_name, out_dir, voc_size, writers, atlas, host=args.host_draw,
                            encode=encode, quality=quality)
     except ShowError as e:
         sys.stderr.write("error: %s\n" % e)
         return 2
+    if routes is not None:
+        print_draw_routes(routes, walk)
     return 0
 
 

@@ -860,7 +860,16 @@ int gom_mask_pairs_emit_f64(const uint32_t* gt_words, const int32_t* gt_boxes, c
  * their buffers (a mask word outside the words its box owns, or outside the buffer, reads as 0).
  * GOM_ERR_INVALID_ARG before any HIP call: null pointers, negative sizes, H or W < 1, H * W above INT32_MAX, a_face or a_box
  * outside 0 .. 255, a box array that is not 16-byte aligned, labels without an atlas (L > 0 with G == 0).  F == 0 is GOM_OK
- * without a launch; N == 0 and L == 0 with F > 0 copy frames to out when they differ. */
+ * without a launch; N == 0 and L == 0 with F > 0 copy frames to out when they differ.
+ *
+ * gom_overlay_compose_gather_u8: the same rule over frames that lie in a ring (the pending frames of an online session):
+ * ring u8 [cap,H,W,3], slots int32 [F] on the device, out u8 [F,H,W,3], dense.  Rule: out[f] is word for word what
+ * gom_overlay_compose_u8 writes for frames[f] = ring[slots[f]].  The ring is only read; a slot may repeat; `out` must not
+ * overlap the ring.  The kernel clamps a slot outside [0, cap) into the ring, so it never reads past it (callers refuse such
+ * a table).  One launch whatever the ring's wrap, the same kernel body with another source address.
+ * GOM_ERR_INVALID_ARG before any HIP call: what the dense entry refuses, cap < 1, a null ring, out or (with F > 0) slots,
+ * and an `out` [F,H,W,3] that overlaps [ring, ring + cap * H * W * 3).  F == 0 is GOM_OK without a launch; N == 0 and L == 0
+ * copy ring[slots[f]] to out[f]. */
 int gom_mask_outline_polygons_u32(const int32_t* points, int P, const int32_t* contour_off, int C, const int32_t* mask_coff,
                                   const int32_t* boxes, const int64_t* word_off, int N, long nwords, const int32_t* sel,
                                   int M, int H, int W, uint32_t* words, void* stream);
@@ -870,6 +879,12 @@ int gom_overlay_compose_u8(const uint8_t* frames, uint8_t* out, int F, int H, in
                            const int32_t* label_pos, const int32_t* label_glyph, const uint8_t* label_rgb, int L,
                            const int32_t* glyph_wh, const int64_t* glyph_woff, const uint32_t* glyph_words, int G,
                            long glyph_nwords, int a_face, int a_box, void* stream);
+int gom_overlay_compose_gather_u8(const uint8_t* ring, int cap, const int32_t* slots, uint8_t* out, int F, int H, int W,
+                                  const uint32_t* face_words, const uint32_t* outline_words, const int32_t* boxes,
+                                  const int64_t* word_off, int N, long nwords, const int32_t* inst_off, const uint8_t* inst_rgb,
+                                  const int32_t* label_off, const int32_t* label_pos, const int32_t* label_glyph,
+                                  const uint8_t* label_rgb, int L, const int32_t* glyph_wh, const int64_t* glyph_woff,
+                                  const uint32_t* glyph_words, int G, long glyph_nwords, int a_face, int a_box, void* stream);
 /* ---- Lexicon correction of transcriptions (csrc/lexicon.hip; python -m gomatching_amd.lexicon) ------------------
  * The reference's `find_match_word` (third_party/adet/evaluation/text_evaluation_all.py:249-264, accepted at :332): a
  * recognised word is snapped to the first lexicon word at the smallest edit distance.  THE RULE, integer-exact, so that the
