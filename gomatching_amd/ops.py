@@ -1627,6 +1627,109 @@ def result_text(words, pts, keep, frame_rows, first_frame, tables, ov=None, read
     return js, xs, frame_off[0], frame_off[1]
 
 
+RESULT_PARSE_MAX_SIZE = _lib_mod.CONSTANTS["GOM_RP_MAX_SIZE"]
+RESULT_PARSE_BAD_SIZE = _lib_mod.CONSTANTS["GOM_RP_BAD_SIZE"]
+
+
+def result_parse(data):
+    """The rows of a result file, read from its bytes on the GPU (csrc/result_parse.hip; THE RULE is in
+    include/gomatching_hip.h, `gom_result_parse_*`): data uint8 [size] CUDA, the bytes of jsons/<video>.json.
+    -> (status, rows): status 0 and a dict of CUDA tensors -- frame_rows int32 [F+1], ids int64 [N], pts int32 [N,8], has_seg
+    uint8 [N], t_off int64 [N], t_len int32 [N] (the transcriptions' byte spans in `data`, still escaped), poly_off int32 [N+1],
+    poly_xy int32 [P,2] -- with the counts "L", "F", "N", "P"; or a nonzero set of GOM_RP_BAD_* bits and None: the file is not
+    the canonical text, which is no error.  Three calls around three synchronising reads of the totals (L; F and N; P and the
+    status), because each sizes the next call's buffers; a refusal ends the sequence at the stage that found it.  A size the
+    calls do not take (0 bytes, 2^31 - 1 or more) is refused here, without a launch."""
+    if not data.is_cuda or data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise ValueError("data must be a contiguous CUDA uint8 vector")
+    C = _lib_mod.CONSTANTS
+    dev, size = data.device, data.shape[0]
+    if size < 1 or size > RESULT_PARSE_MAX_SIZE - 1:
+        return RESULT_PARSE_BAD_SIZE, None
+    i32, i64 = torch.int32, torch.int64
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    with torch.cuda.device(dev):
+        nblk = -(-size // C["GOM_RP_BLOCK_BYTES"])
+        blk = new((nblk,), i32)
+        totals = torch.zeros((C["GOM_RP_TOTALS"],), dtype=i64, device=dev)
+        _call("gom_result_parse_lines", _p(data), size, _p(blk), nblk, _p(totals), _stream())
+        t = totals.tolist()
+        L, status = t[C["GOM_RP_L"]], t[C["GOM_RP_STATUS_LINES"]]
+        if status:
+            return status, None
+        if L == 1:                                            # the two bytes {}
+            rows = dict(L=1, F=0, N=0, P=0, frame_rows=torch.zeros((1,), dtype=i32, device=dev), ids=new((0,), i64),
+                        pts=new((0, 8), i32), has_seg=new((0,), torch.uint8), t_off=new((0,), i64), t_len=new((0,), i32),
+                        poly_off=torch.zeros((1,), dtype=i32, device=dev), poly_xy=new((0, 2), i32))
+            return 0, rows
+        nmblk = -(-L // C["GOM_RP_BLOCK"])
+        line_start, mblk, sblk = new((L + 1,), i32), new((2, nmblk), i32), new((nmblk,), i32)
+        _call("gom_result_parse_marks", _p(data), size, _p(blk), nblk, L, _p(line_start), _p(mblk), _p(sblk), nmblk, _p(totals),
+              _stream())
+        t = totals.tolist()
+        F, N, status = t[C["GOM_RP_F"]], t[C["GOM_RP_N"]], t[C["GOM_RP_STATUS_MARKS"]]
+        if status:
+            return status, None
+        cap_p = L // 4
+        n1 = max(N, 1)                                        # (an empty tensor has no address to pass)
+        rows = dict(frame_rows=new((F + 1,), i32), ids=new((n1,), i64), pts=new((n1, 8), i32), has_seg=new((n1,), torch.uint8),
+                    t_off=new((n1,), i64), t_len=new((n1,), i32), poly_off=new((N + 1,), i32))
+        poly_xy = new((max(cap_p, 1), 2), i32)
+        mark_line, obj_mark, frame_mark = new((N + F + 1,), i32), new((n1,), i32), new((F,), i32)
+        unit_status = new((N + F,), i32)
+        _call("gom_result_parse_emit", _p(data), size, _p(line_start), L, _p(mblk), nmblk, F, N, _p(mark_line), _p(obj_mark),
+              _p(frame_mark), _p(rows["frame_rows"]), _p(rows["poly_off"]), _p(rows["ids"]), _p(rows["pts"]),
+              _p(rows["has_seg"]), _p(rows["t_off"]), _p(rows["t_len"]), _p(poly_xy), cap_p, _p(unit_status), _p(totals),
+              _stream())
+        t = totals.tolist()
+        P, status = t[C["GOM_RP_P"]], t[C["GOM_RP_STATUS"]]
+        if status:
+            return status, None
+        for k in ("ids", "pts", "has_seg", "t_off", "t_len"):
+            rows[k] = rows[k][:N]
+        rows.update(L=L, F=F, N=N, P=P, poly_xy=poly_xy[:P])
+    return 0, rows
+
+
+SCENE_PALETTE = _lib_mod.CONSTANTS["GOM_SP_PALETTE"]
+SCENE_BAD_COORD = _lib_mod.CONSTANTS["GOM_SP_BAD_COORD"]
+
+
+def scene_polygons(frame_rows, ids, poly_off, poly_xy, f0, f1, n_inst, n_cont, p0, p1, H, W, palette, bgr):
+    """The polygon side of a drawing scene for frames f0 .. f1 - 1, from the rows `result_parse` left on the GPU
+    (csrc/scene_polygons.hip; the rule is in include/gomatching_hip.h, `gom_scene_polygons_i32`): frame_rows int32 [F+1], ids
+    int64 [N], poly_off int32 [N+1], poly_xy int32 [P,2], palette uint8 [SCENE_PALETTE,3], all CUDA.  The caller counts, from
+    its host copy of frame_rows and poly_off, the chunk's instances `n_inst`, those of them with at least one point `n_cont`,
+    and its points p0 = poly_off[frame_rows[f0]] .. p1 = poly_off[frame_rows[f1]].
+    -> (points, coff, mcoff, boxes, woff, inst_off, inst_rgb, status): the arrays of `show.device_arrays` (points is the view
+    poly_xy[p0:p1]) and an int32 [1] status the caller reads with its next copy back.  Two launches, no
+    synchronisation; a chunk without instances launches nothing."""
+    dev = frame_rows.device
+    i32 = torch.int32
+    _chk_i(dev, ("frame_rows", frame_rows, i32, (None,)), ("ids", ids, torch.int64, (None,)), ("poly_off", poly_off, i32, (None,)),
+           ("poly_xy", poly_xy, i32, (None, 2)), ("palette", palette, torch.uint8, (SCENE_PALETTE, 3)))
+    F, N, P = frame_rows.shape[0] - 1, ids.shape[0], poly_xy.shape[0]
+    f0, f1, n_inst, n_cont, p0, p1 = int(f0), int(f1), int(n_inst), int(n_cont), int(p0), int(p1)
+    if poly_off.shape[0] != N + 1 or not 0 <= f0 < f1 <= F or not 0 <= n_cont <= n_inst <= N or not 0 <= p0 <= p1 <= P:
+        raise ValueError("poly_off must be [N+1], 0 <= f0 < f1 <= F, n_cont <= n_inst <= N and p0 <= p1 point offsets")
+    if int(H) < 1 or int(W) < 1 or int(H) * int(W) > 2 ** 31 - 1:
+        raise ValueError("H x W must lie in [1, 2^31 - 1]")
+    zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+    with torch.cuda.device(dev):
+        if n_inst == 0:
+            return (poly_xy[p0:p0], zeros((1,), i32), zeros((1,), i32), zeros((0, 4), i32), zeros((1,), torch.int64),
+                    zeros((f1 - f0 + 1,), i32), zeros((0, 3), torch.uint8), zeros((1,), i32))
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        coff, mcoff, boxes = new((n_cont + 1,), i32), new((n_inst + 1,), i32), new((n_inst, 4), i32)
+        woff, inst_off, inst_rgb = new((n_inst + 1,), torch.int64), new((f1 - f0 + 1,), i32), new((n_inst, 3), torch.uint8)
+        inst_status, status = new((n_inst,), i32), new((1,), i32)
+        some_xy = poly_xy if P else new((1, 2), i32)         # (an empty tensor has no address to pass; P = 0 reads nothing)
+        _call("gom_scene_polygons_i32", _p(frame_rows), F, _p(ids), _p(poly_off), N, _p(some_xy), P, f0, f1, int(H), int(W),
+              _p(palette), 1 if bgr else 0, _p(coff), n_cont, _p(mcoff), _p(boxes), _p(woff), _p(inst_off), _p(inst_rgb),
+              _p(inst_status), n_inst, _p(status), _stream())
+    return poly_xy[p0:p1], coff, mcoff, boxes, woff, inst_off, inst_rgb, status
+
+
 TRACK_VOTE_RECORD_WORDS = _lib_mod.CONSTANTS["GOM_TV_RECORD_WORDS"]
 TRACK_VOTE_ENTRY_MAX = _lib_mod.CONSTANTS["GOM_TV_ENTRY_MAX"]
 TRACK_VOTE_BLOCK = _lib_mod.CONSTANTS["GOM_TV_BLOCK"]

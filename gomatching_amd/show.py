@@ -4,7 +4,7 @@ wrote -- the counterpart of the reference's `eval.py --show` (eval.py:364-369, t
     python -m gomatching_amd.show --input DIR --results OUT [--output DIR] [--font FILE] [--host-draw]
                                   [--device-encode | --host-encode] [--jpeg-quality N]
                                   [--device-decode [--decode-walk {auto,segments,chunks}]]
-                                  [--voc-size N | --config-file F | --builtin NAME]
+                                  [--device-read] [--voc-size N | --config-file F | --builtin NAME]
       -> DIR/results/<video name>/<basename of the source frame>   (DIR defaults to OUT)
 
 Drawing is a pure function of the frames and the result rows `[x1..y4, id, text, [polygon]]` (what `results.frame_lines` /
@@ -52,6 +52,14 @@ by chunk.  One opt-in flag keeps the pixels off the host:
                     --device-encode a frame enters the GPU as entropy bytes and leaves it as entropy bytes.  The run prints the
                     route counts.  Not with --host-draw (status 2); without a GPU status 1.
   --decode-walk W   with --device-decode: the decoder's entropy walk, as in `eval` (default auto); alone status 2.
+  --device-read     every jsons/<video>.json goes to the GPU as bytes and is parsed there (csrc/result_parse.hip; the rule is
+                    `gom_result_parse_*` in include/gomatching_hip.h: exactly the text json.dumps(indent=4,
+                    ensure_ascii=False) writes for a result file); each chunk's contours, boxes, word offsets and colours are
+                    made from the parsed rows where they lie (`ops.scene_polygons`), about 430 bytes per instance come back
+                    for the labels, which stay host work (`label_anchors`, Pillow's bitmaps).  Any other text -- another
+                    indent, escapes json.dumps would not write, several contours -- is refused by the parser and read by
+                    json.load, per file; the run prints how many files went each way and why.  The same pictures, byte for
+                    byte.  Not with --host-draw (status 2); without a GPU status 1.  A choice, not a fall-back.
 The same drawing functions serve frames that already lie in device memory elsewhere: `draw_chunk_resident` / `compose_resident`
 take a CUDA u8 [F,H,W,3] tensor and draw it where it lies, `draw_gather_resident` draws frames that wait in a ring through
 one `gom_overlay_compose_gather_u8` launch (`online.OnlineSpotter(draw=...)`, `eval --online --show --device-decode`), and
@@ -145,6 +153,44 @@ def label_anchor(polygon):
         else:
             pt = c[-1]
     return int(pt[0]), int(pt[1])
+
+
+def label_anchors(poly_xy, poly_off):
+    """`label_anchor` of many polygons at once: poly_xy int [P,2], poly_off int [N+1] (polygon k = poly_xy[poly_off[k] :
+    poly_off[k+1]]) -> int64 [N,2], bit for bit what `label_anchor` gives for each.  Polygons of one vertex count are taken
+    together, a row each: every step is the scalar function's own expression over rows -- np.hypot per element, the sum of a
+    row's lengths by the same reduction over the same count (numpy reduces a contiguous row as it reduces a vector of that
+    length), the walk as a running sum along the row (sequential additions, as the loop makes them)."""
+    xy = np.asarray(poly_xy, dtype=np.float64).reshape(-1, 2)
+    off = np.asarray(poly_off, dtype=np.int64).reshape(-1)
+    N = len(off) - 1
+    out = np.zeros((N, 2), dtype=np.int64)
+    counts = off[1:] - off[:-1]
+    for n in np.unique(counts).tolist():
+        if n == 0:
+            continue
+        ks = np.nonzero(counts == n)[0]
+        P = xy[off[ks][:, None] + np.arange(n)[None, :]]     # [G,n,2]
+        half = (n + 1) // 2
+        c = (P[:, :half] + P[:, ::-1][:, :half]) / 2.0
+        pt = c[:, 0].copy()
+        if half > 1:
+            d = c[:, 1:] - c[:, :-1]
+            seg = np.ascontiguousarray(np.hypot(d[:, :, 0], d[:, :, 1]))     # [G,half-1]
+            total = seg.sum(axis=1)
+            target = total / 2.0
+            after = np.cumsum(seg, axis=1)                    # walked + d at every step
+            before = np.concatenate([np.zeros((len(ks), 1)), after[:, :-1]], axis=1)
+            hit = (seg > 0.0) & (after >= target[:, None])
+            first = hit.argmax(axis=1)
+            rows = np.arange(len(ks))
+            w, dd = before[rows, first], seg[rows, first]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                on = c[rows, first] + ((target - w) / dd)[:, None] * (c[rows, first + 1] - c[rows, first])
+            walked = np.where(hit.any(axis=1)[:, None], on, c[:, -1])
+            pt = np.where((total > 0.0)[:, None], walked, pt)
+        out[ks] = pt.astype(np.int64)                         # (truncation toward zero, as int() does)
+    return out
 
 
 # ------------------------------------------------------------------------------------------ label bitmaps
@@ -409,6 +455,105 @@ def _chunk_scene(frames_u8, rows_per_frame, voc_size, atlas, bgr):
     return part, _scene_of_rows(rows_per_frame, voc_size, atlas, part.shape[1], part.shape[2], bgr)
 
 
+class _Dims:
+    """What `launch` reads of a scene whose arrays were made on the device."""
+
+    def __init__(self, F, H, W):
+        self.F, self.H, self.W = int(F), int(H), int(W)
+
+
+INK = np.asarray([text_color(track_color(i)) for i in range(PALETTE_SIZE)], dtype=np.uint8)     # a label's colour, by id % 500
+_palette_dev = {}
+
+
+def _device_palette(dev):
+    """PALETTE on `dev`, uploaded once."""
+    import torch
+    if dev not in _palette_dev:
+        _palette_dev[dev] = torch.from_numpy(PALETTE.copy()).to(dev)
+    return _palette_dev[dev]
+
+
+class ParsedScenes:
+    """The scenes of one video whose rows `results.parse_json_device` read (`show --device-read`): the polygons stay on the
+    device, where `ops.scene_polygons` makes each chunk's contour offsets, boxes, word offsets and colours from them; the labels
+    are host work, done here once per video from the compact arrays that came back -- the anchors (`label_anchors`), the
+    colours (`INK[id % 500]`) -- and per frame size the atlas indices, rendered once per distinct (id, transcription)."""
+
+    def __init__(self, parsed, voc_size, atlas, bgr=True):
+        self.parsed, self.voc_size, self.atlas, self.bgr = parsed, voc_size, atlas, bool(bgr)
+        self.anchors = label_anchors(parsed.poly_xy, parsed.poly_off).astype(np.int32)
+        ink = INK[np.mod(parsed.ids, PALETTE_SIZE)]          # (numpy's mod is Python's %: non-negative)
+        self.label_rgb = np.ascontiguousarray(ink[:, ::-1] if self.bgr else ink)
+        self.kept = (np.diff(parsed.poly_off) > 0).astype(np.int64)
+        self._glyphs = {}
+
+    def glyphs(self, px, i0, i1):
+        """The atlas index of the labels of rows i0 .. i1 - 1 at pixel size px: int32 [i1 - i0].  A label is rendered when its
+        row is first asked for, in row order -- the order in which `_scene_of_rows` meets the labels of the same chunks."""
+        if px not in self._glyphs:
+            self._glyphs[px] = ({}, np.full(self.parsed.N, -1, dtype=np.int32))
+        seen, out = self._glyphs[px]
+        todo = np.nonzero(out[i0:i1] < 0)[0] + i0
+        if len(todo):
+            ids, texts = self.parsed.ids[todo].tolist(), self.parsed.texts
+            for k, track in zip(todo.tolist(), ids):
+                key = (track, texts[k])
+                g = seen.get(key)
+                if g is None:
+                    g = seen[key] = self.atlas.index(label_text(track, key[1], self.voc_size), px)
+                out[k] = g
+        return out[i0:i1]
+
+    def chunk(self, f0, f1, H, W, dev):
+        """Frames f0 .. f1 - 1 at H x W -> (what `launch` takes as its scene, its `arrays`): two launches, one upload of the
+        label arrays and ONE synchronising read (the chunk's word count and status: the bit rows are sized by the first)."""
+        import torch
+        from . import ops
+        p = self.parsed
+        if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+            raise ShowError("image size %d x %d is not supported" % (H, W))
+        i0, i1 = int(p.frame_rows[f0]), int(p.frame_rows[f1])
+        d = p.dev
+        points, coff, mcoff, boxes, woff, inst_off, inst_rgb, status = ops.scene_polygons(
+            d["frame_rows"], d["ids"], d["poly_off"], d["poly_xy"], f0, f1, i1 - i0, int(self.kept[i0:i1].sum()),
+            int(p.poly_off[i0]), int(p.poly_off[i1]), H, W, _device_palette(dev), self.bgr)
+        used, local = np.unique(self.glyphs(font_px(H, W), i0, i1), return_inverse=True)
+        gwh, gwoff, gwords = self.atlas.arrays(used)
+        label_off = (p.frame_rows[f0:f1 + 1] - i0).astype(np.int32)
+        up = _upload([label_off, self.anchors[i0:i1], local.astype(np.int32).reshape(-1), self.label_rgb[i0:i1],
+                      gwh.astype(np.int32), gwoff.astype(np.int64), gwords.astype(np.uint32)], dev)
+        nwords, bad = torch.cat((woff[-1:], status.to(torch.int64))).tolist()
+        if bad & ops.SCENE_BAD_COORD:
+            raise ShowError("a polygon coordinate beyond +-2^20")
+        if bad:
+            raise ShowError("the parsed rows are not the ones the scene was counted from (status %d)" % bad)
+        face = torch.empty((nwords,), dtype=torch.int32, device=dev)
+        line = torch.empty((nwords,), dtype=torch.int32, device=dev)
+        area = torch.empty((i1 - i0,), dtype=torch.int32, device=dev)
+        return _Dims(f1 - f0, H, W), ([points, coff, mcoff, boxes, woff, inst_off, inst_rgb] + up, face, line, area)
+
+
+def draw_chunk_parsed(frames_u8, scenes, f0, bgr=True):
+    """`draw_chunk_resident` with the scene made from parsed rows: the chunk is frames f0 .. f0 + len(frames_u8) - 1 of the
+    video `scenes` (a `ParsedScenes`) describes.  -> a CUDA u8 tensor [F,H,W,3]; resident frames are drawn in place."""
+    import torch
+    if not len(frames_u8):
+        raise ValueError("no frames")
+    if is_resident(frames_u8):
+        fr = _resident_frames(frames_u8)
+    else:
+        if not torch.cuda.is_available():
+            raise ShowError("no GPU: drawing runs in csrc/overlay.hip (use --host-draw for the numpy path)")
+        part = np.ascontiguousarray(np.stack([np.asarray(f) for f in frames_u8]), dtype=np.uint8)
+        if part.ndim != 4 or part.shape[3] != 3:
+            raise ValueError("frames must be u8 [F,H,W,3]")
+        fr = torch.from_numpy(part).to(torch.device("cuda", torch.cuda.current_device()))
+    with torch.cuda.device(fr.device):
+        dims, arrays = scenes.chunk(f0, f0 + fr.shape[0], int(fr.shape[1]), int(fr.shape[2]), fr.device)
+        return launch(fr, dims, arrays)
+
+
 def draw_chunk_resident(frames_u8, rows_per_frame, voc_size, atlas, bgr=True):
     """One chunk of `draw_clip` on the GPU, the drawn frames left there for the encoder: -> a CUDA u8 tensor [F,H,W,3].
     `frames_u8` may be a CUDA u8 [F,H,W,3] tensor (frames decoded on the GPU): it is drawn where it lies, in place, and
@@ -502,7 +647,8 @@ def _write_encoded(drawn, targets, pool, encode, quality):
         list(pool.map(write_frame, others, [targets[i] for i in rest]))
 
 
-def draw_video(frames, annotation, paths, video_name, out_dir, voc_size, pool, atlas, host=False, encode=None, quality=95):
+def draw_video(frames, annotation, paths, video_name, out_dir, voc_size, pool, atlas, host=False, encode=None, quality=95,
+               parsed=None):
     """Draw a whole video (BGR frames, `annotation` = {1-based frame id as str: rows}) chunk by chunk and write
     out_dir/results/<video name>/<basename of the frame's source path> through `pool`.  encode = None: Pillow writes every
     file; "device" / "host": the JPEG frames go through csrc/jpeg.hip (the drawn chunk never leaves the GPU) / through
@@ -510,21 +656,38 @@ def draw_video(frames, annotation, paths, video_name, out_dir, voc_size, pool, a
     `frames` may be, instead of the list of host frames, a function `frames(f0, f1)` that returns frames f0 .. f1 - 1 of the
     video (one per path) as ONE CUDA u8 [f1 - f0,H,W,3] tensor, called once per chunk of at most CHUNK frames in order (a
     `DecodedChunks`): the chunk is drawn where it lies and no more than one chunk of pixels is ever held.  It raises
-    `ShowError` for frames of a chunk that differ in size."""
+    `ShowError` for frames of a chunk that differ in size.
+    parsed = a `results.ParsedRows` (status 0) in place of `annotation` (then None): every chunk's scene is made from the rows
+    where the parser left them (`ParsedScenes`: `ops.scene_polygons` plus the host's label arrays) and drawn on the GPU, for
+    host frames (uploaded as ever) and for a provider alike; the same bytes.  Not with host=True."""
     provider = frames if callable(frames) else None
     count = len(paths) if provider is not None else len(frames)
-    if len(annotation) != count:
-        raise ShowError("video %s: %d frames but results for %d" % (video_name, count, len(annotation)))
+    have = parsed.F if parsed is not None else len(annotation)
+    if have != count:
+        raise ShowError("video %s: %d frames but results for %d" % (video_name, count, have))
+    if parsed is not None and host:
+        raise ValueError("parsed rows are drawn on the GPU")
+    if parsed is not None and not parsed.has_seg.all():
+        raise ShowError("video %s: result rows without a segmentation cannot be drawn" % video_name)
     save_dir = os.path.join(out_dir, "results", video_name)
     os.makedirs(save_dir, exist_ok=True)
-    try:
-        rows = [annotation[str(i + 1)] for i in range(count)]
-    except KeyError as e:
-        raise ShowError("video %s: no results for frame %s" % (video_name, e))
+    if parsed is not None:
+        scenes = ParsedScenes(parsed, voc_size, atlas)
+    else:
+        try:
+            rows = [annotation[str(i + 1)] for i in range(count)]
+        except KeyError as e:
+            raise ShowError("video %s: no results for frame %s" % (video_name, e))
     for f0 in range(0, count, CHUNK):
         targets = [os.path.join(save_dir, os.path.basename(p)) for p in paths[f0:f0 + CHUNK]]
         try:
-            if provider is not None:
+            if parsed is not None:
+                part = provider(f0, min(f0 + CHUNK, count)) if provider is not None else frames[f0:f0 + CHUNK]
+                drawn = draw_chunk_parsed(part, scenes, f0)
+                if encode != "device":
+                    drawn = drawn.cpu().numpy()
+                del part
+            elif provider is not None:
                 part = provider(f0, min(f0 + CHUNK, count))
                 if host:                                    # (the numpy rule on frames decoded on the GPU: one copy back)
                     drawn = draw_clip(part.cpu().numpy(), rows[f0:f0 + CHUNK], voc_size, host=True, atlas=atlas)
@@ -585,6 +748,13 @@ def print_draw_routes(counts, walk, shared=False):
           " with another extension, ", counts["refused"], " refused by the parser, ", counts["flagged"],
           " with a status word set; walk (--decode-walk ", walk, "): ", counts.get("chunks", 0), " segments by the chunk walk, ",
           counts.get("serial", 0), " by the serial walk")
+
+
+def print_read_routes(counts):
+    """The routes the result files took under --device-read, on a line of their own; for the refused ones, why."""
+    why = ", ".join("%s: %d" % kv for kv in sorted(counts["causes"].items()))
+    print("result files: ", counts["device"], " read on the GPU, ", counts["host"], " through json.load",
+          " (refused by the parser -- %s)" % why if why else "", sep="")
 
 
 def rows_of_json(tracks):
@@ -652,6 +822,10 @@ def get_parser():
                         "file (not with --host-draw)")
     p.add_argument("--decode-walk", choices=("auto", "segments", "chunks"), default=None,
                    help="with --device-decode: the decoder's entropy walk, as in gomatching_amd.eval (default auto)")
+    p.add_argument("--device-read", action="store_true",
+                   help="read every result file on the GPU (csrc/result_parse.hip) and build each chunk's polygons there from "
+                        "the parsed rows; a file that is not the canonical json.dumps(indent=4) text goes through json.load, "
+                        "per file (not with --host-draw)")
     p.add_argument("--voc-size", type=int, default=None, metavar="N",
                    help="vocabulary size of the model: 37 upper-cases the labels (default 37)")
     p.add_argument("--config-file", default=None, metavar="FILE", help="take the vocabulary size from a config file")
@@ -683,10 +857,22 @@ def main(argv=None):
         sys.stderr.write("error: --device-decode leaves the frames in device memory, where they are drawn: it does not go with "
                          "--host-draw\n")
         return 2
+    if args.device_read and args.host_draw:
+        sys.stderr.write("error: --device-read leaves the rows in device memory, where the scene is made from them: it does not "
+                         "go with --host-draw\n")
+        return 2
     encode, quality, status, message = encode_choice(args)
     if status:
         sys.stderr.write("error: %s\n" % message)
         return status
+    read_routes = None
+    if args.device_read:
+        import torch
+        if not torch.cuda.is_available():
+            sys.stderr.write("error: --device-read needs a GPU: the parser runs in csrc/result_parse.hip\n")
+            return 1
+        read_routes = {"device": 0, "host": 0, "causes": {}}
+        read_device = torch.device("cuda", torch.cuda.current_device())
     routes = None
     if args.device_decode:
         import torch
@@ -709,12 +895,29 @@ def main(argv=None):
                 json_path = os.path.join(args.results, "jsons", "%s.json" % _results.result_names(video_name, data_type)[1])
                 if not os.path.isfile(json_path):
                     raise ShowError("video %s: result file %s not found" % (video_name, json_path))
-                with open(json_path, "r", encoding="utf-8") as fp:
-                    annotation = rows_of_json(json.load(fp))
+                parsed = None
+                if read_routes is not None:                 # the file's bytes to the GPU; a refused file is read as ever
+                    with open(json_path, "rb") as fp:
+                        data = fp.read()
+                    parsed = _results.parse_json_device(data, read_device)
+                    if parsed.status:
+                        read_routes["host"] += 1
+                        for cause in parsed.causes():
+                            read_routes["causes"][cause] = read_routes["causes"].get(cause, 0) + 1
+                        parsed, annotation = None, rows_of_json(json.loads(data.decode("utf-8")))
+                    else:
+                        read_routes["device"] += 1
+                        annotation = None
+                    del data
+                else:
+                    with open(json_path, "r", encoding="utf-8") as fp:
+                        annotation = rows_of_json(json.load(fp))
                 paths = _eval.frame_paths(video_dir)
-                if len(paths) != len(annotation):
-                    raise ShowError("video %s: %d frames but results for %d" % (video_name, len(paths), len(annotation)))
-                if any(len(row) < 11 for rows in annotation.values() for row in rows):
+                have = parsed.F if parsed is not None else len(annotation)
+                if len(paths) != have:
+                    raise ShowError("video %s: %d frames but results for %d" % (video_name, len(paths), have))
+                if (not parsed.has_seg.all()) if parsed is not None else \
+                        any(len(row) < 11 for rows in annotation.values() for row in rows):
                     raise ShowError("video %s: result rows without a segmentation cannot be drawn" % video_name)
                 print("drawing {}...".format(video_name))
                 if routes is not None:                      # bytes one chunk ahead, pixels made and drawn on the GPU
@@ -722,12 +925,14 @@ def main(argv=None):
                 else:
                     frames = list(readers.map(_eval.read_frame, paths))
                 draw_video(frames, annotation, paths, video_name, out_dir, voc_size, writers, atlas, host=args.host_draw,
-                           encode=encode, quality=quality)
+                           encode=encode, quality=quality, parsed=parsed)
     except ShowError as e:
         sys.stderr.write("error: %s\n" % e)
         return 2
     if routes is not None:
         print_draw_routes(routes, walk)
+    if read_routes is not None:
+        print_read_routes(read_routes)
     return 0
 
 

@@ -626,6 +626,128 @@ int gom_result_text_emit(const int32_t* words, int ld, const int64_t* pts, const
                          const int32_t* frame_rows, int F, long first_frame, const uint8_t* json_tab, const uint8_t* xml_tab,
                          int ntab, const int32_t* row_len, const int64_t* row_off, const int32_t* row_kept,
                          const int64_t* frame_off, uint8_t* json, long json_cap, uint8_t* xml, long xml_cap, void* stream);
+/* ---- Result parse (csrc/result_parse.hip, csrc/result_parse_core.h; results.parse_json_device; show --device-read) ----------
+ * The inverse of the JSON stream above: the bytes of jsons/<video>.json -> the rows, where they lie on the device.
+ * THE RULE.  ACCEPTED is a byte string that equals, byte for byte, json.dumps(A, ensure_ascii=False, indent=4) for an annotation
+ * A of the canonical shape: keys "1", "2", .. "F" in that order (F = 0: the two bytes {}); every value a list of objects; every
+ * object "points" (exactly 8 integers), "ID" (an integer), "transcription" (a string), in that order, and then possibly
+ * "segmentation": a list of exactly one contour of n >= 0 [x, y] integer pairs.  Integers are plain decimal: an optional '-',
+ * no leading zero, no "-0", no fraction, no exponent; ID fits int64, every other integer int32.  Everything else is REFUSED
+ * with a status word (a set of the GOM_RP_BAD_* bits below); a refused file is no error: its caller reads it with json.load.
+ * THE PROPERTY: for any bytes, either the status is nonzero or json.dumps(.., ensure_ascii=False, indent=4) of the parsed rows
+ * gives the input back byte for byte.  The rule may refuse too much; it never accepts what json.loads reads differently.
+ * The text holds one token per line and a raw 0x0A never lies inside a JSON string, so every value sits at a fixed line offset
+ * from the line that opens its object; the rule is stated over LINES (<k> is k spaces, \n one byte 0x0A):
+ *   Lines   : the bytes between the 0x0A bytes; L = (number of 0x0A) + 1; line i is [line_start[i], line_start[i+1] - 1),
+ *             line_start[0] = 0, line_start[L] = size + 1.
+ *   Stage 1 : L == 1: accepted with F = 0 iff the bytes are {} , else GOM_RP_BAD_ENDS.  L >= 2: the file begins {\n and ends
+ *             \n} or GOM_RP_BAD_ENDS.  A nonzero status ends the parse here (and after stage 2): the later stages are not run.
+ *   Stage 2 : a line longer than GOM_RP_MAX_LINE bytes: GOM_RP_BAD_LINE.  MARKS: an object line is exactly <8>{ ; a key line
+ *             begins <4>" .  N = the object lines, F = the key lines; F == 0 here: GOM_RP_BAD_PLACE.  The marks in line order,
+ *             and the file's last line after them, bound each other's spans.
+ *   Stage 3 : every object and every frame is held against its template; the status is the OR over all of them.
+ *     object o, opened at line s, the next mark (or the last line) at line e: nl = e - s if that mark is an object line, else
+ *             e - s - 1 (the frame's closing line).  n = (nl - 18) / 4 if nl >= 22 and 4 divides nl - 18, else 0; poly_off is
+ *             the exclusive scan of n.  Among the offsets j = 2 .. min(nl, 64) - 1 the first line that is <12>], : none:
+ *             GOM_RP_BAD_PLACE; not at j = 10: GOM_RP_BAD_POINTS; either way the object is checked no further.  nl not 14, 17
+ *             or 18 + 4 n with n >= 1: GOM_RP_BAD_PLACE, and no further.  Else line s + j must be, for
+ *               j = 0 <8>{    1 <12>"points": [    2 .. 9 <16>P,  (no comma at 9; int32)    10 <12>],    11 <12>"ID": I,  (int64)
+ *               12 <12>"transcription": "T"  followed by a comma iff nl > 14        nl - 1 <8>}  followed by a comma iff the
+ *               next mark is an object line;        and for nl > 14:   13 <12>"segmentation": [    nl - 2 <12>]
+ *               nl == 17: 14 <16>[]        nl > 17: 14 <16>[    nl - 3 <16>]    and for point p < n at j = 15 + 4 p:
+ *               <20>[    <24>X,    <24>Y    <20>]  followed by a comma iff p < n - 1.
+ *             A line that is not its template: GOM_RP_BAD_PLACE.  An integer token (the bytes between the indent or key and
+ *             the line's end or comma) that holds a byte outside -+.eE0-9 or begins with none of -0123456789:
+ *             GOM_RP_BAD_PLACE; one that is not canonical or out of range: GOM_RP_BAD_INT.  T ends at the first " that no
+ *             backslash precedes (a backslash takes the byte after it with it); none on the line: GOM_RP_BAD_LINE.
+ *     frame f, its key at line k, the next mark at line e, the next key line (or the last line) at line x, rows r0 .. r1 - 1:
+ *             f == 0 and (k != 1 or r0 != 0): GOM_RP_BAD_PLACE.  The key line is <4>"K": [ or <4>"K": [] and then possibly
+ *             a comma, or GOM_RP_BAD_PLACE and the frame is checked no further; K not canonical or K != f + 1:
+ *             GOM_RP_BAD_KEY.  Without rows: the [] form, e == k + 1, a comma iff f < F - 1.  With rows: the [ form without a
+ *             comma, e == k + 1, and line x - 1 is <4>] followed by a comma iff f < F - 1.  Else GOM_RP_BAD_PLACE.
+ *   Strings : the device only locates T (t_off, t_len: the bytes between the quotes).  The host decodes every distinct span
+ *             once with json.loads and refuses the file (GOM_RP_BAD_STRING) unless json.dumps(.., ensure_ascii=False) of the
+ *             decoded string gives the span back.
+ * Three calls, because L, then F and N, are results the next call's buffers are sized by; totals int64 [GOM_RP_TOTALS] is what
+ * the caller reads between them (zeroed by the caller before the first; every slot has one writing call):
+ *   gom_result_parse_lines : a thread per GOM_RP_THREAD_BYTES bytes counts the 0x0A bytes, a block per GOM_RP_BLOCK_BYTES; ONE
+ *             block scans the nblk = ceil(size / GOM_RP_BLOCK_BYTES) block counts in place (tiles of GOM_RP_BLOCK) and does
+ *             stage 1.  -> totals[GOM_RP_L], totals[GOM_RP_STATUS_LINES].
+ *   gom_result_parse_marks : writes line_start int32 [L + 1]; a lane per line flags the marks and the long lines, a block per
+ *             GOM_RP_BLOCK lines (nmblk = ceil(L / GOM_RP_BLOCK); mblk int32 [2][nmblk], sblk int32 [nmblk]); ONE block scans.
+ *             -> totals[GOM_RP_F], totals[GOM_RP_N], totals[GOM_RP_STATUS_MARKS].
+ *   gom_result_parse_emit  : writes mark_line int32 [N + F + 1], obj_mark int32 [N], frame_mark int32 [F], frame_rows int32
+ *             [F + 1]; ONE block scans n -> poly_off int32 [N + 1]; a wavefront per object and per frame does stage 3, a lane
+ *             per line, and stores ids int64 [N], pts int32 [N][8], has_seg u8 [N], t_off int64 [N], t_len int32 [N], poly_xy
+ *             int32 [cap_p][2] (cap_p >= P; floor(L / 4) always is) and its status into unit_status int32 [N + F]; ONE block
+ *             folds them.  -> totals[GOM_RP_P], totals[GOM_RP_STATUS].  A value that does not fit its array (cap_p too
+ *             small) is not stored: GOM_RP_BAD_CAP.
+ * No atomics, no scratch, one writer per output word; every read is bounded by the file's end, every store index checked; the
+ * result depends on nothing but the input: bitwise reproducible.  The outputs of a refused file are unspecified.
+ * GOM_ERR_INVALID_ARG before any HIP call: a null pointer, size < 1 or size >= 2^31 - 1 (the wrapper refuses such a file with
+ * GOM_RP_BAD_SIZE and launches nothing), nblk or nmblk that is not the count above, L < 2 or L > size + 1, F < 1, N < 0,
+ * F + N > L, cap_p < 0. */
+#define GOM_RP_BAD_PLACE 1
+#define GOM_RP_BAD_INT 2
+#define GOM_RP_BAD_KEY 4
+#define GOM_RP_BAD_POINTS 8
+#define GOM_RP_BAD_LINE 16
+#define GOM_RP_BAD_ENDS 32
+#define GOM_RP_BAD_SIZE 64
+#define GOM_RP_BAD_STRING 128
+#define GOM_RP_BAD_CAP 256
+#define GOM_RP_BLOCK 256
+#define GOM_RP_THREAD_BYTES 16
+#define GOM_RP_BLOCK_BYTES 4096
+#define GOM_RP_MAX_LINE 1024
+#define GOM_RP_MAX_SIZE 2147483646
+#define GOM_RP_TOTALS 8
+#define GOM_RP_L 0
+#define GOM_RP_F 1
+#define GOM_RP_N 2
+#define GOM_RP_P 3
+#define GOM_RP_STATUS 4
+#define GOM_RP_STATUS_LINES 5
+#define GOM_RP_STATUS_MARKS 6
+int gom_result_parse_lines(const uint8_t* data, long size, int32_t* blk, int nblk, int64_t* totals, void* stream);
+int gom_result_parse_marks(const uint8_t* data, long size, const int32_t* blk, int nblk, long L, int32_t* line_start,
+                           int32_t* mblk, int32_t* sblk, int nmblk, int64_t* totals, void* stream);
+int gom_result_parse_emit(const uint8_t* data, long size, const int32_t* line_start, long L, const int32_t* mblk, int nmblk,
+                          int F, int N, int32_t* mark_line, int32_t* obj_mark, int32_t* frame_mark, int32_t* frame_rows,
+                          int32_t* poly_off, int64_t* ids, int32_t* pts, uint8_t* has_seg, int64_t* t_off, int32_t* t_len,
+                          int32_t* poly_xy, long cap_p, int32_t* unit_status, int64_t* totals, void* stream);
+/* ---- The scene of parsed rows (csrc/scene_polygons.hip; show.draw_video(parsed=...); show --device-read) ------------------
+ * What `show.Scene` / `score_json.MaskSet` build on the host for the rows of frames f0 .. f1 - 1 of a video, made from the
+ * arrays gom_result_parse_emit left (frame_rows int32 [F + 1], ids int64 [N], poly_off int32 [N + 1], poly_xy int32 [P][2]) for
+ * an H x W frame, without the polygons becoming host lists.  The chunk's instances are i0 = frame_rows[f0] .. i1 - 1,
+ * i1 = frame_rows[f1]; instance k of the chunk is row i0 + k with the points poly_xy[poly_off[i0 + k] .. poly_off[i0 + k + 1]).
+ *   points   : poly_xy from point poly_off[i0] on, as it lies (the caller passes that address on; nothing is copied)
+ *   mcoff    int32 [n_inst + 1] : the exclusive scan of (an instance has at least one point): an empty contour is dropped
+ *   coff     int32 [n_cont + 1] : coff[mcoff[k]] = poly_off[i0 + k] - poly_off[i0] for a kept contour; coff[n_cont] = the points
+ *   boxes    int32 [n_inst][4]  : with (xmin, xmax, ymin, ymax) over the instance's points, x0 = max(xmin, 0), y0 = max(ymin, 0),
+ *                                 x1 = min(xmax, W - 1), y1 = min(ymax, H - 1): (y0, y1 + 1, x0 >> 5, (x1 >> 5) + 1) if x0 <= x1 and
+ *                                 y0 <= y1, else (and without points) four zeros
+ *   woff     int64 [n_inst + 1] : the exclusive scan of (boxes[k][1] - boxes[k][0]) * (boxes[k][3] - boxes[k][2])
+ *   inst_off int32 [f1 - f0 + 1]: frame_rows[f0 + j] - i0
+ *   inst_rgb u8 [n_inst][3]     : palette[m][c] with m = ids mod GOM_SP_PALETTE, the non-negative remainder (Python's %); with
+ *                                 bgr != 0 the channels reversed.  palette: u8 [GOM_SP_PALETTE][3].
+ *   status   int32 [1]          : GOM_SP_BAD_COORD if a coordinate of a point lies beyond +-GOM_SP_MAX_COORD (the wrapper raises
+ *                                 MaskSet's message); GOM_SP_BAD_SHAPE if n_inst is not i1 - i0 or n_cont not the kept contours
+ *                                 (the caller counts both from its copy of frame_rows and poly_off).
+ * Two launches: a lane per instance (boxes, colours, a status word each in inst_status int32 [n_inst]), then ONE block of
+ * GOM_SP_BLOCK threads (the scans, coff, inst_off, the fold of the status words).  No atomics, no scratch, one writer per output
+ * word; every index read from the arrays is clamped into its array before use, every store index checked.  Bitwise
+ * reproducible.  GOM_ERR_INVALID_ARG before any HIP call: a null pointer, F < 1, N < 0, P < 0, not 0 <= f0 < f1 <= F, n_inst < 0,
+ * n_cont < 0 or > n_inst, H < 1, W < 1, H * W > 2^31 - 1, boxes not 16-byte aligned, poly_xy not 8-byte aligned. */
+#define GOM_SP_PALETTE 500
+#define GOM_SP_MAX_COORD 1048576
+#define GOM_SP_BLOCK 256
+#define GOM_SP_BAD_COORD 1
+#define GOM_SP_BAD_SHAPE 2
+int gom_scene_polygons_i32(const int32_t* frame_rows, int F, const int64_t* ids, const int32_t* poly_off, int N,
+                           const int32_t* poly_xy, int P, int f0, int f1, int H, int W, const uint8_t* palette, int bgr,
+                           int32_t* coff, int n_cont, int32_t* mcoff, int32_t* boxes, int64_t* woff, int32_t* inst_off,
+                           uint8_t* inst_rgb, int32_t* inst_status, int n_inst, int32_t* status, void* stream);
 /* ---- Track vote (csrc/track_vote.hip, csrc/track_vote_core.h; results.TrackVote; eval --device-write --device-vote) --------
  * The bytes of <out>/preds/res_<video>.txt, one line per track with the track's majority transcription, made from the rows
  * where they lie on the device.  THE RULE: the bytes are those `results.write_track_transcriptions` writes after parsing the
