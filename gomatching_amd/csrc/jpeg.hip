@@ -26,6 +26,7 @@
 //                          up to four bytes gathered from one or more intervals' stuffed staging.
 // The width limit GOM_JPEG_MAX_WIDTH = 4096 is the size of the LDS array of block starts (1 537 ints).
 #include "common.h"
+#include "wave_block.h"
 
 #define JP_THREADS 256
 #define JP_STAGE_WORDS 52                                              // 1 660 bits of a block's code, rounded up to words
@@ -125,29 +126,7 @@ inline bool jp_layout(int F, int H, int W, JpLayout& L) {
     return true;
 }
 
-// ---- device helpers ---------------------------------------------------------------------------------------------------------
-// Exclusive scan of one int per thread over the 256 threads of a workgroup; *total = the sum.  Two barriers.
-__device__ __forceinline__ int jp_block_scan(int v, int* red, int tid, int& total) {
-    const int lane = tid & 63, w = tid >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) red[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < JP_THREADS / 64; ++i) {
-        const int r = red[i];
-        base += i < w ? r : 0;
-        tot += r;
-    }
-    __syncthreads();
-    total = tot;
-    return base + inc - v;
-}
+// (the exclusive scans of one int per thread over the workgroup: wb_block_excl_scan of wave_block.h, two barriers each)
 
 // ---- launch 1: colour, 2x2 mean, DCT, quantisation, zigzag --------------------------------------------------------------------
 __global__ __launch_bounds__(JP_THREADS) void jpeg_transform_kernel(const unsigned char* __restrict__ frames, int H, int W, int MH,
@@ -295,7 +274,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_entropy_kernel(const short* _
         int sum = 0;
         for (int j = a; j < b; ++j) sum += s_start[j];
         int total;
-        int at = jp_block_scan(sum, s_red, tid, total);
+        int at = wb_block_excl_scan<JP_THREADS>(sum, s_red, total);
         for (int j = a; j < b; ++j) {
             const int len = s_start[j];
             s_start[j] = at;
@@ -349,7 +328,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_entropy_kernel(const short* _
 #pragma unroll
         for (int i = 0; i < 4; ++i) cnt += (i < nv && ((word >> (24 - 8 * i)) & 255u) == 255u) ? 1 : 0;
         int tot;
-        const int excl = jp_block_scan(cnt, s_red, tid, tot);
+        const int excl = wb_block_excl_scan<JP_THREADS>(cnt, s_red, tot);
         if (nv > 0) {
             long p = 4L * wi + carry + excl;
 #pragma unroll
@@ -384,7 +363,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_offsets_kernel(const int* __r
         const long i = base + tid;
         const int v = i < NI ? min(max(lens[i], 0), (int)min(cap, 8388607L)) : 0;   // 256 of them fit an int
         int tot;
-        const int excl = jp_block_scan(v, s_red, tid, tot);
+        const int excl = wb_block_excl_scan<JP_THREADS>(v, s_red, tot);
         if (i < NI) {
             ioff[i] = carry + excl;
             if (i % MH == 0) frame_off[i / MH] = carry + excl;

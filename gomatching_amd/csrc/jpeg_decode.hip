@@ -23,6 +23,7 @@
 #include "common.h"
 #include "jpeg_decode_core.h"
 #include "jpeg_decode_chunks.h"
+#include "wave_block.h"
 
 #define JD_WIN_BYTES 2048
 #define JC_THREADS GOM_JC_MAX_LANES
@@ -206,17 +207,14 @@ __global__ __launch_bounds__(JC_THREADS) void jpeg_decode_chunks_kernel(const ui
             truth.slot = (ew >> 3) & 7;
             truth.k = ew >> 6;
         }
-        // (c), (d) exclusive scans of the blocks begun and the DC sums: within the wave by shuffles, across the waves through LDS
+        // (c), (d) exclusive scans of the blocks begun and the DC sums: within the wave by the shared scan (wave_block.h), across the
+        // waves through LDS, the four values behind ONE barrier (which is why this is not four block scans)
         uint32_t inc[4] = {active ? (uint32_t)tot.blocks : 0u, active ? tot.dc0 : 0u, active ? tot.dc1 : 0u, active ? tot.dc2 : 0u};
         const uint32_t own[4] = {inc[0], inc[1], inc[2], inc[3]};
         const int wl = tid & 63, wv = tid >> 6;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int dlt = 1; dlt < 64; dlt <<= 1) {
-                const uint32_t up = (uint32_t)__shfl_up((int)inc[q], dlt, 64);
-                if (wl >= dlt) inc[q] += up;
-            }
+            inc[q] = wb_wave_incl_scan<uint32_t>(inc[q]);
             if (wl == 63) s_wave[wv][q] = inc[q];
         }
         __syncthreads();

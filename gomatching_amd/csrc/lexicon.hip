@@ -14,6 +14,7 @@
 // depends on an acceptance bound.  (dist << 32 | index) is minimised with shuffles within the wave and through four LDS
 // words across the waves; thread 0 writes.  Offsets, segment numbers and lengths are device data: every index is clamped.
 #include "common.h"
+#include "wave_block.h"
 
 #define LX_THREADS 256
 #define LX_TABLE 256                                                   // == LX_THREADS: thread c builds entry c
@@ -90,18 +91,9 @@ __global__ __launch_bounds__(LX_THREADS) void lexicon_match_kernel(
     }
 
     // the smallest (dist, index): nothing found is (100, 0xffffffff), above every real key
-    unsigned long long key = ((unsigned long long)(unsigned)bd << 32) | (unsigned)bi;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned hi = (unsigned)__shfl_xor((int)(key >> 32), o, 64), lo = (unsigned)__shfl_xor((int)key, o, 64);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        key = other < key ? other : key;
-    }
-    if ((tid & 63) == 0) red[tid >> 6] = key;
-    __syncthreads();
+    const unsigned long long mine = ((unsigned long long)(unsigned)bd << 32) | (unsigned)bi;
+    const unsigned long long key = wb_block_reduce<LX_THREADS, WbMin>(mine, red);
     if (tid == 0) {
-#pragma unroll
-        for (int i = 1; i < LX_THREADS / 64; ++i) key = red[i] < key ? red[i] : key;
         best_index[s] = (int)(unsigned)key;
         best_dist[s] = (int)(key >> 32);
     }

@@ -14,6 +14,7 @@
 // counted extent and the cap; a match index against the lexicon's size.
 #include "common.h"
 #include "lexicon_rows_core.h"
+#include "wave_block.h"
 
 namespace {
 
@@ -26,33 +27,12 @@ __global__ __launch_bounds__(GOM_LR_BLOCK) void lexicon_rows_count_kernel(const 
     q_len[r] = lr_query_len(words + r * (long)ld, keep[r] != 0, tab, ntab);
 }
 
-__device__ __forceinline__ int wave_incl_scan_i32(int v, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ int wave_min_i32(int v) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int o = __shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(GOM_LR_BLOCK) void lexicon_rows_scan_kernel(const int32_t* __restrict__ q_len, int n,
                                                                          int32_t* __restrict__ q_off,
                                                                          int32_t* __restrict__ q_status) {
     __shared__ int wsum[GOM_LR_BLOCK / 64];
     __shared__ int wlong[GOM_LR_BLOCK / 64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     int carry = 0, first_long = 0x7FFFFFFF;                   // (n <= GOM_LR_MAX_ROWS: the sum of the lengths fits an int)
     for (long base = 0; base < n; base += GOM_LR_BLOCK) {
         const long r = base + t;
@@ -64,25 +44,11 @@ __global__ __launch_bounds__(GOM_LR_BLOCK) void lexicon_rows_scan_kernel(const i
                 len = 0;
             }
         }
-        const int incl = wave_incl_scan_i32(len, lane);
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        int before = 0, tot = 0;
-        for (int i = 0; i < GOM_LR_BLOCK / 64; ++i) {
-            const int s = wsum[i];
-            if (i < w) before += s;
-            tot += s;
-        }
-        if (r < n) q_off[r] = carry + before + incl - len;
-        carry += tot;
-        __syncthreads();
+        const int at = wb_block_excl_scan_carry<GOM_LR_BLOCK>(len, wsum, carry);
+        if (r < n) q_off[r] = at;
     }
-    first_long = wave_min_i32(first_long);
-    if (lane == 0) wlong[w] = first_long;
-    __syncthreads();
+    const int m = wb_block_reduce<GOM_LR_BLOCK, WbMin>(first_long, wlong);
     if (t == 0) {
-        int m = 0x7FFFFFFF;
-        for (int i = 0; i < GOM_LR_BLOCK / 64; ++i) m = wlong[i] < m ? wlong[i] : m;
         q_off[n] = carry;
         q_status[0] = m != 0x7FFFFFFF ? GOM_LR_TOO_LONG : 0;
         q_status[1] = m != 0x7FFFFFFF ? m : -1;
@@ -113,7 +79,7 @@ __global__ __launch_bounds__(GOM_LR_BLOCK) void lexicon_rows_apply_kernel(const 
                                                                           unsigned char* __restrict__ keep_out,
                                                                           int64_t* __restrict__ totals) {
     __shared__ int sums[3][GOM_LR_BLOCK / 64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     int kept = 0, accepted = 0, dropped = 0;                  // (n < 2^25 rows: an int holds a thread's and the block's counts)
     for (long r = t; r < n; r += GOM_LR_BLOCK) {
         const bool k = keep[r] != 0;
@@ -125,25 +91,14 @@ __global__ __launch_bounds__(GOM_LR_BLOCK) void lexicon_rows_apply_kernel(const 
         accepted += i >= 0 ? 1 : 0;
         dropped += k && !out ? 1 : 0;
     }
-    kept = wave_sum_i32(kept);
-    accepted = wave_sum_i32(accepted);
-    dropped = wave_sum_i32(dropped);
-    if (lane == 0) {
-        sums[0][w] = kept;
-        sums[1][w] = accepted;
-        sums[2][w] = dropped;
-    }
+    wb_block_stage<WbSum>(kept, sums[0]);
+    wb_block_stage<WbSum>(accepted, sums[1]);
+    wb_block_stage<WbSum>(dropped, sums[2]);
     __syncthreads();
     if (t == 0) {
-        int64_t s0 = 0, s1 = 0, s2 = 0;
-        for (int i = 0; i < GOM_LR_BLOCK / 64; ++i) {
-            s0 += sums[0][i];
-            s1 += sums[1][i];
-            s2 += sums[2][i];
-        }
-        totals[GOM_LR_KEPT] = s0;
-        totals[GOM_LR_ACCEPTED] = s1;
-        totals[GOM_LR_DROPPED] = s2;
+        totals[GOM_LR_KEPT] = wb_block_fold<GOM_LR_BLOCK, WbSum>(sums[0]);
+        totals[GOM_LR_ACCEPTED] = wb_block_fold<GOM_LR_BLOCK, WbSum>(sums[1]);
+        totals[GOM_LR_DROPPED] = wb_block_fold<GOM_LR_BLOCK, WbSum>(sums[2]);
         totals[GOM_LR_STATUS] = q_status[0];
         totals[GOM_LR_FIRST_LONG] = q_status[1];
     }

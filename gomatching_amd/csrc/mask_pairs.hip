@@ -26,25 +26,13 @@
 // scan and areas are device data the host cannot vouch for: every index made from them is clamped.
 #include "common.h"
 #include "mask_rule.h"
+#include "wave_block.h"
 
 #define MK_FILL_THREADS 256
 #define MK_WAVES 4
 #define MK_S 16
 
 namespace {
-
-// sum over the block -> thread 0
-__device__ __forceinline__ int block_sum(int v, int* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) lds[w] = v;
-    __syncthreads();
-    int s = 0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += lds[i];
-    return s;
-}
 
 __global__ __launch_bounds__(MK_FILL_THREADS) void fill_polygon_kernel(
     const int* __restrict__ points, int P, const int* __restrict__ contour_off, int C, const int* __restrict__ mask_coff,
@@ -96,7 +84,7 @@ __global__ __launch_bounds__(MK_FILL_THREADS) void fill_polygon_kernel(
         words[base + i] = word;
         pop += __popc(word);
     }
-    const int total = block_sum(pop, red);
+    const int total = wb_block_reduce<MK_FILL_THREADS, WbSum>(pop, red);   // (in thread 0)
     if (threadIdx.x == 0) area[k] = total;
 }
 
@@ -135,7 +123,7 @@ __global__ __launch_bounds__(MK_FILL_THREADS) void fill_rle_kernel(
         words[base + i] = word;
         pop += __popc(word);
     }
-    const int total = block_sum(pop, red);
+    const int total = wb_block_reduce<MK_FILL_THREADS, WbSum>(pop, red);   // (in thread 0)
     if (threadIdx.x == 0) area[k] = total;
 }
 
@@ -197,8 +185,7 @@ __global__ __launch_bounds__(64 * MK_WAVES) void mask_pairs_kernel(
                 const long long di = clampl(dbase + (long long)(y0 + r - db.x) * dnw + (x0 + c - db.z), 0, det_nwords - 1);
                 inter += __popc(gt_words[gi] & det_words[di]);
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) inter += __shfl_xor(inter, o, 64);
+            inter = wb_wave_reduce<WbSum>(inter);
             double v = 0.0;
             if (inter >= 1) {
                 const long long uni = ag + (long long)det_area[d] - inter;

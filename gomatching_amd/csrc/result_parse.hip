@@ -15,43 +15,11 @@
 // file; every store index is compared with its array's length.
 #include "common.h"
 #include "result_parse_core.h"
+#include "wave_block.h"
 
 namespace {
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ int wave_or_i(int v) {
-    for (int d = 32; d >= 1; d >>= 1) v |= __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ int wave_incl_scan_i(int v, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// exclusive scan over the block's threads -> this thread's prefix; total = the block's sum.  wsum: GOM_RP_BLOCK / 64 ints
-__device__ __forceinline__ int block_excl_scan_i(int v, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int incl = wave_incl_scan_i(v, lane);
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-    for (int i = 0; i < GOM_RP_BLOCK / 64; ++i) {
-        const int s = wsum[i];
-        if (i < w) base += s;
-        total += s;
-    }
-    __syncthreads();
-    return base + incl - v;
-}
+// (the block scans and reductions: wave_block.h; wsum / the slots: GOM_RP_BLOCK / 64 ints)
 
 // a bit 7 per byte of w that equals 0x0A (exact: no carry crosses a byte)
 __device__ __forceinline__ uint32_t newline_bits(uint32_t w) {
@@ -83,15 +51,9 @@ __global__ __launch_bounds__(GOM_RP_BLOCK) void rp_lines_count_kernel(const unsi
                                                                       bool aligned, int32_t* __restrict__ blk) {
     __shared__ int wsum[GOM_RP_BLOCK / 64];
     const long base = ((long)blockIdx.x * GOM_RP_BLOCK + threadIdx.x) * GOM_RP_THREAD_BYTES;
-    int c = base < size ? count16(load16(data, size, base, aligned)) : 0;
-    c = wave_sum_i(c);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int i = 0; i < GOM_RP_BLOCK / 64; ++i) s += wsum[i];
-        blk[blockIdx.x] = s;
-    }
+    const int c = base < size ? count16(load16(data, size, base, aligned)) : 0;
+    const int s = wb_block_reduce<GOM_RP_BLOCK, WbSum>(c, wsum);
+    if (threadIdx.x == 0) blk[blockIdx.x] = s;
 }
 
 // in-place exclusive scan of a[0 .. n) by the one block, tiles of the block with a carry -> the sum
@@ -100,10 +62,8 @@ __device__ __forceinline__ int scan_in_place(int32_t* a, int n, int* wsum) {
     for (long base = 0; base < n; base += GOM_RP_BLOCK) {
         const long i = base + threadIdx.x;
         const int v = i < n ? a[i] : 0;
-        int total;
-        const int ex = block_excl_scan_i(v, wsum, total);
-        if (i < n) a[i] = carry + ex;
-        carry += total;
+        const int ex = wb_block_excl_scan_carry<GOM_RP_BLOCK>(v, wsum, carry);
+        if (i < n) a[i] = ex;
     }
     return carry;
 }
@@ -128,7 +88,7 @@ __global__ __launch_bounds__(GOM_RP_BLOCK) void rp_lines_emit_kernel(const unsig
     uint4 v = make_uint4(0, 0, 0, 0);
     if (base < size) v = load16(data, size, base, aligned);
     int total;
-    long q = (long)blk[blockIdx.x] + block_excl_scan_i(count16(v), wsum, total);      // newlines before this thread's bytes
+    long q = (long)blk[blockIdx.x] + wb_block_excl_scan<GOM_RP_BLOCK>(count16(v), wsum, total);     // newlines before this thread's bytes
     const uint32_t bits[4] = {newline_bits(v.x), newline_bits(v.y), newline_bits(v.z), newline_bits(v.w)};
 #pragma unroll
     for (int i = 0; i < GOM_RP_THREAD_BYTES; ++i) {
@@ -156,23 +116,14 @@ __global__ __launch_bounds__(GOM_RP_BLOCK) void rp_marks_count_kernel(GomRpText 
                                                                       int32_t* __restrict__ sblk, int nmblk) {
     __shared__ int wo[GOM_RP_BLOCK / 64], wk[GOM_RP_BLOCK / 64], ws[GOM_RP_BLOCK / 64];
     const int fl = line_flags(t, (long)blockIdx.x * GOM_RP_BLOCK + threadIdx.x);
-    const int o = wave_sum_i(fl & 1), k = wave_sum_i((fl >> 1) & 1), s = wave_or_i(fl & 4);
-    if ((threadIdx.x & 63) == 0) {
-        wo[threadIdx.x >> 6] = o;
-        wk[threadIdx.x >> 6] = k;
-        ws[threadIdx.x >> 6] = s;
-    }
+    wb_block_stage<WbSum>(fl & 1, wo);
+    wb_block_stage<WbSum>((fl >> 1) & 1, wk);
+    wb_block_stage<WbOr>(fl & 4, ws);
     __syncthreads();
     if (threadIdx.x == 0) {
-        int so = 0, sk = 0, ss = 0;
-        for (int i = 0; i < GOM_RP_BLOCK / 64; ++i) {
-            so += wo[i];
-            sk += wk[i];
-            ss |= ws[i];
-        }
-        mblk[blockIdx.x] = so;
-        mblk[(long)nmblk + blockIdx.x] = sk;
-        sblk[blockIdx.x] = ss ? GOM_RP_BAD_LINE : 0;
+        mblk[blockIdx.x] = wb_block_fold<GOM_RP_BLOCK, WbSum>(wo);
+        mblk[(long)nmblk + blockIdx.x] = wb_block_fold<GOM_RP_BLOCK, WbSum>(wk);
+        sblk[blockIdx.x] = wb_block_fold<GOM_RP_BLOCK, WbOr>(ws) ? GOM_RP_BAD_LINE : 0;
     }
 }
 
@@ -185,12 +136,8 @@ __global__ __launch_bounds__(GOM_RP_BLOCK) void rp_marks_scan_kernel(int32_t* __
     const int F = scan_in_place(mblk + nmblk, nmblk, wsum);
     int st = 0;
     for (long i = threadIdx.x; i < nmblk; i += GOM_RP_BLOCK) st |= sblk[i];
-    st = wave_or_i(st);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = st;
-    __syncthreads();
+    int all = wb_block_reduce<GOM_RP_BLOCK, WbOr>(st, ws);
     if (threadIdx.x == 0) {
-        int all = 0;
-        for (int i = 0; i < GOM_RP_BLOCK / 64; ++i) all |= ws[i];
         if (F == 0) all |= GOM_RP_BAD_PLACE;
         totals[GOM_RP_N] = N;
         totals[GOM_RP_F] = F;
@@ -207,8 +154,8 @@ __global__ __launch_bounds__(GOM_RP_BLOCK) void rp_marks_emit_kernel(GomRpText t
     const long i = (long)blockIdx.x * GOM_RP_BLOCK + threadIdx.x;
     const int fl = line_flags(t, i);
     int total;
-    const long oi = (long)mblk[blockIdx.x] + block_excl_scan_i(fl & 1, wsum, total);
-    const long ki = (long)mblk[(long)nmblk + blockIdx.x] + block_excl_scan_i((fl >> 1) & 1, wsum, total);
+    const long oi = (long)mblk[blockIdx.x] + wb_block_excl_scan<GOM_RP_BLOCK>(fl & 1, wsum, total);
+    const long ki = (long)mblk[(long)nmblk + blockIdx.x] + wb_block_excl_scan<GOM_RP_BLOCK>((fl >> 1) & 1, wsum, total);
     const long m = oi + ki, M = (long)N + F;
     if ((fl & 1) && oi >= 0 && oi < N && m < M) {
         mark_line[m] = (int32_t)i;
@@ -237,10 +184,8 @@ __global__ __launch_bounds__(GOM_RP_BLOCK) void rp_poly_scan_kernel(GomRpMarks m
             rp_object_span(m, L, o, s, nl, next_obj);
             n = rp_points_of(nl);
         }
-        int total;
-        const int ex = block_excl_scan_i(n, wsum, total);
-        if (o < m.N) poly_off[o] = carry + ex;
-        carry += total;
+        const int ex = wb_block_excl_scan_carry<GOM_RP_BLOCK>(n, wsum, carry);
+        if (o < m.N) poly_off[o] = ex;
     }
     if (threadIdx.x == 0) {
         poly_off[m.N] = carry;
@@ -268,7 +213,7 @@ __global__ __launch_bounds__(64 * RP_WAVES) void rp_emit_kernel(GomRpText t, Gom
             const long poff = poly_off[unit];
             for (long j = lane; j < nl; j += 64) st |= rp_object_line(t, s, nl, next_obj, j, unit, poff, r);
         }
-        st = wave_or_i(st);
+        st = wb_wave_reduce<WbOr>(st);
     } else if (lane == 0) {
         st = rp_frame(t, m, unit - m.N);
     }
@@ -280,12 +225,8 @@ __global__ __launch_bounds__(GOM_RP_BLOCK) void rp_fold_kernel(const int32_t* __
     __shared__ int ws[GOM_RP_BLOCK / 64];
     int st = 0;
     for (long i = threadIdx.x; i < units; i += GOM_RP_BLOCK) st |= unit_status[i];
-    st = wave_or_i(st);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = st;
-    __syncthreads();
+    const int all = wb_block_reduce<GOM_RP_BLOCK, WbOr>(st, ws);
     if (threadIdx.x == 0) {
-        int all = 0;
-        for (int i = 0; i < GOM_RP_BLOCK / 64; ++i) all |= ws[i];
         totals[GOM_RP_STATUS] = (int64_t)all | totals[GOM_RP_STATUS_LINES] | totals[GOM_RP_STATUS_MARKS];
     }
 }

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "result_text_core.h"
 #include "lexicon_rows_core.h"
+#include "wave_block.h"
 
 #define RT_WAVES 4
 
@@ -65,20 +66,6 @@ __device__ __forceinline__ bool rt_keeps(const unsigned char* keep, const RtOv& 
     return keep[r] && (!OV || v.keep_out[r]);
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_incl_scan(T v, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 __device__ __forceinline__ int clamp_row(int v, int n) { return v < 0 ? 0 : (v > n ? n : v); }
 
 template <bool OV>
@@ -98,9 +85,9 @@ __device__ __forceinline__ void result_text_count_body(const int32_t* __restrict
         o.pos = 0;
         if (lane < GOM_RT_XML_PIECES) rt_xml_piece(o, row, lane);
         const int px = (int)o.pos;
-        const int bad = wave_sum(lane < 25 && rt_char_bad(row, lane) ? 1 : 0);
-        lj = wave_sum(pj);
-        lx = wave_sum(px);
+        const int bad = wb_wave_reduce<WbSum>(lane < 25 && rt_char_bad(row, lane) ? 1 : 0);
+        lj = wb_wave_reduce<WbSum>(pj);
+        lx = wb_wave_reduce<WbSum>(px);
         if (bad) lj = lx = -1;
     }
     if (lane == 0) {
@@ -127,25 +114,7 @@ __global__ __launch_bounds__(64 * RT_WAVES) void result_text_count_ov_kernel(con
     result_text_count_body<true>(words, ld, pts, keep, n, jt, xt, ntab, row_len, v);
 }
 
-// exclusive scan of one chunk of the block: -> this thread's exclusive prefix (carry included); the carry moves on
-template <typename T>
-__device__ __forceinline__ T block_excl_scan(T v, T& carry, T* wsum) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const T incl = wave_incl_scan(v, lane);
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    T base = 0, tot = 0;
-    for (int i = 0; i < GOM_RT_SCAN_BLOCK / 64; ++i) {
-        const T s = wsum[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    const T excl = carry + base + incl - v;
-    carry += tot;
-    __syncthreads();
-    return excl;
-}
-
+// (the scans of one chunk of the block: wb_block_excl_scan_carry of wave_block.h -> this thread's exclusive prefix, carry included)
 __global__ __launch_bounds__(GOM_RT_SCAN_BLOCK) void result_text_scan_kernel(const int32_t* __restrict__ row_len, int n,
                                                                              const int32_t* __restrict__ frame_rows, int F,
                                                                              long first_frame, int64_t* __restrict__ row_off,
@@ -170,9 +139,9 @@ __global__ __launch_bounds__(GOM_RT_SCAN_BLOCK) void result_text_scan_kernel(con
                 lj = lx = 0;
             }
         }
-        const long long oj = block_excl_scan<long long>(lj, cj, wj);
-        const long long ox = block_excl_scan<long long>(lx, cx, wx);
-        const int ok = block_excl_scan<int>(lj > 0 ? 1 : 0, ck, wk);
+        const long long oj = wb_block_excl_scan_carry<GOM_RT_SCAN_BLOCK, long long>(lj, wj, cj);
+        const long long ox = wb_block_excl_scan_carry<GOM_RT_SCAN_BLOCK, long long>(lx, wx, cx);
+        const int ok = wb_block_excl_scan_carry<GOM_RT_SCAN_BLOCK, int>(lj > 0 ? 1 : 0, wk, ck);
         if (r < n) {
             row_off[r] = oj;
             row_off[(long)n + 1 + r] = ox;
@@ -184,8 +153,7 @@ __global__ __launch_bounds__(GOM_RT_SCAN_BLOCK) void result_text_scan_kernel(con
         row_off[(long)n + 1 + n] = cx;
         row_kept[n] = ck;
     }
-    bad = wave_sum(bad);
-    if ((t & 63) == 0) bad_any[t >> 6] = bad;
+    wb_block_stage<WbOr>(bad, bad_any);
     __syncthreads();                                      // the block's own stores to row_off / row_kept are visible to it from here
     // ---- frames
     long long fj = 0, fx = 0;
@@ -200,8 +168,8 @@ __global__ __launch_bounds__(GOM_RT_SCAN_BLOCK) void result_text_scan_kernel(con
             lj = rt_json_frame_len(first_frame + f, kept, bj);
             lx = rt_xml_frame_len(first_frame + f, kept, bx);
         }
-        const long long oj = block_excl_scan<long long>(lj, fj, wj);
-        const long long ox = block_excl_scan<long long>(lx, fx, wx);
+        const long long oj = wb_block_excl_scan_carry<GOM_RT_SCAN_BLOCK, long long>(lj, wj, fj);
+        const long long ox = wb_block_excl_scan_carry<GOM_RT_SCAN_BLOCK, long long>(lx, wx, fx);
         if (f < F) {
             frame_off[f] = oj;
             frame_off[(long)F + 1 + f] = ox;
@@ -210,8 +178,7 @@ __global__ __launch_bounds__(GOM_RT_SCAN_BLOCK) void result_text_scan_kernel(con
     if (t == 0) {
         frame_off[F] = fj;
         frame_off[(long)F + 1 + F] = fx;
-        int any = 0;
-        for (int i = 0; i < GOM_RT_SCAN_BLOCK / 64; ++i) any |= bad_any[i];
+        const int any = wb_block_fold<GOM_RT_SCAN_BLOCK, WbOr>(bad_any);
         totals[0] = fj;
         totals[1] = fx;
         totals[GOM_RT_STATUS] = any ? GOM_RT_BAD_ID : 0;
@@ -317,7 +284,7 @@ __device__ __forceinline__ void result_text_emit_body(
         GomRtOut cnt = {nullptr, 0, 0};
         if (lj > 0 && lane < GOM_RT_JSON_PIECES) rt_json_piece(cnt, row, lane, sep);
         const long mine = cnt.pos;
-        const long at = wave_incl_scan<long>(mine, lane) - mine;
+        const long at = wb_wave_incl_scan<long>(mine) - mine;
         if (lj > 0 && lane < GOM_RT_JSON_PIECES) {
             GomRtOut o = {stage, (long)shift + lj, shift + at};
             rt_json_piece(o, row, lane, sep);
@@ -333,7 +300,7 @@ __device__ __forceinline__ void result_text_emit_body(
         GomRtOut cnt = {nullptr, 0, 0};
         if (lx > 0 && lane < GOM_RT_XML_PIECES) rt_xml_piece(cnt, row, lane);
         const long mine = cnt.pos;
-        const long at = wave_incl_scan<long>(mine, lane) - mine;
+        const long at = wb_wave_incl_scan<long>(mine) - mine;
         if (lx > 0 && lane < GOM_RT_XML_PIECES) {
             GomRtOut o = {stage, (long)shift + lx, shift + at};
             rt_xml_piece(o, row, lane);

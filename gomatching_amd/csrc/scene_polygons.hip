@@ -9,6 +9,7 @@
 // No atomics, no scratch, one writer per output word.  The offsets are data: every one is clamped into its array before it is used
 // as an index, and every store index is compared with the length the caller gave.
 #include "common.h"
+#include "wave_block.h"
 
 namespace {
 
@@ -74,33 +75,6 @@ __global__ __launch_bounds__(GOM_SP_BLOCK) void scene_boxes_kernel(SpIn in, cons
     inst_status[k] = st;
 }
 
-template <typename T>
-__device__ __forceinline__ T sp_wave_incl_scan(T v, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T sp_block_excl_scan(T v, T& carry, T* wsum) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const T incl = sp_wave_incl_scan(v, lane);
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    T base = 0, tot = 0;
-    for (int i = 0; i < GOM_SP_BLOCK / 64; ++i) {
-        const T s = wsum[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    const T excl = carry + base + incl - v;
-    carry += tot;
-    __syncthreads();
-    return excl;
-}
-
 __global__ __launch_bounds__(GOM_SP_BLOCK) void scene_scan_kernel(SpIn in, const int32_t* __restrict__ boxes,
                                                                   const int32_t* __restrict__ inst_status, int n_inst,
                                                                   int32_t* __restrict__ coff, int n_cont,
@@ -127,8 +101,8 @@ __global__ __launch_bounds__(GOM_SP_BLOCK) void scene_scan_kernel(SpIn in, const
                 kept = e > a ? 1 : 0;
             }
         }
-        const int c = sp_block_excl_scan<int>(kept, cc, wc);
-        const long long w = sp_block_excl_scan<long long>(words, cw, ww);
+        const int c = wb_block_excl_scan_carry<GOM_SP_BLOCK>(kept, wc, cc);
+        const long long w = wb_block_excl_scan_carry<GOM_SP_BLOCK>(words, ww, cw);
         if (k < n_inst) {
             mcoff[k] = c;
             woff[k] = w;
@@ -140,12 +114,9 @@ __global__ __launch_bounds__(GOM_SP_BLOCK) void scene_scan_kernel(SpIn in, const
     }
     for (long j = threadIdx.x; j <= in.f1 - in.f0; j += GOM_SP_BLOCK)
         inst_off[j] = sp_clamp((long)in.frame_rows[in.f0 + j] - i0, 0, n_inst);
-    for (int d = 32; d >= 1; d >>= 1) st |= __shfl_xor(st, d);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = st;
-    __syncthreads();
+    int all = wb_block_reduce<GOM_SP_BLOCK, WbOr>(st, ws);
     if (threadIdx.x == 0) {
-        int all = cc == n_cont ? 0 : GOM_SP_BAD_SHAPE;
-        for (int i = 0; i < GOM_SP_BLOCK / 64; ++i) all |= ws[i];
+        if (cc != n_cont) all |= GOM_SP_BAD_SHAPE;
         mcoff[n_inst] = cc;
         woff[n_inst] = cw;
         int a, e = p0;

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "track_vote_core.h"
 #include "lexicon_rows_core.h"
+#include "wave_block.h"
 
 #define TV_WAVES (GOM_TV_BLOCK / 64)
 
@@ -43,14 +44,6 @@ __global__ __launch_bounds__(GOM_TV_BLOCK) void track_vote_records_ov_kernel(
     const int len = i >= 0 ? lr_display(doff, W, dbytes, i, 4 * GOM_TV_TEXT_WORDS, at) : 0;
     tv_record_ov(words + r * (long)ld, keep[r] != 0 && keep_out[r] != 0, tab, ntab, i >= 0 ? disp + at : nullptr, len,
                  records + r * GOM_TV_RECORD_WORDS);
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 __device__ __forceinline__ long clamp_idx(long v, long n) { return v < 0 ? 0 : (v > n ? n : v); }
@@ -91,18 +84,12 @@ __global__ __launch_bounds__(GOM_TV_BLOCK) void track_vote_count_kernel(const in
             best = k > best ? k : best;
         }
     }
-    best = wave_max_u64(best);
-    for (int d = 32; d >= 1; d >>= 1) bad |= __shfl_xor(bad, d);
-    if ((tid & 63) == 0) {
-        wbest[tid >> 6] = best;
-        wbad[tid >> 6] = bad;
-    }
+    wb_block_stage<WbMax>(best, wbest);
+    wb_block_stage<WbOr>(bad, wbad);
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < TV_WAVES; ++w) {
-            best = wbest[w] > best ? wbest[w] : best;
-            bad |= wbad[w];
-        }
+        best = wb_block_fold<GOM_TV_BLOCK, WbMax>(wbest);
+        bad = wb_block_fold<GOM_TV_BLOCK, WbOr>(wbad);
         int pos = -1, count = 0, bytes = 0;
         if (best != 0) {
             const long place = (long)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull));
@@ -127,7 +114,7 @@ __global__ __launch_bounds__(GOM_TV_BLOCK) void track_vote_scan_kernel(const int
                                                                        int64_t* __restrict__ totals) {
     __shared__ long long wsum[TV_WAVES];
     __shared__ int wbad[TV_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     long long carry = 0;
     int bad = 0;
     for (long base = 0; base < T; base += GOM_TV_BLOCK) {
@@ -138,28 +125,11 @@ __global__ __launch_bounds__(GOM_TV_BLOCK) void track_vote_scan_kernel(const int
             bad |= winner[t * GOM_TV_WINNER_WORDS + 3];
             if (v < 0) v = 0;
         }
-        long long incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        long long before = 0, tot = 0;
-        for (int i = 0; i < TV_WAVES; ++i) {
-            const long long x = wsum[i];
-            if (i < w) before += x;
-            tot += x;
-        }
-        if (t < T) line_off[t] = carry + before + incl - v;
-        carry += tot;
-        __syncthreads();
+        const long long at = wb_block_excl_scan_carry<GOM_TV_BLOCK>(v, wsum, carry);
+        if (t < T) line_off[t] = at;
     }
-    for (int d = 32; d >= 1; d >>= 1) bad |= __shfl_xor(bad, d);
-    if (lane == 0) wbad[w] = bad;
-    __syncthreads();
+    bad = wb_block_reduce<GOM_TV_BLOCK, WbOr>(bad, wbad);
     if (tid == 0) {
-        for (int i = 1; i < TV_WAVES; ++i) bad |= wbad[i];
         line_off[T] = carry;
         totals[0] = carry;
         totals[GOM_TV_STATUS] = bad;

@@ -32,6 +32,23 @@ def _longer_video():
             "7": [o(poly(7, 0, 32, 0, 46), 3)]}
 
 
+TILE_EDGE_EMPTY = (255, 256, 511, 512)                         # chunk positions on both sides of the scan's tile edges
+
+
+def _tile_edge_video():
+    """Three frames of 255, 3 and 255 tiny polygons: the chunk 0..3 has 2 * 256 + 1 instances, three tiles of the scan kernel's
+    block with a carry between them.  The instances at the chunk positions TILE_EDGE_EMPTY have an empty contour, so the kept
+    count and the word offset cross both tile edges with a zero on each side."""
+    rng = random.Random(47)
+    objects = []
+    for k in range(2 * 256 + 1):
+        x, y = rng.randint(0, 60), rng.randint(0, 44)
+        seg = [] if k in TILE_EDGE_EMPTY else [[x, y], [x + 3, y + 1], [x + 1, y + 3]]
+        objects.append({"points": [1, 2, 3, 4, 5, 6, 7, 8], "ID": k % 255, "transcription": "t%d" % (k % 7),
+                        "segmentation": [seg]})
+    return {"1": objects[:255], "2": objects[255:258], "3": objects[258:]}
+
+
 def _families():
     skip = ("int32 limits", "long")                           # coordinates beyond 2^20 (tested below); size
     fams = [(n, json.loads(d)) for n, d in rc.clean_cases() if n not in skip]
@@ -79,6 +96,16 @@ def test_a_middle_frame_range_of_a_longer_video(bgr):
     for f0, f1 in ((1, 4), (2, 3), (4, 5), (3, 7), (0, 7), (6, 7)):
         for H, W in SIZES:
             _compare(video, f0, f1, H, W, bgr, dev)
+
+
+def test_a_chunk_longer_than_the_scan_block_crosses_its_tile_edges():
+    dev = torch.device("cuda", torch.cuda.current_device())
+    video = _tile_edge_video()
+    assert [len(video[f]) for f in ("1", "2", "3")] == [255, 3, 255]
+    flat = [o for f in ("1", "2", "3") for o in video[f]]
+    assert [k for k, o in enumerate(flat) if o["segmentation"] == [[]]] == list(TILE_EDGE_EMPTY)
+    for f0, f1 in ((0, 3), (1, 3)):
+        _compare(video, f0, f1, 48, 64, False, dev)
 
 
 def test_a_coordinate_beyond_the_limit_raises():
