@@ -37,6 +37,10 @@ struct RowArgs {
     int* flag;
     int lda, ldr, ldc, M, chunks, cpg, r_chunks, relu, r_period;
     int tiles, frames, tpf;                                  // frame-interleaved tile order (periodic residual): see tile_of()
+    // the ROW-LIST form (ROWS): row r of tile t is rows[t * 128 + r] for the A loads and the C stores, *count rows are listed
+    const int* rows;
+    const int* count;
+    unsigned char* clear;                                    // or nullptr: byte clear[row] = 0 for every listed row
 };
 
 // Which 128-row tile a workgroup takes.  Plain launches: its index.  With a PERIODIC residual (the encoder's position table
@@ -72,8 +76,14 @@ __device__ __forceinline__ f32x16 mfma_either(const half8 w, const half8 x, cons
 // 368 -> 274 us at M = 297 368, N = 640) -- and whole lines cost it 6-7 % less (368 -> 345 us; N = 1536: 816 -> 763 us); short
 // ones (the decoder, less than one workgroup per CU) are not, and pay 3 % for the twelve extra store instructions (18.7 -> 19.5 us
 // at M = 20 000, N = 256): the launcher picks by M.
-template <bool LINES>
-__global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
+// ROWS (with LINES = false, where the lane addresses its row by itself): the rows of the problem are a LIST, rows[0 .. *count) on the
+// device -- the decoder's value projection of the rows its sampling reads (dec_value_rows.hip).  The grid is the dense problem's
+// (M = the capacity of the list), so a captured launch serves every count; a workgroup whose first list index is at or beyond
+// *count exits at once, and the tail of the last one repeats the last listed row, as the dense tail repeats row M - 1.  Per-row
+// arithmetic is the dense form's: a listed row gets the bits the dense launch gives it (tests/test_dec_value_rows_gpu.py).
+template <bool LINES, bool ROWS>
+__device__ __forceinline__ void gemm_k256_body(const RowArgs& p) {
+    static_assert(!(LINES && ROWS), "the row-list form stores by lane = row");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -84,6 +94,12 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
     if (tile < 0) return;                                    // padding of the interleaved id space (whole workgroup)
     long row = tile * BM + wave * 32 + fr;
     if (row > p.M - 1) row = p.M - 1;                        // tail rows recompute AND re-store the last row (same bits)
+    if constexpr (ROWS) {
+        const int cnt = min(*p.count, p.M);                  // (uniform: a scalar load)
+        if (tile * BM >= cnt) return;                        // nothing listed for this workgroup (whole workgroup)
+        const int listed = p.rows[min((int)(tile * BM) + wave * 32 + fr, cnt - 1)];
+        row = min(max(listed, 0), p.M - 1);                  // (a list is rows of the problem; held to them whatever it says)
+    }
     const __amdgpu_buffer_rsrc_t rs_img = gom_buffer_rsrc(p.img, p.chunks * CHUNK_BYTES);
     auto dma_stage = [&](int c, int stage) {                 // 33 fragments, dealt to the four waves
         const unsigned src = (unsigned)c * CHUNK_BYTES + lane * 16;
@@ -103,6 +119,7 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
         auto arow = [&](int r) {
             long m = wrow0 + r;
             if (m > p.M - 1) m = p.M - 1;                     // tail rows recompute (and re-store) the last row: same bits
+            if constexpr (ROWS) m = __shfl((int)row, r, 64);  // lane r (< 32) holds the wave's listed row r
             return p.A + (size_t)m * p.lda;
         };
         auto a2row = [&](int r) {
@@ -229,7 +246,19 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
         }
     }
 
+    if constexpr (ROWS) {                                    // the marks of the listed rows are consumed: clear them for the next list
+        if (p.clear && fh == 0 && blockIdx.y == 0) p.clear[row] = 0;
+    }
     if (bad && p.flag) atomicOr(p.flag, 1);                  // an operand left fp16's range (gemm_f16x3.hip contract)
+}
+
+template <bool LINES>
+__global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const RowArgs p) {
+    gemm_k256_body<LINES, false>(p);
+}
+
+__global__ __launch_bounds__(256, 2) void gemm_k256_rows_kernel(const RowArgs p) {
+    gemm_k256_body<false, true>(p);
 }
 
 // Fragment-linear image of W[N, 256] (row-scaled planes of gom_split_f16x2).  Per chunk c of 32 output columns 33 KB:
@@ -332,4 +361,22 @@ extern "C" int gom_gemm_k256_f32(const float* A, const float* A2, int lda, const
                                  int r_cols, int relu, float* C, int ldc, int M, int N, int K, int col_groups, int* flag,
                                  void* stream) {
     return gom_gemm_k256_rp_f32(A, A2, lda, image, R, ldr, r_cols, 0, relu, C, ldc, M, N, K, col_groups, flag, stream);
+}
+
+// Row-list form (see the kernel): C[rows[i]] = A[rows[i]] . W^T + bias for i < *count, every other row of C untouched.
+extern "C" int gom_gemm_k256_rows_f32(const float* A, int lda, const void* image, const int* rows, const int* count,
+                                      unsigned char* clear, float* C, int ldc, int M, int N, int K, int* flag, void* stream) {
+    GOM_CHECK_ARG(A && image && rows && count && C && M >= 0 && K == KD && N > 0 && (N % CW) == 0);
+    GOM_CHECK_ARG(lda >= KD && (lda % 4) == 0 && ldc >= N && (ldc % 4) == 0);
+    GOM_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)C % 16) == 0 && ((uintptr_t)image % 16) == 0 && ((uintptr_t)rows % 4) == 0);
+    if (M == 0) return GOM_OK;
+    RowArgs a{};
+    a.A = A; a.img = (const unsigned char*)image; a.C = C; a.flag = flag;
+    a.lda = lda; a.ldc = ldc; a.M = M; a.chunks = N / CW; a.cpg = a.chunks;
+    a.tiles = cdiv(M, BM); a.frames = 1; a.tpf = a.tiles;
+    a.rows = rows; a.count = count; a.clear = clear;
+    hipError_t e = hipFuncSetAttribute((const void*)gemm_k256_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (e != hipSuccess) return GOM_ERR_HIP_BASE + (int)e;
+    hipLaunchKernelGGL(gemm_k256_rows_kernel, dim3((unsigned)a.tiles), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
+    return gom_launch_status();
 }

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.h"
+#include "msda_corners.h"
 
 namespace {
 
@@ -294,33 +295,21 @@ __global__ __launch_bounds__(256) void msda_fused_lanes_kernel(const float* __re
     unsigned so1[2], so2[2], so3[2], so4[2];                 // BYTE offsets of the four corners' head slice in the batch image
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        const float ox = off[2 * t], oy = off[2 * t + 1];
-        float qx = ox * rW, qy = oy * rH;
-        qx = fmaf(fmaf(-qx, Wf, ox), rW, qx);
-        qy = fmaf(fmaf(-qy, Hf, oy), rH, qy);
-        const float lx = (HAS_VR ? rx * vr[2 * l] : rx) + qx, ly = (HAS_VR ? ry * vr[2 * l + 1] : ry) + qy;
+        // the four loads and their bilinear terms: msda_corners.h (shared with the decoder's row marking, dec_value_rows.hip)
+        const MsdaCorners c = msda_corners(off[2 * t], off[2 * t + 1], HAS_VR ? rx * vr[2 * l] : rx, HAS_VR ? ry * vr[2 * l + 1] : ry,
+                                           H, W, Hf, Wf, rW, rH);
         const float w = (t ? e1 : e0) * inv_sum;
-        const float h_im = ly * H - 0.5f, w_im = lx * W - 0.5f;
-        const bool inside = h_im > -1.f && w_im > -1.f && h_im < Hf && w_im < Wf;
-        const float hf = floorf(h_im), wf = floorf(w_im);
-        const float lh = h_im - hf, lw = w_im - wf;
-        const float hh = 1.f - lh, hw = 1.f - lw;
-        const int h_low = inside ? (int)hf : 0, w_low = inside ? (int)wf : 0;
-        const bool y0 = h_low >= 0, y1 = h_low + 1 <= H - 1;
-        const bool x0 = w_low >= 0, x1 = w_low + 1 <= W - 1;
-        const int yc0 = y0 ? h_low : 0, yc1 = y1 ? h_low + 1 : H - 1;
-        const int xc0 = x0 ? w_low : 0, xc1 = x1 ? w_low + 1 : W - 1;
-        const unsigned r0 = lvl + (unsigned)(yc0 * W), r1 = lvl + (unsigned)(yc1 * W);
+        const unsigned r0 = lvl + (unsigned)(c.yc0 * W), r1 = lvl + (unsigned)(c.yc1 * W);
         const unsigned head = (unsigned)(m * CH) * 4u;
-        so1[t] = (r0 + xc0) * (unsigned)v_rs * 4u + head;
-        so2[t] = (r0 + xc1) * (unsigned)v_rs * 4u + head;
-        so3[t] = (r1 + xc0) * (unsigned)v_rs * 4u + head;
-        so4[t] = (r1 + xc1) * (unsigned)v_rs * 4u + head;
-        const float ww = inside ? w : 0.f;
-        sw1[t] = ((y0 && x0) ? hh * hw : 0.f) * ww;
-        sw2[t] = ((y0 && x1) ? hh * lw : 0.f) * ww;
-        sw3[t] = ((y1 && x0) ? lh * hw : 0.f) * ww;
-        sw4[t] = ((y1 && x1) ? lh * lw : 0.f) * ww;
+        so1[t] = (r0 + c.xc0) * (unsigned)v_rs * 4u + head;
+        so2[t] = (r0 + c.xc1) * (unsigned)v_rs * 4u + head;
+        so3[t] = (r1 + c.xc0) * (unsigned)v_rs * 4u + head;
+        so4[t] = (r1 + c.xc1) * (unsigned)v_rs * 4u + head;
+        const float ww = c.inside ? w : 0.f;
+        sw1[t] = ((c.y0 && c.x0) ? c.hh * c.hw : 0.f) * ww;
+        sw2[t] = ((c.y0 && c.x1) ? c.hh * c.lw : 0.f) * ww;
+        sw3[t] = ((c.y1 && c.x0) ? c.lh * c.hw : 0.f) * ww;
+        sw4[t] = ((c.y1 && c.x1) ? c.lh * c.lw : 0.f) * ww;
     }
 
     // ---- gather part: every lane, all 16 samples, 4 channels ----

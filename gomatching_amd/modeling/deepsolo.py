@@ -10,7 +10,8 @@ reference's:
   * sampling_offsets and attention_weights share one GEMM (N = 384) fed by (src + pos) added in the
     operand loader; residual adds ride in GEMM epilogues, LayerNorm fuses the add it needs;
   * the six decoder cross-attention value projections (same memory, six weights,
-    ms_deform_attn.py:133) are ONE GEMM with N = 1536 right after the encoder;
+    ms_deform_attn.py:133) are ONE GEMM with N = 1536 right after the encoder -- or, per layer, the projection of
+    just the rows that layer's sampling loads (ops.DEC_VALUE_SPARSE: mark, compact, row-list GEMM);
   * the Bezier-coordinate MLP runs on the nq selected tokens only (the reference runs it on all S
     tokens and gathers afterwards, deformable_transformer.py:185-196) -- same values, ~S/nq fewer FLOPs;
   * instead of zero-filling invalid-proposal rows before enc_output (:136-137), their class logit
@@ -31,6 +32,14 @@ _f32 = torch.float32
 
 def _dev(t, device):
     return t.detach().float().contiguous().to(device)
+
+
+class _SparseValues:
+    """What the decoder layers of ONE step get in place of the dense value buffer: the resolution's ops.DecValueRows, the encoder
+    memory the listed rows are projected from, and whether this step measures the layers' shares."""
+
+    def __init__(self, state, memory, measure):
+        self.state, self.memory, self.measure = state, memory, measure
 
 
 class DeepSolo:
@@ -136,6 +145,12 @@ class DeepSolo:
         vp = [t + "decoder.layers.%d.attn_cross.value_proj" % i for i in range(self.n_dec)]
         self.dec_value = qlin((ops.prep_weight(torch.cat([g(n + ".weight") for n in vp], 0).contiguous()),
                                torch.cat([g(n + ".bias") for n in vp], 0).contiguous()))
+        # ... and each layer's [256, 256] row slice of it for the sparse form (ops.DEC_VALUE_SPARSE): the same planes and row scales
+        self.dec_value_layers = [ops.K256Linear(self.dec_value.W[i * E:(i + 1) * E], self.dec_value.bias[i * E:(i + 1) * E])
+                                 for i in range(self.n_dec)] if isinstance(self.dec_value, ops.K256Linear) else None
+        self.dec_value_share = {}                                # decoder layer -> measured share of value rows its sampling loads
+        self.dec_value_dense = None                              # None: not decided yet (ops.DEC_VALUE_POLICY); True: the dense launch
+        self._dec_value_states = {}                              # (frames, tokens, device) -> ops.DecValueRows
         self.ref_point_head = [qlin(lin(t + "decoder.ref_point_head.layers.%d" % i)) for i in range(2)]
 
         def mlp2(name, relu_out):                            # two 256 x 256 layers as ONE launch (f16x3 back-end), else None
@@ -398,8 +413,15 @@ class DeepSolo:
         nq, P, S = self.nq, self.P, geo["S"]
         Q = B * nq * P
         tgt = ops.broadcast_rows(self.point_embed, B).view(Q, 256)
-        values = ops.linear(memory, self.dec_value)                                           # [B*S, 1536]
         vr = geo["vr"]
+        # value_proj of the six layers: only the rows each layer's sampling loads (`_dec_value_rows`), or every row in one launch
+        sparse = self._dec_value_state(geo, B, memory.device)
+        decide = sparse is not None and self.dec_value_dense is None and ops.DEC_VALUE_POLICY and \
+            not torch.cuda.is_current_stream_capturing()
+        if sparse is not None:
+            values = _SparseValues(sparse, memory, decide)
+        else:
+            values = ops.linear(memory, self.dec_value)                                       # [B*S, 1536]
         if vr is not None:
             zero = ops.zero_padded_tokens_frames_ if geo.get("frames", False) else ops.zero_padded_tokens_
             zero(values, 0, values.shape[1], geo["shapes"], geo["lsi"], geo["vshapes"], B, S)
@@ -411,7 +433,31 @@ class DeepSolo:
         for lid, L in enumerate(self.dec):
             refs, tgt, emb, qpos = self._decoder_layer(lid, L, tgt, refs, values, geo, B, vr, emb, lid + 1 < len(self.dec), qpos)
             inter_refs.append(refs)
+        if decide:                   # one layer above the threshold keeps the dense launch, and the launch then serves all six
+            self.dec_value_dense = max(self.dec_value_share.values()) > ops.DEC_VALUE_MAX_SHARE
         return tgt, inter_refs
+
+    def _dec_value_state(self, geo, B, device):
+        """The sparse value projection's device state for this resolution (ops.DecValueRows, cached: one zero-filled [B*S, 256] buffer
+        that all six layers reuse -- layer l's rows are consumed before layer l + 1's are written on the same stream), or None when
+        the step runs the dense launch: switched off, another GEMM back-end, a padded batch (its masked value rows are zeroed in the
+        dense buffer), or a measured share above ops.DEC_VALUE_MAX_SHARE."""
+        if not ops.DEC_VALUE_SPARSE or geo["vr"] is not None or self.dec_value_dense or self.dec_value_layers is None:
+            return None
+        key = (B, geo["S"], str(device))
+        if key not in self._dec_value_states:
+            self._dec_value_states[key] = ops.DecValueRows(B * geo["S"], device)
+        return self._dec_value_states[key]
+
+    def _dec_value_rows(self, lid, sv, raw, ref, geo, B, Lq):
+        """Layer `lid`'s value rows: mark what the gather kernel will load for these offsets | logits, compact, project the listed rows
+        (the GEMM clears their marks).  Nothing on the host, unless this call measures the layer's share."""
+        st = sv.state
+        ops.dec_value_mark(raw, ref, geo["shapes"], geo["lsi"], B, Lq, geo["S"], st)
+        ops.dec_value_compact(st)
+        if sv.measure:
+            self.dec_value_share[lid] = float(st.count.item()) / st.n
+        return ops.linear_rows(sv.memory, self.dec_value_layers[lid], st)
 
     def _decoder_layer(self, lid, L, tgt, refs, values, geo, B, vr, emb=None, more=False, qpos=None):
         nq, P, E = self.nq, self.P, 256
@@ -464,9 +510,13 @@ class DeepSolo:
                              [nq * P * ld, ld, P * ld] * 3 + [nq * P * E, E, P * E])
                 tgt = self._out_norm(attn, L, "inter", tgt)
             # deformable cross attention into the encoder memory (:406-422)
-            value = values[:, lid * E:(lid + 1) * E]
-            samp = self._msda_strided(L["cross"], tgt, qpos, refs.view(Q, 1, 2), value, values.stride(0), geo, B,
-                                      nq * P, vr, raw=raw)
+            if isinstance(values, _SparseValues):
+                if raw is None:      # (the inter block's launch did not make the offsets | logits: the unfused path)
+                    raw = ops.linear(tgt, L["cross"]["raw"], A2=qpos)
+                value, ld_value = self._dec_value_rows(lid, values, raw, refs, geo, B, nq * P), E
+            else:
+                value, ld_value = values[:, lid * E:(lid + 1) * E], values.stride(0)
+            samp = self._msda_strided(L["cross"], tgt, qpos, refs.view(Q, 1, 2), value, ld_value, geo, B, nq * P, vr, raw=raw)
             tail = L.get("tail") if vr is None else None
             if tail is not None and tail.proj is not None:
                 # out_proj + norm_cross, FFN + norm3, the coordinate MLP + reference refinement (:484-488) and the next layer's query

@@ -1254,6 +1254,55 @@ def msda_fused(raw, ref, value2d, batch_stride, shapes, lsi, B, Lq, valid_ratios
     return out
 
 
+# The decoder's cross-attention value projection on the rows its sampling reads (csrc/dec_value_rows.hip): per layer mark -> compact ->
+# the row-list form of the K = 256 kernel, into one [frames x tokens, 256] buffer, instead of one dense N = 1536 launch for the six
+# layers.  Every value the sampling reads keeps its bits (value projection is row-local).  GOM_DEC_VALUE_SPARSE=0: the dense launch.
+DEC_VALUE_SPARSE = _switch("DEC_VALUE_SPARSE")
+# Each decoder layer measures its share of marked rows on its first eager call; a layer above DEC_VALUE_MAX_SHARE makes the model keep
+# the dense launch (tools/dec_value_bench.py: the three sparse launches of a layer cost a sixth of the dense launch at a share of
+# 48 %; the threshold keeps a margin below that; docs/LAB_NOTES.md).  GOM_DEC_VALUE_POLICY=0: sparse whatever the share.
+DEC_VALUE_POLICY = _switch("DEC_VALUE_POLICY")
+DEC_VALUE_MAX_SHARE = 0.35
+
+
+class DecValueRows:
+    """Device state of the sparse value projection at one (frames x tokens): the byte flags (zero between layers), the row list and
+    its count, and the [n, 256] value buffer -- zero-filled once, so that a row never listed holds finite values; a row listed by
+    an earlier layer or step keeps that stale projection, and no sampling reads it."""
+
+    def __init__(self, n, device):
+        self.n = n
+        self.flags = torch.zeros((_L().gom_dec_value_flag_bytes(n),), dtype=torch.uint8, device=device)
+        self.rows = torch.zeros((n,), dtype=torch.int32, device=device)
+        self.count = torch.zeros((1,), dtype=torch.int32, device=device)
+        self.value = torch.zeros((n, 256), dtype=_f32, device=device)
+
+
+def dec_value_mark(raw, ref, shapes, lsi, B, Lq, S, state):
+    """Flag the rows that `msda_fused(raw, ref, ...)` (the gather kernel: no windows, no valid ratios) loads, in state.flags."""
+    assert raw.stride(1) == 1 and state.n == B * S
+    _chk_f32(ref)
+    _call("gom_dec_value_mark", _p(raw), raw.stride(0), _p(ref), _p(shapes), _p(lsi), B, Lq, S, _p(state.flags), _stream())
+
+
+def dec_value_compact(state):
+    """state.flags -> state.rows[:state.count], ascending."""
+    _call("gom_dec_value_compact", _p(state.flags), state.n, _p(state.rows), _p(state.count), _stream())
+
+
+def linear_rows(x, lin, state, out=None, clear=True):
+    """out[r] = x[r] @ W^T + b for the rows r listed in `state` (K256Linear, N = lin.N; `out` defaults to state.value), with the bits
+    `linear` gives those rows; other rows of `out` stay.  clear: the listed rows' flags go back to zero."""
+    if not isinstance(lin, K256Linear):
+        raise _lib_mod.GomError("the row-list GEMM runs on the row-resident K = 256 kernel only (f16x3 back-end)")
+    out = state.value if out is None else out
+    assert x.dim() == 2 and x.stride(1) == 1 and x.shape == (state.n, lin.K) and x.dtype == _f32
+    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == state.n and out.shape[1] >= lin.N and out.dtype == _f32
+    _call("gom_gemm_k256_rows_f32", _p(x), _ld(x), _p(lin.image), _p(state.rows), _p(state.count), _p(state.flags) if clear else None,
+          _p(out), _ld(out), state.n, lin.N, lin.K, _p(range_flag(x.device)), _stream())
+    return out
+
+
 def msda_prepare(raw, ref, spatial_shapes, ref_levels=1):
     """raw [Q, >=384] (offsets | logits), ref [Q, ref_levels, 2] -> loc [Q,8,4,4,2], w [Q,8,4,4]."""
     _chk_f32(ref)

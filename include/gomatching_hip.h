@@ -340,6 +340,23 @@ void gom_gemm_k256_set_lines(int mode);
  * table rows of a position are fetched into an XCD's L2 once for all frames (1 = on, 0 = index order = default: the interleave
  * measured 3 % slower, the re-reads hit the Infinity Cache; same bits). */
 void gom_gemm_k256_set_interleave(int on);
+/* Row-list form: C[rows[i]] = A[rows[i]] . W^T + bias for i < *count (rows, count: device memory; rows of [0, M)), every other row
+ * of C untouched; per listed row the bits of gom_gemm_k256_f32.  The grid is the dense problem's (M = the list's capacity), so a
+ * captured launch serves any count.  clear (may be NULL): byte clear[rows[i]] = 0 for every listed row. */
+int gom_gemm_k256_rows_f32(const float* A, int lda, const void* image, const int* rows, const int* count, unsigned char* clear,
+                           float* C, int ldc, int M, int N, int K, int* flag, void* stream);
+
+/* The rows of the encoder memory that a decoder layer's fused MSDA call LOADS (csrc/dec_value_rows.hip; raw, ref, shapes and level
+ * starts as for gom_msda_fused_forward, whose gather kernel shares the corner arithmetic): gom_dec_value_mark sets the byte
+ * flags[frame * rows_per_frame + row] = 1 for every such row, weight-0 loads included; gom_dec_value_compact turns flags[0, n) into
+ * the ascending list rows[0, *count) (rows: n ints).  flags: gom_dec_value_flag_bytes(n) bytes (n rounded up to the compaction's
+ * tile), zero where nothing is marked; the marks stay set until gom_gemm_k256_rows_f32 (clear = flags) or the caller clears them.
+ * No atomics, deterministic. */
+long gom_dec_value_flag_bytes(int n);
+int gom_dec_value_mark(const float* raw, int ld_raw, const float* ref, const int64_t* spatial_shapes,
+                       const int64_t* level_start_index, int batch, int num_query, int rows_per_frame, unsigned char* flags,
+                       void* stream);
+int gom_dec_value_compact(const unsigned char* flags, int n, int* rows, int* count, void* stream);
 
 /* Fused FFN block of a DeepSolo transformer layer (deformable_transformer.py:250-251,266-273 encoder linear1/ReLU/linear2 +
  * residual + norm2; :352-354,368-369 decoder + norm3):
