@@ -256,14 +256,27 @@ int launch(const GemmArgs& a, hipStream_t s) {
     return gom_launch_status();
 }
 
+// N <= 32 (the heads with 1 / 4 / 8 outputs): 256-row tiles put M = 20 000 on 79 workgroups, each walking all of K alone.  Below
+// NARROW_MAX_TILES of them -- half of the chip's 256 CUs -- the rows go out in 128-row tiles (a wave owns 32 rows instead of 64):
+// twice the workgroups, half the MFMAs and A loads in each one's k-loop.  A row's k order is the same in both tiles, so C keeps its
+// bits; the rule reads M and N alone.  gom_gemm_f32_set_narrow_tile(0): the 256-row tile whatever M is.
+constexpr int NARROW_MAX_TILES = 128;
+int g_narrow_tile = 1;
+
 template <int KH, int KW>
 int dispatch_tile(const GemmArgs& a, hipStream_t s) {
+    if (a.N <= 32 && g_narrow_tile && cdiv(a.M, 256) < NARROW_MAX_TILES) return launch<128, 32, 32, 32, KH, KW>(a, s);
     if (a.N <= 32) return launch<256, 32, 64, 32, KH, KW>(a, s);
     if (a.N <= 64) return launch<256, 64, 64, 64, KH, KW>(a, s);
     return launch<128, 128, 64, 64, KH, KW>(a, s);
 }
 
 }  // namespace
+
+extern "C" int gom_gemm_f32_set_narrow_tile(int on) {
+    g_narrow_tile = on ? 1 : 0;
+    return GOM_OK;
+}
 
 extern "C" int gom_gemm_f32(const float* A, const float* A2, const int* a_rows, int lda, const float* W, int ldw,
                             const float* scale, const float* shift, const float* R, int ldr, int relu, float* C,

@@ -178,6 +178,23 @@ def _switch(name, default=True):
     return default if v is None else v not in ("0", "false", "False", "")
 
 
+_lib_forms = {}
+
+
+def _lib_form(setter, on):
+    """A library-side kernel-form switch follows its ops.<NAME> value (set again only when that changed)."""
+    on = bool(on)
+    if _lib_forms.get(setter) is not on:
+        getattr(_L(), setter)(1 if on else 0)
+        _lib_forms[setter] = on
+
+
+# Small launches of the detector pass in their lean forms (same results bit for bit; off = the forms before them, for A/B runs):
+TOPK_LEAN = _switch("TOPK_LEAN")                 # proposal top-k: k-bounded chunk sort, merge network sized by the candidates
+DEC_VALUE_MARK_LEAN = _switch("DEC_VALUE_MARK_LEAN")   # decoder row marking: a flag is read before it is stored
+GEMM_NARROW_TILE = _switch("GEMM_NARROW_TILE")   # exact-fp32 GEMM, N <= 32: 128-row tiles while 256-row tiles would leave most CUs empty
+
+
 def _dev_index(device):
     d = torch.device(device)
     return d.index if d.index is not None else torch.cuda.current_device()
@@ -352,6 +369,7 @@ def gemm(A, W, bias=None, scale=None, A2=None, rows=None, R=None, relu=False, ou
         return out
     with _timed(N > 64 and M > 0 and GEMM_MODE == "fp32", lambda: (
             2.0 * M * N * K, 4.0 * (M * K + N * K + M * N + (M * N if R is not None else 0)), "%dx%dx%d" % (M, N, K))):
+        _lib_form("gom_gemm_f32_set_narrow_tile", GEMM_NARROW_TILE)
         _call("gom_gemm_f32", _p(A), _p(A2), _p(rows), lda, _p(W), ldw, _p(scale), _p(bias), _p(R), ldr, 1 if relu else 0, _p(out),
               ldc, M, N, K, _stream())
     return out
@@ -447,6 +465,7 @@ def conv2d_nhwc(x, w_ohwi, scale=None, shift=None, R=None, relu=False, stride=1,
         _call("gom_conv2d_nhwc_f32_bf16x6_splitk", _p(x), _p(pl), pl.stride(0), pl.stride(1), _p(scale), _p(shift), _p(R),
               1 if relu else 0, _p(y), B, H, Wd, Cin, Cout, KH, KW, stride, pad, _p(ws), nbytes, splits, _stream())
         return y
+    _lib_form("gom_gemm_f32_set_narrow_tile", GEMM_NARROW_TILE)
     _call("gom_conv2d_nhwc_f32", _p(x), _p(w_ohwi), _p(scale), _p(shift), _p(R), 1 if relu else 0, _p(y), B, H, Wd, Cin, Cout, KH,
           KW, stride, pad, _stream())
     return y
@@ -1282,6 +1301,7 @@ def dec_value_mark(raw, ref, shapes, lsi, B, Lq, S, state):
     """Flag the rows that `msda_fused(raw, ref, ...)` (the gather kernel: no windows, no valid ratios) loads, in state.flags."""
     assert raw.stride(1) == 1 and state.n == B * S
     _chk_f32(ref)
+    _lib_form("gom_dec_value_set_lean_mark", DEC_VALUE_MARK_LEAN)
     _call("gom_dec_value_mark", _p(raw), raw.stride(0), _p(ref), _p(shapes), _p(lsi), B, Lq, S, _p(state.flags), _stream())
 
 
@@ -2495,6 +2515,7 @@ def topk_tokens(logits, B, S, k, valid=None, invalid_logit=None, with_rows=False
     ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=logits.device)
     idx = torch.empty((B, k), dtype=torch.int32, device=logits.device)
     rows = torch.empty((B, k), dtype=torch.int32, device=logits.device) if with_rows else None
+    _lib_form("gom_topk_set_lean", TOPK_LEAN)
     if frame_valid is not None:
         assert valid is None, "valid and frame_valid are exclusive"
         _chk_frame_desc(frame_valid, B, (S,), torch.uint8, "frame_valid")

@@ -124,6 +124,7 @@ int gom_msda_prepare(const float* raw, int ld_raw, const float* ref, int ref_lev
  * C[M,N] = act( (A[+A2])[M,K] . W[N,K]^T * scale[N] + shift[N] + R[M,N] )
  * nn.Linear: W = weight, shift = bias, scale = NULL.  a_rows (optional) gathers rows of A (and A2).
  * K, lda, ldw multiples of 4. */
+int gom_gemm_f32_set_narrow_tile(int on);   /* [host] 1 (default): N <= 32 on 128-row tiles while 256-row tiles would fill under half the CUs; same bits */
 int gom_gemm_f32(const float* A, const float* A2, const int* a_rows, int lda, const float* W, int ldw,
                  const float* scale, const float* shift, const float* R, int ldr, int relu, float* C, int ldc, int M,
                  int N, int K, void* stream);
@@ -352,6 +353,7 @@ int gom_gemm_k256_rows_f32(const float* A, int lda, const void* image, const int
  * the ascending list rows[0, *count) (rows: n ints).  flags: gom_dec_value_flag_bytes(n) bytes (n rounded up to the compaction's
  * tile), zero where nothing is marked; the marks stay set until gom_gemm_k256_rows_f32 (clear = flags) or the caller clears them.
  * No atomics, deterministic. */
+int gom_dec_value_set_lean_mark(int on);   /* [host] 1 (default): gom_dec_value_mark reads a flag before it stores it; same bytes */
 long gom_dec_value_flag_bytes(int n);
 int gom_dec_value_mark(const float* raw, int ld_raw, const float* ref, const int64_t* spatial_shapes,
                        const int64_t* level_start_index, int batch, int num_query, int rows_per_frame, unsigned char* flags,
@@ -1363,6 +1365,7 @@ int gom_broadcast_rows_f32(const float* src, float* out, long n, int B, void* st
 
 /* top-k token indices per batch element (deformable_transformer.py:188-190); idx_out [B,k] int32, sorted by
  * logit descending; rows_out (optional) [B,k] = b*S + idx.  valid/invalid_logit (optional): tokens with valid[s]==0 take *invalid_logit. */
+int gom_topk_set_lean(int on);   /* [host] 1 (default): k-bounded chunk sort (k <= 128), merge network sized by the candidates; same result */
 long gom_topk_workspace_bytes(int B, long S, int k);
 int gom_topk_tokens(const float* logits, int ld, const unsigned char* valid, const float* invalid_logit, int B, long S,
                     int k, void* workspace, int* idx_out, int* rows_out, void* stream);
